@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- cells/sec screened on MI355X (BASELINE.json metric), one process per GPU.
 
-    python bench.py --gpus N --steps K --warmup W          (N = 1)
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]         (N = 1)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -12,7 +12,16 @@ ending with the per-cell results on the host of rank 0 (for N > 1: after the RCC
 N = 1 runs BASELINE.json configs[2] (1M crops on one GPU); N > 1 runs configs[3]'s layout at its per-GPU size: 1.25 M crops
 per GPU (10 M global at N = 8), contiguous index ranges, no data-path collective before the final RCCL gather (weak scaling).
 
-Rank 0 prints ONE JSON line; besides the contract keys it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline keys (metric, value,
+unit, ms_per_step = milliseconds per timed step, higher_is_better, dtype, ...) and `config`.  --dump-outputs DIR then also
+writes the results of the last timed step, the arrays a caller of cs_screen receives, as DIR/<name>.npy: mse and mae in
+float32, cons_score and mod_score in float64, cons_pred and mod_pred (+1 / -1) as float32.  Above 64 MB in all they are a
+sample of cells drawn with --seed, whose indices are in cell_index.npy.  With the same arguments every run screens the same
+crops with the same weights.  The detector is fit on this build's encoder features of seeded crops, so a build that
+changes the encoder's rounding also shifts the detector slightly.
+With --full, the line also carries
+  whole_path    executed and algorithmic FLOP/s and HBM rates of the whole step, from the per-kernel figures below
+  kernels       every kernel family's device time in the timed steps (HIP events on the library's stream) and its rates
   roofline      the dominant kernel priced against the matrix pipes it runs on.  `achieved` counts the matrix-pipe work
                 the kernel EXECUTES (its fp32 MFMAs x 2,048 FLOP + its bf16 MFMAs x 16,384 FLOP -- the library reports
                 both counts, their sum is what SQ_INSTS_MFMA shows) over its launch time from HIP events recorded on
@@ -90,15 +99,43 @@ def parse():
                                                          "1,250,000 at N > 1 [configs[3]: 10 M over 8 GPUs])")
     ap.add_argument("--chunk", type=int, default=65536, help="cells per internal pass (workspace ~0.3 MB per cell)")
     ap.add_argument("--train-cells", type=int, default=5000, help="synthetic crops the detector is fit on")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: HBM traffic, per-kernel "
+                                                          "figures and the roofline, the CPU baselines and the extra legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's results as DIR/<name>.npy")
     ap.add_argument("--cpu-sample", type=int, default=0, help="cells for the CPU port baseline (0 = auto, ~10 s)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="do not collect HBM traffic with rocprofv3 child passes")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the exact-fp32, raw-crop, training, 128x128-variant and small-N legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: do not collect HBM traffic with rocprofv3 child passes")
+    ap.add_argument("--no-extra-legs", action="store_true", help="with --full: skip the exact-fp32, raw-crop, training, 128x128-variant and small-N legs")
     ap.add_argument("--train-steps", type=int, default=0, help="timed training steps (0 = one configs[1] epoch: 1,250)")
     ap.add_argument("--raw-crops", type=int, default=1_000_000, help="raw crops of the e2e_raw leg")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--seed", type=int, default=42)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+# ------------------------------------------------------------------------------------------- --dump-outputs
+DUMP_BYTES = 64_000_000 - 4096          # 64 MB in all, less room for the .npy headers
+
+
+def dump_outputs(path, res, seed):
+    """The results of the last timed step (pinned host tensors of n cells) as <path>/<name>.npy in float32 / float64; the labels
+    are int8 in the library and float32 here.  When they do not fit DUMP_BYTES, a sorted sample of cells drawn with `seed` is
+    written instead, with its indices (float64, exact) in cell_index.npy."""
+    import numpy as np
+    arrs = {k: v.numpy() for k, v in res.items()}
+    arrs = {k: a if a.dtype in (np.float32, np.float64) else a.astype(np.float32) for k, a in arrs.items()}
+    n = len(arrs["mse"])
+    per_cell = sum(a.itemsize for a in arrs.values())
+    os.makedirs(path, exist_ok=True)
+    if n * per_cell > DUMP_BYTES:
+        idx = np.sort(np.random.default_rng(seed).choice(n, size=DUMP_BYTES // (per_cell + 8), replace=False))
+        np.save(os.path.join(path, "cell_index.npy"), idx.astype(np.float64))
+        arrs = {k: a[idx] for k, a in arrs.items()}
+    for k, a in arrs.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 # ------------------------------------------------------------------------------------------- HBM traffic (PMC)
@@ -661,7 +698,7 @@ def main():
     # ---- HBM traffic of this tree: PMC child passes first, while this process has not touched the GPU yet
     pmc, pmc_src = None, None
     under_profiler = any(k.startswith(("ROCPROFILER_", "ROCP_")) for k in os.environ) or "rocprofiler" in os.environ.get("LD_PRELOAD", "")
-    if world == 1 and not args.pmc_child and not args.no_pmc and not under_profiler:      # never nest profiler runs
+    if args.full and world == 1 and not args.pmc_child and not args.no_pmc and not under_profiler:      # never nest profiler runs
         pmc, pmc_src = collect_pmc_traffic(args)
 
     import numpy as np
@@ -730,104 +767,26 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    eng.profile_enable(True)
-    eng.profile_reset()
+    if args.full:                 # per-kernel HIP events inside the timed steps: the kernels, whole_path and roofline figures
+        eng.profile_enable(True)
+        eng.profile_reset()
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         res = step()
     fence()
     elapsed = time.perf_counter() - t0
-    eng.profile_enable(False)
+    if args.full:
+        eng.profile_enable(False)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, res, args.seed)
 
-    prof = eng.profile()
     if rank == 0:
         value = n_total * args.steps / elapsed
-        kern = {k: v for k, v in prof.items() if v["launches"] > 0}
-        total_ms = sum(v["ms"] for v in kern.values())
-        ex_tf = lambda v: v["mfma_per_cell"] * FLOP_PER_MFMA * v["cells"] / (v["ms"] * 1e-3) / 1e12      # noqa: E731
-        bf_tf = lambda v: v["bf16_mfma_per_cell"] * FLOP_PER_BF16_MFMA * v["cells"] / (v["ms"] * 1e-3) / 1e12      # noqa: E731
-        # ---- roofline: dominant kernel by device time, EXECUTED matrix-pipe FLOPs / measured duration
-        # a kernel's matrix work at the peaks of the pipes it runs on: seconds at peak, executed FLOP (fp32-MFMA + bf16-MFMA)
-        def at_peak(v):
-            f32 = v["mfma_per_cell"] * FLOP_PER_MFMA * v["cells"]
-            b16 = v.get("bf16_mfma_per_cell", 0) * FLOP_PER_BF16_MFMA * v["cells"]
-            return f32 / (FP32_MFMA_PEAK_TFLOPS * 1e12) + b16 / (BF16_MFMA_PEAK_TFLOPS * 1e12), f32 + b16, b16
-        dom = max((k for k in kern if at_peak(kern[k])[1] > 0), key=lambda k: kern[k]["ms"])
-        d = kern[dom]
-        avg_ms = d["ms"] / d["launches"]
-        cpl = d["cells"] / d["launches"]
-        t_pk, fl_ex, fl_b16 = at_peak(d)
-        ach = fl_ex / (d["ms"] * 1e-3) / 1e12
-        # the peak the kernel's own mix of instructions could reach: all of it fp32-MFMA -> 157.3; with bf16 MFMAs in the mix, higher
-        peak_mix = fl_ex / t_pk / 1e12
-        alg = d["flops"] / (d["ms"] * 1e-3) / 1e12
-        if pmc is None and not args.pmc_child:
-            pmc, pmc_src = committed_pmc_traffic()
-        tk = pmc["kernels"] if pmc else {}
-        traffic = round(tk[dom]["hbm_bytes_per_cell"] * cpl) if dom in tk else None
-        # cross-check of the MFMA count against SQ_INSTS_MFMA when a counters file of this tree is committed
-        sq_check = None
-        try:
-            from build import source_hash
-            for f in sorted(os.listdir(os.path.join(ROOT, "profiles")), reverse=True):
-                if f.endswith("_sq_counters.json"):
-                    sj = json.load(open(os.path.join(ROOT, "profiles", f)))
-                    if sj.get("source_hash") == source_hash() and dom in sj["kernels"] and "SQ_INSTS_MFMA" in sj["kernels"][dom]:
-                        per_cell = sj["kernels"][dom]["SQ_INSTS_MFMA"] / sj.get("cells_per_launch", 65536)
-                        sq_check = dict(file="profiles/" + f, sq_insts_mfma_per_cell=round(per_cell, 2),
-                                        library_mfma_per_cell=d["mfma_per_cell"] + d.get("bf16_mfma_per_cell", 0),
-                                        equal=bool(abs(per_cell - d["mfma_per_cell"] - d.get("bf16_mfma_per_cell", 0)) < 0.5))
-                    break
-        except Exception:  # noqa: BLE001
-            pass
-        roofline = dict(bound="mfma", kernel=dom, achieved=round(ach, 3), peak=round(peak_mix, 1), unit="TFLOP/s",
-                        frac=round(ach / peak_mix, 4),
-                        executed_mfma_per_cell=d["mfma_per_cell"], executed_bf16_mfma_per_cell=d.get("bf16_mfma_per_cell", 0),
-                        executed_flop_per_launch=int(fl_ex / d["launches"]),
-                        peak_note=("peak = executed FLOP / (fp32-MFMA FLOP / 157.3 TFLOP/s + bf16-MFMA FLOP / 2,500 TFLOP/s): the rate this kernel's "
-                                   "own instruction mix would reach with both matrix pipes at their peaks; 157.3 for a pure fp32-MFMA kernel"),
-                        achieved_algorithmic=round(alg, 3), algorithmic_speedup=round(alg / ach, 4) if ach > 0 else None,
-                        note="achieved/frac price the multiply-adds the kernel executes (fp32 MFMAs x 2,048 FLOP + bf16 MFMAs x 16,384 FLOP); achieved_algorithmic "
-                             "counts the reference graph's FLOPs of the same layers, of which Winograd / folded-upsample kernels execute a fraction",
-                        sq_insts_mfma_check=sq_check,
-                        traffic=traffic, traffic_unit="HBM bytes per launch", traffic_source=pmc_src,
-                        algorithmic_bytes_per_launch=int(ALG_BYTES[dom] * cpl) if dom in ALG_BYTES else None,
-                        avg_launch_ms=round(avg_ms, 4), cells_per_launch=int(cpl),
-                        share_of_device_time=round(d["ms"] / total_ms, 4))
-        kernels = {k: dict(ms=round(v["ms"], 3), launches=v["launches"], share=round(v["ms"] / total_ms, 4),
-                           # fp32-MFMA pricing; a kernel whose main contraction runs on bf16 MFMAs is priced by the bf16 keys below
-                           tflops_executed=round(ex_tf(v), 2) if v["mfma_per_cell"] > 0 and not v.get("bf16_mfma_per_cell", 0) else None,
-                           frac_executed=round(ex_tf(v) / FP32_MFMA_PEAK_TFLOPS, 4) if v["mfma_per_cell"] > 0 and not v.get("bf16_mfma_per_cell", 0) else None,
-                           tflops_algorithmic=round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 2) if v["flops"] > 0 else None,
-                           # seconds the kernel's executed matrix work takes with both pipes at their peaks / its device time
-                           frac_matrix_peaks=round(at_peak(v)[0] / (v["ms"] * 1e-3), 4) if at_peak(v)[1] > 0 else None,
-                           **({"bf16_mfma_per_cell": v["bf16_mfma_per_cell"],
-                               "tflops_executed_bf16": round(bf_tf(v), 1), "frac_bf16_mfma_peak": round(bf_tf(v) / BF16_MFMA_PEAK_TFLOPS, 4)}
-                              if v.get("bf16_mfma_per_cell", 0) > 0 else {}),
-                           hbm_bytes_per_cell=tk[k]["hbm_bytes_per_cell"] if k in tk else None,
-                           algorithmic_bytes_per_cell=ALG_BYTES.get(k))
-                   for k, v in kern.items()}
-        enc_k = [k for k in ENCODER_KERNELS if k in kern]
-        enc_ms = sum(kern[k]["ms"] for k in enc_k)
-        enc_cells = kern[enc_k[0]]["cells"]
-        enc_hbm = {"kernels": enc_k, "algorithmic_bytes_per_cell": 16384 + 8192,
-                   "algorithmic_gbs_at_encoder_rate": round(enc_cells * 24576 / (enc_ms * 1e-3) / 1e9, 1),
-                   "frac_hbm_peak_algorithmic": round(enc_cells * 24576 / (enc_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
-                   "measured_bytes_per_cell": None, "frac_hbm_peak_measured": None, "encoder_ms_per_step": round(enc_ms / args.steps, 3)}
-        if tk and all(k in tk for k in enc_k):
-            mb = sum(tk[k]["hbm_bytes_per_cell"] for k in enc_k)
-            enc_hbm["measured_bytes_per_cell"] = round(mb)
-            enc_hbm["frac_hbm_peak_measured"] = round(enc_cells * mb / (enc_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
-            enc_hbm["measured_source"] = pmc_src
-        conv_cells = max(kern[k]["cells"] for k in kern if k.startswith("conv"))
-        exec_flop_per_cell = sum(kern[k]["mfma_per_cell"] * FLOP_PER_MFMA * kern[k]["cells"] for k in kern if k.startswith("conv")) / max(1, conv_cells)
-        exec_bf16_flop_per_cell = sum(kern[k].get("bf16_mfma_per_cell", 0) * FLOP_PER_BF16_MFMA * kern[k]["cells"] for k in kern if k.startswith("conv")) / max(1, conv_cells)
-        whole_traffic = round(sum(tk[k]["hbm_bytes_per_cell"] for k in kern if k in tk)) if tk else None
         line = {
             "metric": "cells/sec screened (CAE fwd + recon-MSE + SVM score), 64x64",
             "value": round(value, 1), "unit": "cells/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -846,82 +805,164 @@ def main():
                        "n_sv": [int(det.conservative.n_sv), int(det.moderate.n_sv)], "detector_train_cells": args.train_cells,
                        "weights": "random init (Glorot, non-trivial BN), seed %d" % args.seed,
                        "parallelism": "dp%d" % world},
-            "whole_path": {"tflops_executed_fp32_mfma": round(value * exec_flop_per_cell / 1e12 / world, 3),
-                           "tflops_executed_bf16_mfma": round(value * exec_bf16_flop_per_cell / 1e12 / world, 3),
-                           # device time the executed matrix work would take at the two pipes' peaks / the time it takes
-                           "frac_matrix_peaks": round(value / world * (exec_flop_per_cell / (FP32_MFMA_PEAK_TFLOPS * 1e12)
-                                                                        + exec_bf16_flop_per_cell / (BF16_MFMA_PEAK_TFLOPS * 1e12)), 4),
-                           "executed_fp32_mfma_flop_per_cell": int(exec_flop_per_cell),
-                           "executed_bf16_mfma_flop_per_cell": int(exec_bf16_flop_per_cell),
-                           "tflops_algorithmic": round(value * FLOP_PER_CELL / 1e12 / world, 3),
-                           "note": "executed = the conv kernels' MFMA counts per cell: v_mfma_f32_16x16x4_f32 x 2,048 FLOP (conv1+conv2, conv3, conv7's contraction) "
-                                   "and the 16-bit forms v_mfma_f32_16x16x32_{bf16,f16} x 16,384 FLOP (the fp32 contraction as six bf16 or three fp16 products); "
-                                   "algorithmic = the reference graph's 100.27 MFLOP/cell",
-                           "hbm_gbs_algorithmic": round(value * BYTES_PER_CELL / 1e9 / world, 2),
-                           "frac_hbm_peak": round(value * BYTES_PER_CELL / 1e9 / world / HBM_PEAK_GBS, 5),
-                           "hbm_bytes_per_cell_measured": whole_traffic,
-                           "hbm_gbs_measured": round(value * whole_traffic / 1e9 / world, 1) if whole_traffic else None,
-                           "device_ms_per_step": round(total_ms / args.steps, 3),
-                           # BASELINE.json asks for the fraction of the HBM roofline on the conv encoder (conv1-3): algorithmic
-                           # bytes = one crop in + 8 KB of features out; measured = PMC traffic of its kernels.  Exact-fp32
-                           # convs are MFMA-bound, so neither can approach 1.
-                           "conv_encoder_hbm": enc_hbm},
-            "roofline": roofline,
-            "kernels": kernels,
         }
-        oracle_ref = None
-        if world == 1 and not args.no_cpu_baseline and not args.pmc_child:
-            cb, ref_seq = cpu_reference_sequence(weights, sk, args.seed)
-            port, ref, xs = cpu_port(weights, det, args.seed, args.cpu_sample)
-            oracle_ref = ref
-            # the contract's object is the oracle port ("port"); the reference's own call sequence on torch-CPU + scikit-learn rides along
-            port["reference_sequence"] = cb
-            line["cpu_baseline"] = port
-            # the bounded samples double as live parity checks of the benchmarked run
-            n = len(xs)
-            mse = res["mse"][:n].numpy()
-            rel = float(np.max(np.abs(mse - ref["mse"]) / ref["mse"]))
-            tol = 1e-4 * float(np.abs(det.conservative.dual_coef).sum())
-            derr = float(np.max(np.abs(res["cons_score"][:n].numpy() - ref["cons_score"])))
-            line["parity_on_cpu_sample"] = {"cells": n, "mse_max_rel": rel, "cons_score_max_abs": derr,
-                                            "ok": bool(rel <= 1e-5 and derr <= tol)}
-            m = len(ref_seq["mse"])       # the reference sequence itself (fp32 library arithmetic): looser by its own rounding
-            rel2 = float(np.max(np.abs(res["mse"][:m].numpy() - ref_seq["mse"]) / ref_seq["mse"]))
-            derr2 = float(np.max(np.abs(res["cons_score"][:m].numpy() - ref_seq["cons_score"])))
-            sure = np.abs(ref_seq["cons_score"]) > tol
-            line["parity_vs_reference_sequence"] = {"cells": m, "mse_max_rel": rel2, "cons_score_max_abs": derr2, "score_tol": tol,
-                                                    "labels_equal_away_from_0": bool(np.array_equal(res["cons_pred"][:m].numpy()[sure], ref_seq["cons_pred"][sure]))}
-        if world == 1 and not args.no_extra_legs and not args.pmc_child:
+        if args.full:
+            kern = {k: v for k, v in eng.profile().items() if v["launches"] > 0}
+            total_ms = sum(v["ms"] for v in kern.values())
+            ex_tf = lambda v: v["mfma_per_cell"] * FLOP_PER_MFMA * v["cells"] / (v["ms"] * 1e-3) / 1e12      # noqa: E731
+            bf_tf = lambda v: v["bf16_mfma_per_cell"] * FLOP_PER_BF16_MFMA * v["cells"] / (v["ms"] * 1e-3) / 1e12      # noqa: E731
+            # ---- roofline: dominant kernel by device time, EXECUTED matrix-pipe FLOPs / measured duration
+            # a kernel's matrix work at the peaks of the pipes it runs on: seconds at peak, executed FLOP (fp32-MFMA + bf16-MFMA)
+            def at_peak(v):
+                f32 = v["mfma_per_cell"] * FLOP_PER_MFMA * v["cells"]
+                b16 = v.get("bf16_mfma_per_cell", 0) * FLOP_PER_BF16_MFMA * v["cells"]
+                return f32 / (FP32_MFMA_PEAK_TFLOPS * 1e12) + b16 / (BF16_MFMA_PEAK_TFLOPS * 1e12), f32 + b16, b16
+            dom = max((k for k in kern if at_peak(kern[k])[1] > 0), key=lambda k: kern[k]["ms"])
+            d = kern[dom]
+            avg_ms = d["ms"] / d["launches"]
+            cpl = d["cells"] / d["launches"]
+            t_pk, fl_ex, fl_b16 = at_peak(d)
+            ach = fl_ex / (d["ms"] * 1e-3) / 1e12
+            # the peak the kernel's own mix of instructions could reach: all of it fp32-MFMA -> 157.3; with bf16 MFMAs in the mix, higher
+            peak_mix = fl_ex / t_pk / 1e12
+            alg = d["flops"] / (d["ms"] * 1e-3) / 1e12
+            if pmc is None and not args.pmc_child:
+                pmc, pmc_src = committed_pmc_traffic()
+            tk = pmc["kernels"] if pmc else {}
+            traffic = round(tk[dom]["hbm_bytes_per_cell"] * cpl) if dom in tk else None
+            # cross-check of the MFMA count against SQ_INSTS_MFMA when a counters file of this tree is committed
+            sq_check = None
             try:
-                line["small_n"] = small_n_leg(eng, args.seed)
-            except Exception as e:  # noqa: BLE001 - an extra leg never costs the headline line
-                line["small_n"] = {"error": repr(e)}
-            try:
-                line["exact_fp32"], head = exact_fp32_leg(weights, det, x, out, host, args, local_rank)
-                if oracle_ref is not None:          # the exact mode's own live parity check, same sample and bars as the headline's
-                    n = len(oracle_ref["mse"])
-                    rel = float(np.max(np.abs(head["mse"][:n] - oracle_ref["mse"]) / oracle_ref["mse"]))
-                    derr = float(np.max(np.abs(head["cons_score"][:n] - oracle_ref["cons_score"])))
-                    tol = 1e-4 * float(np.abs(det.conservative.dual_coef).sum())
-                    line["exact_fp32"]["parity_on_cpu_sample"] = {"cells": n, "mse_max_rel": rel, "cons_score_max_abs": derr, "ok": bool(rel <= 1e-5 and derr <= tol)}
-            except Exception as e:  # noqa: BLE001
-                line["exact_fp32"] = {"error": repr(e)}
-            del x
-            torch.cuda.empty_cache()
-            try:
-                line["e2e_raw"] = e2e_raw_leg(weights, args.raw_crops, args.seed, local_rank)
-            except Exception as e:  # noqa: BLE001
-                line["e2e_raw"] = {"error": repr(e)}
-            torch.cuda.empty_cache()
-            try:
-                line["train_leg"] = train_leg(args.train_steps, local_rank, args.seed)
-            except Exception as e:  # noqa: BLE001
-                line["train_leg"] = {"error": repr(e)}
-            torch.cuda.empty_cache()
-            try:
-                line["large_variant"] = large_variant_leg(local_rank, args.seed)
-            except Exception as e:  # noqa: BLE001
-                line["large_variant"] = {"error": repr(e)}
+                from build import source_hash
+                for f in sorted(os.listdir(os.path.join(ROOT, "profiles")), reverse=True):
+                    if f.endswith("_sq_counters.json"):
+                        sj = json.load(open(os.path.join(ROOT, "profiles", f)))
+                        if sj.get("source_hash") == source_hash() and dom in sj["kernels"] and "SQ_INSTS_MFMA" in sj["kernels"][dom]:
+                            per_cell = sj["kernels"][dom]["SQ_INSTS_MFMA"] / sj.get("cells_per_launch", 65536)
+                            sq_check = dict(file="profiles/" + f, sq_insts_mfma_per_cell=round(per_cell, 2),
+                                            library_mfma_per_cell=d["mfma_per_cell"] + d.get("bf16_mfma_per_cell", 0),
+                                            equal=bool(abs(per_cell - d["mfma_per_cell"] - d.get("bf16_mfma_per_cell", 0)) < 0.5))
+                        break
+            except Exception:  # noqa: BLE001
+                pass
+            roofline = dict(bound="mfma", kernel=dom, achieved=round(ach, 3), peak=round(peak_mix, 1), unit="TFLOP/s",
+                            frac=round(ach / peak_mix, 4),
+                            executed_mfma_per_cell=d["mfma_per_cell"], executed_bf16_mfma_per_cell=d.get("bf16_mfma_per_cell", 0),
+                            executed_flop_per_launch=int(fl_ex / d["launches"]),
+                            peak_note=("peak = executed FLOP / (fp32-MFMA FLOP / 157.3 TFLOP/s + bf16-MFMA FLOP / 2,500 TFLOP/s): the rate this kernel's "
+                                       "own instruction mix would reach with both matrix pipes at their peaks; 157.3 for a pure fp32-MFMA kernel"),
+                            achieved_algorithmic=round(alg, 3), algorithmic_speedup=round(alg / ach, 4) if ach > 0 else None,
+                            note="achieved/frac price the multiply-adds the kernel executes (fp32 MFMAs x 2,048 FLOP + bf16 MFMAs x 16,384 FLOP); achieved_algorithmic "
+                                 "counts the reference graph's FLOPs of the same layers, of which Winograd / folded-upsample kernels execute a fraction",
+                            sq_insts_mfma_check=sq_check,
+                            traffic=traffic, traffic_unit="HBM bytes per launch", traffic_source=pmc_src,
+                            algorithmic_bytes_per_launch=int(ALG_BYTES[dom] * cpl) if dom in ALG_BYTES else None,
+                            avg_launch_ms=round(avg_ms, 4), cells_per_launch=int(cpl),
+                            share_of_device_time=round(d["ms"] / total_ms, 4))
+            kernels = {k: dict(ms=round(v["ms"], 3), launches=v["launches"], share=round(v["ms"] / total_ms, 4),
+                               # fp32-MFMA pricing; a kernel whose main contraction runs on bf16 MFMAs is priced by the bf16 keys below
+                               tflops_executed=round(ex_tf(v), 2) if v["mfma_per_cell"] > 0 and not v.get("bf16_mfma_per_cell", 0) else None,
+                               frac_executed=round(ex_tf(v) / FP32_MFMA_PEAK_TFLOPS, 4) if v["mfma_per_cell"] > 0 and not v.get("bf16_mfma_per_cell", 0) else None,
+                               tflops_algorithmic=round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 2) if v["flops"] > 0 else None,
+                               # seconds the kernel's executed matrix work takes with both pipes at their peaks / its device time
+                               frac_matrix_peaks=round(at_peak(v)[0] / (v["ms"] * 1e-3), 4) if at_peak(v)[1] > 0 else None,
+                               **({"bf16_mfma_per_cell": v["bf16_mfma_per_cell"],
+                                   "tflops_executed_bf16": round(bf_tf(v), 1), "frac_bf16_mfma_peak": round(bf_tf(v) / BF16_MFMA_PEAK_TFLOPS, 4)}
+                                  if v.get("bf16_mfma_per_cell", 0) > 0 else {}),
+                               hbm_bytes_per_cell=tk[k]["hbm_bytes_per_cell"] if k in tk else None,
+                               algorithmic_bytes_per_cell=ALG_BYTES.get(k))
+                       for k, v in kern.items()}
+            enc_k = [k for k in ENCODER_KERNELS if k in kern]
+            enc_ms = sum(kern[k]["ms"] for k in enc_k)
+            enc_cells = kern[enc_k[0]]["cells"]
+            enc_hbm = {"kernels": enc_k, "algorithmic_bytes_per_cell": 16384 + 8192,
+                       "algorithmic_gbs_at_encoder_rate": round(enc_cells * 24576 / (enc_ms * 1e-3) / 1e9, 1),
+                       "frac_hbm_peak_algorithmic": round(enc_cells * 24576 / (enc_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
+                       "measured_bytes_per_cell": None, "frac_hbm_peak_measured": None, "encoder_ms_per_step": round(enc_ms / args.steps, 3)}
+            if tk and all(k in tk for k in enc_k):
+                mb = sum(tk[k]["hbm_bytes_per_cell"] for k in enc_k)
+                enc_hbm["measured_bytes_per_cell"] = round(mb)
+                enc_hbm["frac_hbm_peak_measured"] = round(enc_cells * mb / (enc_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
+                enc_hbm["measured_source"] = pmc_src
+            conv_cells = max(kern[k]["cells"] for k in kern if k.startswith("conv"))
+            exec_flop_per_cell = sum(kern[k]["mfma_per_cell"] * FLOP_PER_MFMA * kern[k]["cells"] for k in kern if k.startswith("conv")) / max(1, conv_cells)
+            exec_bf16_flop_per_cell = sum(kern[k].get("bf16_mfma_per_cell", 0) * FLOP_PER_BF16_MFMA * kern[k]["cells"] for k in kern if k.startswith("conv")) / max(1, conv_cells)
+            whole_traffic = round(sum(tk[k]["hbm_bytes_per_cell"] for k in kern if k in tk)) if tk else None
+            line["whole_path"] = {"tflops_executed_fp32_mfma": round(value * exec_flop_per_cell / 1e12 / world, 3),
+                                  "tflops_executed_bf16_mfma": round(value * exec_bf16_flop_per_cell / 1e12 / world, 3),
+                                  # device time the executed matrix work would take at the two pipes' peaks / the time it takes
+                                  "frac_matrix_peaks": round(value / world * (exec_flop_per_cell / (FP32_MFMA_PEAK_TFLOPS * 1e12)
+                                                                               + exec_bf16_flop_per_cell / (BF16_MFMA_PEAK_TFLOPS * 1e12)), 4),
+                                  "executed_fp32_mfma_flop_per_cell": int(exec_flop_per_cell),
+                                  "executed_bf16_mfma_flop_per_cell": int(exec_bf16_flop_per_cell),
+                                  "tflops_algorithmic": round(value * FLOP_PER_CELL / 1e12 / world, 3),
+                                  "note": "executed = the conv kernels' MFMA counts per cell: v_mfma_f32_16x16x4_f32 x 2,048 FLOP (conv1+conv2, conv3, conv7's contraction) "
+                                          "and the 16-bit forms v_mfma_f32_16x16x32_{bf16,f16} x 16,384 FLOP (the fp32 contraction as six bf16 or three fp16 products); "
+                                          "algorithmic = the reference graph's 100.27 MFLOP/cell",
+                                  "hbm_gbs_algorithmic": round(value * BYTES_PER_CELL / 1e9 / world, 2),
+                                  "frac_hbm_peak": round(value * BYTES_PER_CELL / 1e9 / world / HBM_PEAK_GBS, 5),
+                                  "hbm_bytes_per_cell_measured": whole_traffic,
+                                  "hbm_gbs_measured": round(value * whole_traffic / 1e9 / world, 1) if whole_traffic else None,
+                                  "device_ms_per_step": round(total_ms / args.steps, 3),
+                                  # BASELINE.json asks for the fraction of the HBM roofline on the conv encoder (conv1-3): algorithmic
+                                  # bytes = one crop in + 8 KB of features out; measured = PMC traffic of its kernels.  Exact-fp32
+                                  # convs are MFMA-bound, so neither can approach 1.
+                                  "conv_encoder_hbm": enc_hbm}
+            line["roofline"] = roofline
+            line["kernels"] = kernels
+            oracle_ref = None
+            if world == 1 and not args.no_cpu_baseline and not args.pmc_child:
+                cb, ref_seq = cpu_reference_sequence(weights, sk, args.seed)
+                port, ref, xs = cpu_port(weights, det, args.seed, args.cpu_sample)
+                oracle_ref = ref
+                # the contract's object is the oracle port ("port"); the reference's own call sequence on torch-CPU + scikit-learn rides along
+                port["reference_sequence"] = cb
+                line["cpu_baseline"] = port
+                # the bounded samples double as live parity checks of the benchmarked run
+                n = len(xs)
+                mse = res["mse"][:n].numpy()
+                rel = float(np.max(np.abs(mse - ref["mse"]) / ref["mse"]))
+                tol = 1e-4 * float(np.abs(det.conservative.dual_coef).sum())
+                derr = float(np.max(np.abs(res["cons_score"][:n].numpy() - ref["cons_score"])))
+                line["parity_on_cpu_sample"] = {"cells": n, "mse_max_rel": rel, "cons_score_max_abs": derr,
+                                                "ok": bool(rel <= 1e-5 and derr <= tol)}
+                m = len(ref_seq["mse"])       # the reference sequence itself (fp32 library arithmetic): looser by its own rounding
+                rel2 = float(np.max(np.abs(res["mse"][:m].numpy() - ref_seq["mse"]) / ref_seq["mse"]))
+                derr2 = float(np.max(np.abs(res["cons_score"][:m].numpy() - ref_seq["cons_score"])))
+                sure = np.abs(ref_seq["cons_score"]) > tol
+                line["parity_vs_reference_sequence"] = {"cells": m, "mse_max_rel": rel2, "cons_score_max_abs": derr2, "score_tol": tol,
+                                                        "labels_equal_away_from_0": bool(np.array_equal(res["cons_pred"][:m].numpy()[sure], ref_seq["cons_pred"][sure]))}
+            if world == 1 and not args.no_extra_legs and not args.pmc_child:
+                try:
+                    line["small_n"] = small_n_leg(eng, args.seed)
+                except Exception as e:  # noqa: BLE001 - an extra leg never costs the headline line
+                    line["small_n"] = {"error": repr(e)}
+                try:
+                    line["exact_fp32"], head = exact_fp32_leg(weights, det, x, out, host, args, local_rank)
+                    if oracle_ref is not None:          # the exact mode's own live parity check, same sample and bars as the headline's
+                        n = len(oracle_ref["mse"])
+                        rel = float(np.max(np.abs(head["mse"][:n] - oracle_ref["mse"]) / oracle_ref["mse"]))
+                        derr = float(np.max(np.abs(head["cons_score"][:n] - oracle_ref["cons_score"])))
+                        tol = 1e-4 * float(np.abs(det.conservative.dual_coef).sum())
+                        line["exact_fp32"]["parity_on_cpu_sample"] = {"cells": n, "mse_max_rel": rel, "cons_score_max_abs": derr, "ok": bool(rel <= 1e-5 and derr <= tol)}
+                except Exception as e:  # noqa: BLE001
+                    line["exact_fp32"] = {"error": repr(e)}
+                del x
+                torch.cuda.empty_cache()
+                try:
+                    line["e2e_raw"] = e2e_raw_leg(weights, args.raw_crops, args.seed, local_rank)
+                except Exception as e:  # noqa: BLE001
+                    line["e2e_raw"] = {"error": repr(e)}
+                torch.cuda.empty_cache()
+                try:
+                    line["train_leg"] = train_leg(args.train_steps, local_rank, args.seed)
+                except Exception as e:  # noqa: BLE001
+                    line["train_leg"] = {"error": repr(e)}
+                torch.cuda.empty_cache()
+                try:
+                    line["large_variant"] = large_variant_leg(local_rank, args.seed)
+                except Exception as e:  # noqa: BLE001
+                    line["large_variant"] = {"error": repr(e)}
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()

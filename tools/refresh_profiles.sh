@@ -12,8 +12,8 @@ mkdir -p "$OUT" profiles
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 QUIET="--no-cpu-baseline --no-pmc --no-extra-legs"
 
-python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -- python3 bench.py --steps 1 --warmup 1 $QUIET \
+python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench rc=$?"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -- python3 bench.py --full --steps 1 --warmup 1 $QUIET \
     > "$OUT/bench_under_rocprof.json" 2> "$OUT/prof.err"; echo "stats rc=$?"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch" -- python3 bench.py --steps 1 --warmup 0 \
     --cells 131072 $QUIET > /dev/null 2>&1; echo "fetch rc=$?"
