@@ -121,6 +121,8 @@ SIGNATURES = {
     "cs_fit_wait_stream": (_I, [_P, _P]),
     "cs_fit_scaler": (_I, [_P, _P, _L, C.c_int32, _I, _P, _P]),
     "cs_fit_pca_moments": (_I, [_P, _P, _L, C.c_int32, _I, _P, _P, _P, _P]),
+    "cs_fit_pca_subspace": (_I, [_P, _P, _L, C.c_int32, _I, _P, _P, C.c_int32, C.c_uint64, _P, _P, _P, C.POINTER(C.c_double),
+                                 C.POINTER(C.c_int32)]),
     "cs_fit_project": (_I, [_P, _P, _L, C.c_int32, _I, _P, _P, _P, _P, C.c_int32, _P]),
     "cs_fit_ocsvm": (_I, [_P, _P, _L, C.c_int32, C.c_double, C.c_double, C.c_double, _L, _P, C.POINTER(C.c_double),
                           C.POINTER(C.c_double), C.POINTER(_L), C.POINTER(C.c_int32)]),

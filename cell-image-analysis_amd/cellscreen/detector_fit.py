@@ -6,8 +6,9 @@ Two implementations of the same fit:
 * `fit_detector_device` -- on the GPU through the C ABI (csrc/fit.hip): the per-feature order
   statistics, the scaled/centred moments, the projection and the whole SMO iteration run on the
   device; the host does numpy's interpolation arithmetic on the selected order statistics, the
-  F x F symmetric eigenproblem (LAPACK through scipy) and libsvm's final rho sum.  No CPU route
-  for the data-proportional work.
+  F x F symmetric eigenproblem (LAPACK through scipy; F a multiple of 128 up to 8192) and libsvm's
+  final rho sum.  Wider features take block subspace iteration on the device (cs_fit_pca_subspace:
+  the host sees L x L matrices only).  No CPU route for the data-proportional work.
 * `fit_detector` -- scikit-learn on the host, the library the reference itself calls; kept as the
   explicit alternative (`method="sklearn"` in the training mirror) and as the oracle of the
   device fit in the tests.
@@ -32,6 +33,8 @@ from .spec import DetectorParams, OCSVMParams
 MEM_HOST, MEM_DEVICE = 0, 1
 SVM_TOL = 1e-3              # OneClassSVM(tol=1e-3) default -> libsvm eps
 EIGH_THREADS = 16           # BLAS threads for the F x F eigenproblem (measured: 0.18 s at 8-16, 0.79 s at 256)
+SUBSPACE_SEED = 0           # start block of the subspace iteration (cs_fit_pca_subspace): fixed, so fits repeat bit for bit
+PCA_SOLVERS = ("auto", "covariance", "subspace")
 
 
 def _write_pickles(output_dir, scaler, pca, detectors):                # :437-444
@@ -134,6 +137,23 @@ class Fitter:
                                              mean.ctypes.data, scatter.ctypes.data))
         return mean, scatter
 
+    def pca_subspace(self, features, center: np.ndarray, scale: np.ndarray, n_components: int,
+                     seed: int = SUBSPACE_SEED) -> Tuple[np.ndarray, np.ndarray, np.ndarray, float, int]:
+        """PCA of the scaled features by block subspace iteration on the device (cs_fit_pca_subspace): nothing
+        F x F, any width.  Returns (mean_ float32 (F,), components float64 (C, F) ordered and signed as PCA.fit
+        leaves components_, explained_variance (C,), total_variance, n_iter)."""
+        keep, ptr, n, F, kind = self._features(features)
+        center = np.ascontiguousarray(center, np.float32)
+        scale = np.ascontiguousarray(scale, np.float64)
+        k = int(n_components)
+        mean = np.empty(F, np.float32)
+        comps = np.empty((max(k, 0), F), np.float64)
+        ev = np.empty(max(k, 0), np.float64)
+        total, n_iter = C.c_double(), C.c_int32()
+        L.check(self._lib.cs_fit_pca_subspace(self._h, ptr, n, F, kind, center.ctypes.data, scale.ctypes.data, k, int(seed),
+                                              mean.ctypes.data, comps.ctypes.data, ev.ctypes.data, C.byref(total), C.byref(n_iter)))
+        return mean, comps, ev, total.value, n_iter.value
+
     def project(self, features, center, scale, components, mean_proj) -> np.ndarray:
         """pca.transform(scaler.transform(features)) with the given parameters -> (N, C) float32."""
         keep, ptr, n, F, kind = self._features(features)
@@ -195,7 +215,12 @@ def _sklearn_scaler(center, scale):
     return s
 
 
-def _sklearn_pca(components, mean, explained_variance, total_var, n_samples):
+def covariance_path_fits(n_features: int) -> bool:
+    """Where cs_fit_pca_moments builds the F x F scatter matrix: F a multiple of 128 up to 8192."""
+    return n_features % 128 == 0 and n_features <= 8192
+
+
+def _sklearn_pca(components, mean, explained_variance, total_var, n_samples, solver="covariance_eigh"):
     from sklearn.decomposition import PCA
     k, F = components.shape
     p = PCA(n_components=k)
@@ -206,7 +231,7 @@ def _sklearn_pca(components, mean, explained_variance, total_var, n_samples):
     p.singular_values_ = np.sqrt(explained_variance * max(n_samples - 1, 1))
     rest = min(F, n_samples) - k
     p.noise_variance_ = float((total_var - explained_variance.sum()) / rest) if rest > 0 else 0.0
-    p._fit_svd_solver = "covariance_eigh"
+    p._fit_svd_solver = solver
     return p
 
 
@@ -232,11 +257,17 @@ def sklearn_ocsvm(x: np.ndarray, alpha: np.ndarray, rho: float, gamma: float, nu
     return d
 
 
-def fit_detector_device(features_flat, output_dir: Optional[str] = None, device_id: int = 0, timings: Optional[dict] = None):
+def fit_detector_device(features_flat, output_dir: Optional[str] = None, device_id: int = 0, timings: Optional[dict] = None,
+                        pca_solver: str = "auto"):
     """The same fit with the data-proportional work on the GPU (csrc/fit.hip).  PCA: the exact
     principal axes (eigenvectors of the covariance) where the reference's PCA(svd_solver='auto')
     takes the randomized solver with an unseeded generator (:413) -- the two agree to the
-    randomized solver's accuracy, see DESIGN.md section 3f."""
+    randomized solver's accuracy, see DESIGN.md section 3f.
+    pca_solver: "covariance" -- the device scatter matrix and a host eigensolve (F a multiple of 128 up to 8192);
+    "subspace" -- block subspace iteration on the device (cs_fit_pca_subspace, any F); "auto" -- the covariance
+    path where it applies, the subspace iteration otherwise."""
+    if pca_solver not in PCA_SOLVERS:
+        raise ValueError(f"pca_solver must be one of {PCA_SOLVERS}, got {pca_solver!r}")
     t = timings if timings is not None else {}
     with Fitter(device_id) as fit:
         n, F = int(features_flat.shape[0]), int(features_flat.shape[1])
@@ -244,17 +275,25 @@ def fit_detector_device(features_flat, output_dir: Optional[str] = None, device_
         center, scale = fit.scaler(features_flat)                                         # :408
         t["scaler_s"], t["scaler_device_ms"] = time.perf_counter() - t0, fit.last_ms
         n_components = min(spec.PCA_MAX_COMPONENTS, F, n - 1)                              # :412
+        solver = pca_solver if pca_solver != "auto" else ("covariance" if covariance_path_fits(F) else "subspace")
+        t["pca_solver"] = solver
+        if solver == "covariance":
+            t0 = time.perf_counter()
+            mean, scatter = fit.pca_moments(features_flat, center, scale)                  # :413-414
+            t["pca_moments_s"], t["pca_moments_device_ms"] = time.perf_counter() - t0, fit.last_ms
+            t0 = time.perf_counter()
+            comps64, ev, total_var = principal_axes(scatter, n, n_components)
+            t["pca_eigh_s"] = time.perf_counter() - t0
+        else:
+            t0 = time.perf_counter()
+            mean, comps64, ev, total_var, n_iter = fit.pca_subspace(features_flat, center, scale, n_components)
+            t["pca_subspace_s"], t["pca_subspace_device_ms"] = time.perf_counter() - t0, fit.last_ms
+            t["pca_subspace_iter"] = n_iter
         t0 = time.perf_counter()
-        mean, scatter = fit.pca_moments(features_flat, center, scale)                      # :413-414
-        t["pca_moments_s"], t["pca_moments_device_ms"] = time.perf_counter() - t0, fit.last_ms
-        t0 = time.perf_counter()
-        comps64, ev, total_var = principal_axes(scatter, n, n_components)
         components = comps64.astype(np.float32)
         mean_proj = (mean.reshape(1, -1) @ components.T).ravel()                           # sklearn _base.py:152-153
-        t["pca_eigh_s"] = time.perf_counter() - t0
-        t0 = time.perf_counter()
         reduced = fit.project(features_flat, center, scale, components, mean_proj)
-        t["project_s"] = time.perf_counter() - t0
+        t["project_s"], t["project_device_ms"] = time.perf_counter() - t0, fit.last_ms
         x64 = reduced.astype(np.float64)                                                   # sklearn svm/_base.py:190 (dtype=np.float64)
         x_var = x64.var()
         gamma = 1.0 / (x64.shape[1] * x_var) if x_var != 0 else 1.0                        # svm/_base.py:244-247
@@ -271,7 +310,8 @@ def fit_detector_device(features_flat, output_dir: Optional[str] = None, device_
     det = DetectorParams(center, scale, components, mean, mean_proj.astype(np.float32),
                          params(solved["Conservative"]), params(solved["Moderate"]))
     objs = dict(scaler=_sklearn_scaler(center, scale),
-                pca=_sklearn_pca(components, mean, ev, total_var, n),
+                pca=_sklearn_pca(components, mean, ev, total_var, n,
+                                 "covariance_eigh" if solver == "covariance" else "randomized"),
                 detectors={k: sklearn_ocsvm(x64, r["alpha"], r["rho"], gamma, nu, r["n_iter"], r["status"])
                            for (k, r), nu in zip(solved.items(), (spec.NU_CONSERVATIVE, spec.NU_MODERATE))},
                 features_reduced=reduced, solved=solved)

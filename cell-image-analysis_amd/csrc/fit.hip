@@ -524,6 +524,153 @@ __global__ __launch_bounds__(SMO_B) void smo_update_kernel(SmoArgs a, int parity
     if (blockIdx.x == 0 && tid == 0) a.state->n_iter += 1;
 }
 
+// ================================================================== PCA: block subspace iteration (wide features)
+// Every product of the iteration is one shape, C = A^T B summed over the rows of A and B: A [K][lda] (fp32 or fp64,
+// C's rows i < ma), B [K][SUB_TILE * gridDim.y] fp64.  With Xc stored both ways round (xs [n][F], xT [F][n]):
+//   Y = Xc Q    : A = xT, B = Q  [F][Lp], K = F        Z = Xc^T Y : A = xs, B = Y [n][Lp], K = n
+//   Gram(M)     : A = B = M, K = rows of M             (Y^T Y and the Gram matrices of the orthonormalisation)
+// v_mfma_f64_16x16x4_f64 with scatter_kernel's operand layout (A[i = l & 15][k = l >> 4] = a[r + k][i0 + i], B[k][j = l & 15],
+// D[i = (l >> 4) + 4 reg][j = l & 15]); a workgroup owns a 128 x 128 tile of C for one slice of the rows, a wave a 64 x 64
+// quarter.  Slices land in part[slice][ma][ldc] and are summed in slice order (subspace_merge_kernel): deterministic.
+constexpr int SUB_TILE = 128;
+template <class TA>
+__global__ __launch_bounds__(256) void atb_kernel(const TA* __restrict__ A, long lda, int ma, const double* __restrict__ B, int ldb,
+                                                  long K, long rows_per_slice, double* __restrict__ part)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int li = lane & 15, kq = lane >> 4;
+    const int i0 = blockIdx.x * SUB_TILE + (wave >> 1) * 64, j0 = blockIdx.y * SUB_TILE + (wave & 1) * 64;
+    const long r0 = (long)blockIdx.z * rows_per_slice, r1 = K < r0 + rows_per_slice ? K : r0 + rows_per_slice;
+    bool iok[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) iok[i] = i0 + 16 * i + li < ma;
+
+    f64x4 acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = f64x4{0.0, 0.0, 0.0, 0.0};
+
+    auto load = [&](long r, double a[4], double b[4]) {
+        const long row = r + kq;
+        const bool ok = row < r1;
+        const TA* pa = A + (ok ? row : r0) * lda;
+        const double* pb = B + (ok ? row : r0) * (long)ldb;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            a[i] = (ok && iok[i]) ? (double)pa[i0 + 16 * i + li] : 0.0;
+            const double vb = pb[j0 + 16 * i + li];
+            b[i] = ok ? vb : 0.0;
+        }
+    };
+    if (r0 < r1) {
+        double a[4], b[4], na[4], nb[4];
+        load(r0, a, b);
+        for (long r = r0; r < r1; r += 4) {
+            const long rn = r + 4 < r1 ? r + 4 : r0;
+            load(rn, na, nb);                                   // prefetch; the wrap-around load of the last step is unused
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], b[j], acc[i][j], 0, 0, 0);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { a[i] = na[i]; b[i] = nb[i]; }
+        }
+    }
+    const int ldc = SUB_TILE * gridDim.y;
+    double* o = part + (size_t)blockIdx.z * ma * ldc;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int rg = 0; rg < 4; ++rg) {
+            const int row = i0 + 16 * i + kq + 4 * rg;
+            if (row < ma)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) o[(size_t)row * ldc + j0 + 16 * j + li] = acc[i][j][rg];
+        }
+}
+
+__global__ __launch_bounds__(256) void subspace_merge_kernel(const double* __restrict__ part, long total, int slices, double* __restrict__ out)
+{
+    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+        double s = 0.0;
+        for (int k = 0; k < slices; ++k) s += part[(size_t)k * total + e];
+        out[e] = s;
+    }
+}
+
+// xs [n][F] -> xT [F][n] (32 x 32 tiles through LDS, keys_transpose_kernel's pattern)
+__global__ __launch_bounds__(256) void transpose_kernel(const float* __restrict__ x, long n, int F, float* __restrict__ xT)
+{
+    __shared__ float tile[32][33];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const long r0 = (long)blockIdx.x * 32;
+    const int c0 = blockIdx.y * 32;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const long r = r0 + ty + 8 * k;
+        const int c = c0 + tx;
+        tile[ty + 8 * k][tx] = (r < n && c < F) ? x[r * F + c] : 0.0f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int c = c0 + ty + 8 * k;
+        const long r = r0 + tx;
+        if (r < n && c < F) xT[(size_t)c * n + r] = tile[tx][ty + 8 * k];
+    }
+}
+
+// sum over the rows of xc[r][f]^2 in fp64, row after row (total_variance = sum_f of it / (n - 1))
+__global__ __launch_bounds__(64) void column_sumsq_kernel(const float* __restrict__ xc, long n, int F, double* __restrict__ out)
+{
+    const int f = blockIdx.x * 64 + threadIdx.x;
+    if (f >= F) return;
+    double s = 0.0;
+    for (long r = 0; r < n; ++r) {
+        const double v = (double)xc[r * F + f];
+        s = fma(v, v, s);
+    }
+    out[f] = s;
+}
+
+// A seeded standard normal per (salt, row, column): splitmix64 of a counter, Box-Muller
+__device__ __forceinline__ unsigned long long splitmix64(unsigned long long z)
+{
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+__device__ __forceinline__ double gauss(unsigned long long seed, unsigned salt, long row, int col)
+{
+    const unsigned long long h = splitmix64(seed ^ splitmix64(((unsigned long long)salt << 40) ^ ((unsigned long long)row << 12) ^ (unsigned)col));
+    const unsigned long long h2 = splitmix64(h);
+    const double u1 = ((double)(h >> 11) + 1.0) * 0x1.0p-53;                // (0, 1]
+    const double u2 = (double)(h2 >> 11) * 0x1.0p-53;
+    return sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
+}
+
+// out[r][j] = sum_i z[r][i] t[i][j] (i in fixed order) + (fresh[j] ? gauss(...) * rscale : 0), r < rows, j < Lp.
+// The orthonormalisation's triangular multiply (t = R^-1, columns found deficient replaced by fresh random ones),
+// the random start (z == nullptr) and the final rotation to the Ritz vectors (t = W).
+__global__ __launch_bounds__(256) void small_mm_kernel(const double* __restrict__ z, long rows, int Lp, const double* __restrict__ t,
+                                                       const int* __restrict__ fresh, unsigned long long seed, unsigned salt,
+                                                       double rscale, double* __restrict__ out)
+{
+    const int per = 256 / Lp;
+    const int j = threadIdx.x % Lp;
+    const long r = (long)blockIdx.x * per + threadIdx.x / Lp;
+    if (r >= rows) return;
+    double s = 0.0;
+    if (z) {
+        const double* zr = z + (size_t)r * Lp;
+        for (int i = 0; i < Lp; ++i) s = fma(zr[i], t[(size_t)i * Lp + j], s);
+    }
+    if (fresh[j]) s += gauss(seed, salt, r, j) * rscale;
+    out[(size_t)r * Lp + j] = s;
+}
+
 }  // namespace
 }  // namespace cs
 
@@ -536,6 +683,7 @@ struct cs_fit {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     DevBuf feat, keys, sel, nanc, cen, scl, xs, mean, part, scat, comps, mproj, proj;
     DevBuf x, xT, xsq, alpha0, alpha1, G0, G1, Qi, part_i, part_j, state;
+    DevBuf sxT, sY, sQ, sZ, sgram, st, sfresh, ssq;            // cs_fit_pca_subspace
     double last_ms = 0.0;
 };
 
@@ -882,5 +1030,371 @@ int cs_fit_ocsvm(cs_fit* f, const double* x, int64_t n, int32_t n_components, do
     }
     if (n_iter) *n_iter = st.n_iter;
     if (status) *status = st.done == 2 ? 1 : 0;                       // 1: stopped at max_iter (libsvm's solve_timed_out)
+    return CS_OK;
+}
+
+// ---- PCA by block subspace iteration ------------------------------------------------------
+namespace {
+
+constexpr int SUB_MAX_ITER = 100;           // cap on the power steps
+constexpr double SUB_RTOL = 1e-5;           // stop when no top-k Ritz value moved by more than this, relative
+constexpr double SUB_ATOL = 1e-12;          // ... or by more than this fraction of the largest (values at the noise floor)
+constexpr double CHOL_REL = 1e-12;          // a column whose residual norm^2 after the previous ones is below this share
+constexpr double CHOL_ABS = 1e-24;          // of its own, or whose norm^2 is below this share of the largest, is deficient
+
+// Symmetric eigenproblem of a small matrix (the L x L Rayleigh quotients): Householder tridiagonalisation and
+// implicit QL (EISPACK tred2 / tql2).  a [n][n] row-major; w ascending; v [n][n] row-major, eigenvectors as
+// columns, only when vectors is set.
+int sym_eig(int n, const double* a, double* w, double* vout, bool vectors)
+{
+    std::vector<double> V(a, a + (size_t)n * n), d(n), e(n);
+    auto A = [&](int i, int j) -> double& { return V[(size_t)i * n + j]; };
+    for (int j = 0; j < n; ++j) d[j] = A(n - 1, j);
+    for (int i = n - 1; i > 0; --i) {
+        double scale = 0.0, h = 0.0;
+        for (int k = 0; k < i; ++k) scale += std::fabs(d[k]);
+        if (scale == 0.0) {
+            e[i] = d[i - 1];
+            for (int j = 0; j < i; ++j) { d[j] = A(i - 1, j); A(i, j) = 0.0; A(j, i) = 0.0; }
+        } else {
+            for (int k = 0; k < i; ++k) { d[k] /= scale; h += d[k] * d[k]; }
+            double f = d[i - 1], g = std::sqrt(h);
+            if (f > 0) g = -g;
+            e[i] = scale * g;
+            h -= f * g;
+            d[i - 1] = f - g;
+            for (int j = 0; j < i; ++j) e[j] = 0.0;
+            for (int j = 0; j < i; ++j) {
+                f = d[j];
+                A(j, i) = f;
+                g = e[j] + A(j, j) * f;
+                for (int k = j + 1; k <= i - 1; ++k) { g += A(k, j) * d[k]; e[k] += A(k, j) * f; }
+                e[j] = g;
+            }
+            f = 0.0;
+            for (int j = 0; j < i; ++j) { e[j] /= h; f += e[j] * d[j]; }
+            const double hh = f / (h + h);
+            for (int j = 0; j < i; ++j) e[j] -= hh * d[j];
+            for (int j = 0; j < i; ++j) {
+                f = d[j]; g = e[j];
+                for (int k = j; k <= i - 1; ++k) A(k, j) -= (f * e[k] + g * d[k]);
+                d[j] = A(i - 1, j);
+                A(i, j) = 0.0;
+            }
+        }
+        d[i] = h;
+    }
+    if (vectors) {
+        for (int i = 0; i < n - 1; ++i) {
+            A(n - 1, i) = A(i, i);
+            A(i, i) = 1.0;
+            const double h = d[i + 1];
+            if (h != 0.0) {
+                for (int k = 0; k <= i; ++k) d[k] = A(k, i + 1) / h;
+                for (int j = 0; j <= i; ++j) {
+                    double g = 0.0;
+                    for (int k = 0; k <= i; ++k) g += A(k, i + 1) * A(k, j);
+                    for (int k = 0; k <= i; ++k) A(k, j) -= g * d[k];
+                }
+            }
+            for (int k = 0; k <= i; ++k) A(k, i + 1) = 0.0;
+        }
+        for (int j = 0; j < n; ++j) { d[j] = A(n - 1, j); A(n - 1, j) = 0.0; }
+        A(n - 1, n - 1) = 1.0;
+    } else {
+        for (int j = 0; j < n; ++j) d[j] = A(j, j);                // the tridiagonal's diagonal
+    }
+    e[0] = 0.0;
+    for (int i = 1; i < n; ++i) e[i - 1] = e[i];
+    e[n - 1] = 0.0;
+    double f = 0.0, tst1 = 0.0;
+    const double eps = std::ldexp(1.0, -52);
+    for (int l = 0; l < n; ++l) {
+        tst1 = std::max(tst1, std::fabs(d[l]) + std::fabs(e[l]));
+        int m = l;
+        while (m < n - 1 && std::fabs(e[m]) > eps * tst1) ++m;
+        if (m > l) {
+            int iter = 0;
+            do {
+                if (++iter > 64) return fail(CS_ERR_UNSUPPORTED, "tridiagonal QL did not converge");
+                double g = d[l];
+                double p = (d[l + 1] - g) / (2.0 * e[l]);
+                double r = std::hypot(p, 1.0);
+                if (p < 0) r = -r;
+                d[l] = e[l] / (p + r);
+                d[l + 1] = e[l] * (p + r);
+                const double dl1 = d[l + 1];
+                double h = g - d[l];
+                for (int i = l + 2; i < n; ++i) d[i] -= h;
+                f += h;
+                p = d[m];
+                double c = 1.0, c2 = c, c3 = c, s = 0.0, s2 = 0.0;
+                const double el1 = e[l + 1];
+                for (int i = m - 1; i >= l; --i) {
+                    c3 = c2; c2 = c; s2 = s;
+                    g = c * e[i]; h = c * p;
+                    r = std::hypot(p, e[i]);
+                    e[i + 1] = s * r;
+                    s = e[i] / r; c = p / r;
+                    p = c * d[i] - s * g;
+                    d[i + 1] = h + s * (c * g + s * d[i]);
+                    if (vectors)
+                        for (int k = 0; k < n; ++k) {
+                            h = A(k, i + 1);
+                            A(k, i + 1) = s * A(k, i) + c * h;
+                            A(k, i) = c * A(k, i) - s * h;
+                        }
+                }
+                p = -s * s2 * c3 * el1 * e[l] / dl1;
+                e[l] = s * p;
+                d[l] = c * p;
+            } while (std::fabs(e[l]) > eps * tst1);
+        }
+        d[l] += f;
+        e[l] = 0.0;
+    }
+    std::vector<int> idx(n);
+    for (int i = 0; i < n; ++i) idx[i] = i;
+    std::stable_sort(idx.begin(), idx.end(), [&](int x, int y) { return d[x] < d[y]; });
+    for (int j = 0; j < n; ++j) {
+        w[j] = d[idx[j]];
+        if (vectors)
+            for (int k = 0; k < n; ++k) vout[(size_t)k * n + j] = A(k, idx[j]);
+    }
+    return CS_OK;
+}
+
+// Cholesky G = R^T R of the active L x L block of a Gram matrix, column by column; a deficient column (see CHOL_*)
+// gets the unit row and column in R and is flagged.  t = R^-1 ([Lp][Lp], zero outside the block, zero in the
+// flagged columns: those are replaced by fresh random vectors).  Returns the number of flagged columns.
+int chol_inverse(const double* g, int L, int Lp, double* t, int* fresh)
+{
+    std::vector<double> R((size_t)L * L, 0.0);
+    double gmax = 0.0;
+    for (int j = 0; j < L; ++j) gmax = std::max(gmax, g[(size_t)j * Lp + j]);
+    int nd = 0;
+    for (int j = 0; j < L; ++j) {
+        fresh[j] = 0;
+        double d = g[(size_t)j * Lp + j];
+        const double gjj = d;
+        for (int i = 0; i < j; ++i) {
+            if (fresh[i]) continue;
+            double s = g[(size_t)i * Lp + j];
+            for (int p = 0; p < i; ++p) s -= R[(size_t)p * L + i] * R[(size_t)p * L + j];
+            R[(size_t)i * L + j] = s / R[(size_t)i * L + i];
+            d -= R[(size_t)i * L + j] * R[(size_t)i * L + j];
+        }
+        if (!(gjj > CHOL_ABS * gmax) || !(d > CHOL_REL * gjj)) {
+            fresh[j] = 1;
+            ++nd;
+            for (int i = 0; i < j; ++i) R[(size_t)i * L + j] = 0.0;
+            R[(size_t)j * L + j] = 1.0;
+        } else {
+            R[(size_t)j * L + j] = std::sqrt(d);
+        }
+    }
+    std::fill(t, t + (size_t)Lp * Lp, 0.0);
+    for (int j = 0; j < L; ++j) {                       // column j of R^-1 by back substitution
+        if (fresh[j]) continue;
+        t[(size_t)j * Lp + j] = 1.0 / R[(size_t)j * L + j];
+        for (int i = j - 1; i >= 0; --i) {
+            double s = 0.0;
+            for (int p = i + 1; p <= j; ++p) s += R[(size_t)i * L + p] * t[(size_t)p * Lp + j];
+            t[(size_t)i * Lp + j] = -s / R[(size_t)i * L + i];
+        }
+    }
+    for (int j = L; j < Lp; ++j) fresh[j] = 0;
+    return nd;
+}
+
+// rows per slice of a split over K rows: enough workgroups to fill the device, slices of at least 256 rows
+long slice_rows(long tiles, long K)
+{
+    long ks = std::max(1L, std::min(64L, 2048 / std::max(1L, tiles)));
+    ks = std::min(ks, std::max(1L, K / 256));
+    return (K + ks - 1) / ks;
+}
+
+struct Sub {
+    cs_fit* f;
+    long n;
+    int F, L, Lp;
+    const float* xs;                 // [n][F] centred
+    const float* xT;                 // [F][n]
+    double *Y, *Q, *Z, *part, *gram, *t;
+    int* fresh;
+
+    template <class TA>
+    int atb(const TA* A, long lda, int ma, const double* B, long K, double* out)
+    {
+        const long tiles = (long)((ma + SUB_TILE - 1) / SUB_TILE) * (Lp / SUB_TILE);
+        const long rows = slice_rows(tiles, K);
+        const int slices = (int)((K + rows - 1) / rows);
+        hipLaunchKernelGGL(atb_kernel<TA>, dim3((unsigned)((ma + SUB_TILE - 1) / SUB_TILE), (unsigned)(Lp / SUB_TILE), (unsigned)slices),
+                           dim3(256), 0, f->stream, A, lda, ma, B, Lp, K, rows, part);
+        HIPCHK(hipGetLastError());
+        const long total = (long)ma * Lp;
+        hipLaunchKernelGGL(subspace_merge_kernel, dim3((unsigned)std::min<long>((total + 255) / 256, 256L * 64)), dim3(256), 0, f->stream,
+                           part, total, slices, out);
+        HIPCHK(hipGetLastError());
+        return CS_OK;
+    }
+    // host copy of the Gram matrix M^T M of a [rows][Lp] fp64 block
+    int gram_of(const double* M, long rows, std::vector<double>& g)
+    {
+        int rc = atb<double>(M, Lp, Lp, M, rows, gram);
+        if (rc) return rc;
+        g.resize((size_t)Lp * Lp);
+        HIPCHK(hipMemcpyAsync(g.data(), gram, g.size() * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+        HIPCHK(hipStreamSynchronize(f->stream));
+        return CS_OK;
+    }
+    int small_mm(const double* z, long rows, const std::vector<double>& th, const std::vector<int>& fh, unsigned long long seed,
+                 unsigned salt, double* out)
+    {
+        HIPCHK(hipMemcpyAsync(t, th.data(), th.size() * sizeof(double), hipMemcpyHostToDevice, f->stream));
+        HIPCHK(hipMemcpyAsync(fresh, fh.data(), fh.size() * sizeof(int), hipMemcpyHostToDevice, f->stream));
+        const int per = 256 / Lp;
+        hipLaunchKernelGGL(small_mm_kernel, dim3((unsigned)((rows + per - 1) / per)), dim3(256), 0, f->stream, z, rows, Lp, t, fresh, seed,
+                           salt, 1.0 / std::sqrt((double)rows), out);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(f->stream));           // th / fh are host memory the caller reuses
+        return CS_OK;
+    }
+    // Q = orth(src) by CholeskyQR2: Gram on the device, L x L Cholesky here, Q = src R^-1 on the device; a third or
+    // fourth pass only when the second still met a deficient column.  src is overwritten.
+    int orth(double* src, unsigned long long seed, unsigned salt)
+    {
+        std::vector<double> g, th((size_t)Lp * Lp);
+        std::vector<int> fh(Lp);
+        double* a = src;
+        double* b = Q;
+        for (int pass = 0; pass < 4; ++pass) {
+            int rc = gram_of(a, F, g);
+            if (rc) return rc;
+            const int nd = chol_inverse(g.data(), L, Lp, th.data(), fh.data());
+            if ((rc = small_mm(a, F, th, fh, seed, salt * 4 + pass, b))) return rc;
+            std::swap(a, b);
+            if (pass >= 1 && nd == 0) break;
+        }
+        if (a != Q) HIPCHK(hipMemcpyAsync(Q, a, (size_t)F * Lp * sizeof(double), hipMemcpyDeviceToDevice, f->stream));
+        return CS_OK;
+    }
+};
+
+}  // namespace
+
+int cs_fit_pca_subspace(cs_fit* f, const float* features, int64_t n, int32_t n_features, int kind, const float* center,
+                        const double* scale, int32_t n_components, uint64_t seed, float* mean, double* components,
+                        double* explained_variance, double* total_variance, int32_t* n_iter)
+{
+    int rc = check_features(f, features, n, n_features, kind);
+    if (rc) return rc;
+    if (!center || !scale || !mean || !components || !explained_variance || !total_variance) return fail(CS_ERR_INVALID, "NULL argument");
+    const int F = n_features, k = n_components;
+    const long kmax = std::min<long>(std::min<long>(128, F), (long)n - 1);
+    if (k < 1 || k > kmax) return fail(CS_ERR_INVALID, "n_components=%d: need 1 .. min(128, n_features, n - 1) = %ld", k, kmax);
+    HIPCHK(hipSetDevice(f->device));
+    const float* d_feat;
+    if ((rc = stage_features(f, features, n, F, kind, &d_feat))) return rc;
+    Sub s{};
+    s.f = f; s.n = (long)n; s.F = F;
+    s.Lp = k + 10 <= SUB_TILE ? SUB_TILE : 2 * SUB_TILE;                        // block of L >= k + 10 columns, clamped below
+    s.L = (int)std::min<long>(std::min<long>(s.Lp, F), (long)n - 1);
+    const int L = s.L, Lp = s.Lp;
+    const size_t NF = (size_t)n * F;
+    size_t part_elems = 0;
+    for (long ma : {(long)n, (long)F, (long)Lp}) {
+        const long tiles = (ma + SUB_TILE - 1) / SUB_TILE * (Lp / SUB_TILE);
+        for (long K : {(long)n, (long)F}) {
+            const long rows = slice_rows(tiles, K);
+            part_elems = std::max(part_elems, (size_t)((K + rows - 1) / rows) * ma * Lp);
+        }
+    }
+    if ((rc = f->cen.ensure(sizeof(float) * F)) || (rc = f->scl.ensure(sizeof(double) * F)) || (rc = f->mean.ensure(sizeof(float) * F)) ||
+        (rc = f->xs.ensure(NF * sizeof(float))) || (rc = f->sxT.ensure(NF * sizeof(float))) ||
+        (rc = f->sY.ensure((size_t)n * Lp * sizeof(double))) || (rc = f->sQ.ensure((size_t)F * Lp * sizeof(double))) ||
+        (rc = f->sZ.ensure((size_t)F * Lp * sizeof(double))) || (rc = f->part.ensure(part_elems * sizeof(double))) ||
+        (rc = f->sgram.ensure((size_t)Lp * Lp * sizeof(double))) || (rc = f->st.ensure((size_t)Lp * Lp * sizeof(double))) ||
+        (rc = f->sfresh.ensure((size_t)Lp * sizeof(int))) || (rc = f->ssq.ensure((size_t)F * sizeof(double))))
+        return rc;
+    s.xs = f->xs.as<float>(); s.xT = f->sxT.as<float>();
+    s.Y = f->sY.as<double>(); s.Q = f->sQ.as<double>(); s.Z = f->sZ.as<double>(); s.part = f->part.as<double>();
+    s.gram = f->sgram.as<double>(); s.t = f->st.as<double>(); s.fresh = f->sfresh.as<int>();
+    HIPCHK(hipMemcpyAsync(f->cen.p, center, sizeof(float) * F, hipMemcpyHostToDevice, f->stream));
+    HIPCHK(hipMemcpyAsync(f->scl.p, scale, sizeof(double) * F, hipMemcpyHostToDevice, f->stream));
+    Timer tm(f);
+    // Xc exactly as cs_fit_pca_moments leaves it (and PCA.fit centres it): scaled, mean_ in float32, centred in float32
+    const long total = (long)n * F;
+    const unsigned eg = (unsigned)std::min<long>((total + 255) / 256, 256L * 64);
+    hipLaunchKernelGGL(scale_kernel, dim3(eg), dim3(256), 0, f->stream, d_feat, f->cen.as<float>(), f->scl.as<double>(), total, F,
+                       f->xs.as<float>());
+    hipLaunchKernelGGL(column_mean_kernel, dim3((unsigned)((F + 63) / 64)), dim3(64), 0, f->stream, f->xs.as<float>(), (long)n, F,
+                       f->mean.as<float>());
+    hipLaunchKernelGGL(center_kernel, dim3(eg), dim3(256), 0, f->stream, f->xs.as<float>(), f->mean.as<float>(), total, F);
+    hipLaunchKernelGGL(column_sumsq_kernel, dim3((unsigned)((F + 63) / 64)), dim3(64), 0, f->stream, s.xs, (long)n, F, f->ssq.as<double>());
+    hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)((n + 31) / 32), (unsigned)((F + 31) / 32)), dim3(256), 0, f->stream, s.xs, (long)n,
+                       F, f->sxT.as<float>());
+    HIPCHK(hipGetLastError());
+    std::vector<double> ssq((size_t)F);
+    HIPCHK(hipMemcpyAsync(mean, f->mean.p, sizeof(float) * F, hipMemcpyDeviceToHost, f->stream));
+    HIPCHK(hipMemcpyAsync(ssq.data(), f->ssq.p, sizeof(double) * F, hipMemcpyDeviceToHost, f->stream));
+
+    // the start: a seeded Gaussian F x L block, orthonormalised
+    {
+        std::vector<double> t0((size_t)Lp * Lp, 0.0);
+        std::vector<int> f0(Lp, 0);
+        for (int j = 0; j < L; ++j) f0[j] = 1;
+        if ((rc = s.small_mm(nullptr, F, t0, f0, seed, 0u, s.Z))) return rc;
+        if ((rc = s.orth(s.Z, seed, 1u))) return rc;
+    }
+    // scikit-learn's 'auto' power-iteration count is the floor (extmath.randomized_svd: 7 when k < 0.1 min(n, F), else 4)
+    const int min_iter = k < 0.1 * (double)std::min<long>((long)n, (long)F) ? 7 : 4;
+    std::vector<double> h, wv((size_t)L), prev((size_t)L, 0.0), hl((size_t)L * L);
+    int it = 0;
+    for (;; ++it) {
+        if ((rc = s.atb<float>(s.xT, (long)n, (int)n, s.Q, (long)F, s.Y))) return rc;             // Y = Xc Q
+        if ((rc = s.gram_of(s.Y, (long)n, h))) return rc;                                          // H = Y^T Y = Q^T S Q
+        for (int i = 0; i < L; ++i)
+            for (int j = 0; j < L; ++j) hl[(size_t)i * L + j] = h[(size_t)i * Lp + j];
+        if ((rc = sym_eig(L, hl.data(), wv.data(), nullptr, false))) return rc;
+        bool moved = it == 0;
+        const double top = std::fabs(wv[L - 1]);
+        for (int i = 0; i < k && !moved; ++i) {
+            const double cur = wv[L - 1 - i], old = prev[(size_t)(L - 1 - i)];
+            moved = std::fabs(cur - old) > SUB_RTOL * std::fabs(cur) + SUB_ATOL * top;
+        }
+        if ((it >= min_iter && !moved) || it >= SUB_MAX_ITER) break;
+        prev = wv;
+        if ((rc = s.atb<float>(s.xs, (long)F, F, s.Y, (long)n, s.Z))) return rc;                  // Z = Xc^T Y
+        if ((rc = s.orth(s.Z, seed, 2u + (unsigned)it))) return rc;                                // Q = orth(Z)
+    }
+    // Rayleigh-Ritz: the top k eigenvectors W of H; components = (Q W)^T, explained_variance = eigenvalue / (n - 1)
+    std::vector<double> vv((size_t)L * L);
+    if ((rc = sym_eig(L, hl.data(), wv.data(), vv.data(), true))) return rc;
+    std::vector<double> w((size_t)Lp * Lp, 0.0);
+    std::vector<int> none(Lp, 0);
+    for (int c = 0; c < k; ++c)
+        for (int i = 0; i < L; ++i) w[(size_t)i * Lp + c] = vv[(size_t)i * L + (L - 1 - c)];
+    if ((rc = s.small_mm(s.Q, F, w, none, seed, 0u, s.Z))) return rc;
+    std::vector<double> qw((size_t)F * Lp);
+    HIPCHK(hipMemcpyAsync(qw.data(), s.Z, qw.size() * sizeof(double), hipMemcpyDeviceToHost, f->stream));
+    if ((rc = tm.stop())) return rc;
+    const double dof = (double)std::max<int64_t>(n - 1, 1);
+    for (int c = 0; c < k; ++c) {
+        double* row = components + (size_t)c * F;
+        int arg = 0;
+        for (int j = 0; j < F; ++j) {
+            row[j] = qw[(size_t)j * Lp + c];
+            if (std::fabs(row[j]) > std::fabs(row[arg])) arg = j;
+        }
+        if (row[arg] < 0)                                                      // svd_flip(u_based_decision=False)
+            for (int j = 0; j < F; ++j) row[j] = -row[j];
+        explained_variance[c] = std::max(wv[L - 1 - c], 0.0) / dof;
+    }
+    double tv = 0.0;
+    for (int j = 0; j < F; ++j) tv += ssq[(size_t)j];
+    *total_variance = tv / dof;
+    if (n_iter) *n_iter = it;
     return CS_OK;
 }

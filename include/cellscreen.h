@@ -21,7 +21,7 @@
  *        stage-level taps used by the parity tests (oracle inputs to each stage)
  *   cs_preprocess
  *        equalize_adapthist + resize of each crop   improved_detection.py:98-99, CAE...:92-93
- *   cs_fit_scaler / cs_fit_pca_moments / cs_fit_project / cs_fit_ocsvm
+ *   cs_fit_scaler / cs_fit_pca_moments / cs_fit_pca_subspace / cs_fit_project / cs_fit_ocsvm
  *        RobustScaler / PCA / OneClassSVM fits of create_anomaly_detector
  *                                                 CAE_improved_modeltrain.py:408-427
  *   cs_synth_crops
@@ -284,7 +284,20 @@ int cs_preproc_last_timing(const cs_preproc *p, double *kernel_ms, int64_t *pixe
  *                       of the scaled features and the fp64 scatter matrix Xc^T Xc of the centred scaled features
  *                       ([F][F], host).  The principal axes are the leading eigenvectors of scatter / (n - 1); the
  *                       F x F eigenproblem is the host's (cellscreen/detector_fit.py uses LAPACK through numpy).
- *                       n_features must be a multiple of 128, at most 8192.
+ *                       n_features must be a multiple of 128, at most 8192; wider features: cs_fit_pca_subspace.
+ *   cs_fit_pca_subspace PCA(n_components).fit without anything F x F, for any n_features (1 .. 2^20): block subspace
+ *                       iteration on the centred scaled features Xc with a Rayleigh-Ritz step (the class of
+ *                       scikit-learn's randomized solver, which PCA(svd_solver='auto') picks for wide features).  A
+ *                       seeded Gaussian block of L = min(128 (256 when n_components > 118), n_features, n - 1) columns;
+ *                       per step Y = Xc Q, Z = Xc^T Y, Q = orth(Z) (CholeskyQR2, deficient columns replaced by fresh
+ *                       random ones), all fp64 on the device; the host sees L x L matrices only.  Stops when no top-k
+ *                       Ritz value of Q^T Xc^T Xc Q moves by more than 1e-5 relative, after at least scikit-learn's
+ *                       'auto' iteration count (7, or 4 when n_components >= 0.1 min(n, F)) and at most 100 steps.
+ *                       Outputs (host): mean [n_features] float32 (bit-identical to cs_fit_pca_moments'), components
+ *                       [n_components][n_features] fp64 (descending variance, largest-magnitude entry of each row
+ *                       positive), explained_variance [n_components], total_variance (sum of the column variances,
+ *                       ddof 1), n_iter (power steps taken; may be NULL).  n_components: 1 .. min(128, n_features,
+ *                       n - 1).  Same seed, same input: bit-identical results.
  *   cs_fit_project      scaler.transform + pca.transform of the training features with freshly fitted parameters
  *                       (the kernel cs_screen uses), out [n][n_components] fp32 on the host.
  *   cs_fit_ocsvm        OneClassSVM(kernel='rbf', nu).fit (:420-427): libsvm's SMO (second-order working-set selection,
@@ -300,6 +313,9 @@ int cs_fit_wait_stream(cs_fit *f, void *hip_stream);
 int cs_fit_scaler(cs_fit *f, const float *features, int64_t n, int32_t n_features, int kind, float *center, double *scale);
 int cs_fit_pca_moments(cs_fit *f, const float *features, int64_t n, int32_t n_features, int kind, const float *center,
                        const double *scale, float *mean, double *scatter);
+int cs_fit_pca_subspace(cs_fit *f, const float *features, int64_t n, int32_t n_features, int kind, const float *center,
+                        const double *scale, int32_t n_components, uint64_t seed, float *mean, double *components,
+                        double *explained_variance, double *total_variance, int32_t *n_iter);
 int cs_fit_project(cs_fit *f, const float *features, int64_t n, int32_t n_features, int kind, const float *center,
                    const double *scale, const float *components, const float *mean_proj, int32_t n_components, float *out);
 int cs_fit_ocsvm(cs_fit *f, const double *x, int64_t n, int32_t n_components, double gamma, double nu, double eps,
