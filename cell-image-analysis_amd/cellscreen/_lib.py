@@ -91,6 +91,18 @@ class CSModelInfo(C.Structure):
                 ("precision", C.c_int32), ("debug_flags", C.c_uint32)]
 
 
+class CSQcParams(C.Structure):
+    _fields_ = [("border", C.c_int32), ("min_area", C.c_int32), ("max_area", C.c_int32), ("reserved", C.c_int32),
+                ("max_eccentricity", C.c_double), ("min_mean", C.c_double), ("min_std", C.c_double), ("clip_limit", C.c_double)]
+
+
+# cs_region of include/cellscreen.h as a numpy record (80 bytes)
+REGION_DTYPE = np.dtype([("image", np.int32), ("label", np.int32), ("minr", np.int32), ("minc", np.int32), ("maxr", np.int32),
+                         ("maxc", np.int32), ("area", np.int64), ("convex_area", np.int64), ("eccentricity", np.float64),
+                         ("solidity", np.float64), ("mean_intensity", np.float64), ("std_intensity", np.float64),
+                         ("failed", np.uint32), ("cell", np.int32)])
+
+
 # every exported symbol of include/cellscreen.h: (restype, argtypes)
 _P, _I, _L = C.c_void_p, C.c_int, C.c_int64
 SIGNATURES = {
@@ -116,6 +128,10 @@ SIGNATURES = {
     "cs_preproc_wait_stream": (_I, [_P, _P]),
     "cs_preprocess": (_I, [_P, _P, _I, _L, _I, _P, _P, _P, _L, C.c_double, _P, _P, _I]),
     "cs_preproc_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(_L)]),
+    "cs_extract_measure": (_I, [_P, _P, _I, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _I, C.c_int32,
+                                C.POINTER(CSQcParams), C.POINTER(_L), C.POINTER(_L)]),
+    "cs_extract_fill": (_I, [_P, _P, _P, _I, _P, _P, _I]),
+    "cs_extract_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "cs_fit_create": (_I, [_I, C.POINTER(_P)]),
     "cs_fit_free": (None, [_P]),
     "cs_fit_wait_stream": (_I, [_P, _P]),

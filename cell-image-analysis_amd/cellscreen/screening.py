@@ -2,8 +2,9 @@
 same class name, method names, argument meaning, result keys, skip rules and CSV schemas,
 with the arithmetic of compute_anomaly_scores executed by libcellscreen on the GPU.
 
-Out of scope here: StarDist cell extraction (:48-115) -- supply a
-`cell_extractor(image_path) -> (list_of_64x64_arrays, list_of_stat_dicts)` or pre-extracted
+Out of scope here: the StarDist segmentation itself (:44, :59-60) -- supply a
+`cell_extractor(image_path) -> (list_of_64x64_arrays, list_of_stat_dicts)`, e.g.
+cellscreen.extract.label_cell_extractor(segment), which runs the rest of :48-115 on the GPU, or pre-extracted
 `.npy` crop files; plots and the text report (:263-403)."""
 from __future__ import annotations
 

@@ -5,6 +5,8 @@ anywhere in the reference: its .gitignore:105-129 excludes them all).
   (csrc/detector.hip:hash24) and to oracle/cae_oracle.c:orc_hash24.
 * blob_crops: structured crops (1-3 Gaussian blobs + noise) for training runs, so the
   reconstruction loss means something.
+* label_images: segmented fluorescence images (3-channel stacks + int32 label images) that exercise every
+  rule of the quality-cell extraction (cellscreen/extract.py).
 * random_cae: Glorot-uniform kernels and zero biases (Keras Conv2D defaults) with
   non-trivial BatchNormalization statistics so BN is exercised.
 """
@@ -71,6 +73,74 @@ def raw_crops(seed: int, n: int, dtype=np.uint8, min_side: int = 8, max_side: in
             img = 0.5 + 0.01 * img
         out.append(np.round(np.clip(img, 0.0, 1.0) * top).astype(dtype))
     return out
+
+
+def label_images(seed: int, n: int, hw=(256, 256), n_cells: int = 24, dtype=np.uint16, channels: int = 3):
+    """n images [n,H,W,channels] (dtype) and their int32 labels [n,H,W], seeded.  Ellipses are painted in order, later
+    over earlier, so overlaps leave non-convex (and sometimes split) regions; label ids are distinct, shuffled and
+    non-consecutive.  Every image also holds: a cell on the border, a too small one, a too large one (if the image is big
+    enough), an elongated one, a dark one (analysis channel 0 over its bbox), a flat one (constant there) and one label
+    made of two separated blobs.  Channel 2 is the segmentation channel (bright cells), channel 1 the analysis channel;
+    with channels == 1 the single channel is both."""
+    rng = np.random.default_rng(seed)
+    H, W = hw
+    top = 255 if np.dtype(dtype) == np.uint8 else 65535
+    imgs = np.empty((n, H, W, channels), dtype)
+    labs = np.zeros((n, H, W), np.int32)
+    def window(cy, cx, rad):                               # the pixels an ellipse of radius <= rad can touch
+        r0, r1 = max(int(cy - rad) - 1, 0), min(int(cy + rad) + 2, H)
+        c0, c1 = max(int(cx - rad) - 1, 0), min(int(cx + rad) + 2, W)
+        yy, xx = np.mgrid[r0:r1, c0:c1]
+        return (slice(r0, r1), slice(c0, c1)), yy, xx
+
+    for b in range(n):
+        lab = labs[b]
+        ana = rng.uniform(0.02, 0.08, (H, W))
+        shapes = []                                        # (cy, cx, ry, rx, angle, kind)
+        m = max(12, min(H, W) // 12)
+        for _ in range(n_cells):
+            shapes.append((rng.uniform(m, H - m), rng.uniform(m, W - m), rng.uniform(8, 22), rng.uniform(8, 22),
+                           rng.uniform(0, np.pi), "cell"))
+        shapes.append((rng.uniform(2, 6), rng.uniform(m, W - m), 12, 12, 0.0, "border"))
+        shapes.append((rng.uniform(m, H - m), rng.uniform(m, W - m), 4, 5, 0.0, "small"))
+        if min(H, W) >= 200:
+            shapes.append((H / 2, W / 2, 58, 60, 0.3, "large"))
+        shapes.append((rng.uniform(40, H - 40), rng.uniform(40, W - 40), 28, 5, rng.uniform(0, np.pi), "elongated"))
+        shapes.append((rng.uniform(m + 10, H - m - 10), rng.uniform(m + 10, W - m - 10), 12, 11, 0.0, "dark"))
+        shapes.append((rng.uniform(m + 10, H - m - 10), rng.uniform(m + 10, W - m - 10), 11, 12, 0.0, "flat"))
+        order = rng.permutation(len(shapes))
+        ids = rng.choice(np.arange(1, 5 * (len(shapes) + 2)), size=len(shapes) + 1, replace=False).astype(np.int32)
+        rects = []
+        for k, si in enumerate(order):
+            cy, cx, ry, rx, ang, kind = shapes[si]
+            ca, sa = np.cos(ang), np.sin(ang)
+            win, yy, xx = window(cy, cx, max(ry, rx))
+            u = ((yy - cy) * ca + (xx - cx) * sa) / ry
+            v = (-(yy - cy) * sa + (xx - cx) * ca) / rx
+            mask = u * u + v * v <= 1.0
+            lab[win][mask] = ids[k]
+            ana[win][mask] = rng.uniform(0.3, 0.8) + 0.15 * np.exp(-((yy[mask] - cy) ** 2 + (xx[mask] - cx) ** 2) / (2 * (0.4 * ry) ** 2))
+            if kind in ("dark", "flat"):
+                rects.append((int(cy - ry - 2), int(cy + ry + 3), int(cx - rx - 2), int(cx + rx + 3), kind))
+        # one label made of two separated blobs (painted last: both pieces survive)
+        for cy, cx in ((rng.uniform(m, H / 2 - 10), rng.uniform(m, W / 2 - 10)), (rng.uniform(H / 2 + 10, H - m), rng.uniform(W / 2 + 10, W - m))):
+            win, yy, xx = window(cy, cx, 7.5)
+            mask = (yy - cy) ** 2 + (xx - cx) ** 2 <= 7.5 ** 2
+            lab[win][mask] = ids[-1]
+            ana[win][mask] = 0.6
+        ana += rng.normal(0.0, 0.02, (H, W))
+        for r0, r1, c0, c1, kind in rects:
+            ana[max(r0, 0):r1, max(c0, 0):c1] = 0.0 if kind == "dark" else 0.5
+        seg = np.where(lab > 0, 0.7, 0.05) + rng.normal(0.0, 0.02, (H, W))
+        a = np.round(np.clip(ana, 0.0, 1.0) * top).astype(dtype)
+        if channels == 1:
+            imgs[b, ..., 0] = a
+        else:
+            imgs[b] = np.round(np.clip(rng.uniform(0.0, 0.2, (H, W, 1)), 0, 1) * top).astype(dtype)
+            imgs[b, ..., 1] = a
+            if channels > 2:
+                imgs[b, ..., 2] = np.round(np.clip(seg, 0.0, 1.0) * top).astype(dtype)
+    return imgs, labs
 
 
 def random_cae(seed: int = 42, hw=spec.INPUT_HW, channels=spec.CHANNELS, n_enc=spec.N_ENC,

@@ -3,8 +3,8 @@ same class and method names, argument meaning, hyper-parameters, callback semant
 files, with the per-batch arithmetic (fit step, validation pass, reconstruction errors,
 encoder features, detector fit) executed by libcellscreen on the GPU.
 
-Out of scope: StarDist cell extraction / dataset assembly (:39-182), plots
-and text reports (:304-326, 345-392, 448-478).
+Out of scope: the StarDist segmentation itself (create_training_dataset takes a cell_extractor,
+e.g. cellscreen.extract.label_cell_extractor), plots and text reports (:153-182, 304-326, 345-392, 448-478).
 
 * Augmentation (:246-254): the default `augment="reference"` runs the reference's ImageDataGenerator
   settings on the GPU (cellscreen/augment.py + cs_train_augment) -- the reference always trains through
@@ -80,6 +80,42 @@ class ImprovedAnomalyDetectionTraining:
         self._best_autoencoder: Optional[CAEWeights] = None
 
     # ---- model -------------------------------------------------------------------------
+    # ---- training set from segmented images ---------------------------------------------------------------------------------
+    def create_training_dataset(self, folder_path: str, cell_extractor: Callable[[str], tuple], file_pattern: str = "*.tif"):
+        """:113-151 with the cell extraction of :39-111 supplied by the caller: `cell_extractor(image_path) -> (cells, stats)`,
+        e.g. cellscreen.extract.label_cell_extractor(segment) (quality rules + crop preprocess on the GPU; the segmenter is
+        the caller's, StarDist in the reference).  Writes cell_statistics.csv and file_summary.csv with the reference's
+        columns and pandas calls, returns (np.array(cells), stats_df).  The text report (:153-182) is out of scope."""
+        import pandas as pd
+        from glob import glob
+        print("=== Creating High-Quality Training Dataset ===")
+        file_paths = sorted(glob(os.path.join(folder_path, file_pattern)))               # :121
+        print(f"Found {len(file_paths)} image files")
+        all_cells, all_stats, file_summary = [], [], []
+        for i, file_path in enumerate(file_paths):
+            filename = os.path.basename(file_path)
+            print(f"Processing {i+1}/{len(file_paths)}: {filename}")
+            try:                                                                          # :104-107 (the extractor's own try)
+                cells, stats = cell_extractor(file_path)
+                stats = [dict(s, file=filename) for s in stats]                           # :101 'file'
+            except Exception as e:
+                print(f"Error processing {file_path}: {e}")
+                cells, stats = [], []
+            all_cells.extend(cells)
+            all_stats.extend(stats)
+            file_summary.append({                                                         # :137-141
+                "filename": filename,
+                "cells_extracted": len(cells),
+                "mean_cell_intensity": np.mean([s["mean_intensity"] for s in stats]) if stats else 0,
+            })
+            print(f"  Extracted {len(cells)} quality cells")
+        print(f"\nTotal quality cells extracted: {len(all_cells)}")
+        stats_df = pd.DataFrame(all_stats)                                                # :148-152
+        file_summary_df = pd.DataFrame(file_summary)
+        stats_df.to_csv(os.path.join(self.output_dir, "cell_statistics.csv"), index=False)
+        file_summary_df.to_csv(os.path.join(self.output_dir, "file_summary.csv"), index=False)
+        return np.array(all_cells), stats_df
+
     def create_improved_autoencoder(self, input_shape=(64, 64, 1)):
         """:184-229.  Returns (autoencoder, encoder) as the reference does: the initial weight set (Glorot-uniform
         kernels, zero biases, BN gamma 1 / beta 0 / moving mean 0 / moving var 1 -- the Keras defaults) and its encoder

@@ -66,8 +66,41 @@ inline int wait_on_stream(hipStream_t mine, void* other)
     return CS_OK;
 }
 
+// ---- crop preprocess (preprocess.hip), shared with the extraction front end (extract.hip) -------------------------------
+struct CropDesc {
+    long long off;      // element offset of the crop's first pixel in the ragged pixel buffer
+    int H, W;
+};
+// Enqueues the preprocess kernel on n crops whose descriptors are already in device (or mapped) memory; lds = the dynamic LDS
+// bytes the largest crop needs (preprocess_lds_bytes).  The arithmetic is cs_preprocess's, so the cells are bit-identical.
+hipError_t launch_preprocess(const void* pix, int pixel_type, const CropDesc* desc, int64_t n, double clip_limit, size_t lds,
+                             uint16_t* clahe, float* out, hipStream_t stream);
+struct ExtractState;                            // extract.hip: the state between cs_extract_measure and cs_extract_fill
+void extract_state_free(ExtractState* s);
+
 int upload(DevBuf& d, const void* src, size_t bytes);
 int check_arch(const cs_cae_weights* w, int expect_convs, const char* what);
 int require_gfx950(int device_id);
 
 }  // namespace cs
+
+// The preprocess handle (include/cellscreen.h); its extraction entry points live in extract.hip.
+struct cs_preproc {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    cs::DevBuf pix, clahe, out;
+    // crop descriptors: pinned host memory the kernel reads directly (24 B per crop).  A host-to-device COPY of them would
+    // queue on the DMA engine behind whatever the caller has in flight there -- e.g. the raw pixels of the NEXT chunk it is
+    // uploading while this one computes -- and the kernel would start only when that upload has finished.
+    void* hdesc = nullptr;
+    const void* ddesc = nullptr;        // the same memory as the device sees it
+    double last_kernel_ms = 0.0;
+    int64_t last_pixels = 0;
+    cs::ExtractState* ext = nullptr;    // created by the first cs_extract_measure
+    ~cs_preproc()
+    {
+        cs::extract_state_free(ext);
+        if (hdesc) (void)hipHostFree(hdesc);
+    }
+};

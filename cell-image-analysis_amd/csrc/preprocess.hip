@@ -25,11 +25,6 @@
 
 namespace cs {
 
-struct CropDesc {
-    long long off;      // element offset of the crop's first pixel in the ragged pixel buffer
-    int H, W;
-};
-
 static constexpr int PP_THREADS = 512;
 static constexpr int PP_WAVES = PP_THREADS / 64;
 static constexpr int PP_NBINS = 256;
@@ -404,25 +399,29 @@ __global__ __launch_bounds__(PP_THREADS) void preprocess_kernel(const PIX* __res
     }
 }
 
+hipError_t launch_preprocess(const void* pix, int pixel_type, const CropDesc* desc, int64_t n, double clip_limit, size_t lds,
+                             uint16_t* clahe, float* out, hipStream_t stream)
+{
+    if (n <= 0) return hipSuccess;
+    hipError_t e;
+    if (pixel_type == CS_PIX_U8) {
+        e = hipFuncSetAttribute((const void*)preprocess_kernel<unsigned char>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(preprocess_kernel<unsigned char>, dim3((unsigned)n), dim3(PP_THREADS), lds, stream,
+                           (const unsigned char*)pix, desc, clip_limit, (unsigned short*)clahe, out);
+    } else {
+        e = hipFuncSetAttribute((const void*)preprocess_kernel<unsigned short>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(preprocess_kernel<unsigned short>, dim3((unsigned)n), dim3(PP_THREADS), lds, stream,
+                           (const unsigned short*)pix, desc, clip_limit, (unsigned short*)clahe, out);
+    }
+    return hipGetLastError();
+}
+
 }  // namespace cs
 
 // ---- C ABI ----------------------------------------------------------------------------------
 using namespace cs;
-
-struct cs_preproc {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    DevBuf pix, clahe, out;
-    // crop descriptors: pinned host memory the kernel reads directly (24 B per crop).  A host-to-device COPY of them would
-    // queue on the DMA engine behind whatever the caller has in flight there -- e.g. the raw pixels of the NEXT chunk it is
-    // uploading while this one computes -- and the kernel would start only when that upload has finished.
-    void* hdesc = nullptr;
-    const void* ddesc = nullptr;        // the same memory as the device sees it
-    double last_kernel_ms = 0.0;
-    int64_t last_pixels = 0;
-    ~cs_preproc() { if (hdesc) (void)hipHostFree(hdesc); }
-};
 
 static const int64_t kChunkPixels = 256ll << 20;        // pixel span of one launch (staging + uint16 plane)
 static const int64_t kChunkCrops = 1 << 16;

@@ -21,6 +21,11 @@
  *        stage-level taps used by the parity tests (oracle inputs to each stage)
  *   cs_preprocess
  *        equalize_adapthist + resize of each crop   improved_detection.py:98-99, CAE...:92-93
+ *   cs_extract_measure / cs_extract_fill
+ *        the quality-cell extraction that follows segmentation: regionprops + the border / area /
+ *        eccentricity / intensity rules + the bbox crop + the preprocess above
+ *                                   improved_detection.py:61-111, CAE_improved_modeltrain.py:54-107
+ *        (the StarDist segmentation itself, :59-60 / :52-53, stays with the caller)
  *   cs_fit_scaler / cs_fit_pca_moments / cs_fit_pca_subspace / cs_fit_project / cs_fit_ocsvm
  *        RobustScaler / PCA / OneClassSVM fits of create_anomaly_detector
  *                                                 CAE_improved_modeltrain.py:408-427
@@ -273,6 +278,81 @@ int cs_preprocess(cs_preproc *p, const void *pixels, int pixel_type, int64_t n_p
 /* Device time (HIP events on the handle's stream around the kernel launches) and the pixel count
  * of the last cs_preprocess call. */
 int cs_preproc_last_timing(const cs_preproc *p, double *kernel_ms, int64_t *pixels);
+
+/* ---- quality-cell extraction from label images (improved_detection.py:61-111) ---------------
+ * Input: B images of one shape H x W -- the analysis channel (uint8 / uint16) read in place from a
+ * [B][H][W][channels] stack at `channel`, and int32 labels [B][H][W] from any segmenter (0 =
+ * background).  Every label value > 0 present in an image is one region, connected or not, in
+ * ascending label order per image (regionprops' order).  Per region, as the reference applies them:
+ *   border        minr < border or minc < border or maxr > H-border or maxc > W-border (max exclusive)
+ *   area          pixel count < min_area or > max_area
+ *   eccentricity  > max_eccentricity; scikit-image 0.18.3's definition (inertia tensor of the central
+ *                 moments, eigenvalues clipped at 0, sqrt(1 - l2/l1), 0 when l1 == 0) from exact int64
+ *                 moment sums
+ *   intensity     mean < min_mean or std < min_std, over the whole bbox rectangle of the analysis
+ *                 channel (not masked: green_channel[minr:maxr, minc:maxc]), population std
+ * and solidity = area / convex_area (reported, not filtered on): convex_area counts the bbox pixel
+ * centres inside or on the convex hull of the region's pixel-edge midpoints (convex_hull_image with
+ * offset_coordinates=True + grid_points_in_poly), exactly, in integer arithmetic.  Each passing
+ * region's bbox crop goes through the cs_preprocess kernel on the device; the cells are bit-identical
+ * to cs_preprocess on the same crops cut on the host.
+ * Whole-image rules (status per image): a passing region with a bbox side < 8 makes skimage raise inside
+ * the reference's per-file try (improved_detection.py:113-115), so the image yields no cells
+ * (CS_IMAGE_NO_CELLS); a passing side > 1024 is beyond cs_preprocess (CS_IMAGE_UNSUPPORTED, no cells).
+ * Two calls per batch: cs_extract_measure runs the label pass, the per-region pass and the compaction
+ * scan and returns the counts (one host synchronisation); cs_extract_fill writes the region table and
+ * the cells (one more).  Between the two, CS_MEM_DEVICE inputs must stay valid and unchanged (the fill
+ * reads the analysis channel again). */
+typedef struct cs_qc_params {
+    int32_t border;                   /* 10 */
+    int32_t min_area, max_area;       /* 200, 8000 */
+    int32_t reserved;                 /* must be 0 */
+    double max_eccentricity;          /* 0.95 */
+    double min_mean, min_std;         /* 0.5, 0.1 */
+    double clip_limit;                /* 0.02: equalize_adapthist of the cells */
+} cs_qc_params;
+
+#define CS_QC_BORDER       0x1u       /* failed-rule bits of cs_region.failed */
+#define CS_QC_AREA         0x2u
+#define CS_QC_ECCENTRICITY 0x4u
+#define CS_QC_INTENSITY    0x8u
+
+#define CS_IMAGE_OK          0        /* per-image status of cs_extract_fill */
+#define CS_IMAGE_NO_CELLS    1        /* a passing region has a bbox side < 8: the reference's extraction raises */
+#define CS_IMAGE_UNSUPPORTED 2        /* a passing region has a bbox side > 1024 */
+
+/* One record per region, passing or not, in (image, label) order. */
+typedef struct cs_region {
+    int32_t image, label;
+    int32_t minr, minc, maxr, maxc;   /* regionprops bbox, max exclusive */
+    int64_t area, convex_area;
+    double eccentricity, solidity;
+    double mean_intensity, std_intensity;
+    uint32_t failed;                  /* CS_QC_* bits of every rule the region fails; 0 = passes */
+    int32_t cell;                     /* index of its cell in the output, -1 if none */
+} cs_region;
+
+/* image:  [batch][height][width][channels] uint8 / uint16 (pixel_type); the analysis channel is `channel`.
+ * labels: [batch][height][width] int32.  Both in_kind.  Negative labels, or labels above max_label:
+ *         CS_ERR_INVALID (detected on the device, reported by this call).
+ * max_label: an upper bound of the batch's labels; it sizes the per-label tables.  Above 2^20, or
+ *         batch * max_label above 2^22: CS_ERR_UNSUPPORTED (relabel sparse ids first: the order of the
+ *         labels, and so every result, is kept by an order-preserving relabel).
+ * height, width: 1..4096.  qc: NULL = the reference's values.
+ * n_regions, n_cells: out, the sizes cs_extract_fill writes.  Without a gfx950 device (p == NULL because
+ * cs_preproc_create failed): CS_ERR_NO_DEVICE. */
+int cs_extract_measure(cs_preproc *p, const void *image, int pixel_type, int32_t channels, int32_t channel,
+                       const int32_t *labels, int32_t batch, int32_t height, int32_t width, int in_kind,
+                       int32_t max_label, const cs_qc_params *qc, int64_t *n_regions, int64_t *n_cells);
+/* After cs_extract_measure on the same handle.  Each output may be NULL.
+ *   regions      [n_regions] cs_region                         (table_kind)
+ *   image_status [batch] int32 CS_IMAGE_*                      (table_kind)
+ *   cells        [n_cells][64][64] float32, in region order    (cells_kind)
+ *   cell_image   [n_cells] int32: the image index of each cell (cells_kind) */
+int cs_extract_fill(cs_preproc *p, cs_region *regions, int32_t *image_status, int table_kind, float *cells, int32_t *cell_image,
+                    int cells_kind);
+/* Device time of the last measure + fill: label pass, per-region pass (with the scan), gather + preprocess. */
+int cs_extract_last_timing(const cs_preproc *p, double *label_ms, double *region_ms, double *cells_ms);
 
 /* ---- detector fitting (create_anomaly_detector, CAE_improved_modeltrain.py:394-446) -------- */
 /* The fit of what cs_screen's tail evaluates, for the training set's encoder features

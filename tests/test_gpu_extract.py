@@ -1,0 +1,234 @@
+"""Quality-cell extraction from label images on the device (csrc/extract.hip + the preprocess kernel, through
+cellscreen.extract) against the CPU restatement of tests/extract_reference.py, on synth.label_images batches.
+
+Region set, order, bbox, area, convex area, failed-rule bits, pass set and image status: exact.  mean_intensity and
+solidity are quotients of exact integers: bit-exact.  eccentricity and std_intensity: the restatement spells out the same
+float operations, so they are bit-exact too; the stated bound is 1e-12 relative.  Cells: bit-identical to Preprocessor
+on the crops cut on the host (the preprocess golden pins that path to scikit-image 0.18.3)."""
+import numpy as np
+import pytest
+
+import extract_reference as R
+from cellscreen import extract as X
+from cellscreen import preprocess as pp
+from cellscreen import synth
+
+pytestmark = pytest.mark.gpu
+
+FIELDS_EXACT = ("label", "minr", "minc", "maxr", "maxc", "area", "convex_area", "failed")
+
+
+@pytest.fixture(scope="module")
+def ext():
+    e = X.CellExtractor(0)
+    yield e
+    e.close()
+
+
+@pytest.fixture(scope="module")
+def proc():
+    p = pp.Preprocessor(0)
+    yield p
+    p.close()
+
+
+def _ana(images, channel):
+    return images if images.ndim == 3 else images[..., channel]
+
+
+def check_against_restatement(r, images, labels, proc, channel=None, qc=None):
+    B = labels.shape[0]
+    ch = channel if channel is not None else (0 if images.ndim == 3 or images.shape[3] == 1 else 1)
+    ana = _ana(images, ch)
+    crops, n_cells = [], 0
+    reg = r.regions
+    assert np.all(np.diff(reg["image"]) >= 0)
+    for b in range(B):
+        c, regs, st = R.extract(labels[b], ana[b], qc)
+        assert r.status[b] == st, (b, r.status[b], st)
+        got = reg[reg["image"] == b]
+        assert len(got) == len(regs), (b, len(got), len(regs))
+        for g, e in zip(got, regs):
+            for f in FIELDS_EXACT:
+                assert int(g[f]) == e[f], (b, e["label"], f, g[f], e[f])
+            assert g["mean_intensity"] == e["mean_intensity"] and g["solidity"] == e["solidity"], (b, e["label"])
+            for f in ("eccentricity", "std_intensity"):
+                assert abs(g[f] - e[f]) <= 1e-12 * max(abs(e[f]), 1e-300), (b, e["label"], f, g[f], e[f])
+            passing = st == R.IMAGE_OK and e["failed"] == 0
+            assert (g["cell"] >= 0) == passing
+            if passing:
+                assert g["cell"] == n_cells
+                n_cells += 1
+        crops += c
+    assert len(r.cells) == n_cells == len(r.cell_image)
+    assert np.array_equal(r.cell_image, reg["image"][reg["cell"] >= 0])
+    if n_cells:
+        ref = proc(crops, clip_limit=(qc or {}).get("clip_limit", pp.CLIP_LIMIT))
+        cells = r.cells if isinstance(r.cells, np.ndarray) else r.cells.cpu().numpy()
+        assert np.array_equal(cells.view(np.uint32), ref.view(np.uint32))
+    return n_cells
+
+
+@pytest.mark.parametrize("dtype,channels,hw", [(np.uint16, 3, (256, 256)), (np.uint8, 3, (192, 224)), (np.uint8, 1, (160, 200)),
+                                               (np.uint16, 1, (250, 203))])
+def test_batch_matches_restatement(ext, proc, dtype, channels, hw):
+    imgs, labs = synth.label_images(11, 3, hw=hw, dtype=dtype, channels=channels)
+    if channels == 1:
+        imgs = np.ascontiguousarray(imgs[..., 0])                   # 2-D images
+    r = ext.extract_batch(imgs, labs)
+    assert check_against_restatement(r, imgs, labs, proc) > 0
+    assert set(np.unique(r.regions["failed"])) >= {0, X.QC_BORDER, X.QC_AREA, X.QC_ECCENTRICITY, X.QC_INTENSITY}
+
+
+def test_batch_equals_single_images_and_is_deterministic(ext):
+    imgs, labs = synth.label_images(12, 4)
+    r = ext.extract_batch(imgs, labs)
+    r2 = ext.extract_batch(imgs, labs)
+    assert np.array_equal(r.cells, r2.cells) and np.array_equal(r.regions, r2.regions) and np.array_equal(r.status, r2.status)
+    cells, regs = [], []
+    for b in range(4):
+        s = ext.extract_batch(imgs[b:b + 1], labs[b:b + 1])
+        rg = s.regions.copy()
+        rg["image"] = b
+        rg["cell"][rg["cell"] >= 0] += sum(len(c) for c in cells)
+        cells.append(s.cells)
+        regs.append(rg)
+    assert np.array_equal(np.concatenate(cells).view(np.uint32), r.cells.view(np.uint32))
+    assert np.array_equal(np.concatenate(regs), r.regions)
+
+
+def test_single_image_api_returns_reference_stats(ext, proc):
+    imgs, labs = synth.label_images(13, 1)
+    cells, stats = ext.extract(imgs[0], labs[0])
+    crops, regs, st = R.extract(labs[0], imgs[0, ..., 1])
+    assert st == R.IMAGE_OK and len(stats) == len(crops) == len(cells)
+    exp = R.stats(regs)
+    for g, e in zip(stats, exp):
+        assert tuple(g) == X.STAT_KEYS and isinstance(g["area"], int) and g["area"] == e["area"]
+        assert g["mean_intensity"] == e["mean_intensity"] and g["solidity"] == e["solidity"]
+    assert np.array_equal(cells, proc(crops))
+
+
+def test_narrow_passing_region_gives_no_cells():
+    """A passing region with a bbox side < 8: skimage raises inside the reference's per-file try, the image yields nothing.
+    With the reference's thresholds that is unreachable (area >= 200 at eccentricity <= 0.95 needs sides >= 8)."""
+    H, W = 96, 96
+    lab = np.zeros((1, H, W), np.int32)
+    lab[0, 20:60, 30:36] = 3                                      # 40 x 6: area 240
+    lab[0, 20:50, 50:80] = 5                                      # a normal cell beside it
+    rng = np.random.default_rng(1)
+    img = rng.integers(100, 4000, (1, H, W), dtype=np.uint16)
+    qc = dict(min_area=10, max_eccentricity=1.0)
+    e = X.CellExtractor(0, **qc)
+    r = e.extract_batch(img, lab)
+    assert r.status[0] == X.IMAGE_NO_CELLS and len(r.cells) == 0 and np.all(r.regions["cell"] == -1)
+    regs = R.regions(lab[0], img[0], qc)
+    assert R.image_status(regs) == R.IMAGE_NO_CELLS and [g["failed"] for g in regs] == [0, 0]
+    with pytest.raises(ValueError):
+        e.extract(img[0], lab[0])
+    e.close()
+
+
+def test_far_apart_blobs_wider_than_1024_are_unsupported(ext, proc):
+    H = W = 1200
+    lab = np.zeros((1, H, W), np.int32)
+    for r0, c0 in ((20, 20), (20, 1160), (1160, 20), (1160, 1160)):
+        lab[0, r0:r0 + 8, c0:c0 + 8] = 7                          # area 256, eccentricity ~0, bbox 1148 x 1148
+    lab[0, 500:530, 600:640] = 9
+    rng = np.random.default_rng(2)
+    img = rng.integers(0, 60000, (1, H, W, 3), dtype=np.uint16)
+    r = ext.extract_batch(img, lab)
+    assert r.status[0] == X.IMAGE_UNSUPPORTED and len(r.cells) == 0
+    assert list(r.regions["label"]) == [7, 9] and list(r.regions["failed"]) == [0, 0]
+    check_against_restatement(r, img, lab, proc)
+
+
+def test_sparse_labels_equal_relabelled(ext):
+    imgs, labs = synth.label_images(14, 2)
+    ids = np.unique(labs)
+    big = np.zeros(ids.max() + 1, np.int64)
+    big[ids[1:]] = (1 << 30) - 4000 + 7 * ids[1:]                # order-preserving, far above the table cap
+    sparse = big[labs].astype(np.int32)
+    r0 = ext.extract_batch(imgs, labs)
+    r1 = ext.extract_batch(imgs, sparse)
+    assert np.array_equal(r0.cells, r1.cells) and np.array_equal(r0.status, r1.status)
+    assert np.array_equal(r1.regions["label"], big[r0.regions["label"]])
+    a, b = r0.regions.copy(), r1.regions.copy()
+    a["label"] = 0
+    b["label"] = 0
+    assert np.array_equal(a, b)
+
+
+def test_device_tensors_in_and_out(ext):
+    import torch
+    imgs, labs = synth.label_images(15, 2)
+    r0 = ext.extract_batch(imgs, labs)
+    dev = torch.device("cuda", 0)
+    ti = torch.from_numpy(imgs.view(np.int16)).to(dev)
+    tl = torch.from_numpy(labs).to(dev)
+    r1 = ext.extract_batch(ti, tl)
+    assert r1.cells.is_cuda and np.array_equal(r1.cells.cpu().numpy(), r0.cells)
+    assert np.array_equal(r1.regions, r0.regions) and np.array_equal(r1.cell_image, r0.cell_image)
+    out = torch.full((len(r0.cells) + 3, 64, 64), -1.0, device=dev)
+    r2 = ext.extract_batch(ti, tl, out=out)
+    assert torch.equal(out[:len(r0.cells)], r1.cells) and bool((out[len(r0.cells):] == -1).all())
+
+
+def _threshold_segmenter(seg):
+    from scipy import ndimage
+    lab, _ = ndimage.label(seg > int(seg.max()) // 2)
+    return lab.astype(np.int32)
+
+
+def test_screening_with_label_cell_extractor_end_to_end(tmp_path, golden_cae, golden_det, proc):
+    """ProductionMutantScreening over folders of .npy images with label_cell_extractor(threshold + ndimage.label) writes the
+    CSVs that screen_cell_arrays writes for the restatement's crops preprocessed by Preprocessor."""
+    import helpers as H
+    from cellscreen import model_io
+    from cellscreen.screening import ProductionMutantScreening
+    mdir = str(tmp_path / "models")
+    model_io.save_model_dir(mdir, H.cae_from_golden(golden_cae), None, H.det_from_golden(golden_det))
+    folders, expected = {}, {}
+    for k, (seed, n) in enumerate(((21, 2), (22, 3))):
+        d = tmp_path / f"strain{k}"
+        d.mkdir()
+        imgs, _ = synth.label_images(seed, n)
+        crops = []
+        for i in range(n):
+            np.save(d / f"img{i}.npy", imgs[i])
+            c, _, st = R.extract(_threshold_segmenter(imgs[i, ..., 2]), imgs[i, ..., 1])
+            assert st == R.IMAGE_OK
+            crops += c
+        folders[f"S{k}"] = str(d)
+        expected[f"S{k}"] = proc(crops)
+    s = ProductionMutantScreening(mdir, cell_extractor=X.label_cell_extractor(_threshold_segmenter), file_pattern="*.npy")
+    s.screen_mutant_samples(folders, str(tmp_path / "a"))
+    s.screen_cell_arrays(expected, str(tmp_path / "b"), files_processed=0)
+    da = open(tmp_path / "a" / "detailed_cell_results.csv").read()
+    db = open(tmp_path / "b" / "detailed_cell_results.csv").read()
+    assert da == db and len(da.splitlines()) > 10
+    import pandas as pd
+    sa = pd.read_csv(tmp_path / "a" / "screening_summary.csv", index_col=0)
+    sb = pd.read_csv(tmp_path / "b" / "screening_summary.csv", index_col=0)
+    assert list(sa["files_processed"]) == [2, 3]
+    sb["files_processed"] = sa["files_processed"]
+    pd.testing.assert_frame_equal(sa, sb, check_exact=True)
+
+
+def test_create_training_dataset_on_device(tmp_path, proc):
+    import pandas as pd
+    from cellscreen.training import ImprovedAnomalyDetectionTraining
+    d = tmp_path / "train"
+    d.mkdir()
+    imgs, _ = synth.label_images(31, 3)
+    for i in range(3):
+        np.save(d / f"f{i}.npy", imgs[i])
+    tr = ImprovedAnomalyDetectionTraining(str(tmp_path / "out"))
+    cells, df = tr.create_training_dataset(str(d), X.label_cell_extractor(_threshold_segmenter), file_pattern="*.npy")
+    crops = []
+    for i in range(3):
+        crops += R.extract(_threshold_segmenter(imgs[i, ..., 2]), imgs[i, ..., 1])[0]
+    assert np.array_equal(cells.astype(np.float32), proc(crops))
+    assert list(df.columns) == ["area", "eccentricity", "solidity", "mean_intensity", "std_intensity", "file"]
+    fs = pd.read_csv(tmp_path / "out" / "file_summary.csv")
+    assert list(fs.columns) == ["filename", "cells_extracted", "mean_cell_intensity"] and fs["cells_extracted"].sum() == len(cells)
