@@ -40,6 +40,7 @@
 #endif
 
 #define ORC_MAX_LAYERS 16
+#define ORC_MAX_COUT 1024      /* per-pixel accumulators on the stack */
 
 /* ---------------------------------------------------------------- synthetic crops */
 /* Counter-based generator keyed (seed, cell, pixel): the HIP library implements the
@@ -87,7 +88,7 @@ static void conv3x3(const float *in, int H, int W, int cin, int ups,
         for (int x = 0; x < W; ++x) {
             float *o = out + ((size_t)y * W + x) * cout;
             if (acc64) {
-                double acc[256];
+                double acc[ORC_MAX_COUT];
                 for (int co = 0; co < cout; ++co) acc[co] = (double)b[co];
                 for (int dy = -1; dy <= 1; ++dy) {
                     int yy = y + dy; if (yy < 0 || yy >= H) continue;
@@ -104,7 +105,7 @@ static void conv3x3(const float *in, int H, int W, int cin, int ups,
                 }
                 for (int co = 0; co < cout; ++co) o[co] = (float)acc[co];
             } else {
-                float acc[256];
+                float acc[ORC_MAX_COUT];
                 for (int co = 0; co < cout; ++co) acc[co] = 0.0f;
                 for (int dy = -1; dy <= 1; ++dy) {
                     int yy = y + dy; if (yy < 0 || yy >= H) continue;
@@ -216,7 +217,7 @@ int orc_cae_forward(int H, int W, int n_conv, int n_enc, const int *cin, const i
     orc_cae m; memset(&m, 0, sizeof m);
     m.H = H; m.W = W; m.n_conv = n_conv; m.n_enc = n_enc;
     for (int l = 0; l < n_conv; ++l) {
-        if (cout[l] > 256) return -2;
+        if (cout[l] > ORC_MAX_COUT) return -2;
         m.cin[l] = cin[l]; m.cout[l] = cout[l];
         m.kernel[l] = kernels[l]; m.bias[l] = biases[l];
         m.bn_scale[l] = bn_scale ? bn_scale[l] : NULL;

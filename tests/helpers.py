@@ -59,3 +59,21 @@ def flags_agree(dec_got, pred_got, dec_ref, pred_ref, tol_abs, what):
     sure = np.abs(dec_ref) > tol_abs
     assert np.array_equal(np.asarray(pred_got)[sure], np.asarray(pred_ref)[sure]), f"{what}: label mismatch away from 0"
     return int((~sure).sum())
+
+
+# ---- training on the run-time-shaped kernels
+def activation_pattern(tr, w, n):
+    """The trainer's ReLU masks and max-pool routing from its relu outputs (stage tap 0), for any instance of the grammar
+    (see tests/test_gpu_train.py: fp32 and fp64 disagree on a handful of those discontinuous decisions)."""
+    nl, ne = w.n_conv - 1, w.n_enc
+    masks, args = [], []
+    for l in range(nl):
+        r = tr.tensor(0, l, n)
+        masks.append(r > 0)
+        if l < ne:
+            N, Hh, Ww, C = r.shape
+            win = r.reshape(N, Hh // 2, 2, Ww // 2, 2, C).transpose(0, 1, 3, 5, 2, 4).reshape(N, Hh // 2, Ww // 2, C, 4)
+            args.append(np.argmax(win * np.sign(w.bn_gamma[l])[None, None, None, :, None], axis=-1))
+        else:
+            args.append(None)
+    return masks + [None], args + [None]

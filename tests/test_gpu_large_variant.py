@@ -185,23 +185,6 @@ def test_unsupported_shapes_are_refused():
 
 
 # ---- training on the run-time-shaped kernels (csrc/train_generic.hip) ------------------------------------------------
-def _activation_pattern(tr, w, n):
-    """The trainer's ReLU masks and max-pool routing from its relu outputs (stage tap 0), for any instance of the grammar
-    (see tests/test_gpu_train.py: fp32 and fp64 disagree on a handful of those discontinuous decisions)."""
-    nl, ne = w.n_conv - 1, w.n_enc
-    masks, args = [], []
-    for l in range(nl):
-        r = tr.tensor(0, l, n)
-        masks.append(r > 0)
-        if l < ne:
-            N, Hh, Ww, C = r.shape
-            win = r.reshape(N, Hh // 2, 2, Ww // 2, 2, C).transpose(0, 1, 3, 5, 2, 4).reshape(N, Hh // 2, Ww // 2, C, 4)
-            args.append(np.argmax(win * np.sign(w.bn_gamma[l])[None, None, None, :, None], axis=-1))
-        else:
-            args.append(None)
-    return masks + [None], args + [None]
-
-
 @pytest.mark.parametrize("hw,channels,n", [((64, 128), (8, 16, 32, 32, 16, 8, 1), 5), (LARGE_HW, LARGE_CH, 2)])
 def test_generic_trainer_gradients_against_the_oracle(hw, channels, n):
     """BASELINE.json configs[4]'s training half: forward (BN batch statistics) + backward of a non-reference instance of the
@@ -216,7 +199,7 @@ def test_generic_trainer_gradients_against_the_oracle(hw, channels, n):
     try:
         assert tr.n_trainable == w.n_params() - 2 * sum(c for c in channels[:-1])
         loss, mae = tr.forward_backward(x, y)
-        masks, args = _activation_pattern(tr, w, n)
+        masks, args = H.activation_pattern(tr, w, n)
         st = T.TrainState(w, dtype=np.float64)
         ref = T.forward_backward(st, x, y, relu_masks=masks, pool_args=args)
         free = T.forward_backward(T.TrainState(w, dtype=np.float64), x, y)
