@@ -1304,6 +1304,10 @@ int cs_profile_mfma_per_cell(cs_model* m, int k, double* mfma)
 {
     if (!m || !mfma || k < 0 || k >= K_COUNT) return fail(CS_ERR_INVALID, "bad kernel id");
     double v = 0.0;
+    if (k == K_SCALER_PCA) {                                               // any architecture: scaler_pca_kernel, fpad x cpad per cell
+        *mfma = m->has_det && !m->split16 ? (double)m->fpad * m->cpad / 1024.0 : 0.0;
+        return CS_OK;
+    }
     if (m->arch.ref) {
         const bool h2 = m->split16;
         switch (k) {
@@ -1316,7 +1320,6 @@ int cs_profile_mfma_per_cell(cs_model* m, int k, double* mfma)
             case K_CONV67_FUSED: v = h2 ? 512 : 4608 + 512; break;          // conv6 phases (unless on the 16-bit pipe) + conv7's 32 -> 16 contraction
             case K_CONV12_FUSED: v = h2 ? 0 : 4608 + 1536 + 48; break;      // conv2 F(4x4,3x3): 36 points x 4 groups x 8 x 4; conv1 direct
                                                                             // + the discarded fourth row of a cell's last 4-row batch
-            case K_SCALER_PCA: v = h2 ? 0.0 : (double)m->fpad * m->cpad / 1024.0; break;
             default: v = 0.0;
         }
     } else if (k <= K_CONV6 || k == K_CONV7_ERR) {

@@ -77,3 +77,75 @@ def activation_pattern(tr, w, n):
         else:
             args.append(None)
     return masks + [None], args + [None]
+
+
+# ---- the detector tail in float64 (csrc/detector.hip restated; pinned to the C oracle and scikit-learn by
+# tests/test_detector_envelope_cpu.py)
+def scaled_features(det, f):
+    """RobustScaler.transform as the kernels stage it: (f - center_) in float32, divided by the float64 scale_ and
+    rounded once to float32 (detector.hip:67-68, 194-195; numpy's float32 /= float64)."""
+    t = np.asarray(f, np.float32) - np.asarray(det.scaler_center, np.float32)
+    return (t.astype(np.float64) / np.asarray(det.scaler_scale, np.float64)).astype(np.float32)
+
+
+def pca_ref(det, f):
+    """scaled @ components_.T - mean_proj, all in float64 from the float32 scaled features and parameters."""
+    s = scaled_features(det, f).astype(np.float64)
+    return s @ np.asarray(det.pca_components, np.float32).astype(np.float64).T - np.asarray(det.pca_mean_proj, np.float32)
+
+
+def ocsvm_ref(p, pca, block=256):
+    """OneClassSVM.decision_function in float64: sum_i a_i exp(-gamma |x - sv_i|^2) - rho, the
+    distance taken directly (libsvm svm.cpp:461-476, 2818-2838)."""
+    x = np.asarray(pca).astype(np.float64)                          # float32 kernel input, or a float64 reference PCA
+    sv = np.asarray(p.support_vectors, np.float64)
+    coef = np.ravel(p.dual_coef).astype(np.float64)
+    out = np.empty(len(x))
+    for i in range(0, len(x), block):
+        d2 = ((x[i:i + block, None, :] - sv[None, :, :]) ** 2).sum(axis=-1)
+        out[i:i + block] = np.exp(-p.gamma * d2) @ coef - p.rho
+    return out
+
+
+def random_detector(F, C, n_sv, gamma_mult=(1.0, 1.0), seed=0, cells=None, rho=(None, None)):
+    """A DetectorParams for F features and C components (any C in 1..128, also C > F) whose decisions mean something:
+    the scaler is fitted to `cells` ((n, F) features; synthetic ones when None) with awkward scale_ values and a few
+    constant columns (scale_ = 1, as RobustScaler sets for a zero IQR); components_ are random unit rows (orthonormal
+    where C <= F); each detector's support vectors are PCA outputs of those cells, perturbed, with positive dual
+    coefficients; gamma is gamma_mult / (C var) of the PCA outputs (sklearn's gamma='scale'), and rho, unless given, is
+    the median of the cells' float64 decisions, so the flags split."""
+    from cellscreen.spec import DetectorParams, OCSVMParams
+    rng = np.random.default_rng(seed)
+    if cells is None:
+        z = rng.normal(size=(512, 8)) @ rng.normal(size=(8, F))
+        cells = np.maximum(z + rng.normal(0, 0.5, (512, F)), 0).astype(np.float32)
+    cells = np.asarray(cells, np.float32)
+    center = np.median(cells, axis=0).astype(np.float32)
+    q75, q25 = np.percentile(cells.astype(np.float64), [75, 25], axis=0)
+    scale = np.where(q75 - q25 > 0, q75 - q25, 1.0) * np.exp(rng.normal(0.0, 0.5, F)) * (1.0 + 2.0 ** -30)
+    odd = rng.choice(F, min(F, 8), replace=False)
+    scale[odd] *= np.array([1.0 / 3.0, 0.1, 7.0, 3.0, 1.0, 0.5, 2.0 ** -4, 10.0])[:len(odd)]
+    const = rng.choice(F, max(1, F // 64), replace=False)
+    scale[const] = 1.0
+    center[const] = cells[0, const]
+    g = rng.normal(size=(C, F))
+    if C <= F:
+        g = np.linalg.qr(g.T)[0].T
+    comps = (g / np.linalg.norm(g, axis=1, keepdims=True)).astype(np.float32)
+    mean = cells.mean(axis=0, dtype=np.float64).astype(np.float32)
+    mean_proj = (mean.reshape(1, -1) @ comps.T).ravel().astype(np.float32)
+    det = DetectorParams(center, scale.astype(np.float64), comps, mean, mean_proj)
+    red = pca_ref(det, cells).astype(np.float32)
+    sd = red.astype(np.float64).std(axis=0) + 1e-30
+    var = red.astype(np.float64).var()
+    svms = []
+    for k in range(2):
+        pick = rng.choice(len(red), n_sv[k], replace=n_sv[k] > len(red))
+        sv = red[pick].astype(np.float64) + rng.normal(0.0, 0.1, (n_sv[k], C)) * sd
+        coef = rng.uniform(0.05, 1.0, n_sv[k])
+        gamma = gamma_mult[k] / (C * var) if var > 0 else 1.0
+        p = OCSVMParams(sv, coef, float(gamma), 0.0)
+        p.rho = float(np.median(ocsvm_ref(p, red))) if rho[k] is None else float(rho[k])
+        svms.append(p)
+    det.conservative, det.moderate = svms
+    return det

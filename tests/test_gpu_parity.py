@@ -179,15 +179,18 @@ def test_small_calls_run_the_detector_tail_split_with_identical_results(weights,
     """A call of at most 16,384 cells runs the PCA GEMM's feature ranges and the SVMs' support-vector ranges side by side in separate
     workgroups (a 128-cell call is otherwise two workgroups / one workgroup walking everything in sequence) and adds the range sums in
     the order the one-workgroup kernels add them: every output is bit-identical to the same cells screened inside a large call, and to
-    the one-workgroup form forced by CS_DEBUG_NO_SMALL_SPLIT."""
+    the one-workgroup form forced by CS_DEBUG_NO_SMALL_SPLIT.  Host input runs in passes of 16,384 cells unless the pass size is
+    set (api.hip:410-413), so the large calls set it to the whole call: one pass of 17,084 cells, above the limit."""
     n_big = 16384 + 700
     x = oracle.synth_crops(23, 0, n_big)
     e = Engine.from_weights(weights, None, det)
     try:
-        whole = e.screen(x)                                  # above the limit: the one-workgroup kernels
+        e.set_chunk(n_big)
+        whole = e.screen(x)                                  # one pass above the limit: the one-workgroup kernels
+        pca_big = e.scaler_pca(e.encode(x))[:300]            # the same cells inside 17,084: not split
+        e.set_chunk(0)
         f = e.encode(x[:300])
         pca_small = e.scaler_pca(f)                          # 300 cells: split
-        pca_big = e.scaler_pca(e.encode(x))[:300]            # the same cells inside 17,084: not split
         assert np.array_equal(pca_small, pca_big)
         for idx in (slice(0, 1), slice(0, 300), slice(300, 1337), slice(0, 16384)):
             part = e.screen(x[idx])
@@ -504,9 +507,9 @@ def test_plain_c_program_screens_through_the_abi(tmp_path, weights, det):
 
 
 def test_scaler_is_bit_exact_through_one_hot_pca(weights, det):
-    """The scaler inside scaler_pca_kernel avoids the fp64 division (reciprocal multiply + a tie test that falls
-    back to the division); with one-hot PCA rows and zero mean projection the kernel's output IS the scaled feature,
-    so it can be compared bit-for-bit with numpy's float32((x - center) / float64 scale) on two million values."""
+    """The scaler inside the PCA kernels divides the float32 centred feature by the float64 scale_ in double and rounds
+    once (detector.hip:67-68, 194-195); with one-hot PCA rows and zero mean projection the kernel's output IS the scaled
+    feature, so it can be compared bit-for-bit with numpy's float32((x - center) / float64 scale) on two million values."""
     import copy
     rng = np.random.default_rng(123)
     F, C = 2048, 100
