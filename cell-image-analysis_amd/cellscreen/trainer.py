@@ -132,6 +132,11 @@ class Trainer:
         `train` alive and unchanged while steps are in flight; metrics as for step_async."""
         if idx.dtype != np.int32 or not idx.flags["C_CONTIGUOUS"]:
             idx = np.ascontiguousarray(idx, dtype=np.int32)
+        # the library receives a bare pointer: memory of another device or crops of another size would be read out of range
+        if not getattr(train, "is_cuda", False) or train.device.index != self._device_id:
+            raise ValueError(f"train must be a CUDA tensor on this trainer's device cuda:{self._device_id}")
+        if tuple(train.shape[1:3]) != self.input_hw or not (train.dim() == 3 or (train.dim() == 4 and train.shape[3] == 1)):
+            raise ValueError(f"train must hold {self.input_hw[0]}x{self.input_hw[1]} crops, got shape {tuple(train.shape)}")
         if self._fit_train is not train:                      # ordered after whatever produced the training set, once
             if not train.is_contiguous() or str(train.dtype) != "torch.float32":
                 raise ValueError("train must be a contiguous float32 CUDA tensor")

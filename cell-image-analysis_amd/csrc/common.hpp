@@ -185,9 +185,9 @@ hipError_t launch_wgrad(int layer, const float* xin, const float* dz, float* par
 // errpart / nparts / nelem / out2 (optional): thread 0 also reduces the forward pass's error partial sums to {loss, mae}
 hipError_t launch_reduce_all(const ReduceDesc* descs_dev, int ndesc, long total_len, float* flat_grad, hipStream_t s,
                              const float* errpart = nullptr, long nparts = 0, long nelem = 0, float* out2 = nullptr);
-// alpha_dev == NULL: the step size is alpha_val; macc (optional): {sum loss, sum mae, batches} += batch_scal's {loss, mae}, 1
-hipError_t launch_adam(float* p, const float* g, float* m, float* v, long n, const float* alpha_dev, float b1, float b2, float eps,
-                       hipStream_t s, float alpha_val = 0.0f, const float* batch_scal = nullptr, double* macc = nullptr);
+// macc (optional): {sum loss, sum mae, batches} += batch_scal's {loss, mae}, 1
+hipError_t launch_adam(float* p, const float* g, float* m, float* v, long n, float alpha, float b1, float b2, float eps, hipStream_t s,
+                       const float* batch_scal, double* macc);
 // run-time-shaped conv for non-reference architectures (conv_generic.hip)
 // GEN_EPI_RELU (bias -> ReLU, full resolution) and GEN_EPI_PLAIN (the raw sums; ep may be NULL) serve training:
 // forward with BatchNormalization in batch mode, and the backward-data convs (train_generic.hip)

@@ -670,12 +670,12 @@ __global__ __launch_bounds__(256) void reduce_all_kernel(const ReduceDesc* __res
     }
 }
 
-// Keras Adam: w -= alpha * m / (sqrt(v) + eps), alpha = lr*sqrt(1-b2^t)/(1-b1^t) computed on the host and passed by value
-// (alpha_dev, when not NULL, overrides it from device memory).  macc (optional): the running sums Keras keeps over an epoch --
-// {sum of batch losses, sum of batch MAEs, batches} in double, advanced by the step's {loss, mae} in batch_scal -- so that an
-// epoch of steps needs no host round trip (cs_train_step_async / cs_train_read_metrics).
+// Keras Adam: w -= alpha * m / (sqrt(v) + eps), alpha = lr*sqrt(1-b2^t)/(1-b1^t) computed on the host and passed by value.
+// macc (optional): the running sums Keras keeps over an epoch -- {sum of batch losses, sum of batch MAEs, batches} in double,
+// advanced by the step's {loss, mae} in batch_scal -- so that an epoch of steps needs no host round trip (cs_train_step_async /
+// cs_train_read_metrics).
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                            float* __restrict__ v, long n, const float* __restrict__ alpha_dev, float alpha_val, float b1, float b2, float eps,
+                            float* __restrict__ v, long n, float alpha, float b1, float b2, float eps,
                             const float* __restrict__ batch_scal, double* __restrict__ macc)
 {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -685,7 +685,6 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
         macc[2] += 1.0;
     }
     if (i >= n) return;
-    const float alpha = alpha_dev ? *alpha_dev : alpha_val;
     const float gi = g[i];
     const float mi = m[i] + (gi - m[i]) * (1.0f - b1);
     const float vi = v[i] + (gi * gi - v[i]) * (1.0f - b2);
@@ -893,11 +892,10 @@ hipError_t launch_reduce_all(const ReduceDesc* descs_dev, int ndesc, long total_
     return hipGetLastError();
 }
 
-hipError_t launch_adam(float* p, const float* g, float* m, float* v, long n, const float* alpha, float b1, float b2, float eps,
-                       hipStream_t s, float alpha_val, const float* batch_scal, double* macc)
+hipError_t launch_adam(float* p, const float* g, float* m, float* v, long n, float alpha, float b1, float b2, float eps, hipStream_t s,
+                       const float* batch_scal, double* macc)
 {
-    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p, g, m, v, n, alpha, alpha_val, b1, b2, eps,
-                       batch_scal, macc);
+    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p, g, m, v, n, alpha, b1, b2, eps, batch_scal, macc);
     return hipGetLastError();
 }
 

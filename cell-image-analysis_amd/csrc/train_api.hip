@@ -14,7 +14,8 @@ static int cin_of(int l) { return l == 0 ? 1 : kRefChannels[l - 1]; }
 static size_t a_floats(int l) { return kLayerFloats[l]; }                                   // stored BN output per cell
 static size_t r_floats(int l) { return (size_t)kConvGrid[l] * kConvGrid[l] * kRefChannels[l]; }  // conv-grid tensor per cell
 
-static int repack(cs_trainer* t)
+// ---- the reference form's operations (train_generic.hip has the run-time-shaped ones) ----------------------------------------
+static int ref_repack(cs_trainer* t)
 {
     float* P = t->P.as<float>();
     PackTable tab;
@@ -30,7 +31,7 @@ constexpr int kTrainMaxBatch = 8192;
 static_assert((long)kTrainMaxBatch * 4 <= (long)BN_MAX_PARTS * 64, "conv7's loss epilogue leaves 4 partials per cell in dzsum_part[6]");
 static_assert((long)kTrainMaxBatch * 64 * 64 * 32 < (1L << 31), "the BatchNormalization kernels index below 2^31");
 
-static int ensure_batch(cs_trainer* t, int64_t b)
+static int ref_ensure_batch(cs_trainer* t, int64_t b)
 {
     if (b <= t->maxb) return CS_OK;
     // conv7's loss epilogue leaves 4 bias-gradient partials per cell in dzsum_part[6] (BN_MAX_PARTS * 64 floats), and the
@@ -48,6 +49,28 @@ static int ensure_batch(cs_trainer* t, int64_t b)
         (rc = t->errpart.ensure((size_t)b * 8 * 4)))
         return rc;
     t->maxb = b;
+    return CS_OK;
+}
+
+// the gradient reduction both forms end their backward with (train_internal.hpp)
+int reduce_gradient(cs_trainer* t, int64_t B, const float* errpart)
+{
+    hipStream_t s = t->stream;
+    HIPCHK(hipEventRecord(t->ev_wg, t->stream2));
+    HIPCHK(hipStreamWaitEvent(s, t->ev_wg, 0));
+    long total = 0;
+    for (int l = 0; l < t->n_conv; ++l) total += 9L * t->cin(l) * t->ch[l] + t->ch[l];
+    if (t->descs_batch != B) {          // the partial counts depend on the batch size only
+        for (int l = 0; l < t->n_conv; ++l) {
+            const long klen = 9L * t->cin(l) * t->ch[l];
+            t->hdescs[2 * l] = ReduceDesc{t->off_k[l], klen, t->wpart[l].as<float>(), t->np_w[l], klen};
+            t->hdescs[2 * l + 1] = ReduceDesc{t->off_b[l], (long)t->ch[l], t->dzsum_part[l].as<float>(), t->np_b[l], (long)t->ch[l]};
+        }
+        HIPCHK(hipMemcpyAsync(t->descs.p, t->hdescs, 2 * t->n_conv * sizeof(ReduceDesc), hipMemcpyHostToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));
+        t->descs_batch = B;
+    }
+    LCHK(launch_reduce_all(t->descs.as<ReduceDesc>(), 2 * t->n_conv, total, t->G, s, errpart, B * 4, B * (long)t->H * t->W, t->scal.as<float>()));
     return CS_OK;
 }
 
@@ -91,6 +114,7 @@ static int describe_trainer(cs_trainer* t, const cs_cae_weights* w)
         t->afl[l] = (size_t)h * wd * t->ch[l];
     }
     if (t->ch[t->n_conv - 1] != 1) return fail(CS_ERR_UNSUPPORTED, "initial weights: the last conv must have 1 filter");
+    t->eval_chunk = t->ref ? 4096 : 1024;
     if (!t->ref) {
         char why[160];
         for (int l = 0; l < t->n_conv; ++l) {
@@ -121,6 +145,20 @@ int cs_train_param_count_of(const cs_trainer* t, int64_t* n_trainable, int64_t* 
     return CS_OK;
 }
 
+// the handle's stream, the second stream the weight gradients run on and the events that join the two, the event behind a step's
+// input copies, and the pinned {loss, mae} of the synchronous paths
+static int create_stream_state(cs_trainer* t)
+{
+    HIPCHK(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
+    HIPCHK(hipStreamCreateWithFlags(&t->stream2, hipStreamNonBlocking));
+    for (auto& e : t->ev_dz) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&t->ev_wg, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&t->ev_in, hipEventDisableTiming));
+    HIPCHK(hipHostMalloc((void**)&t->hloss, 2 * sizeof(float), hipHostMallocDefault));
+    t->hloss[0] = t->hloss[1] = 0.0f;
+    return CS_OK;
+}
+
 int cs_train_create(const cs_cae_weights* init, const cs_train_cfg* cfg, int device_id, cs_trainer** out)
 {
     if (!out) return fail(CS_ERR_INVALID, "out is NULL");
@@ -134,10 +172,7 @@ int cs_train_create(const cs_cae_weights* init, const cs_train_cfg* cfg, int dev
     t->cfg = *cfg;
 #define TFAIL(x) do { int r__ = (x); if (r__) { delete t; return r__; } } while (0)
     TFAIL(describe_trainer(t, init));
-    {
-        hipError_t e = hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking);
-        if (e != hipSuccess) { delete t; return fail(CS_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e)); }
-    }
+    TFAIL(create_stream_state(t));
     const int NL = t->n_conv;
     long o = 0, mo = 0;
     for (int l = 0; l < NL; ++l) {
@@ -163,18 +198,11 @@ int cs_train_create(const cs_cae_weights* init, const cs_train_cfg* cfg, int dev
             memcpy(&hm[t->off_mv[l]], init->bn_var[l], sizeof(float) * c);
         }
     }
-    {
-        hipError_t e = hipHostMalloc((void**)&t->hloss, 4 * sizeof(float), hipHostMallocDefault);
-        if (e != hipSuccess) { delete t; return fail(CS_ERR_HIP, "hipHostMalloc: %s", hipGetErrorString(e)); }
-        t->hloss[0] = t->hloss[1] = t->hloss[2] = t->hloss[3] = 0.0f;
-    }
     TFAIL(upload(t->P, hp.data(), o * 4));
     TFAIL(upload(t->MOV, hm.data(), mo * 4));
     {
         const double z3[4] = {0.0, 0.0, 0.0, 0.0};
         TFAIL(upload(t->macc, z3, sizeof z3));
-        hipError_t e = hipEventCreateWithFlags(&t->ev_in, hipEventDisableTiming);
-        if (e != hipSuccess) { delete t; return fail(CS_ERR_HIP, "hipEventCreate: %s", hipGetErrorString(e)); }
     }
     TFAIL(t->Gown.ensure(o * 4)); TFAIL(t->M.ensure(o * 4)); TFAIL(t->V.ensure(o * 4));
     t->G = t->Gown.as<float>();
@@ -182,31 +210,27 @@ int cs_train_create(const cs_cae_weights* init, const cs_train_cfg* cfg, int dev
         hipError_t e1 = hipMemset(t->M.p, 0, o * 4), e2 = hipMemset(t->V.p, 0, o * 4), e3 = hipMemset(t->Gown.p, 0, o * 4);
         if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) { delete t; return fail(CS_ERR_HIP, "hipMemset failed"); }
     }
-    if (!t->ref) {
+    TFAIL(t->descs.ensure(2 * NL * sizeof(ReduceDesc)));
+    TFAIL(t->scal.ensure(2 * sizeof(float)));
+    if (t->ref) {
+        for (int l = 0; l < 6; ++l) {
+            TFAIL(t->wf[l].ensure(pack_conv_fragments(cin_of(l), kRefChannels[l], nullptr, nullptr) * 4));
+            TFAIL(t->ep_inf[l].ensure(3 * kRefChannels[l] * 4));
+            TFAIL(t->stats[l].ensure(2 * kRefChannels[l] * 4));
+        }
+        for (int l = 1; l < 7; ++l)   // backward-data fragments: effective conv (cin' = cout, cout' = cin)
+            TFAIL(t->wft[l].ensure(pack_conv_fragments(kRefChannels[l], cin_of(l), nullptr, nullptr) * 4));
+        TFAIL(t->w7eff.ensure(16 * 32 * 4));
+        TFAIL(t->part_stats.ensure((size_t)BN_MAX_PARTS * 3 * 64 * 4));
+        TFAIL(t->part_bwd.ensure((size_t)BN_MAX_PARTS * 2 * 64 * 4));
+        TFAIL(t->bwd_sums.ensure(2 * 64 * 4));
+        for (int l = 0; l < 7; ++l) {
+            TFAIL(t->dzsum_part[l].ensure((size_t)BN_MAX_PARTS * 64 * 4));
+            TFAIL(t->wpart[l].ensure((size_t)TRAIN_MAX_PARTS * 9 * cin_of(l) * kRefChannels[l] * 4));
+        }
+        TFAIL(ref_repack(t));
+    } else
         TFAIL(gen_train_setup(t));
-        hipError_t e = hipStreamSynchronize(t->stream);
-        if (e != hipSuccess) { delete t; return fail(CS_ERR_HIP, "initial repack: %s", hipGetErrorString(e)); }
-        *out = t;
-        return CS_OK;
-    }
-    for (int l = 0; l < 6; ++l) {
-        TFAIL(t->wf[l].ensure(pack_conv_fragments(cin_of(l), kRefChannels[l], nullptr, nullptr) * 4));
-        TFAIL(t->ep_inf[l].ensure(3 * kRefChannels[l] * 4));
-        TFAIL(t->stats[l].ensure(2 * kRefChannels[l] * 4));
-    }
-    for (int l = 1; l < 7; ++l)   // backward-data fragments: effective conv (cin' = cout, cout' = cin)
-        TFAIL(t->wft[l].ensure(pack_conv_fragments(kRefChannels[l], cin_of(l), nullptr, nullptr) * 4));
-    TFAIL(t->w7eff.ensure(16 * 32 * 4));
-    TFAIL(t->part_stats.ensure((size_t)BN_MAX_PARTS * 3 * 64 * 4));
-    TFAIL(t->part_bwd.ensure((size_t)BN_MAX_PARTS * 2 * 64 * 4));
-    TFAIL(t->bwd_sums.ensure(2 * 64 * 4));
-    for (int l = 0; l < 7; ++l) {
-        TFAIL(t->dzsum_part[l].ensure((size_t)BN_MAX_PARTS * 64 * 4));
-        TFAIL(t->wpart[l].ensure((size_t)TRAIN_MAX_PARTS * 9 * cin_of(l) * kRefChannels[l] * 4));
-    }
-    TFAIL(t->descs.ensure(14 * sizeof(ReduceDesc)));
-    TFAIL(t->scal.ensure(16));
-    TFAIL(repack(t));
     {
         hipError_t e = hipStreamSynchronize(t->stream);
         if (e != hipSuccess) { delete t; return fail(CS_ERR_HIP, "initial repack: %s", hipGetErrorString(e)); }
@@ -261,43 +285,9 @@ static int sync_gather(cs_trainer* t, int64_t floats_per_rank)
     return CS_OK;
 }
 
-static int copy_in(cs_trainer* t, DevBuf& dst, const float* src, int kind, size_t floats)
-{
-    HIPCHK(hipMemcpyAsync(dst.p, src, floats * 4, kind == CS_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, t->stream));
-    return CS_OK;
-}
-
-static int fb_enqueue(cs_trainer* t, int64_t B);
-
-// loss / mae of the batch -> the caller: a pinned read-back enqueued behind the step's kernels.  Within cs_train_step
-// the wait is left to the single synchronisation at the end of cs_train_apply (one host round trip per step, not three).
-static int finish_forward_backward(cs_trainer* t, float* loss, float* mae)
-{
-    HIPCHK(hipMemcpyAsync(t->hloss, t->scal.p, 8, hipMemcpyDeviceToHost, t->stream));
-    if (t->defer_sync) return CS_OK;
-    HIPCHK(hipStreamSynchronize(t->stream));
-    if (loss) *loss = t->hloss[0];
-    if (mae) *mae = t->hloss[1];
-    return CS_OK;
-}
-
-int cs_train_forward_backward(cs_trainer* t, const float* x, const float* y, int64_t batch, int kind, float* loss, float* mae)
-{
-    if (!t) return fail(CS_ERR_INVALID, "trainer is NULL");
-    if (!x || !y || batch <= 0) return fail(CS_ERR_INVALID, "x/y NULL or batch <= 0");
-    if (kind != CS_MEM_HOST && kind != CS_MEM_DEVICE) return fail(CS_ERR_INVALID, "bad mem kind");
-    HIPCHK(hipSetDevice(t->device));
-    if (!t->ref) return gen_train_forward_backward(t, x, y, batch, kind, loss, mae);
-    int rc = ensure_batch(t, batch);
-    if (rc) return rc;
-    if ((rc = copy_in(t, t->x, x, kind, (size_t)batch * kH * kW)) || (rc = copy_in(t, t->y, y, kind, (size_t)batch * kH * kW))) return rc;
-    if ((rc = fb_enqueue(t, batch))) return rc;
-    return finish_forward_backward(t, loss, mae);
-}
-
 // Everything of forward + backward between the input copies and the loss read-back, as stream work only (no host
-// synchronisation once the reduction descriptors of this batch size are uploaded): what a captured step graph replays.
-static int fb_enqueue(cs_trainer* t, int64_t B)
+// synchronisation once the reduction descriptors of this batch size are uploaded).
+static int ref_fb_enqueue(cs_trainer* t, int64_t B)
 {
     hipStream_t s = t->stream;
     float* P = t->P.as<float>();
@@ -334,11 +324,6 @@ static int fb_enqueue(cs_trainer* t, int64_t B)
     // The weight gradient of a layer needs only that layer's dz and input; it runs on a second stream beside the
     // backward-data conv and the BatchNormalization-backward kernels of the layers below, none of which fills the chip at
     // batch 32.  Both streams join again before the partial sums are reduced.
-    if (!t->stream2) {
-        HIPCHK(hipStreamCreateWithFlags(&t->stream2, hipStreamNonBlocking));
-        for (int l = 0; l < 7; ++l) HIPCHK(hipEventCreateWithFlags(&t->ev_dz[l], hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&t->ev_wg, hipEventDisableTiming));
-    }
     hipStream_t s2 = t->stream2;
     HIPCHK(hipEventRecord(t->ev_dz[6], s));
     HIPCHK(hipStreamWaitEvent(s2, t->ev_dz[6], 0));
@@ -370,71 +355,119 @@ static int fb_enqueue(cs_trainer* t, int64_t B)
         LCHK(launch_wgrad(l, in, t->dz[l].as<float>(), t->wpart[l].as<float>(), B, &t->np_w[l], s2));
         if (l > 0) LCHK(launch_conv_dgrad(l, t->dz[l].as<float>(), t->wft[l].as<float>(), t->da[l - 1].as<float>(), B, s));
     }
-    HIPCHK(hipEventRecord(t->ev_wg, s2));
-    HIPCHK(hipStreamWaitEvent(s, t->ev_wg, 0));
-    // ---- all partial sums -> flat gradient, in workgroup order -----------------------------
-    long total = 0;
-    for (int l = 0; l < 7; ++l) total += 9L * cin_of(l) * kRefChannels[l] + kRefChannels[l];
-    if (t->descs_batch != B) {          // the partial counts depend on the batch size only
-        for (int l = 0; l < 7; ++l) {
-            const long klen = 9L * cin_of(l) * kRefChannels[l];
-            t->hdescs[2 * l] = ReduceDesc{t->off_k[l], klen, t->wpart[l].as<float>(), t->np_w[l], klen};
-            t->hdescs[2 * l + 1] = ReduceDesc{t->off_b[l], (long)kRefChannels[l], t->dzsum_part[l].as<float>(), t->np_b[l], (long)kRefChannels[l]};
-        }
-        HIPCHK(hipMemcpyAsync(t->descs.p, t->hdescs, 14 * sizeof(ReduceDesc), hipMemcpyHostToDevice, s));
-        HIPCHK(hipStreamSynchronize(s));
-        t->descs_batch = B;
-    }
     // ... and the batch's {loss, mae} from the forward pass's error partial sums (thread 0 of the same launch)
-    LCHK(launch_reduce_all(t->descs.as<ReduceDesc>(), 14, total, G, s, t->errpart.as<float>(), B * 4, B * (long)kH * kW, t->scal.as<float>()));
+    return reduce_gradient(t, B, t->errpart.as<float>());
+}
+
+// inference forward of the nc cells in t->x / t->y: their error partial sums in t->errpart
+static int ref_eval_enqueue(cs_trainer* t, int64_t nc)
+{
+    for (int l = 0; l < 6; ++l) {
+        const float* in = l == 0 ? t->x.as<float>() : t->a[l - 1].as<float>();
+        LCHK(launch_conv_mfma(l, in, t->wf[l].as<float>(), t->ep_inf[l].as<float>(), t->a[l].as<float>(), nc, t->stream));
+    }
+    LCHK(launch_conv7_err(t->a[5].as<float>(), t->y.as<float>(), t->w7eff.as<float>(), t->P.as<float>() + t->off_b[6],
+                          t->errpart.as<float>(), nullptr, nc, t->stream));
     return CS_OK;
 }
 
-// Adam's step size alpha = lr sqrt(1 - b2^t) / (1 - b1^t) changes every step: it reaches the kernel through device memory
-// (scal[2]), staged from pinned host memory, so that the update is the same stream work every step (graph-replayable).
-static int stage_alpha(cs_trainer* t, float lr)
+// ---- the four operations the two forms differ in; everything below is written once for both ---------------------------------
+static int ensure_batch(cs_trainer* t, int64_t b) { return t->ref ? ref_ensure_batch(t, b) : gen_train_ensure_batch(t, b); }
+static int fb_enqueue(cs_trainer* t, int64_t B) { return t->ref ? ref_fb_enqueue(t, B) : gen_train_fb_enqueue(t, B); }
+static int repack(cs_trainer* t) { return t->ref ? ref_repack(t) : gen_train_repack(t); }
+static int eval_enqueue(cs_trainer* t, int64_t nc) { return t->ref ? ref_eval_enqueue(t, nc) : gen_train_eval_enqueue(t, nc); }
+
+static int check_batch(const cs_trainer* t, const float* x, const float* y, int64_t batch, int kind)
+{
+    if (!t) return fail(CS_ERR_INVALID, "trainer is NULL");
+    if (!x || !y || batch <= 0) return fail(CS_ERR_INVALID, "x/y NULL or batch <= 0");
+    if (kind != CS_MEM_HOST && kind != CS_MEM_DEVICE) return fail(CS_ERR_INVALID, "bad mem kind");
+    return CS_OK;
+}
+
+static int copy_in(cs_trainer* t, DevBuf& dst, const float* src, int kind, size_t floats)
+{
+    HIPCHK(hipMemcpyAsync(dst.p, src, floats * 4, kind == CS_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, t->stream));
+    return CS_OK;
+}
+
+// a training batch -> t->x / t->y, the batch buffers grown to it first
+static int stage_batch(cs_trainer* t, const float* x, const float* y, int64_t batch, int kind)
+{
+    const size_t n = (size_t)batch * t->H * t->W;
+    int rc = ensure_batch(t, batch);
+    if (rc || (rc = copy_in(t, t->x, x, kind, n))) return rc;
+    return copy_in(t, t->y, y, kind, n);
+}
+
+// Keras Adam with this step's size alpha = lr sqrt(1 - b2^t) / (1 - b1^t), then the re-pack of the updated weights.  metrics: the
+// batch's {loss, mae} in scal are added to the epoch sums in macc (the asynchronous steps)
+static int update_enqueue(cs_trainer* t, float lr, bool metrics)
 {
     t->step += 1;
     const double b1 = t->cfg.beta1, b2 = t->cfg.beta2;
-    t->hloss[2] = (float)((double)lr * std::sqrt(1.0 - std::pow(b2, (double)t->step)) / (1.0 - std::pow(b1, (double)t->step)));
-    HIPCHK(hipMemcpyAsync(t->scal.as<float>() + 2, t->hloss + 2, sizeof(float), hipMemcpyHostToDevice, t->stream));
+    const float alpha = (float)((double)lr * std::sqrt(1.0 - std::pow(b2, (double)t->step)) / (1.0 - std::pow(b1, (double)t->step)));
+    LCHK(launch_adam(t->P.as<float>(), t->G, t->M.as<float>(), t->V.as<float>(), t->nparam, alpha, t->cfg.beta1, t->cfg.beta2,
+                     t->cfg.adam_eps, t->stream, metrics ? t->scal.as<float>() : nullptr, metrics ? t->macc.as<double>() : nullptr));
+    return repack(t);
+}
+
+// the asynchronous step over the batch in t->x / t->y: ev_in marks the inputs as read (cs_train_inputs_consumed), then forward,
+// backward, Adam with the device-side epoch metrics and the re-pack
+static int step_tail(cs_trainer* t, int64_t B, float lr)
+{
+    HIPCHK(hipEventRecord(t->ev_in, t->stream));
+    int rc = fb_enqueue(t, B);
+    if (rc) return rc;
+    return update_enqueue(t, lr, true);
+}
+
+// forward + backward of a batch, its {loss, mae} read back into the pinned hloss behind the step's kernels
+static int fb_readback(cs_trainer* t, const float* x, const float* y, int64_t batch, int kind)
+{
+    int rc = stage_batch(t, x, y, batch, kind);
+    if (rc || (rc = fb_enqueue(t, batch))) return rc;
+    HIPCHK(hipMemcpyAsync(t->hloss, t->scal.p, 2 * sizeof(float), hipMemcpyDeviceToHost, t->stream));
     return CS_OK;
 }
 
-static int apply_enqueue(cs_trainer* t)
+static int sync_readback(cs_trainer* t, float* loss, float* mae)
 {
-    LCHK(launch_adam(t->P.as<float>(), t->G, t->M.as<float>(), t->V.as<float>(), t->nparam, t->scal.as<float>() + 2, t->cfg.beta1,
-                     t->cfg.beta2, t->cfg.adam_eps, t->stream));
-    return t->ref ? repack(t) : gen_train_repack(t);
+    HIPCHK(hipStreamSynchronize(t->stream));
+    if (loss) *loss = t->hloss[0];
+    if (mae) *mae = t->hloss[1];
+    return CS_OK;
+}
+
+int cs_train_forward_backward(cs_trainer* t, const float* x, const float* y, int64_t batch, int kind, float* loss, float* mae)
+{
+    int rc = check_batch(t, x, y, batch, kind);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(t->device));
+    if ((rc = fb_readback(t, x, y, batch, kind))) return rc;
+    return sync_readback(t, loss, mae);
 }
 
 int cs_train_apply(cs_trainer* t, float lr)
 {
     if (!t) return fail(CS_ERR_INVALID, "trainer is NULL");
     HIPCHK(hipSetDevice(t->device));
-    int rc = stage_alpha(t, lr);
-    if (rc || (rc = apply_enqueue(t))) return rc;
+    int rc = update_enqueue(t, lr, false);
+    if (rc) return rc;
     HIPCHK(hipStreamSynchronize(t->stream));
     return CS_OK;
 }
 
-// cs_train_step = forward_backward + apply with ONE host synchronisation (at the end of apply).  Replaying the step as a
-// captured hipGraph (~65 launches on two streams) was measured SLOWER on ROCm 7.2 -- 0.74 ms against 0.59 ms for the plain
-// two-stream launches at batch 32 -- and aborted inside the runtime in the test suite; it was taken out again.
+// cs_train_step = forward_backward + apply with ONE host synchronisation, at the end.  Replaying the step as a captured hipGraph
+// (~65 launches on two streams) was measured SLOWER on ROCm 7.2 -- 0.74 ms against 0.59 ms for the plain two-stream launches at
+// batch 32 -- and aborted inside the runtime in the test suite; it was taken out again.
 int cs_train_step(cs_trainer* t, const float* x, const float* y, int64_t batch, int kind, float lr, float* loss, float* mae)
 {
-    if (!t) return fail(CS_ERR_INVALID, "trainer is NULL");
-    t->defer_sync = t->ref;             // the generic path keeps its own synchronisation
-    int rc = cs_train_forward_backward(t, x, y, batch, kind, loss, mae);
-    t->defer_sync = false;
+    int rc = check_batch(t, x, y, batch, kind);
     if (rc) return rc;
-    rc = cs_train_apply(t, lr);         // ends with the step's one synchronisation
-    if (rc) return rc;
-    if (t->ref) {
-        if (loss) *loss = t->hloss[0];
-        if (mae) *mae = t->hloss[1];
-    }
-    return CS_OK;
+    HIPCHK(hipSetDevice(t->device));
+    if ((rc = fb_readback(t, x, y, batch, kind)) || (rc = update_enqueue(t, lr, false))) return rc;
+    return sync_readback(t, loss, mae);
 }
 
 // One fit() batch with NO host synchronisation: input copies, forward, backward, Adam and the re-pack are enqueued on the
@@ -444,43 +477,19 @@ int cs_train_step(cs_trainer* t, const float* x, const float* y, int64_t batch, 
 // (the Python wrapper does it with torch's current stream, whose allocator may otherwise hand the batch's memory out again).
 int cs_train_step_async(cs_trainer* t, const float* x, const float* y, int64_t batch, int kind, float lr)
 {
-    if (!t) return fail(CS_ERR_INVALID, "trainer is NULL");
-    if (!x || !y || batch <= 0) return fail(CS_ERR_INVALID, "x/y NULL or batch <= 0");
-    if (kind != CS_MEM_HOST && kind != CS_MEM_DEVICE) return fail(CS_ERR_INVALID, "bad mem kind");
-    if (!t->ref && kind == CS_MEM_DEVICE) {
-        // run-time-shaped architectures: the same asynchronous step on train_generic.hip's kernels
-        HIPCHK(hipSetDevice(t->device));
-        int rc = gen_train_fb_enqueue(t, x, y, batch, kind);
-        if (rc) return rc;
-        HIPCHK(hipEventRecord(t->ev_in, t->stream));
-        t->step += 1;
-        const double b1 = t->cfg.beta1, b2 = t->cfg.beta2;
-        const float alpha = (float)((double)lr * std::sqrt(1.0 - std::pow(b2, (double)t->step)) / (1.0 - std::pow(b1, (double)t->step)));
-        LCHK(launch_adam(t->P.as<float>(), t->G, t->M.as<float>(), t->V.as<float>(), t->nparam, nullptr, t->cfg.beta1, t->cfg.beta2,
-                         t->cfg.adam_eps, t->stream, alpha, t->scal.as<float>(), t->macc.as<double>()));
-        return gen_train_repack(t);
-    }
+    int rc = check_batch(t, x, y, batch, kind);
+    if (rc) return rc;
     if (kind == CS_MEM_HOST) {
         // pageable host batches: a synchronous step, its scalars added on the host
         float l = 0.0f, m = 0.0f;
-        int rc = cs_train_step(t, x, y, batch, kind, lr, &l, &m);
-        if (rc) return rc;
+        if ((rc = cs_train_step(t, x, y, batch, kind, lr, &l, &m))) return rc;
         t->hacc[0] += l; t->hacc[1] += m; t->hacc[2] += 1.0;
         HIPCHK(hipEventRecord(t->ev_in, t->stream));
         return CS_OK;
     }
     HIPCHK(hipSetDevice(t->device));
-    int rc = ensure_batch(t, batch);
-    if (rc) return rc;
-    if ((rc = copy_in(t, t->x, x, kind, (size_t)batch * kH * kW)) || (rc = copy_in(t, t->y, y, kind, (size_t)batch * kH * kW))) return rc;
-    HIPCHK(hipEventRecord(t->ev_in, t->stream));
-    if ((rc = fb_enqueue(t, batch))) return rc;
-    t->step += 1;
-    const double b1 = t->cfg.beta1, b2 = t->cfg.beta2;
-    const float alpha = (float)((double)lr * std::sqrt(1.0 - std::pow(b2, (double)t->step)) / (1.0 - std::pow(b1, (double)t->step)));
-    LCHK(launch_adam(t->P.as<float>(), t->G, t->M.as<float>(), t->V.as<float>(), t->nparam, nullptr, t->cfg.beta1, t->cfg.beta2,
-                     t->cfg.adam_eps, t->stream, alpha, t->scal.as<float>(), t->macc.as<double>()));
-    return repack(t);
+    if ((rc = stage_batch(t, x, y, batch, kind))) return rc;
+    return step_tail(t, batch, lr);
 }
 
 // ---- cs_train_fit_step: the generator's draws on the host, counter-based -------------------------------------------------
@@ -548,48 +557,19 @@ int cs_train_fit_step(cs_trainer* t, const float* train_device, int64_t n_train,
     for (int64_t b = 0; b < batch; ++b)
         if (idx[b] < 0 || idx[b] >= n_train) return fail(CS_ERR_INVALID, "idx[%lld] = %d is outside the training set of %lld crops", (long long)b, idx[b], (long long)n_train);
     HIPCHK(hipSetDevice(t->device));
-    int rc = t->ref ? ensure_batch(t, batch) : gen_train_ensure_batch(t, batch);
+    int rc = ensure_batch(t, batch);
     if (rc) return rc;
-    // {transforms, indices} of this step in a pinned slot the gather kernel reads directly; a slot is reused once its kernel ran
-    const size_t need = (size_t)batch * (sizeof(cs_aug_affine) + sizeof(int32_t));
-    if (need > t->fit_pin_slot) {
-        HIPCHK(hipStreamSynchronize(t->stream));
-        if (t->fit_pin) { (void)hipHostFree(t->fit_pin); t->fit_pin = nullptr; }
-        HIPCHK(hipHostMalloc(&t->fit_pin, need * cs_trainer::FIT_SLOTS, hipHostMallocDefault));
-        t->fit_pin_slot = need;
-        for (int k = 0; k < cs_trainer::FIT_SLOTS; ++k) {
-            t->fit_used[k] = false;
-            if (!t->ev_fit[k]) HIPCHK(hipEventCreateWithFlags(&t->ev_fit[k], hipEventDisableTiming));
-        }
-    }
-    const int slot = t->fit_next;
-    t->fit_next = (slot + 1) % cs_trainer::FIT_SLOTS;
-    if (t->fit_used[slot]) HIPCHK(hipEventSynchronize(t->ev_fit[slot]));
-    char* pin = (char*)t->fit_pin + (size_t)slot * t->fit_pin_slot;
+    // {transforms, indices} of this step in a pinned slot the gather kernel reads directly
+    char* pin = nullptr;
+    if ((rc = t->fit_ring.acquire((size_t)batch * (sizeof(cs_aug_affine) + sizeof(int32_t)), t->stream, &pin))) return rc;
     cs_aug_affine* tf = (cs_aug_affine*)pin;
     int32_t* ix = (int32_t*)(pin + (size_t)batch * sizeof(cs_aug_affine));
     if (aug && (rc = cs_train_draw_transforms(aug, seed, step, batch, t->H, t->W, tf))) return rc;
     memcpy(ix, idx, (size_t)batch * sizeof(int32_t));
-    if (!t->ref) {
-        // run-time-shaped architectures: their step synchronises by itself (cs_train_step_async's rule)
-        const size_t bytes = (size_t)batch * t->H * t->W * sizeof(float);
-        if ((rc = t->aug_in.ensure(bytes)) || (rc = t->aug_out.ensure(bytes))) return rc;
-        LCHK(launch_fit_gather(train_device, tf, ix, t->aug_out.as<float>(), t->aug_in.as<float>(), batch, t->H, t->W, aug != nullptr, t->stream));
-        HIPCHK(hipEventRecord(t->ev_fit[slot], t->stream));
-        t->fit_used[slot] = true;
-        return cs_train_step_async(t, t->aug_out.as<float>(), t->aug_in.as<float>(), batch, CS_MEM_DEVICE, lr);
-    }
+    // the gather writes the step's input and target straight into t->x / t->y; the step's ev_in then marks the training set as read
     LCHK(launch_fit_gather(train_device, tf, ix, t->x.as<float>(), t->y.as<float>(), batch, t->H, t->W, aug != nullptr, t->stream));
-    HIPCHK(hipEventRecord(t->ev_fit[slot], t->stream));
-    t->fit_used[slot] = true;
-    HIPCHK(hipEventRecord(t->ev_in, t->stream));          // cs_train_inputs_consumed: the training set has been read
-    if ((rc = fb_enqueue(t, batch))) return rc;
-    t->step += 1;
-    const double b1 = t->cfg.beta1, b2 = t->cfg.beta2;
-    const float alpha = (float)((double)lr * std::sqrt(1.0 - std::pow(b2, (double)t->step)) / (1.0 - std::pow(b1, (double)t->step)));
-    LCHK(launch_adam(t->P.as<float>(), t->G, t->M.as<float>(), t->V.as<float>(), t->nparam, nullptr, t->cfg.beta1, t->cfg.beta2,
-                     t->cfg.adam_eps, t->stream, alpha, t->scal.as<float>(), t->macc.as<double>()));
-    return repack(t);
+    if ((rc = t->fit_ring.release(t->stream))) return rc;
+    return step_tail(t, batch, lr);
 }
 
 int cs_train_inputs_consumed(cs_trainer* t, void* hip_stream)
@@ -620,42 +600,49 @@ int cs_train_read_metrics(cs_trainer* t, double* loss_mean, double* mae_mean, in
     return CS_OK;
 }
 
+// evaluation needs the forward tensors only: x, y, the stored activations, the output and the error partials -- not the
+// relu / gradient buffers of a training batch (~15 GB at 1,024 cells of the 128 x 128 variant)
+static int eval_ensure(cs_trainer* t, int64_t b)
+{
+    if (b <= t->maxb || b <= t->eval_maxb) return CS_OK;
+    int rc;
+    const size_t npix = (size_t)t->H * t->W;
+    if ((rc = t->x.ensure(b * npix * 4)) || (rc = t->y.ensure(b * npix * 4))) return rc;
+    for (int l = 0; l < t->n_conv - 1; ++l)
+        if ((rc = t->a[l].ensure(b * t->afl[l] * 4))) return rc;
+    if ((rc = t->out.ensure(b * npix * 4)) || (rc = t->errpart.ensure((size_t)b * 8 * 4))) return rc;
+    t->eval_maxb = b;
+    return CS_OK;
+}
+
 int cs_train_eval(cs_trainer* t, const float* x, const float* y, int64_t n, int kind, float* loss, float* mae)
 {
-    if (!t) return fail(CS_ERR_INVALID, "trainer is NULL");
-    if (!x || !y || n <= 0) return fail(CS_ERR_INVALID, "x/y NULL or n <= 0");
-    if (kind != CS_MEM_HOST && kind != CS_MEM_DEVICE) return fail(CS_ERR_INVALID, "bad mem kind");
-    HIPCHK(hipSetDevice(t->device));
-    if (!t->ref) return gen_train_eval(t, x, y, n, kind, loss, mae);
-    const int64_t ch = n < 4096 ? n : 4096;
-    int rc = ensure_batch(t, ch);
+    int rc = check_batch(t, x, y, n, kind);
     if (rc) return rc;
+    HIPCHK(hipSetDevice(t->device));
+    const int64_t ch = n < t->eval_chunk ? n : t->eval_chunk;
+    if ((rc = eval_ensure(t, ch))) return rc;
     hipStream_t s = t->stream;
     float* P = t->P.as<float>();
     float* MOV = t->MOV.as<float>();
-    for (int l = 0; l < 6; ++l)
+    for (int l = 0; l < t->n_conv - 1; ++l)
         LCHK(launch_pack_ep(P + t->off_b[l], P + t->off_g[l], P + t->off_be[l], MOV + t->off_mm[l], MOV + t->off_mv[l],
-                            t->cfg.bn_eps, kRefChannels[l], t->ep_inf[l].as<float>(), s));
+                            t->cfg.bn_eps, t->ch[l], t->ep_inf[l].as<float>(), s));
+    const size_t npix = (size_t)t->H * t->W;
     double s2 = 0.0, s1 = 0.0;
     std::vector<float> part;
     for (int64_t off = 0; off < n; off += ch) {
         const int64_t nc = (n - off) < ch ? (n - off) : ch;
-        if ((rc = copy_in(t, t->x, x + (size_t)off * kH * kW, kind, (size_t)nc * kH * kW)) ||
-            (rc = copy_in(t, t->y, y + (size_t)off * kH * kW, kind, (size_t)nc * kH * kW)))
+        if ((rc = copy_in(t, t->x, x + (size_t)off * npix, kind, (size_t)nc * npix)) ||
+            (rc = copy_in(t, t->y, y + (size_t)off * npix, kind, (size_t)nc * npix)) || (rc = eval_enqueue(t, nc)))
             return rc;
-        for (int l = 0; l < 6; ++l) {
-            const float* in = l == 0 ? t->x.as<float>() : t->a[l - 1].as<float>();
-            LCHK(launch_conv_mfma(l, in, t->wf[l].as<float>(), t->ep_inf[l].as<float>(), t->a[l].as<float>(), nc, s));
-        }
-        LCHK(launch_conv7_err(t->a[5].as<float>(), t->y.as<float>(), t->w7eff.as<float>(), P + t->off_b[6],
-                              t->errpart.as<float>(), nullptr, nc, s));
         part.resize((size_t)nc * 8);
         HIPCHK(hipMemcpyAsync(part.data(), t->errpart.p, part.size() * 4, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         for (size_t i = 0; i < part.size(); i += 2) { s2 += part[i]; s1 += part[i + 1]; }
     }
-    if (loss) *loss = (float)(s2 / ((double)n * kH * kW));
-    if (mae) *mae = (float)(s1 / ((double)n * kH * kW));
+    if (loss) *loss = (float)(s2 / ((double)n * npix));
+    if (mae) *mae = (float)(s1 / ((double)n * npix));
     return CS_OK;
 }
 
@@ -671,27 +658,13 @@ int cs_train_augment(cs_trainer* t, const float* x, int64_t n, const cs_aug_affi
     const size_t bytes = (size_t)n * t->H * t->W * sizeof(float);
     int rc;
     if ((rc = t->aug_tf.ensure((size_t)n * sizeof(cs_aug_affine)))) return rc;
-    // the parameters travel through a pinned ring (the caller's array may be gone before an asynchronous copy reads it); a slot
-    // is reused only after the copy out of it has run
+    // the parameters travel through a pinned ring (the caller's array may be gone before an asynchronous copy reads it)
     const size_t need = (size_t)n * sizeof(cs_aug_affine);
-    if (need > t->aug_pin_slot) {
-        HIPCHK(hipStreamSynchronize(t->stream));
-        if (t->aug_pin) { (void)hipHostFree(t->aug_pin); t->aug_pin = nullptr; }
-        HIPCHK(hipHostMalloc(&t->aug_pin, need * cs_trainer::AUG_SLOTS, hipHostMallocDefault));
-        t->aug_pin_slot = need;
-        for (int k = 0; k < cs_trainer::AUG_SLOTS; ++k) {
-            t->aug_used[k] = false;
-            if (!t->ev_aug[k]) HIPCHK(hipEventCreateWithFlags(&t->ev_aug[k], hipEventDisableTiming));
-        }
-    }
-    const int slot = t->aug_next;
-    t->aug_next = (slot + 1) % cs_trainer::AUG_SLOTS;
-    if (t->aug_used[slot]) HIPCHK(hipEventSynchronize(t->ev_aug[slot]));
-    char* pin = (char*)t->aug_pin + (size_t)slot * t->aug_pin_slot;
+    char* pin = nullptr;
+    if ((rc = t->aug_ring.acquire(need, t->stream, &pin))) return rc;
     memcpy(pin, tf, need);
     HIPCHK(hipMemcpyAsync(t->aug_tf.p, pin, need, hipMemcpyHostToDevice, t->stream));
-    HIPCHK(hipEventRecord(t->ev_aug[slot], t->stream));
-    t->aug_used[slot] = true;
+    if ((rc = t->aug_ring.release(t->stream))) return rc;
     const float* d_in = x;
     float* d_out = out;
     if (kind == CS_MEM_HOST) {
@@ -751,7 +724,7 @@ int cs_train_import(cs_trainer* t, const float* params_host, const float* moving
     HIPCHK(hipSetDevice(t->device));
     if (params_host) HIPCHK(hipMemcpy(t->P.p, params_host, t->nparam * 4, hipMemcpyHostToDevice));
     if (moving_host) HIPCHK(hipMemcpy(t->MOV.p, moving_host, t->nmov * 4, hipMemcpyHostToDevice));
-    int rc = t->ref ? repack(t) : gen_train_repack(t);
+    int rc = repack(t);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(t->stream));
     return CS_OK;

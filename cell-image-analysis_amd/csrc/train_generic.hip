@@ -13,10 +13,6 @@
 // cs_train_forward_backward -> all-reduce -> cs_train_apply) is what BASELINE.json configs[4] needs from it.
 #include "train_internal.hpp"
 
-#include <cstdlib>
-
-#include <vector>
-
 using namespace cs;
 
 namespace cs {
@@ -274,7 +270,6 @@ int gen_train_setup(cs_trainer* t)
         if ((rc = t->dzsum_part[l].ensure((size_t)BN_MAX_PARTS * cmax * 4))) return rc;
         if ((rc = t->wpart[l].ensure((size_t)gen_parts(t, l) * 9 * t->cin(l) * t->ch[l] * 4))) return rc;
     }
-    if ((rc = t->descs.ensure(2 * TR_MAXL * sizeof(ReduceDesc))) || (rc = t->scal.ensure(16))) return rc;
     // convs that run on bf16 MFMAs (conv_generic_x3.hip: the shape has a plan, cin 32 / 64 / 128, not upsample-fed): forward with
     // the kernel as it is, backward-data with the flipped kernel (channel roles swapped, never upsample-fed: the 2x2 sum follows)
     for (int l = 0; l < t->n_conv; ++l) {
@@ -326,28 +321,18 @@ int gen_train_ensure_batch(cs_trainer* t, int64_t b)
     return CS_OK;
 }
 
-static int gen_copy_in(cs_trainer* t, DevBuf& dst, const float* src, int kind, size_t floats)
-{
-    HIPCHK(hipMemcpyAsync(dst.p, src, floats * 4, kind == CS_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, t->stream));
-    return CS_OK;
-}
-
-// Forward + backward of one batch as stream work only (no host synchronisation once the reduction descriptors of this batch
-// size are uploaded).  The weight gradient of a layer needs only that layer's dz and input: it runs on a second stream beside the
+// Forward + backward of the batch in t->x / t->y as stream work only (no host synchronisation once the reduction descriptors of
+// this batch size are uploaded).  The weight gradient of a layer needs only that layer's dz and input: it runs on a second stream beside the
 // backward-data conv and the BatchNormalization-backward kernels of the layers below (a third of the step's kernel time at
 // batch 32 of the 128 x 128 variant: profiles/r04_*_train_variant_trace.txt); both streams join before the partial sums are reduced.
-int gen_train_fb_enqueue(cs_trainer* t, const float* x, const float* y, int64_t batch, int kind)
+int gen_train_fb_enqueue(cs_trainer* t, int64_t B)
 {
-    int rc = gen_train_ensure_batch(t, batch);
-    if (rc) return rc;
-    const int64_t B = batch;
     hipStream_t s = t->stream;
     float* P = t->P.as<float>();
     float* G = t->G;
     float* MOV = t->MOV.as<float>();
     const int last = t->n_conv - 1;
     const size_t npix = (size_t)t->H * t->W;
-    if ((rc = gen_copy_in(t, t->x, x, kind, B * npix)) || (rc = gen_copy_in(t, t->y, y, kind, B * npix))) return rc;
 
     // ---- forward, BatchNormalization in training mode
     for (int l = 0; l < last; ++l) {
@@ -372,11 +357,6 @@ int gen_train_fb_enqueue(cs_trainer* t, const float* x, const float* y, int64_t 
     // ---- backward
     LCHK(launch_loss_dz(t->out.as<float>(), t->y.as<float>(), (long)B * npix, t->dz[last].as<float>(), t->dzsum_part[last].as<float>(),
                         &t->np_b[last], s, t->errpart.as<float>(), B * 4, t->scal.as<float>()));
-    if (!t->stream2) {
-        HIPCHK(hipStreamCreateWithFlags(&t->stream2, hipStreamNonBlocking));
-        for (int l = 0; l < TR_MAXL; ++l) HIPCHK(hipEventCreateWithFlags(&t->ev_dz[l], hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&t->ev_wg, hipEventDisableTiming));
-    }
     hipStream_t s2 = t->stream2;
     for (int l = last; l >= 0; --l) {
         const int C = t->ch[l], pool = l < t->n_enc, ups = l > t->n_enc;
@@ -406,86 +386,21 @@ int gen_train_fb_enqueue(cs_trainer* t, const float* x, const float* y, int64_t 
             if (ups) LCHK(launch_sumpool2x2(t->dup.as<float>(), t->da[l - 1].as<float>(), B, t->gh[l], t->gw[l], t->cin(l), s));
         }
     }
-    HIPCHK(hipEventRecord(t->ev_wg, s2));
-    HIPCHK(hipStreamWaitEvent(s, t->ev_wg, 0));
-    // ---- all partial sums -> flat gradient, in workgroup order
-    long total = 0;
-    for (int l = 0; l < t->n_conv; ++l) total += 9L * t->cin(l) * t->ch[l] + t->ch[l];
-    if (t->descs_batch != B) {          // the partial counts depend on the batch size only; hdescs outlives the copy
-        for (int l = 0; l < t->n_conv; ++l) {
-            const long klen = 9L * t->cin(l) * t->ch[l];
-            t->hdescs[2 * l] = ReduceDesc{t->off_k[l], klen, t->wpart[l].as<float>(), t->np_w[l], klen};
-            t->hdescs[2 * l + 1] = ReduceDesc{t->off_b[l], (long)t->ch[l], t->dzsum_part[l].as<float>(), t->np_b[l], (long)t->ch[l]};
-        }
-        HIPCHK(hipMemcpyAsync(t->descs.p, t->hdescs, 2 * t->n_conv * sizeof(ReduceDesc), hipMemcpyHostToDevice, s));
-        HIPCHK(hipStreamSynchronize(s));
-        t->descs_batch = B;
-    }
-    LCHK(launch_reduce_all(t->descs.as<ReduceDesc>(), 2 * t->n_conv, total, G, s));
-    return CS_OK;
+    return reduce_gradient(t, B, nullptr);
 }
 
-int gen_train_forward_backward(cs_trainer* t, const float* x, const float* y, int64_t batch, int kind, float* loss, float* mae)
+int gen_train_eval_enqueue(cs_trainer* t, int64_t nc)
 {
-    int rc = gen_train_fb_enqueue(t, x, y, batch, kind);
-    if (rc) return rc;
-    float h[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(h, t->scal.p, 8, hipMemcpyDeviceToHost, t->stream));
-    HIPCHK(hipStreamSynchronize(t->stream));
-    if (loss) *loss = h[0];
-    if (mae) *mae = h[1];
-    return CS_OK;
-}
-
-// evaluation needs the forward tensors only: x, y, the stored activations, the output and the error partials -- not the
-// relu / gradient buffers of a training batch (~15 GB at 1,024 cells of the 128 x 128 variant)
-static int gen_eval_ensure(cs_trainer* t, int64_t b)
-{
-    if (b <= t->maxb || b <= t->eval_maxb) return CS_OK;
-    int rc;
-    const size_t npix = (size_t)t->H * t->W;
-    if ((rc = t->x.ensure(b * npix * 4)) || (rc = t->y.ensure(b * npix * 4))) return rc;
-    for (int l = 0; l < t->n_conv - 1; ++l)
-        if ((rc = t->a[l].ensure(b * t->afl[l] * 4))) return rc;
-    if ((rc = t->out.ensure(b * npix * 4)) || (rc = t->errpart.ensure((size_t)b * 8 * 4))) return rc;
-    t->eval_maxb = b;
-    return CS_OK;
-}
-
-int gen_train_eval(cs_trainer* t, const float* x, const float* y, int64_t n, int kind, float* loss, float* mae)
-{
-    const int64_t ch = n < 1024 ? n : 1024;
-    int rc = gen_eval_ensure(t, ch);
-    if (rc) return rc;
     hipStream_t s = t->stream;
     float* P = t->P.as<float>();
-    float* MOV = t->MOV.as<float>();
     const int last = t->n_conv - 1;
-    const size_t npix = (size_t)t->H * t->W;
-    for (int l = 0; l < last; ++l)
-        LCHK(launch_pack_ep(P + t->off_b[l], P + t->off_g[l], P + t->off_be[l], MOV + t->off_mm[l], MOV + t->off_mv[l], t->cfg.bn_eps, t->ch[l],
-                            t->ep_inf[l].as<float>(), s));
-    double s2 = 0.0, s1 = 0.0;
-    std::vector<float> part;
-    for (int64_t off = 0; off < n; off += ch) {
-        const int64_t nc = (n - off) < ch ? (n - off) : ch;
-        if ((rc = gen_copy_in(t, t->x, x + (size_t)off * npix, kind, (size_t)nc * npix)) ||
-            (rc = gen_copy_in(t, t->y, y + (size_t)off * npix, kind, (size_t)nc * npix)))
-            return rc;
-        for (int l = 0; l < last; ++l) {
-            const float* in = l == 0 ? t->x.as<float>() : t->a[l - 1].as<float>();
-            LCHK(launch_conv_generic(in, P + t->off_k[l], t->ep_inf[l].as<float>(), t->a[l].as<float>(), nc, t->gh[l], t->gw[l], t->cin(l), t->ch[l],
-                                     l > t->n_enc, l < t->n_enc ? GEN_EPI_BN_POOL : GEN_EPI_BN, s));
-        }
-        LCHK(launch_conv_generic(t->a[last - 1].as<float>(), P + t->off_k[last], P + t->off_b[last], t->out.as<float>(), nc, t->gh[last],
-                                 t->gw[last], t->cin(last), 1, last > t->n_enc, GEN_EPI_SIGMOID, s));
-        LCHK(launch_recon_err(t->out.as<float>(), t->y.as<float>(), nc, (int)npix, t->errpart.as<float>(), s));
-        part.resize((size_t)nc * 8);
-        HIPCHK(hipMemcpyAsync(part.data(), t->errpart.p, part.size() * 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        for (size_t i = 0; i < part.size(); i += 2) { s2 += part[i]; s1 += part[i + 1]; }
+    for (int l = 0; l < last; ++l) {
+        const float* in = l == 0 ? t->x.as<float>() : t->a[l - 1].as<float>();
+        LCHK(launch_conv_generic(in, P + t->off_k[l], t->ep_inf[l].as<float>(), t->a[l].as<float>(), nc, t->gh[l], t->gw[l], t->cin(l), t->ch[l],
+                                 l > t->n_enc, l < t->n_enc ? GEN_EPI_BN_POOL : GEN_EPI_BN, s));
     }
-    if (loss) *loss = (float)(s2 / ((double)n * npix));
-    if (mae) *mae = (float)(s1 / ((double)n * npix));
+    LCHK(launch_conv_generic(t->a[last - 1].as<float>(), P + t->off_k[last], P + t->off_b[last], t->out.as<float>(), nc, t->gh[last],
+                             t->gw[last], t->cin(last), 1, last > t->n_enc, GEN_EPI_SIGMOID, s));
+    LCHK(launch_recon_err(t->out.as<float>(), t->y.as<float>(), nc, t->H * t->W, t->errpart.as<float>(), s));
     return CS_OK;
 }

@@ -5,6 +5,48 @@
 
 constexpr int TR_MAXL = CS_MAX_CONV;
 
+// Pinned host slots for per-step parameters that stream work reads after the call has returned: a slot is written again only
+// once the work recorded behind its last use has run.
+template <int N>
+struct PinnedRing {
+    char* pin = nullptr;
+    size_t slot_bytes = 0;
+    hipEvent_t ev[N] = {nullptr};
+    bool used[N] = {false};
+    int next = 0, cur = 0;
+    // *slot <- the next slot, at least `bytes` long (growing the ring drains `s` first)
+    int acquire(size_t bytes, hipStream_t s, char** slot)
+    {
+        if (bytes > slot_bytes) {
+            HIPCHK(hipStreamSynchronize(s));
+            if (pin) { (void)hipHostFree(pin); pin = nullptr; slot_bytes = 0; }
+            HIPCHK(hipHostMalloc((void**)&pin, bytes * N, hipHostMallocDefault));
+            slot_bytes = bytes;
+            for (int k = 0; k < N; ++k) {
+                used[k] = false;
+                if (!ev[k]) HIPCHK(hipEventCreateWithFlags(&ev[k], hipEventDisableTiming));
+            }
+        }
+        cur = next;
+        next = (cur + 1) % N;
+        if (used[cur]) HIPCHK(hipEventSynchronize(ev[cur]));
+        *slot = pin + (size_t)cur * slot_bytes;
+        return CS_OK;
+    }
+    // the work that reads the slot acquired last is enqueued on s
+    int release(hipStream_t s)
+    {
+        HIPCHK(hipEventRecord(ev[cur], s));
+        used[cur] = true;
+        return CS_OK;
+    }
+    ~PinnedRing()
+    {
+        if (pin) (void)hipHostFree(pin);
+        for (auto& e : ev) if (e) (void)hipEventDestroy(e);
+    }
+};
+
 struct cs_trainer {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -12,7 +54,8 @@ struct cs_trainer {
     hipEvent_t ev_dz[TR_MAXL] = {nullptr}, ev_wg = nullptr;
     cs_train_cfg cfg;
     int64_t maxb = 0;
-    int64_t eval_maxb = 0;              // generic trainer: cells the forward-only buffers of cs_train_eval hold
+    int64_t eval_maxb = 0;              // cells the forward-only buffers of cs_train_eval hold
+    int64_t eval_chunk = 4096;          // cells per cs_train_eval chunk (1,024 for the generic form)
     // architecture: ref = the reference graph (64x64, 32-64-32 | 32-64-32-1) on the tuned kernels
     bool ref = true;
     int H = 64, W = 64, n_conv = 7, n_enc = 3;
@@ -33,15 +76,14 @@ struct cs_trainer {
     // batch tensors
     cs::DevBuf x, y, r[TR_MAXL], a[TR_MAXL], out, errpart, dz[TR_MAXL], da[TR_MAXL], stats[TR_MAXL], dup;
     cs::DevBuf aug_tf, aug_in, aug_out;
-    cs::DevBuf part_stats, part_bwd, bwd_sums, dzsum_part[TR_MAXL], wpart[TR_MAXL], descs, scal, zeros;
+    cs::DevBuf part_stats, part_bwd, bwd_sums, dzsum_part[TR_MAXL], wpart[TR_MAXL], descs, scal;
     int np_w[TR_MAXL], np_b[TR_MAXL];
     // the reduction descriptors depend on the batch size only: uploaded when it changes, from memory that outlives the copy
     cs::ReduceDesc hdescs[2 * TR_MAXL];
     int64_t descs_batch = -1;
-    float* hloss = nullptr;             // pinned {loss, mae, alpha staging, -}: read after the step's single synchronisation
-    bool defer_sync = false;            // cs_train_step: forward_backward leaves its results to the sync at the end of apply
-    // cs_train_step_async: epoch metrics on the device {sum loss, sum mae, batches} (double), what synchronous generic steps add
-    // on the host, the event behind the step's input copies, and a pinned ring for the augmentation parameters
+    float* hloss = nullptr;             // pinned {loss, mae}: read after the step's single synchronisation
+    // cs_train_step_async: epoch metrics on the device {sum loss, sum mae, batches} (double), what synchronous steps add on the
+    // host, and the event behind the step's input copies
     cs::DevBuf macc;
     double hacc[3] = {0.0, 0.0, 0.0};
     // synchronised BatchNormalization under data parallelism (cs_train_set_sync_bn): the caller's all-gather, its exchange buffer
@@ -52,27 +94,12 @@ struct cs_trainer {
     int sync_rank = 0, sync_world = 1;
     cs::DevBuf sync_scratch;
     hipEvent_t ev_in = nullptr;
-    static constexpr int AUG_SLOTS = 8;
-    void* aug_pin = nullptr;
-    size_t aug_pin_slot = 0;            // bytes per slot
-    hipEvent_t ev_aug[AUG_SLOTS] = {nullptr};
-    bool aug_used[AUG_SLOTS] = {false};
-    int aug_next = 0;
-    // cs_train_fit_step: per-step {transforms, indices} in a pinned ring the gather kernel reads directly
-    static constexpr int FIT_SLOTS = 16;
-    void* fit_pin = nullptr;
-    size_t fit_pin_slot = 0;
-    hipEvent_t ev_fit[FIT_SLOTS] = {nullptr};
-    bool fit_used[FIT_SLOTS] = {false};
-    int fit_next = 0;
+    PinnedRing<8> aug_ring;             // cs_train_augment: the transforms on their way to the device
+    PinnedRing<16> fit_ring;            // cs_train_fit_step: per-step {transforms, indices} the gather kernel reads directly
     ~cs_trainer()
     {
         if (hloss) (void)hipHostFree(hloss);
-        if (aug_pin) (void)hipHostFree(aug_pin);
-        if (fit_pin) (void)hipHostFree(fit_pin);
-        for (auto& e : ev_fit) if (e) (void)hipEventDestroy(e);
         if (ev_in) (void)hipEventDestroy(ev_in);
-        for (auto& e : ev_aug) if (e) (void)hipEventDestroy(e);
         for (auto& e : ev_dz) if (e) (void)hipEventDestroy(e);
         if (ev_wg) (void)hipEventDestroy(ev_wg);
         if (stream2) (void)hipStreamDestroy(stream2);
@@ -86,10 +113,13 @@ struct cs_trainer {
         if (le__ != hipSuccess) return cs::fail(CS_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(le__)); \
     } while (0)
 
-// train_generic.hip
+// train_api.hip: the backward's two streams join, every partial sum -> the flat gradient t->G in workgroup order; errpart (the
+// reference form) also reduces the forward pass's error partials to the batch's {loss, mae} in t->scal
+int reduce_gradient(cs_trainer* t, int64_t B, const float* errpart);
+
+// train_generic.hip: the run-time-shaped form of the operations the two forms differ in (train_api.hip dispatches them)
 int gen_train_setup(cs_trainer* t);                      // buffers that depend on the architecture only
 int gen_train_repack(cs_trainer* t);                     // flipped / transposed kernels for the backward-data convs
 int gen_train_ensure_batch(cs_trainer* t, int64_t b);
-int gen_train_fb_enqueue(cs_trainer* t, const float* x, const float* y, int64_t batch, int kind);
-int gen_train_forward_backward(cs_trainer* t, const float* x, const float* y, int64_t batch, int kind, float* loss, float* mae);
-int gen_train_eval(cs_trainer* t, const float* x, const float* y, int64_t n, int kind, float* loss, float* mae);
+int gen_train_fb_enqueue(cs_trainer* t, int64_t B);      // the batch in t->x / t->y -> gradient in t->G, {loss, mae} in t->scal
+int gen_train_eval_enqueue(cs_trainer* t, int64_t nc);   // inference forward of nc cells of t->x / t->y -> t->errpart

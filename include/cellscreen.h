@@ -457,8 +457,8 @@ int cs_train_step(cs_trainer *t, const float *x, const float *y, int64_t batch, 
  * metrics are the means over the epoch's batches (fit(), CAE_improved_modeltrain.py:286-293) -- and cs_train_read_metrics
  * fetches them: one host round trip per epoch instead of one per step.  x / y must stay valid until the step's input copies
  * have run; cs_train_inputs_consumed(t, stream) makes `stream` (the caller's, e.g. torch's current stream) wait for exactly
- * that point, and likewise for the device output of the last cs_train_augment.  Host batches and run-time-shaped
- * architectures fall back to a synchronous step whose scalars are added on the host. */
+ * that point, and likewise for the device output of the last cs_train_augment.  Host batches fall back to a synchronous
+ * step whose scalars are added on the host. */
 int cs_train_step_async(cs_trainer *t, const float *x, const float *y, int64_t batch, int kind, float lr);
 int cs_train_inputs_consumed(cs_trainer *t, void *hip_stream);
 /* Mean loss / mae over the cs_train_step_async calls since the last reset, their number; reset != 0 clears the sums.

@@ -128,27 +128,29 @@ def test_adam_update_is_keras_formula():
     tr.close()
 
 
-def test_asynchronous_steps_are_the_synchronous_steps():
+@pytest.mark.parametrize("shape", ["reference", "generic"])
+def test_asynchronous_steps_are_the_synchronous_steps(shape):
     """cs_train_step_async (no host synchronisation, loss / MAE summed on the device, alpha passed by value) against
     cs_train_step on a twin trainer: the same weights bit for bit after several steps, Keras's epoch metrics = the mean of the
     per-step scalars, device-side augmentation in the loop, and a reset that clears the sums."""
     import torch
     from cellscreen.augment import ImageDataGenerator
-    w = synth.random_cae(seed=12, trivial_bn=True)
+    hw, ch = ((64, 64), spec.CHANNELS) if shape == "reference" else ((64, 128), (8, 16, 32, 32, 16, 8, 1))
+    w = synth.random_cae(seed=12, hw=hw, channels=ch, trivial_bn=True)
     a, b = Trainer(w), Trainer(w)
     gen = ImageDataGenerator.reference()
-    X = torch.from_numpy(synth.blob_crops(4, 96)).cuda()
+    X = torch.from_numpy(synth.blob_crops(4, 96, hw=hw)).cuda()
     losses, maes = [], []
     try:
         for i in range(6):
             yb = X[16 * i:16 * i + 16]
-            tf = gen.random_transforms(16, (64, 64), np.random.default_rng(i))
+            tf = gen.random_transforms(16, hw, np.random.default_rng(i))
             xa = a.augment(yb, tf)
             l, m = a.step(xa, yb, 1e-3)
             losses.append(l); maes.append(m)
             b.step_async(b.augment(yb, tf), yb, 1e-3)
             del xa                                                   # the allocator may hand these bytes out again at once
-            junk = torch.full((16, 64, 64), float("nan"), device="cuda")    # ... to this: the steps must have read them before
+            junk = torch.full((16,) + hw, float("nan"), device="cuda")      # ... to this: the steps must have read them before
             del junk
         lo, ma, n = b.read_metrics(reset=True)
         assert n == 6 and abs(lo - np.mean(losses)) <= 1e-6 * abs(lo) and abs(ma - np.mean(maes)) <= 1e-6 * abs(ma)
@@ -157,7 +159,7 @@ def test_asynchronous_steps_are_the_synchronous_steps():
         assert np.array_equal(pa, pb) and np.array_equal(ma_, mb_)
         assert b.read_metrics()[2] == 0
         # host batches fall back to a synchronous step and still count
-        b.step_async(synth.blob_crops(5, 8), synth.blob_crops(5, 8), 1e-3)
+        b.step_async(synth.blob_crops(5, 8, hw=hw), synth.blob_crops(5, 8, hw=hw), 1e-3)
         assert b.read_metrics()[2] == 1
     finally:
         a.close(); b.close()
@@ -199,6 +201,10 @@ def test_fit_step_is_gather_augment_and_step_in_one_call(shape):
             a.fit_step(X, np.array([0, 200], np.int32), None)                           # outside the training set: refused, nothing enqueued
         with pytest.raises(CellScreenError):
             a.fit_step(X, np.array([-1], np.int32), None)
+        with pytest.raises(ValueError):
+            a.fit_step(X.cpu(), idx, None)                                              # host memory behind the pointer: refused
+        with pytest.raises(ValueError):
+            a.fit_step(X[:, :, :32].contiguous(), idx, None)                            # crops of another H x W: refused
     finally:
         a.close(); b.close(); c.close()
 

@@ -297,3 +297,21 @@ def test_training_mirror_validates_detector_fit_choice(tmp_path):
     assert ImprovedAnomalyDetectionTraining(str(tmp_path), detector_fit="sklearn").detector_fit == "sklearn"
     with pytest.raises(ValueError):
         ImprovedAnomalyDetectionTraining(str(tmp_path), detector_fit="cpu")
+
+
+def test_fit_step_refuses_a_training_set_it_would_read_out_of_range():
+    """Trainer.fit_step hands the library a bare pointer: host memory, another device's memory or crops of another H x W are
+    refused before the call (a handle without a library behind it: nothing here reaches a GPU)."""
+    import types
+    import torch
+    from cellscreen.trainer import Trainer
+    t = Trainer.__new__(Trainer)
+    t._h, t._device_id, t.input_hw, t._fit_train = None, 0, (64, 64), None
+    idx = np.zeros(4, np.int32)
+
+    def on(dev, shape):                      # what fit_step looks at of a CUDA tensor
+        return types.SimpleNamespace(is_cuda=True, device=torch.device("cuda", dev), shape=shape, dim=lambda: len(shape))
+    for train in (torch.zeros(8, 64, 64), np.zeros((8, 64, 64), np.float32), on(1, (8, 64, 64)), on(0, (8, 64, 32)),
+                  on(0, (8, 64, 64, 3)), on(0, (8, 32, 64, 1))):
+        with pytest.raises(ValueError):
+            t.fit_step(train, idx)
