@@ -126,6 +126,8 @@ SIGNATURES = {
     "cs_preproc_create": (_I, [_I, C.POINTER(_P)]),
     "cs_preproc_free": (None, [_P]),
     "cs_preproc_wait_stream": (_I, [_P, _P]),
+    "cs_preproc_set_output_size": (_I, [_P, C.c_int32, C.c_int32]),
+    "cs_preproc_get_output_size": (_I, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "cs_preprocess": (_I, [_P, _P, _I, _L, _I, _P, _P, _P, _L, C.c_double, _P, _P, _I]),
     "cs_preproc_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(_L)]),
     "cs_extract_measure": (_I, [_P, _P, _I, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _I, C.c_int32,

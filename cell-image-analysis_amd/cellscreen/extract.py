@@ -24,7 +24,7 @@ from typing import Callable, List, NamedTuple, Optional
 import numpy as np
 
 from . import _lib as L
-from .preprocess import CLIP_LIMIT, OUT_SIDE, PIX_U8, PIX_U16, Preprocessor
+from .preprocess import CLIP_LIMIT, MAX_RATIO, OUT_SIDE, PIX_U8, PIX_U16, Preprocessor, check_out_hw
 
 QC_BORDER, QC_AREA, QC_ECCENTRICITY, QC_INTENSITY = 1, 2, 4, 8          # cs_region.failed bits
 IMAGE_OK, IMAGE_NO_CELLS, IMAGE_UNSUPPORTED = 0, 1, 2                   # per-image status
@@ -51,7 +51,7 @@ def qc_params(**kw) -> L.CSQcParams:
 
 
 class Extraction(NamedTuple):
-    cells: object               # float32 [n,64,64]: numpy, or a torch CUDA tensor
+    cells: object               # float32 [n,out_h,out_w]: numpy, or a torch CUDA tensor
     cell_image: np.ndarray      # int32 [n]: image index of each cell
     regions: np.ndarray         # L.REGION_DTYPE [n_regions]: every region, passing or not, in (image, label) order
     status: np.ndarray          # int32 [B]: IMAGE_OK / IMAGE_NO_CELLS / IMAGE_UNSUPPORTED
@@ -71,9 +71,11 @@ def _is_tensor(a) -> bool:
 
 
 class CellExtractor:
-    """One preprocess handle (one GPU, one stream) that turns label images into screened-ready cells."""
+    """One preprocess handle (one GPU, one stream) that turns label images into screened-ready cells of
+    out_hw = (out_h, out_w): 64 x 64 by default, (H, W) for a model built with input_shape=(H, W, 1)."""
 
-    def __init__(self, device_id: int = 0, **qc):
+    def __init__(self, device_id: int = 0, out_hw=(OUT_SIDE, OUT_SIDE), **qc):
+        self.out_hw = check_out_hw(out_hw)
         self._lib = L.load_library()
         self.device_id = device_id
         self.qc = dict(REFERENCE_QC, **qc)
@@ -83,7 +85,7 @@ class CellExtractor:
     @property
     def _handle(self):
         if self._pre is None:
-            self._pre = Preprocessor(self.device_id)
+            self._pre = Preprocessor(self.device_id, self.out_hw)
         return self._pre._h
 
     def close(self):
@@ -197,13 +199,14 @@ class CellExtractor:
         """images: [B,H,W] or [B,H,W,C] uint8/uint16 (the analysis channel is `channel`, default 1 of >= 3 channels as
         improved_detection.py:57, 0 of one); labels: [B,H,W] integer, 0 = background.  numpy arrays or CUDA tensors of the
         extractor's device.  out: None -- cells as numpy for numpy inputs, as a CUDA float32 tensor for tensor inputs -- or a
-        CUDA float32 tensor [>= n,64,64] to fill (the result is its first n cells)."""
+        CUDA float32 tensor [>= n,out_h,out_w] to fill (the result is its first n cells)."""
         B, H, W, Cn, channel, ptype, on_dev = self._check(images, labels, channel)
+        oh, ow = self.out_hw
         if out is not None:
             import torch
             if not (_is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 3
-                    and tuple(out.shape[1:]) == (OUT_SIDE, OUT_SIDE) and out.device.index == self.device_id):
-                raise ValueError("out must be a contiguous CUDA float32 tensor [n,64,64] on the extractor's device")
+                    and tuple(out.shape[1:]) == (oh, ow) and out.device.index == self.device_id):
+                raise ValueError(f"out must be a contiguous CUDA float32 tensor [n,{oh},{ow}] on the extractor's device")
         if on_dev:
             lab, max_label, maps = self._relabel_device(labels)
         else:
@@ -225,13 +228,13 @@ class CellExtractor:
                     raise ValueError(f"out holds {out.shape[0]} cells, the batch yields {n}")
                 cells = out[:n]
             else:
-                cells = torch.empty((n, OUT_SIDE, OUT_SIDE), dtype=torch.float32, device=dev)
+                cells = torch.empty((n, oh, ow), dtype=torch.float32, device=dev)
             L.order_after_torch(self._lib.cs_preproc_wait_stream, self._handle, cells)
             L.check(self._lib.cs_extract_fill(self._handle, regions.ctypes.data, status.ctypes.data, L.CS_MEM_HOST,
                                               cells.data_ptr() if n else None, None, L.CS_MEM_DEVICE))
             cell_image = regions["image"][regions["cell"] >= 0].astype(np.int32)     # the same indices, from the host table
         else:
-            cells = np.empty((n, OUT_SIDE, OUT_SIDE), np.float32)
+            cells = np.empty((n, oh, ow), np.float32)
             cell_image = np.empty(n, np.int32)
             L.check(self._lib.cs_extract_fill(self._handle, regions.ctypes.data, status.ctypes.data, L.CS_MEM_HOST,
                                               cells.ctypes.data, cell_image.ctypes.data, L.CS_MEM_HOST))
@@ -242,7 +245,7 @@ class CellExtractor:
         return Extraction(cells, cell_image, regions, status)
 
     def extract(self, image, labels):
-        """One image ([H,W] or [H,W,C]) and its [H,W] labels -> (cells float32 [n,64,64], stats dicts), the return value of
+        """One image ([H,W] or [H,W,C]) and its [H,W] labels -> (cells float32 [n,out_h,out_w], stats dicts), the return value of
         the reference's extract_quality_cells.  An image whose status is not OK raises, as the reference's extraction does
         inside its per-file try (improved_detection.py:113-115)."""
         r = self.extract_batch(image[None], labels[None])
@@ -250,8 +253,15 @@ class CellExtractor:
         if st == IMAGE_NO_CELLS:
             raise ValueError("a passing region has a bounding-box side below 8 px: equalize_adapthist raises on it")
         if st == IMAGE_UNSUPPORTED:
-            raise ValueError("a passing region has a bounding-box side above 1024 px: beyond the preprocess kernel")
+            raise ValueError(self._unsupported_text() + ": beyond the preprocess kernel")
         return r.cells, region_stats(r.regions)
+
+    def _unsupported_text(self) -> str:
+        oh, ow = self.out_hw
+        if (oh, ow) == (OUT_SIDE, OUT_SIDE):
+            return "a passing region has a bounding-box side above 1024 px"
+        return (f"a passing region has a bounding-box side above 1024 px or above {MAX_RATIO} x the output size "
+                f"{oh}x{ow} on its axis")
 
     def last_timing(self):
         a, b, c = C.c_double(), C.c_double(), C.c_double()
@@ -280,11 +290,14 @@ def split_channels(image: np.ndarray):
     raise ValueError(f"image of shape {image.shape}: a 2-D image or [H,W,>=3] channels expected")
 
 
-def label_cell_extractor(segment: Callable[[np.ndarray], np.ndarray], device_id: int = 0, **qc):
+def label_cell_extractor(segment: Callable[[np.ndarray], np.ndarray], device_id: int = 0, out_hw=(OUT_SIDE, OUT_SIDE), **qc):
     """The `cell_extractor(image_path) -> (cells, stats)` that ProductionMutantScreening accepts, from a segmenter
     `segment(seg_channel) -> labels`.  The seg channel is handed over untouched (csbdeep's normalize belongs to the
     segmenter), e.g. label_cell_extractor(lambda seg: model.predict_instances(normalize(seg))[0]).  Errors raise; the
-    screening driver's try turns them into the reference's "Error processing" line and ([], [])."""
+    screening driver's try turns them into the reference's "Error processing" line and ([], []).
+    out_hw: the size of the cells, 64 x 64 as the reference's resize by default; for a model built with
+    input_shape=(H, W, 1) pass out_hw=(H, W)."""
+    out_hw = check_out_hw(out_hw)
     ext = {}
 
     def cell_extractor(image_path: str):
@@ -294,12 +307,12 @@ def label_cell_extractor(segment: Callable[[np.ndarray], np.ndarray], device_id:
         if labels.shape != img.shape[:2]:
             raise ValueError(f"segmenter returned labels of shape {labels.shape} for an image of {img.shape[:2]}")
         if "x" not in ext:
-            ext["x"] = CellExtractor(device_id, **qc)
+            ext["x"] = CellExtractor(device_id, out_hw, **qc)
         r = ext["x"].extract_batch(np.ascontiguousarray(img)[None], np.ascontiguousarray(labels)[None], channel=ch)
         st = int(r.status[0])
         if st != IMAGE_OK:
             raise ValueError("a passing region has a bounding-box side below 8 px (equalize_adapthist raises)" if st == IMAGE_NO_CELLS
-                             else "a passing region has a bounding-box side above 1024 px (beyond the preprocess kernel)")
+                             else ext["x"]._unsupported_text() + " (beyond the preprocess kernel)")
         return list(r.cells), region_stats(r.regions)
 
     return cell_extractor

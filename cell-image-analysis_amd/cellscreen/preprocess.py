@@ -6,7 +6,10 @@
 (improved_detection.py:98-99, CAE_improved_modeltrain.py:92-93), for a whole list of ragged crops
 in one call.  All arithmetic happens in libcellscreen.so (csrc/preprocess.hip); there is no CPU
 fallback.  The result is the float32 [n,64,64] array `compute_anomaly_scores` builds at
-improved_detection.py:122, either as a numpy array or left on the device as a torch tensor."""
+improved_detection.py:122, either as a numpy array or left on the device as a torch tensor.
+
+A model of another input size reads crops of that size: `Preprocessor(out_hw=(H, W))` is the reference's
+`resize(cell_image_eq, (H, W), anti_aliasing=True)`, result [n,H,W]."""
 from __future__ import annotations
 
 import ctypes as C
@@ -17,7 +20,9 @@ import numpy as np
 from . import _lib as L
 
 CLIP_LIMIT = 0.02           # improved_detection.py:98
-OUT_SIDE = 64               # improved_detection.py:99
+OUT_SIDE = 64               # improved_detection.py:99: the default output size is (OUT_SIDE, OUT_SIDE)
+OUT_MIN, OUT_MAX = 8, 512   # accepted output sides (include/cellscreen.h)
+MAX_RATIO = 16              # a crop side may be at most MAX_RATIO x the output side on its axis
 PIX_U8, PIX_U16 = 0, 1
 MEM_HOST, MEM_DEVICE = 0, 1
 
@@ -47,14 +52,45 @@ def pack_crops(crops: Sequence[np.ndarray]) -> Tuple[np.ndarray, np.ndarray, np.
     return pixels, offsets, hs, ws
 
 
-class Preprocessor:
-    """One cs_preproc handle (one GPU, one stream)."""
+def check_out_hw(out_hw) -> Tuple[int, int]:
+    """(out_h, out_w) as two Python ints, or ValueError: a pair of integers, each in [OUT_MIN, OUT_MAX]."""
+    try:
+        hw = tuple(out_hw)
+    except TypeError:
+        raise ValueError(f"out_hw must be a pair (out_h, out_w), got {out_hw!r}") from None
+    if len(hw) != 2:
+        raise ValueError(f"out_hw must be a pair (out_h, out_w), got {out_hw!r}")
+    for v in hw:
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"out_hw must hold integers, got {out_hw!r}")
+        if not OUT_MIN <= int(v) <= OUT_MAX:
+            raise ValueError(f"out_hw {out_hw!r}: each side must lie in [{OUT_MIN}, {OUT_MAX}]")
+    return int(hw[0]), int(hw[1])
 
-    def __init__(self, device_id: int = 0):
+
+class Preprocessor:
+    """One cs_preproc handle (one GPU, one stream) that produces cells of out_hw = (out_h, out_w), 64 x 64 by default."""
+
+    def __init__(self, device_id: int = 0, out_hw=(OUT_SIDE, OUT_SIDE)):
+        out_hw = check_out_hw(out_hw)
         self._lib = L.load_library()
         self._h = C.c_void_p()
         L.check(self._lib.cs_preproc_create(device_id, C.byref(self._h)))
         self.device_id = device_id
+        self._out_hw = (OUT_SIDE, OUT_SIDE)
+        self.out_hw = out_hw
+
+    @property
+    def out_hw(self) -> Tuple[int, int]:
+        return self._out_hw
+
+    @out_hw.setter
+    def out_hw(self, out_hw):
+        """Takes effect from the next call; an untouched handle is never told a size."""
+        out_hw = check_out_hw(out_hw)
+        if out_hw != self._out_hw:
+            L.check(self._lib.cs_preproc_set_output_size(self._h, out_hw[0], out_hw[1]))
+            self._out_hw = out_hw
 
     def close(self):
         if self._h:
@@ -70,9 +106,10 @@ class Preprocessor:
     def run_packed(self, pixels, offsets: np.ndarray, heights: np.ndarray, widths: np.ndarray,
                    clip_limit: float = CLIP_LIMIT, out=None, want_clahe: bool = False):
         """pixels: 1-D numpy array (host) or torch CUDA tensor (device) of uint8/uint16.
-        out: None (numpy result), or a torch CUDA float32 tensor [n,64,64] to fill in place.
+        out: None (numpy result), or a torch CUDA float32 tensor [n,out_h,out_w] to fill in place.
         Returns out, or (out, clahe_u16) with want_clahe."""
         n = int(len(offsets))
+        oh, ow = self._out_hw
         offsets = np.ascontiguousarray(offsets, np.int64)
         heights = np.ascontiguousarray(heights, np.int32)
         widths = np.ascontiguousarray(widths, np.int32)
@@ -99,7 +136,7 @@ class Preprocessor:
             pix_ptr, n_pix = pixels.ctypes.data, pixels.size
         clahe = None
         if out is None:
-            res = np.empty((n, OUT_SIDE, OUT_SIDE), np.float32)
+            res = np.empty((n, oh, ow), np.float32)
             out_ptr, out_kind = res.ctypes.data, MEM_HOST
             if want_clahe:
                 clahe = np.zeros(n_pix, np.uint16)
@@ -107,8 +144,8 @@ class Preprocessor:
         else:
             import torch
             if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
-                    and tuple(out.shape) == (n, OUT_SIDE, OUT_SIDE)):
-                raise ValueError("out must be a contiguous CUDA float32 tensor of shape [n,64,64]")
+                    and tuple(out.shape) == (n, oh, ow)):
+                raise ValueError(f"out must be a contiguous CUDA float32 tensor of shape [n,{oh},{ow}]")
             res, out_ptr, out_kind = out, out.data_ptr(), MEM_DEVICE
             if want_clahe:
                 clahe = torch.zeros(n_pix, dtype=torch.int16, device=out.device)     # gaps between crops read 0; ordered before the kernel below
@@ -120,7 +157,7 @@ class Preprocessor:
         return (res, clahe) if want_clahe else res
 
     def __call__(self, crops: Sequence[np.ndarray], clip_limit: float = CLIP_LIMIT) -> np.ndarray:
-        """List of 2-D uint8/uint16 crops -> float32 [n,64,64]."""
+        """List of 2-D uint8/uint16 crops -> float32 [n,out_h,out_w]."""
         pixels, offsets, hs, ws = pack_crops(crops)
         return self.run_packed(pixels, offsets, hs, ws, clip_limit)
 

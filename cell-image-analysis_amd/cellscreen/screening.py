@@ -5,7 +5,8 @@ with the arithmetic of compute_anomaly_scores executed by libcellscreen on the G
 Out of scope here: the StarDist segmentation itself (:44, :59-60) -- supply a
 `cell_extractor(image_path) -> (list_of_64x64_arrays, list_of_stat_dicts)`, e.g.
 cellscreen.extract.label_cell_extractor(segment), which runs the rest of :48-115 on the GPU, or pre-extracted
-`.npy` crop files; plots and the text report (:263-403)."""
+`.npy` crop files; plots and the text report (:263-403).  For a model of another input size the cells have that size:
+label_cell_extractor(segment, out_hw=(H, W))."""
 from __future__ import annotations
 
 import os
@@ -60,11 +61,12 @@ class ProductionMutantScreening:
 
     def preprocess_crops(self, raw_crops) -> np.ndarray:
         """:98-99 for a list of raw bounding-box crops (uint8 / uint16, ragged):
-        equalize_adapthist(clip_limit=0.02) + resize((64, 64), anti_aliasing=True) on the GPU.
+        equalize_adapthist(clip_limit=0.02) + resize((H, W), anti_aliasing=True) on the GPU, (H, W) being the loaded
+        model's input size (64 x 64 for the reference graph): the result is what compute_anomaly_scores takes.
         A `cell_extractor` that segments images can call this instead of scikit-image."""
         if getattr(self, "_preproc", None) is None:
             from .preprocess import Preprocessor
-            self._preproc = Preprocessor(self.device_id)
+            self._preproc = Preprocessor(self.device_id, (self.engine.info.height, self.engine.info.width))
         return self._preproc(raw_crops)
 
     # ---- the hot path -------------------------------------------------------------------

@@ -85,7 +85,10 @@ class ImprovedAnomalyDetectionTraining:
         """:113-151 with the cell extraction of :39-111 supplied by the caller: `cell_extractor(image_path) -> (cells, stats)`,
         e.g. cellscreen.extract.label_cell_extractor(segment) (quality rules + crop preprocess on the GPU; the segmenter is
         the caller's, StarDist in the reference).  Writes cell_statistics.csv and file_summary.csv with the reference's
-        columns and pandas calls, returns (np.array(cells), stats_df).  The text report (:153-182) is out of scope."""
+        columns and pandas calls, returns (np.array(cells), stats_df).  The text report (:153-182) is out of scope.
+        The cells have the extractor's size: for a model that is not 64 x 64, the reference's two edits (the resize at :93
+        and input_shape) are label_cell_extractor(segment, out_hw=(H, W)) here and
+        create_improved_autoencoder(input_shape=(H, W, 1))."""
         import pandas as pd
         from glob import glob
         print("=== Creating High-Quality Training Dataset ===")
@@ -121,7 +124,10 @@ class ImprovedAnomalyDetectionTraining:
         kernels, zero biases, BN gamma 1 / beta 0 / moving mean 0 / moving var 1 -- the Keras defaults) and its encoder
         half, which shares the same arrays as the reference's two Models share their layers.  input_shape is generic as in
         the reference: the same seven convs on another crop size (whether the kernels take that size is decided where the
-        weights meet them: Trainer / Engine raise CS_ERR_UNSUPPORTED with the reason)."""
+        weights meet them: Trainer / Engine raise CS_ERR_UNSUPPORTED with the reason).  Crops of that size come from
+        label_cell_extractor(segment, out_hw=(H, W)) / Preprocessor(out_hw=(H, W)); the two lines of a non-64 model are
+            cells, _ = trainer.create_training_dataset(folder, label_cell_extractor(segment, out_hw=(H, W)))
+            ae, enc = trainer.create_improved_autoencoder(input_shape=(H, W, 1))"""
         if len(input_shape) not in (2, 3) or (len(input_shape) == 3 and input_shape[2] != 1):
             raise ValueError(f"input_shape {tuple(input_shape)}: the reference's model takes one grey-level channel")
         ae = synth.random_cae(seed=self.seed, hw=(int(input_shape[0]), int(input_shape[1])), trivial_bn=True)

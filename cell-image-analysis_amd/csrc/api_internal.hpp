@@ -71,10 +71,17 @@ struct CropDesc {
     long long off;      // element offset of the crop's first pixel in the ragged pixel buffer
     int H, W;
 };
+// What the preprocess accepts (include/cellscreen.h): output sides, crop sides, and per axis side <= kPreprocMaxRatio * out --
+// the ratio that bounds the anti-aliasing Gaussian's radius (preprocess.hip PP_MAX_TAPS).  cs_preprocess checks crops on the
+// host, the extraction's region pass on the device, both with preproc_side_beyond, so they cannot disagree about a crop.
+static constexpr int kPreprocMin = 8, kPreprocMax = 1024, kPreprocMaxRatio = 16;
+static constexpr int kPreprocOutMin = 8, kPreprocOutMax = 512;
+__host__ __device__ inline bool preproc_side_beyond(int side, int out) { return side > kPreprocMax || side > kPreprocMaxRatio * out; }
 // Enqueues the preprocess kernel on n crops whose descriptors are already in device (or mapped) memory; lds = the dynamic LDS
-// bytes the largest crop needs (preprocess_lds_bytes).  The arithmetic is cs_preprocess's, so the cells are bit-identical.
+// bytes the largest crop needs (preprocess_lds_bytes); out: [n][out_h][out_w].  The arithmetic is cs_preprocess's, so the
+// cells are bit-identical.
 hipError_t launch_preprocess(const void* pix, int pixel_type, const CropDesc* desc, int64_t n, double clip_limit, size_t lds,
-                             uint16_t* clahe, float* out, hipStream_t stream);
+                             uint16_t* clahe, float* out, int out_h, int out_w, hipStream_t stream);
 struct ExtractState;                            // extract.hip: the state between cs_extract_measure and cs_extract_fill
 void extract_state_free(ExtractState* s);
 
@@ -89,6 +96,8 @@ struct cs_preproc {
     int device = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    int out_h = 64, out_w = 64;         // cs_preproc_set_output_size; read by the next cs_preprocess / cs_extract_measure
+    bool extract_pending = false;       // a cs_extract_measure whose cs_extract_fill has not run yet: the size is frozen
     cs::DevBuf pix, clahe, out;
     // crop descriptors: pinned host memory the kernel reads directly (24 B per crop).  A host-to-device COPY of them would
     // queue on the DMA engine behind whatever the caller has in flight there -- e.g. the raw pixels of the NEXT chunk it is

@@ -36,7 +36,6 @@ static constexpr int LP_COLS = 4 * 64;                  // columns per wave (4 p
 static constexpr int kMaxLabel = 1 << 20;               // per image
 static constexpr int64_t kMaxSlots = 1 << 22;           // batch * max_label
 static constexpr int kMaxSide = 4096;                   // image height / width (LDS of the region pass: ~20 B per row)
-static constexpr int kPreprocMin = 8, kPreprocMax = 1024;
 static constexpr int SCAN_THREADS = 1024;
 
 struct ExQc {
@@ -241,7 +240,8 @@ __device__ inline int chain_segment(const int* ch, int n, int y)
 template <typename PIX>
 __global__ __launch_bounds__(EX_THREADS) void ex_region_pass(const int* __restrict__ labels, const PIX* __restrict__ image, int C, int ch,
                                                              int H, int W, int max_label, const int4* __restrict__ bbox, ExQc qc,
-                                                             cs_region* __restrict__ rec, unsigned int* __restrict__ img_flags)
+                                                             int out_h, int out_w, cs_region* __restrict__ rec,
+                                                             unsigned int* __restrict__ img_flags)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char ex_lds[];
     short* rowL = (short*)ex_lds;
@@ -356,7 +356,7 @@ __global__ __launch_bounds__(EX_THREADS) void ex_region_pass(const int* __restri
     rec[s] = r;
     if (failed == 0u) {
         if (min(h, w) < kPreprocMin) atomicOr(&img_flags[b], 1u);
-        if (max(h, w) > kPreprocMax) atomicOr(&img_flags[b], 2u);
+        if (preproc_side_beyond(h, out_h) || preproc_side_beyond(w, out_w)) atomicOr(&img_flags[b], 2u);   // cs_preprocess's rule
     }
 }
 
@@ -483,6 +483,7 @@ struct ExtractState {
     bool measured = false;
     const void* d_img = nullptr;
     int ptype = 0, C = 1, ch = 0, batch = 0, H = 0, W = 0, max_label = 0;
+    int out_h = 64, out_w = 64;                         // the handle's output size at the measure: sizes the fill's cells
     int64_t nslots = 0;
     double clip_limit = 0.02;
     ExCounts host{};
@@ -536,6 +537,8 @@ int cs_extract_measure(cs_preproc* p, const void* image, int pixel_type, int32_t
     if (!p->ext) p->ext = new ExtractState();
     ExtractState& S = *p->ext;
     S.measured = false;
+    p->extract_pending = false;
+    const int out_h = p->out_h, out_w = p->out_w;
     for (hipEvent_t& e : S.ev)
         if (!e) HIPCHK(hipEventCreate(&e));
 
@@ -578,12 +581,12 @@ int cs_extract_measure(cs_preproc* p, const void* image, int pixel_type, int32_t
             HIPCHK(hipFuncSetAttribute((const void*)ex_region_pass<unsigned char>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             hipLaunchKernelGGL(ex_region_pass<unsigned char>, dim3((unsigned)nslots), dim3(EX_THREADS), lds, p->stream, d_lab,
                                (const unsigned char*)d_img, (int)channels, (int)channel, (int)height, (int)width, (int)max_label,
-                               S.bbox.as<int4>(), eq, S.rec.as<cs_region>(), S.flags.as<unsigned int>());
+                               S.bbox.as<int4>(), eq, out_h, out_w, S.rec.as<cs_region>(), S.flags.as<unsigned int>());
         } else {
             HIPCHK(hipFuncSetAttribute((const void*)ex_region_pass<unsigned short>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             hipLaunchKernelGGL(ex_region_pass<unsigned short>, dim3((unsigned)nslots), dim3(EX_THREADS), lds, p->stream, d_lab,
                                (const unsigned short*)d_img, (int)channels, (int)channel, (int)height, (int)width, (int)max_label,
-                               S.bbox.as<int4>(), eq, S.rec.as<cs_region>(), S.flags.as<unsigned int>());
+                               S.bbox.as<int4>(), eq, out_h, out_w, S.rec.as<cs_region>(), S.flags.as<unsigned int>());
         }
         HIPCHK(hipGetLastError());
     }
@@ -605,7 +608,9 @@ int cs_extract_measure(cs_preproc* p, const void* image, int pixel_type, int32_t
     S.ptype = pixel_type; S.C = channels; S.ch = channel; S.batch = batch; S.H = height; S.W = width; S.max_label = max_label;
     S.nslots = nslots;
     S.clip_limit = q.clip_limit;
+    S.out_h = out_h; S.out_w = out_w;
     S.measured = true;
+    p->extract_pending = true;
     *n_regions = S.host.n_regions;
     *n_cells = S.host.n_cells;
     return CS_OK;
@@ -625,6 +630,7 @@ int cs_extract_fill(cs_preproc* p, cs_region* regions, int32_t* image_status, in
     ExtractState& S = *p->ext;
     const int64_t nreg = S.host.n_regions, ncell = S.host.n_cells;
     const bool tdev = table_kind == CS_MEM_DEVICE, dev = cells_kind == CS_MEM_DEVICE;
+    const size_t cell = (size_t)S.out_h * S.out_w;       // floats of one cell, as measured
     int rc;
     cs_region* d_reg = nullptr;
     if (regions && nreg > 0) {
@@ -650,7 +656,7 @@ int cs_extract_fill(cs_preproc* p, cs_region* regions, int32_t* image_status, in
             if ((rc = S.cpix.ensure((size_t)S.host.crop_px * esz)) || (rc = S.clahe.ensure((size_t)S.host.crop_px * sizeof(uint16_t)))) return rc;
             if (dev) d_cells = cells;
             else {
-                if ((rc = S.cells.ensure((size_t)ncell * 64 * 64 * sizeof(float)))) return rc;
+                if ((rc = S.cells.ensure((size_t)ncell * cell * sizeof(float)))) return rc;
                 d_cells = S.cells.as<float>();
             }
         }
@@ -671,7 +677,7 @@ int cs_extract_fill(cs_preproc* p, cs_region* regions, int32_t* image_status, in
                                S.C, S.ch, S.H, S.W, S.desc.as<CropDesc>(), S.gat.as<GatherDesc>(), S.cpix.as<unsigned short>());
         HIPCHK(hipGetLastError());
         HIPCHK(launch_preprocess(S.cpix.p, S.ptype, S.desc.as<CropDesc>(), ncell, S.clip_limit, (size_t)S.host.lds, S.clahe.as<uint16_t>(),
-                                 d_cells, p->stream));
+                                 d_cells, S.out_h, S.out_w, p->stream));
     }
     HIPCHK(hipEventRecord(S.ev[4], p->stream));
     if (image_status) {
@@ -681,12 +687,13 @@ int cs_extract_fill(cs_preproc* p, cs_region* regions, int32_t* image_status, in
     if (!tdev && d_reg) HIPCHK(hipMemcpyAsync(regions, d_reg, nreg * sizeof(cs_region), hipMemcpyDeviceToHost, p->stream));
     if (!dev) {
         if (d_cimg) HIPCHK(hipMemcpyAsync(cell_image, d_cimg, ncell * sizeof(int), hipMemcpyDeviceToHost, p->stream));
-        if (d_cells) HIPCHK(hipMemcpyAsync(cells, d_cells, (size_t)ncell * 64 * 64 * sizeof(float), hipMemcpyDeviceToHost, p->stream));
+        if (d_cells) HIPCHK(hipMemcpyAsync(cells, d_cells, (size_t)ncell * cell * sizeof(float), hipMemcpyDeviceToHost, p->stream));
     }
     HIPCHK(hipStreamSynchronize(p->stream));              // host synchronisation 2 of 2: the table and the cells
     float ms = 0.f;
     HIPCHK(hipEventElapsedTime(&ms, S.ev[3], S.ev[4]));
     S.cells_ms = ms;
+    p->extract_pending = false;                           // the handle's output size may change again
     return CS_OK;
 }
 

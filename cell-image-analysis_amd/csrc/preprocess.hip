@@ -1,21 +1,24 @@
 // preprocess.hip -- per-crop preprocess of the screening path on gfx950:
 //
 //     cell_image_eq      = exposure.equalize_adapthist(cell_image, clip_limit=0.02)
-//     cell_image_resized = resize(cell_image_eq, (64, 64), anti_aliasing=True)
+//     cell_image_resized = resize(cell_image_eq, (out_h, out_w), anti_aliasing=True)
 //
-// (improved_detection.py:98-99, CAE_improved_modeltrain.py:92-93) plus the float32 cast of
-// improved_detection.py:122.  The arithmetic is scikit-image 0.18.3 / SciPy 1.7.1 (see
+// (improved_detection.py:98-99, CAE_improved_modeltrain.py:92-93; the reference writes (64, 64), a model
+// of another input_shape changes that one line) plus the float32 cast of improved_detection.py:122.
+// The arithmetic is scikit-image 0.18.3 / SciPy 1.7.1 (see
 // oracle/preprocess_oracle.py for the restatement and how it is pinned).
 //
-// One workgroup (4 waves) owns one bounding-box crop from its raw integer pixels to the 64x64 fp32
-// tile the autoencoder reads.  CLAHE is integer work and is reproduced bit-exactly, including
+// One workgroup (8 waves) owns one bounding-box crop from its raw integer pixels to the out_h x out_w
+// fp32 tile the autoencoder reads (64x64 unless the handle was told another size).
+// CLAHE is integer work and is reproduced bit-exactly, including
 // skimage's float32 accumulation order of the four blended look-ups; every floating-point step
 // that feeds a rounding or truncation decision is done in fp64 with explicitly rounded operations
 // (no FMA contraction).  The resize (Gaussian anti-alias + bilinear warp) is fp64 as in SciPy.
 //
 // LDS: the contrast maps of all tiles of the crop (uint16 [tiles][256], <= 225 tiles = 115 KB; a
 // typical 8x8..9x9 tiling is 32-41 KB) + one 256-bin histogram per wave.
-// HBM per crop: H*W raw pixels in, 16 KB out; the fp64 blur planes are a per-chunk scratch that
+// HBM per crop: H*W raw pixels in, 4*out_h*out_w bytes out (16 KB at 64x64);
+// the fp64 blur planes are a per-chunk scratch that
 // stays in L2 (a crop is a few thousand pixels).
 #include "api_internal.hpp"
 
@@ -30,8 +33,11 @@ static constexpr int PP_WAVES = PP_THREADS / 64;
 static constexpr int PP_NBINS = 256;
 static constexpr int PP_GRAY = 1 << 14;                 // NR_OF_GRAY, _adapthist.py:23
 static constexpr int PP_BIN_SIZE = 1 + PP_GRAY / PP_NBINS;
-static constexpr int PP_OUT = 64;
-static constexpr int PP_MAX_TAPS = 32;                  // Gaussian radius limit: side <= 1024
+static constexpr int PP_OUT = 64;                       // the default output side (the reference's resize)
+// Gaussian radius limit.  A crop side n is accepted on an axis of output size `out` only if n <= kPreprocMaxRatio * out
+// (= 16): sigma = (n/out - 1)/2 <= 7.5 and the radius int(4*sigma + 0.5) <= 30.  At out = 64 that is the side <= 1024 rule.
+static constexpr int PP_MAX_TAPS = 32;
+static_assert(4 * (kPreprocMaxRatio - 1) / 2 + 1 <= PP_MAX_TAPS, "radius int(4*sigma + 0.5) at the largest accepted ratio");
 
 __device__ inline int wave_sum(int v)
 {
@@ -136,8 +142,12 @@ __device__ inline int fast_div(int p, int d, float rcp, int& rem)
 __device__ inline int reflect_once(int i, int n) { return i >= n ? 2 * (n - 1) - i : i; }   // np.pad 'reflect'
 
 // scipy.ndimage mode='mirror' and skimage's coord_map mode 'R' are the same map (reflect about the
-// centre of the edge pixel).  One reflection is enough here: the Gaussian radius int(4*sigma + 0.5)
-// with sigma = (n/64 - 1)/2 is below n/32, and the warp samples rows -1 .. n at most.
+// centre of the edge pixel).  One reflection is enough here, for every accepted size (8 <= out, 8 <= n):
+//   * an axis is filtered only when n > out, and then the Gaussian radius is
+//     int(4*sigma + 0.5) <= 2*(n/out - 1) + 0.5 = 2n/out - 1.5 <= n/4 - 1.5 < n - 1, so a tap q +- j of a
+//     centre q in [0, n) lies in [-(n-1), 2(n-1)], which one reflection maps into [0, n);
+//   * the warp samples at f*(i + 0.5) - 0.5 with f = n/out and i in [0, out), i.e. inside (-0.5, n - 0.5): floor >= -1
+//     and ceil <= n (reached only when up-scaling), and -1 -> 1, n -> n - 2 lie inside [0, n) for n >= 3.
 __device__ inline int mirror_once(int i, int n)
 {
     i = i < 0 ? -i : i;
@@ -211,11 +221,15 @@ __device__ inline void clip_and_map(int h[4], int clim, double scale, int out[4]
     }
 }
 
-template <typename PIX>
+// SIZED = false: the 64x64 output of the reference, sizes compiled in (one output column per lane, the code of every
+// earlier version).  SIZED = true: out_h x out_w at run time; the lanes walk the output columns in steps of 64.
+template <typename PIX, bool SIZED>
 __global__ __launch_bounds__(PP_THREADS) void preprocess_kernel(const PIX* __restrict__ pix,
                                                                 const CropDesc* __restrict__ desc, double clip_limit,
-                                                                unsigned short* __restrict__ clahe, float* __restrict__ out)
+                                                                unsigned short* __restrict__ clahe, float* __restrict__ out,
+                                                                int out_h, int out_w)
 {
+    const int OH = SIZED ? out_h : PP_OUT, OW = SIZED ? out_w : PP_OUT;
     // [tiles][256] uint16 contrast maps during CLAHE; afterwards the same bytes hold one fp64 line of
     // W values per wave for the resize
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn_lds[];
@@ -231,7 +245,7 @@ __global__ __launch_bounds__(PP_THREADS) void preprocess_kernel(const PIX* __res
     const int H = d.H, W = d.W, npx = H * W;
     const PIX* src = pix + d.off;
     unsigned short* cl = clahe + d.off;
-    float* dst = out + (size_t)blockIdx.x * PP_OUT * PP_OUT;
+    float* dst = out + (size_t)blockIdx.x * OH * OW;
 
     // ---- A: intensity range of the crop, then the grey-level bin of every pixel (parked in cl[]) ----
     const float rcpW = 1.0f / (float)W;
@@ -247,7 +261,8 @@ __global__ __launch_bounds__(PP_THREADS) void preprocess_kernel(const PIX* __res
     for (int p = tid; p < npx; p += PP_THREADS) cl[p] = (unsigned short)gray_bin(to_u16<PIX>(src[p]), vlo, irange, rcp_range);
 
     // per-row / per-column block index and in-block offset of the padded image, the blend weights,
-    // and the two anti-aliasing kernels (scipy _gaussian_kernel1d: sigma = (n/64 - 1)/2, truncate 4)
+    // and the two anti-aliasing kernels (scipy _gaussian_kernel1d: sigma = (n/out - 1)/2 per axis, truncate 4; an axis
+    // that is not scaled down has sigma 0 and is not filtered, each axis by itself)
     const int kh = H / 8, kw = W / 8;
     const int ph0 = kh / 2, pw0 = kw / 2;
     for (int r = tid; r < H; r += PP_THREADS) {
@@ -260,8 +275,8 @@ __global__ __launch_bounds__(PP_THREADS) void preprocess_kernel(const PIX* __res
     }
     if (tid < kh) crow[tid] = __ddiv_rn((double)tid, (double)kh);
     if (tid < kw) ccol[tid] = __ddiv_rn((double)tid, (double)kw);
-    const double sig_r = fmax(0.0, ((double)H / (double)PP_OUT - 1.0) / 2.0);
-    const double sig_c = fmax(0.0, ((double)W / (double)PP_OUT - 1.0) / 2.0);
+    const double sig_r = fmax(0.0, ((double)H / (double)OH - 1.0) / 2.0);
+    const double sig_c = fmax(0.0, ((double)W / (double)OW - 1.0) / 2.0);
     const int lw_r = sig_r > 1e-15 ? (int)(4.0 * sig_r + 0.5) : -1;     // -1: no filter along this axis
     const int lw_c = sig_c > 1e-15 ? (int)(4.0 * sig_c + 0.5) : -1;
     if (tid >= PP_THREADS - 128 && (tid & 63) == 0) {                    // lane 0 of the last two waves
@@ -339,23 +354,20 @@ __global__ __launch_bounds__(PP_THREADS) void preprocess_kernel(const PIX* __res
 
     // ---- D: img_as_float + rescale_intensity + resize, fused -------------------------------------------
     // skimage: eq = (u/65535 - min)/(max - min) (_adapthist.py:93-94), Gaussian along rows then columns,
-    // bilinear warp at r = H/64*(i+0.5)-0.5 (mode 'reflect'), clip to the filtered image's range.  Every
+    // bilinear warp at r = H/out_h*(i+0.5)-0.5 (mode 'reflect'), clip to the filtered image's range.  Every
     // step after the uint16 image is linear with weights that sum to 1, so the same numbers come from
     // filtering + sampling (u - ulo) in fp64 and dividing by (uhi - ulo) at the end (differences ~1e-16
     // relative; the result is rounded to float32 anyway), and the clip can only act on rounding noise:
     // it becomes a clamp to [0,1].  A wave produces one output row: the vertically filtered and
-    // row-interpolated line Y[0..W) goes to LDS, then each lane filters + interpolates along it.
+    // row-interpolated line Y[0..W) goes to LDS (its length is the crop's width, whatever the output size), then the
+    // lanes filter + interpolate along it, one output column each per step of 64.
     double* yline = (double*)dyn_lds + (size_t)wave * W;
-    const double fr = (double)H / (double)PP_OUT, fc = (double)W / (double)PP_OUT;
+    const double fr = (double)H / (double)OH, fc = (double)W / (double)OW;
     const double or_ = fr * 0.5 - 0.5, oc_ = fc * 0.5 - 0.5;
     const bool eflat = ulo == uhi;
     const double inv = eflat ? 0.0 : 1.0 / (double)(uhi - ulo);
     const double cflat = fmin(fmax((double)ulo * (1.0 / 65535.0), 0.0), 1.0);
-    // column sample points of this lane
-    const double cpos = fc * (double)lane + oc_;
-    const double c0f = floor(cpos), dc = cpos - c0f;
-    const int c0 = (int)c0f, c1 = (int)ceil(cpos);
-    for (int i = wave; i < PP_OUT; i += PP_WAVES) {
+    for (int i = wave; i < OH; i += PP_WAVES) {
         const double rpos = fr * (double)i + or_;
         const double r0f = floor(rpos), dr = rpos - r0f;
         const int r0 = (int)r0f, r1 = (int)ceil(rpos);
@@ -378,44 +390,59 @@ __global__ __launch_bounds__(PP_THREADS) void preprocess_kernel(const PIX* __res
             yline[c] = (1.0 - dr) * y0 + dr * y1;
         }
         wave_sync();
-        double z0, z1;
-        const int q0 = mirror_once(c0, W), q1 = mirror_once(c1, W);
-        if (lw_c < 0) {
-            z0 = yline[q0];
-            z1 = yline[q1];
-        } else {
-            z0 = yline[q0] * wts[1][0];
-            z1 = yline[q1] * wts[1][0];
-            for (int j = lw_c; j >= 1; --j) {
-                const double w = wts[1][j];
-                z0 += (yline[mirror_once(q0 - j, W)] + yline[mirror_once(q0 + j, W)]) * w;
-                z1 += (yline[mirror_once(q1 - j, W)] + yline[mirror_once(q1 + j, W)]) * w;
+        for (int col = lane; col < OW; col += 64) {      // SIZED = false: exactly one column per lane
+            // column sample points of this lane
+            const double cpos = fc * (double)col + oc_;
+            const double c0f = floor(cpos), dc = cpos - c0f;
+            const int c0 = (int)c0f, c1 = (int)ceil(cpos);
+            double z0, z1;
+            const int q0 = mirror_once(c0, W), q1 = mirror_once(c1, W);
+            if (lw_c < 0) {
+                z0 = yline[q0];
+                z1 = yline[q1];
+            } else {
+                z0 = yline[q0] * wts[1][0];
+                z1 = yline[q1] * wts[1][0];
+                for (int j = lw_c; j >= 1; --j) {
+                    const double w = wts[1][j];
+                    z0 += (yline[mirror_once(q0 - j, W)] + yline[mirror_once(q0 + j, W)]) * w;
+                    z1 += (yline[mirror_once(q1 - j, W)] + yline[mirror_once(q1 + j, W)]) * w;
+                }
             }
+            const double z = (1.0 - dc) * z0 + dc * z1;
+            const double v = eflat ? cflat : fmin(fmax(z * inv, 0.0), 1.0);
+            dst[i * OW + col] = (float)v;                // .astype('float32'), improved_detection.py:122
         }
-        const double z = (1.0 - dc) * z0 + dc * z1;
-        const double v = eflat ? cflat : fmin(fmax(z * inv, 0.0), 1.0);
-        dst[i * PP_OUT + lane] = (float)v;              // .astype('float32'), improved_detection.py:122
         wave_sync();                                     // yline is rewritten in the next round
     }
 }
 
-hipError_t launch_preprocess(const void* pix, int pixel_type, const CropDesc* desc, int64_t n, double clip_limit, size_t lds,
-                             uint16_t* clahe, float* out, hipStream_t stream)
+template <typename PIX>
+static hipError_t launch_typed(const PIX* pix, const CropDesc* desc, int64_t n, double clip_limit, size_t lds, unsigned short* clahe,
+                               float* out, int out_h, int out_w, hipStream_t stream)
 {
-    if (n <= 0) return hipSuccess;
     hipError_t e;
-    if (pixel_type == CS_PIX_U8) {
-        e = hipFuncSetAttribute((const void*)preprocess_kernel<unsigned char>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (out_h == PP_OUT && out_w == PP_OUT) {
+        e = hipFuncSetAttribute((const void*)preprocess_kernel<PIX, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(preprocess_kernel<unsigned char>, dim3((unsigned)n), dim3(PP_THREADS), lds, stream,
-                           (const unsigned char*)pix, desc, clip_limit, (unsigned short*)clahe, out);
+        hipLaunchKernelGGL((preprocess_kernel<PIX, false>), dim3((unsigned)n), dim3(PP_THREADS), lds, stream, pix, desc, clip_limit, clahe,
+                           out, out_h, out_w);
     } else {
-        e = hipFuncSetAttribute((const void*)preprocess_kernel<unsigned short>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        e = hipFuncSetAttribute((const void*)preprocess_kernel<PIX, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(preprocess_kernel<unsigned short>, dim3((unsigned)n), dim3(PP_THREADS), lds, stream,
-                           (const unsigned short*)pix, desc, clip_limit, (unsigned short*)clahe, out);
+        hipLaunchKernelGGL((preprocess_kernel<PIX, true>), dim3((unsigned)n), dim3(PP_THREADS), lds, stream, pix, desc, clip_limit, clahe,
+                           out, out_h, out_w);
     }
     return hipGetLastError();
+}
+
+hipError_t launch_preprocess(const void* pix, int pixel_type, const CropDesc* desc, int64_t n, double clip_limit, size_t lds,
+                             uint16_t* clahe, float* out, int out_h, int out_w, hipStream_t stream)
+{
+    if (n <= 0) return hipSuccess;
+    if (pixel_type == CS_PIX_U8)
+        return launch_typed((const unsigned char*)pix, desc, n, clip_limit, lds, (unsigned short*)clahe, out, out_h, out_w, stream);
+    return launch_typed((const unsigned short*)pix, desc, n, clip_limit, lds, (unsigned short*)clahe, out, out_h, out_w, stream);
 }
 
 }  // namespace cs
@@ -425,6 +452,7 @@ using namespace cs;
 
 static const int64_t kChunkPixels = 256ll << 20;        // pixel span of one launch (staging + uint16 plane)
 static const int64_t kChunkCrops = 1 << 16;
+static const int64_t kChunkOutBytes = 1ll << 30;        // output of one launch (host output: the staging buffer); 65,536 cells at 64x64
 
 int cs_preproc_create(int device_id, cs_preproc** out)
 {
@@ -464,6 +492,28 @@ void cs_preproc_free(cs_preproc* p)
     delete p;
 }
 
+int cs_preproc_set_output_size(cs_preproc* p, int32_t out_h, int32_t out_w)
+{
+    if (!p) return fail(CS_ERR_INVALID, "handle is NULL");
+    if (out_h < kPreprocOutMin || out_w < kPreprocOutMin || out_h > kPreprocOutMax || out_w > kPreprocOutMax)
+        return fail(CS_ERR_INVALID, "output size %dx%d: each side must lie in [%d, %d]", (int)out_h, (int)out_w, kPreprocOutMin,
+                    kPreprocOutMax);
+    if (p->extract_pending)
+        return fail(CS_ERR_INVALID, "output size set between cs_extract_measure and its cs_extract_fill: the fill's buffers were sized by "
+                    "the measure");
+    p->out_h = out_h;
+    p->out_w = out_w;
+    return CS_OK;
+}
+
+int cs_preproc_get_output_size(const cs_preproc* p, int32_t* out_h, int32_t* out_w)
+{
+    if (!p) return fail(CS_ERR_INVALID, "handle is NULL");
+    if (out_h) *out_h = p->out_h;
+    if (out_w) *out_w = p->out_w;
+    return CS_OK;
+}
+
 int cs_preproc_last_timing(const cs_preproc* p, double* kernel_ms, int64_t* pixels)
 {
     if (!p) return fail(CS_ERR_INVALID, "handle is NULL");
@@ -486,12 +536,18 @@ int cs_preprocess(cs_preproc* p, const void* pixels, int pixel_type, int64_t n_p
         return fail(CS_ERR_INVALID, "memory kind must be CS_MEM_HOST or CS_MEM_DEVICE");
     if (!(clip_limit == clip_limit)) return fail(CS_ERR_INVALID, "clip_limit is NaN");
     const size_t esz = pixel_type == CS_PIX_U8 ? 1 : 2;
+    const int OH = p->out_h, OW = p->out_w;
+    const size_t cell = (size_t)OH * OW;                 // floats of one output cell
     for (int64_t i = 0; i < n; ++i) {
         const int64_t H = heights[i], W = widths[i];
         if (H < 8 || W < 8)
             return fail(CS_ERR_INVALID, "crop %lld is %lldx%lld: below 8 px kernel_size = shape//8 is 0 (skimage raises ZeroDivisionError)",
                         (long long)i, (long long)H, (long long)W);
-        if (H > 1024 || W > 1024) return fail(CS_ERR_UNSUPPORTED, "crop %lld is %lldx%lld: side above 1024", (long long)i, (long long)H, (long long)W);
+        if (H > kPreprocMax || W > kPreprocMax)
+            return fail(CS_ERR_UNSUPPORTED, "crop %lld is %lldx%lld: side above 1024", (long long)i, (long long)H, (long long)W);
+        if (preproc_side_beyond((int)H, OH) || preproc_side_beyond((int)W, OW))
+            return fail(CS_ERR_UNSUPPORTED, "crop %lld is %lldx%lld: a side above %d times the output size %dx%d on its axis",
+                        (long long)i, (long long)H, (long long)W, kPreprocMaxRatio, OH, OW);
         if (offsets[i] < 0 || offsets[i] + H * W > n_pixels)
             return fail(CS_ERR_INVALID, "crop %lld [%lld, +%lld) lies outside the pixel buffer of %lld", (long long)i,
                         (long long)offsets[i], (long long)(H * W), (long long)n_pixels);
@@ -503,11 +559,12 @@ int cs_preprocess(cs_preproc* p, const void* pixels, int pixel_type, int64_t n_p
     p->last_pixels = 0;
     CropDesc* const hdesc = (CropDesc*)p->hdesc;     // free: every launch below is followed by a stream synchronisation
     int64_t i0 = 0;
+    const int64_t chunk_crops = std::max<int64_t>(1, std::min<int64_t>(kChunkCrops, kChunkOutBytes / (int64_t)(cell * sizeof(float))));
     while (i0 < n) {
-        // a chunk: consecutive crops, bounded in count and in the pixel span the fp64 planes must cover
+        // a chunk: consecutive crops, bounded in count, in output bytes and in the pixel span the uint16 plane must cover
         int64_t i1 = i0, lo = offsets[i0], hi = offsets[i0];
         size_t lds = 0;
-        while (i1 < n && i1 - i0 < kChunkCrops) {
+        while (i1 < n && i1 - i0 < chunk_crops) {
             const int64_t H = heights[i1], W = widths[i1];
             const int64_t nlo = std::min(lo, offsets[i1]), nhi = std::max(hi, offsets[i1] + H * W);
             if (i1 > i0 && nhi - nlo > kChunkPixels) break;
@@ -542,27 +599,17 @@ int cs_preprocess(cs_preproc* p, const void* pixels, int pixel_type, int64_t n_p
         }
         float* d_out;
         if (out_kind == CS_MEM_DEVICE) {
-            d_out = out + (size_t)i0 * PP_OUT * PP_OUT;
+            d_out = out + (size_t)i0 * cell;
         } else {
-            if ((rc = p->out.ensure((size_t)nc * PP_OUT * PP_OUT * sizeof(float)))) return rc;
+            if ((rc = p->out.ensure((size_t)nc * cell * sizeof(float)))) return rc;
             d_out = p->out.as<float>();
         }
 
         HIPCHK(hipEventRecord(p->ev0, p->stream));
-        if (pixel_type == CS_PIX_U8) {
-            HIPCHK(hipFuncSetAttribute((const void*)preprocess_kernel<unsigned char>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(preprocess_kernel<unsigned char>, dim3((unsigned)nc), dim3(PP_THREADS), lds, p->stream,
-                               (const unsigned char*)d_pix, (const CropDesc*)p->ddesc, clip_limit, d_clahe, d_out);
-        } else {
-            HIPCHK(hipFuncSetAttribute((const void*)preprocess_kernel<unsigned short>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(preprocess_kernel<unsigned short>, dim3((unsigned)nc), dim3(PP_THREADS), lds, p->stream,
-                               (const unsigned short*)d_pix, (const CropDesc*)p->ddesc, clip_limit, d_clahe, d_out);
-        }
-        HIPCHK(hipGetLastError());
+        HIPCHK(launch_preprocess(d_pix, pixel_type, (const CropDesc*)p->ddesc, nc, clip_limit, lds, d_clahe, d_out, OH, OW, p->stream));
         HIPCHK(hipEventRecord(p->ev1, p->stream));
         if (out_kind == CS_MEM_HOST) {
-            HIPCHK(hipMemcpyAsync(out + (size_t)i0 * PP_OUT * PP_OUT, d_out, (size_t)nc * PP_OUT * PP_OUT * sizeof(float),
-                                  hipMemcpyDeviceToHost, p->stream));
+            HIPCHK(hipMemcpyAsync(out + (size_t)i0 * cell, d_out, (size_t)nc * cell * sizeof(float), hipMemcpyDeviceToHost, p->stream));
             if (clahe_out)
                 HIPCHK(hipMemcpyAsync(clahe_out + lo, d_clahe, (size_t)span * sizeof(unsigned short), hipMemcpyDeviceToHost, p->stream));
         }

@@ -254,21 +254,35 @@ int cs_synth_crops(cs_model *m, uint64_t seed, int64_t first_cell, int64_t n, in
 /* ---- crop preprocess (the caller side of the hot path) ----------------------------- */
 /* What the reference does to every bounding-box crop before compute_anomaly_scores sees it
  * (improved_detection.py:98-99, CAE_improved_modeltrain.py:92-93):
- *     exposure.equalize_adapthist(crop, clip_limit=0.02)  ->  resize(., (64, 64), anti_aliasing=True)
+ *     exposure.equalize_adapthist(crop, clip_limit=0.02)  ->  resize(., (out_h, out_w), anti_aliasing=True)
  * and the float32 cast of improved_detection.py:122.  Arithmetic of scikit-image 0.18.3 /
- * SciPy 1.7.1 (CLAHE bit-exact, resize in fp64).  Independent of cs_model: own handle, own stream. */
+ * SciPy 1.7.1 (CLAHE bit-exact, resize in fp64).  Independent of cs_model: own handle, own stream.
+ * The output size is state of the handle: 64 x 64 (the reference's resize) until
+ * cs_preproc_set_output_size says otherwise -- the size a model of another input_shape reads.
+ * Accepted, and refused outside (never clamped):
+ *   output   8 <= out_h, out_w <= 512, independent of each other              (else CS_ERR_INVALID)
+ *   crops    8 <= side <= 1024 per axis (below 8: CS_ERR_INVALID, skimage raises), and
+ *            side <= 16 * out on that axis: the ratio bounds the anti-aliasing Gaussian's radius
+ *            (sigma = (side/out - 1)/2 <= 7.5); at 64 it is the 1024 rule    (else CS_ERR_UNSUPPORTED)
+ * A crop side below the output side is up-scaled: no filter along that axis, each axis by itself. */
 typedef struct cs_preproc cs_preproc;
 typedef enum cs_pixel_type { CS_PIX_U8 = 0, CS_PIX_U16 = 1 } cs_pixel_type;   /* TIFF channel dtypes */
 
 int cs_preproc_create(int device_id, cs_preproc **out);
 void cs_preproc_free(cs_preproc *p);
 int cs_preproc_wait_stream(cs_preproc *p, void *hip_stream);
+/* The output size of the handle (default 64 x 64); takes effect from the next cs_preprocess /
+ * cs_extract_measure.  Sides outside [8, 512]: CS_ERR_INVALID, the size stays.  Between a successful
+ * cs_extract_measure and its cs_extract_fill: CS_ERR_INVALID (the fill's buffers were sized by the measure). */
+int cs_preproc_set_output_size(cs_preproc *p, int32_t out_h, int32_t out_w);
+int cs_preproc_get_output_size(const cs_preproc *p, int32_t *out_h, int32_t *out_w);
 /* pixels:  ragged buffer of n_pixels elements (pixels_kind: host or device); crop i is the
  *          row-major heights[i] x widths[i] block at element offsets[i].  offsets must ascend
  *          and crops must not overlap.  offsets/heights/widths are host arrays of length n.
  * Sides below 8 return CS_ERR_INVALID (kernel_size = shape // 8 would be 0: skimage raises),
- * above 1024 CS_ERR_UNSUPPORTED.
- * out:       [n][64][64] float32 (out_kind: host or device).
+ * above 1024 or above 16 x the output size on their axis CS_ERR_UNSUPPORTED (the message names the crop,
+ * its sides and the output size); nothing is written then.
+ * out:       [n][out_h][out_w] float32 (out_kind: host or device), the handle's output size.
  * clahe_out: optional stage tap, same layout/offsets as pixels (uint16, out_kind): the image
  *            skimage's _clahe returns before the final rescale.  Elements between crops: 0 / untouched.
  * n == 0 is valid and touches nothing. */
@@ -298,7 +312,9 @@ int cs_preproc_last_timing(const cs_preproc *p, double *kernel_ms, int64_t *pixe
  * to cs_preprocess on the same crops cut on the host.
  * Whole-image rules (status per image): a passing region with a bbox side < 8 makes skimage raise inside
  * the reference's per-file try (improved_detection.py:113-115), so the image yields no cells
- * (CS_IMAGE_NO_CELLS); a passing side > 1024 is beyond cs_preprocess (CS_IMAGE_UNSUPPORTED, no cells).
+ * (CS_IMAGE_NO_CELLS); a passing side > 1024, or > 16 x the handle's output size on its axis, is beyond
+ * cs_preprocess (CS_IMAGE_UNSUPPORTED, no cells) -- the same rule, applied on the device.
+ * The cells have the handle's output size (cs_preproc_set_output_size) as it was at cs_extract_measure.
  * Two calls per batch: cs_extract_measure runs the label pass, the per-region pass and the compaction
  * scan and returns the counts (one host synchronisation); cs_extract_fill writes the region table and
  * the cells (one more).  Between the two, CS_MEM_DEVICE inputs must stay valid and unchanged (the fill
@@ -319,7 +335,7 @@ typedef struct cs_qc_params {
 
 #define CS_IMAGE_OK          0        /* per-image status of cs_extract_fill */
 #define CS_IMAGE_NO_CELLS    1        /* a passing region has a bbox side < 8: the reference's extraction raises */
-#define CS_IMAGE_UNSUPPORTED 2        /* a passing region has a bbox side > 1024 */
+#define CS_IMAGE_UNSUPPORTED 2        /* a passing region has a bbox side > 1024 or > 16 x the output size */
 
 /* One record per region, passing or not, in (image, label) order. */
 typedef struct cs_region {
@@ -347,7 +363,7 @@ int cs_extract_measure(cs_preproc *p, const void *image, int pixel_type, int32_t
 /* After cs_extract_measure on the same handle.  Each output may be NULL.
  *   regions      [n_regions] cs_region                         (table_kind)
  *   image_status [batch] int32 CS_IMAGE_*                      (table_kind)
- *   cells        [n_cells][64][64] float32, in region order    (cells_kind)
+ *   cells        [n_cells][out_h][out_w] float32, in region order (cells_kind)
  *   cell_image   [n_cells] int32: the image index of each cell (cells_kind) */
 int cs_extract_fill(cs_preproc *p, cs_region *regions, int32_t *image_status, int table_kind, float *cells, int32_t *cell_image,
                     int cells_kind);
