@@ -622,7 +622,7 @@ __global__ __launch_bounds__(256) void wgrad_last_kernel(const float* __restrict
 // Four consecutive elements of one descriptor are summed by FOUR threads (16-byte loads; thread q takes the q-th quarter of the
 // partials, the four sums are added in the order ((q0 + q1) + q2) + q3): the pass streams ~60 MB of partial sums at batch 32 at the
 // end of the step's critical path and is bound by the loads it keeps in flight.  A descriptor's tail shorter than four, or one
-// whose rows are not 16-byte aligned, is summed element by element in partial order.  Deterministic either way.
+// whose rows are not 16-byte aligned, is summed element by element in partial order, in double.  Deterministic either way.
 __global__ __launch_bounds__(256) void reduce_all_kernel(const ReduceDesc* __restrict__ descs, int ndesc, float* __restrict__ flat_grad,
                                                          const float* __restrict__ errpart, long nparts, long nelem, float* __restrict__ out2)
 {
@@ -662,10 +662,13 @@ __global__ __launch_bounds__(256) void reduce_all_kernel(const ReduceDesc* __res
     if (vec) {
         *(f32x4*)(flat_grad + D.dst + e) = ((s + red[0][gl]) + red[1][gl]) + red[2][gl];
     } else {
+        // conv7's bias gradient comes this way: ONE element, 4 partials per cell -- 32,768 of mixed sign at the largest batch.  Summed
+        // one after another in fp32 they missed the 1e-5 gradient bar from ~2,000 cells on (1.2e-5 at 2,051); in double the sum is exact
+        // to the partials' own rounding at any batch
         for (long k = e; k < e + 4 && k < D.len; ++k) {
-            float t = 0.0f;
-            for (int p = 0; p < D.nparts; ++p) t += D.src[(size_t)p * D.stride + k];
-            flat_grad[D.dst + k] = t;
+            double t = 0.0;
+            for (int p = 0; p < D.nparts; ++p) t += (double)D.src[(size_t)p * D.stride + k];
+            flat_grad[D.dst + k] = (float)t;
         }
     }
 }

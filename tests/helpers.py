@@ -63,12 +63,19 @@ def flags_agree(dec_got, pred_got, dec_ref, pred_ref, tol_abs, what):
 
 # ---- training on the run-time-shaped kernels
 def activation_pattern(tr, w, n):
-    """The trainer's ReLU masks and max-pool routing from its relu outputs (stage tap 0), for any instance of the grammar
-    (see tests/test_gpu_train.py: fp32 and fp64 disagree on a handful of those discontinuous decisions)."""
+    """The trainer's ReLU masks and max-pool routing from its relu outputs (stage tap 0), for any instance of the grammar:
+    ReLU' and the pooling's routing are discontinuous, and an fp32 and an fp64 evaluation disagree on a handful of the ~1e6
+    decisions per layer, so gradient parity is only meaningful on the same pattern.  BN is monotone in r (increasing for
+    gamma > 0, decreasing for gamma < 0), so the arg-max of BN(r) over a window is the first arg-max of sign(gamma) * r."""
+    return pattern_of_relus([tr.tensor(0, l, n) for l in range(w.n_conv - 1)], w)
+
+
+def pattern_of_relus(relus, w):
+    """(relu_masks, pool_args) for oracle/train_oracle.forward_backward from the relu(conv) tensors of an evaluation."""
     nl, ne = w.n_conv - 1, w.n_enc
     masks, args = [], []
     for l in range(nl):
-        r = tr.tensor(0, l, n)
+        r = np.asarray(relus[l])
         masks.append(r > 0)
         if l < ne:
             N, Hh, Ww, C = r.shape

@@ -4,7 +4,7 @@ Stated tolerance (Appendix G): per-tensor gradient relative L2 <= 1e-5; loss rel
 import numpy as np
 import pytest
 
-import helpers as H  # noqa: F401
+import helpers as H
 from cellscreen import spec, synth
 from cellscreen.trainer import Trainer, flat_from_weights, param_layout, split_flat
 from oracle import train_oracle as T
@@ -24,21 +24,7 @@ def grads_by_name(flat):
     return split_flat(flat, param_layout())
 
 
-def activation_pattern(tr, w, n):
-    """The trainer's ReLU masks and max-pool routing, from its relu outputs (stage tap 0).
-    BN is monotone in r (increasing for gamma > 0, decreasing for gamma < 0), so the arg-max of
-    BN(r) over a window is the first arg-max of sign(gamma) * r."""
-    masks, args = [], []
-    for l in range(6):
-        r = tr.tensor(0, l, n)
-        masks.append(r > 0)
-        if l < 3:
-            N, Hh, Ww, C = r.shape
-            win = r.reshape(N, Hh // 2, 2, Ww // 2, 2, C).transpose(0, 1, 3, 5, 2, 4).reshape(N, Hh // 2, Ww // 2, C, 4)
-            args.append(np.argmax(win * np.sign(w.bn_gamma[l])[None, None, None, :, None], axis=-1))
-        else:
-            args.append(None)
-    return masks + [None], args + [None] * 4
+activation_pattern = H.activation_pattern
 
 
 @pytest.mark.parametrize("n", [32, 5])

@@ -1,0 +1,323 @@
+"""Batch arithmetic of the training step, restated for the tests: for every launch of one cs_train_forward_backward on the
+reference graph, how many work items a cell contributes and where the launch's grid is capped, as a function of the batch
+size; the same for the run-time-shaped trainer on top of generic_plans.plan(); and the batches the GPU tests run
+(tests/test_gpu_train_batches.py), with the proof obligations tests/test_train_plans_cpu.py asserts about them.  Also
+the batches themselves: mixed blob / noise crops, and the replicated batch whose step is its base batch's.
+
+Test code only.  Each entry cites the lines of cell-image-analysis_amd/csrc/ it restates; a change there must change this file.
+
+Occupancy.  The persistent conv launches size their grid by hipOccupancyMaxActiveBlocksPerMultiprocessor, which depends on
+the registers the compiler gave the kernel.  It is bounded here from the code instead of queried: a CU holds 2,048 threads
+= at most 8 workgroups of 256, and 160 KiB of LDS = at most floor(160 KiB / dynamic LDS) workgroups; the launchers raise a
+reported 0 to 1.  Every statement below is proved for EVERY occupancy in that range.
+"""
+from dataclasses import dataclass
+from typing import Callable, Tuple
+
+import numpy as np
+
+import generic_plans as GP
+
+CUS = GP.CUS
+LDS_PER_CU = 160 * 1024
+BN_MAX_PARTS = 1024          # common.hpp:158
+TRAIN_MAX_PARTS = 256        # common.hpp:157
+TRAIN_MAX_BATCH = 8192       # train_api.hip:30 kTrainMaxBatch
+REF_CH = GP.REF[1]
+REF_GRID = (64, 32, 16, 8, 16, 32, 64)          # conv grid of each conv (api_internal.hpp kConvGrid)
+
+# the batches of tests/test_gpu_train_batches.py
+DIRECT_BATCHES = (5, 32, 33, 65, 129, 161)                       # the float64 oracle evaluated on the batch itself
+REPLICATED = ((7, 293), (13, 473), (8, 1024), (32, 256))        # (base cells, copies): 2,051 / 6,149 / 8,192 / 8,192 cells
+RESIZE_SEQUENCE = (32, 161, 5, 2051, 32)                         # one handle: grow, shrink, grow, back
+BATCHES = tuple(sorted(set(DIRECT_BATCHES) | {b * k for b, k in REPLICATED}))
+
+# weights(WSEED) and the seeds of mixed_batch() for the batches above.  The base batches of 7, 8 and 13 cells were chosen on the CPU
+# (six seeds each) so that numpy's float32 evaluation of the oracle differs from the float64 one on less than 1e-5 of the ReLU
+# decisions; tests/test_train_plans_cpu.py holds them to it
+WSEED = 12
+DIRECT_SEED = {5: 105, 32: 3, 33: 133, 65: 165, 129: 229, 161: 261}
+BASE_SEED = {7: 5, 8: 4, 13: 2, 32: 3}
+
+# Max error over the tensor's max of the float32 numpy oracle (TrainState(dtype=float32)) against the float64 one, on the same
+# batch and on the float32 evaluation's activation pattern, per layer: {cells: (dz of conv 1..7, da of BN 1..6)}.  Measured on the
+# CPU with weights(WSEED) and the seeds above; the GPU tests assert 4 x these on the trainer's dz / da (for a replicated batch:
+# its base batch's row).  numpy adds the rows of a float32 mean / variance one after another, so the figures grow with the batch.
+# For the record, the same evaluation's other figures at 5 / 32 / 161 cells: worst gradient tensor 8.6e-5 / 1.6e-3 / 7.7e-3
+# relative L2, relu 3.8e-5 / 2.3e-4 / 1.0e-3 and output 7.1e-5 / 1.1e-3 / 5.2e-3 of the maximum, loss 2.0e-6 / 8.5e-7 / 1.5e-4.
+FP32_ORACLE = {
+    5: ((5.3e-05, 5.4e-05, 5.5e-05, 3.6e-05, 6.4e-05, 6.9e-05, 1.3e-04),
+        (5.2e-05, 4.6e-05, 3.6e-05, 5.7e-05, 6.3e-05, 6.9e-05)),
+    7: ((8.5e-05, 6.3e-05, 7.4e-05, 5.3e-05, 9.7e-05, 1.6e-04, 2.4e-04),
+        (7.3e-05, 6.4e-05, 6.5e-05, 5.8e-05, 1.0e-04, 1.4e-04)),
+    8: ((1.1e-04, 1.3e-04, 8.6e-05, 7.1e-05, 7.7e-05, 1.9e-04, 3.9e-04),
+        (1.4e-04, 7.7e-05, 8.9e-05, 9.9e-05, 1.1e-04, 2.0e-04)),
+    13: ((1.9e-04, 2.1e-04, 2.9e-04, 1.7e-04, 3.0e-04, 2.9e-04, 4.6e-04),
+         (2.8e-04, 2.7e-04, 2.2e-04, 2.6e-04, 2.3e-04, 3.6e-04)),
+    32: ((3.7e-04, 3.9e-04, 4.8e-04, 4.9e-04, 7.2e-04, 1.1e-03, 2.5e-03),
+         (3.6e-04, 3.8e-04, 3.7e-04, 5.0e-04, 1.1e-03, 1.1e-03)),
+    33: ((2.8e-04, 2.9e-04, 3.6e-04, 2.4e-04, 5.0e-04, 6.3e-04, 1.0e-03),
+         (2.7e-04, 2.8e-04, 2.7e-04, 2.9e-04, 4.5e-04, 7.0e-04)),
+    65: ((1.1e-03, 1.1e-03, 1.7e-03, 1.9e-03, 2.1e-03, 2.2e-03, 3.7e-03),
+         (1.5e-03, 1.5e-03, 1.5e-03, 1.2e-03, 1.7e-03, 2.4e-03)),
+    129: ((1.7e-03, 1.5e-03, 2.5e-03, 2.2e-03, 1.9e-03, 3.5e-03, 6.4e-03),
+          (1.8e-03, 2.4e-03, 2.0e-03, 1.9e-03, 2.4e-03, 4.2e-03)),
+    161: ((3.0e-03, 2.6e-03, 4.5e-03, 3.2e-03, 3.5e-03, 4.7e-03, 9.9e-03),
+          (3.4e-03, 2.6e-03, 3.1e-03, 2.9e-03, 3.3e-03, 5.5e-03)),
+}
+
+
+# ---------------------------------------------------------------- launches of the reference graph's step
+@dataclass
+class Launch:
+    name: str
+    kind: str                    # "persistent": items handed out round-robin, item = blockIdx + round * grid
+    #                              "chunked": the items are cut into `grid` contiguous runs, one per workgroup
+    items: Callable[[int], int]  # work items at a batch (strips; 256 float4 elements for bn_apply; pixels or rows for the chunked kernels)
+    caps: Tuple[int, ...]        # every value the grid cap can take (one per occupancy the bound allows)
+    per_wg: int = 1              # items a workgroup takes while the grid is not capped
+    floor: bool = False          # the uncapped grid is items / per_wg rounded down (stat_grid), not up
+    ragged_possible: bool = True
+
+    def grid(self, b, cap):
+        n = self.items(b)
+        return max(1, min(n // self.per_wg if self.floor else -(-n // self.per_wg), cap))
+
+    def capped(self, b, cap):
+        return self.items(b) > cap * self.per_wg
+
+    def rounds(self, b, cap):
+        """A workgroup's share in units of its uncapped share, rounded up: for per_wg = 1 the trips of its loop."""
+        return -(-self.items(b) // (self.grid(b, cap) * self.per_wg))
+
+    def ragged(self, b, cap):
+        """The last round is short (persistent); the runs are of unequal length (chunked)."""
+        return self.items(b) % self.grid(b, cap) != 0
+
+
+def _conv_lds(H, W, cin, ups, sr, db):
+    """ConvCfg::LDS_BYTES, conv_mfma.hip:66-75."""
+    hs_w = W // 2 if ups else W
+    R = sr // 2 + 2 if ups else sr + 2
+    ps = 1 if cin == 1 else cin + 8
+    strip = (R * (hs_w + 2) * ps * 4 + 15) // 16 * 16
+    return strip * (2 if db else 1)
+
+
+def _occupancies(lds):
+    return range(1, min(8, LDS_PER_CU // lds) + 1)
+
+
+# conv_mfma.hip:586-599: (H = W, CIN, COUT, UPS, SR, double-buffered)
+_F = [(64, 1, 32, False, 8, False), (32, 32, 64, False, 4, False), (16, 64, 32, False, 4, True),
+      (8, 32, 32, False, 8, False), (16, 32, 64, True, 4, False), (32, 64, 32, True, 4, True)]
+# D<l+1>: the gradient wrt the input of conv l (0-based l = 1..6)
+_D = {6: (64, 1, 32, False, 8, False), 5: (32, 32, 64, False, 4, False), 4: (16, 64, 32, False, 4, True),
+      3: (8, 32, 32, False, 8, False), 2: (16, 32, 64, False, 2, False), 1: (32, 64, 32, False, 4, True)}
+_WG_ITEMS = (64 // 8, 32 // 4, 16 // 4, 8 // 4, 16 // 4, 32 // 4, 32 // 4)    # train.hip:500-505, 526-527, 865, 876
+
+
+def reference_launches():
+    """Every launch of ref_fb_enqueue (train_api.hip:290-360) whose grid depends on the batch."""
+    out = []
+    per = lambda n: (lambda b: b * n)
+    for l, (H, cin, cout, ups, sr, db) in enumerate(_F):
+        # launch_cfg, conv_mfma.hip:604-635: min(B * NSTRIP, CUs * occupancy, BN_MAX_PARTS * 64 / COUT), kStatsLds = 4,096
+        lds = _conv_lds(H, H, cin, ups, sr, db) + 256 * 16
+        caps = tuple(sorted({min(CUS * o, BN_MAX_PARTS * 64 // cout) for o in _occupancies(lds)}))
+        out.append(Launch(f"conv_mfma_kernel<CfgF{l + 1}>", "persistent", per(H // sr), caps))
+    for l in range(6):
+        # bn_apply, train.hip:807-815: float4 elements of the stored output, grid min(ceil(total4 / 512), 2048), stride grid * 256
+        ho = REF_GRID[l] // 2 if l < 3 else REF_GRID[l]
+        out.append(Launch(f"bn_apply_kernel[{l}]", "persistent", per(ho * ho * REF_CH[l] // 4 // 256), (2048,), per_wg=2))
+    # launch_conv7_err_t<true>, conv_out.hip:165-188: 4 strips per cell, LDS 10 x 34 x 36 floats + 48
+    out.append(Launch("conv7_err_kernel<true>", "persistent", per(4), tuple(CUS * o for o in _occupancies(10 * 34 * 36 * 4 + 48))))
+    for l in range(6, 0, -1):
+        H, cin, cout, ups, sr, db = _D[l]
+        caps = tuple(CUS * o for o in _occupancies(_conv_lds(H, H, cin, ups, sr, db)))
+        out.append(Launch(f"conv_mfma_kernel<CfgD{l + 1}>", "persistent", per(H // sr), caps))
+    for l in range(6):
+        # stat_grid, train.hip:784, 836, 853: clamp(P / 128, 1, BN_MAX_PARTS) over the P pixels of the stored output; the
+        # workgroup takes pixels [P blk / G, P (blk + 1) / G) (train.hip:266, 278, 347, 368)
+        ho = REF_GRID[l] // 2 if l < 3 else REF_GRID[l]
+        for k in ("bn_bwd_reduce_kernel", "bn_bwd_dz_kernel"):
+            out.append(Launch(f"{k}[{l}]", "chunked", per(ho * ho), (BN_MAX_PARTS,), per_wg=128, floor=True,
+                              ragged_possible=ho * ho % BN_MAX_PARTS != 0))
+    names = ["wgrad_first_kernel"] + [f"wgrad_mfma_kernel<WgL{l + 1}>" for l in range(1, 6)] + ["wgrad_last_kernel"]
+    for l in range(7):
+        # launch_wg / launch_wgrad, train.hip:508-522, 859-884: min(B * NSTRIP, TRAIN_MAX_PARTS)
+        out.append(Launch(names[l], "persistent", per(_WG_ITEMS[l]), (TRAIN_MAX_PARTS,)))
+    return out
+
+
+def stats_partials(l, b, cap):
+    """Partials bn_stats_final_kernel merges for layer l (train.hip:79, BNF_THREADS = 256 threads): the forward conv's grid."""
+    return reference_launches()[l].grid(b, cap)
+
+
+def bias7_partials(b):
+    """conv7's bias-gradient partials (train_api.hip:321) and the loss partials thread 0 of reduce_all_kernel sums."""
+    return 4 * b
+
+
+def coverage(launch, batches):
+    """(some batch leaves the grid uncapped, some batch gives >= 3 rounds and a ragged last one) under EVERY cap the launch can
+    have; where no batch at all can be ragged (ragged_possible False) the second asks for the rounds alone."""
+    a = all(any(not launch.capped(b, cap) for b in batches) for cap in launch.caps)
+    b_ = all(any(launch.capped(b, cap) and launch.rounds(b, cap) >= 3 and (launch.ragged(b, cap) or not launch.ragged_possible)
+                 for b in batches) for cap in launch.caps)
+    return a, b_
+
+
+def rounds_table(batches=BATCHES):
+    """{batch: (fewest, most) rounds over the persistent launches, at the smallest and the largest grid each can have}."""
+    out = {}
+    for b in batches:
+        r = [L.rounds(b, cap) for L in reference_launches() if L.kind == "persistent" for cap in (L.caps[0], L.caps[-1])]
+        out[b] = (min(r), max(r))
+    return out
+
+
+# ---------------------------------------------------------------- the run-time-shaped trainer
+TRAIN_CASES = [c for c in GP.SWEEP_CASES if GP.describe_trainer(c[0], c[1], c[2]) is None]
+CONFIG4 = ((128, 128), (32, 64, 128, 128, 64, 32, 1), 3)      # BASELINE.json configs[4]: 128 x 128 crops, 128-filter bottleneck
+
+
+def wgrad_generic_launch(H, cin, cout):
+    """launch_wgrad_generic, train_generic.hip:188-223: the B * H conv rows of the batch are cut into `parts` contiguous runs (a run
+    crosses cell boundaries, train_generic.hip:82-96), parts = min(2048 / workgroups per part, the part cap, rows)."""
+    tm, tn = (cin + 15) // 16, (cout + 15) // 16
+    nco = 2 if tn >= 2 else 1
+    wg_per_part = (tm * ((tn + nco - 1) // nco) + 3) // 4
+    cap = min(2048 // wg_per_part, 4 * TRAIN_MAX_PARTS if 9 * cin * cout <= 16384 else TRAIN_MAX_PARTS)
+    return Launch(f"wgrad_generic_kernel<{nco}> {H} rows x {cin} -> {cout}", "chunked", lambda b: b * H, (max(1, cap),))
+
+
+def _generic_conv_launch(what, H, W, cin, cout, ups, sigmoid, x3):
+    """The grid of one conv of the run-time-shaped trainer: launch_conv_generic_x3 (conv_generic_x3.hip:541-562, three-way bf16
+    split, never upsample-fed here) or launch_conv_generic without folded weights (conv_generic.hip:801-926)."""
+    per = lambda n: (lambda b: b * n)
+    if x3:
+        sr, _, ns, tpw, lds = GP.x3_plan(H, W, cin, cout)
+        return Launch(f"{what} conv_generic_x3_kernel<{cin},{tpw}>", "persistent", per((H // sr) * ((cout + ns * 16 - 1) // (ns * 16))),
+                      (CUS * (2 if tpw <= 8 and lds <= 76 * GP.KB else 1),))
+    ps = 1 if cin == 1 else cin + 4
+    if cout == 1 and sigmoid and cin % 4 == 0 and cin >= 4:
+        sr = 4 if H % 4 == 0 else 2
+        Ws, R = (W // 2, sr // 2 + 2) if ups else (W, sr + 2)
+        if (R * (Ws + 2) * ps + 9 * cin) * 4 <= 64 * GP.KB:
+            return Launch(f"{what} conv_last_generic_kernel", "persistent", per(H // sr), (CUS * 8,))
+    p = GP.gen2_plan(H, W, cin, cout, ups)
+    if p:
+        sr, _, ns, tpw, lds = p
+        return Launch(f"{what} conv_generic2_kernel<{tpw}>", "persistent", per((H // sr) * ((cout + ns * 16 - 1) // (ns * 16))),
+                      (CUS * (2 if lds <= 76 * GP.KB else 1),))
+    return Launch(f"{what} conv_generic_kernel", "persistent", per((H // GP.GEN_SR) * ((cout + 63) // 64)), (CUS * 8,))
+
+
+def generic_launches(hw, channels, n_enc):
+    """The forward, backward-data and weight-gradient launches of gen_train_fb_enqueue (train_generic.hip:328-390)."""
+    a = GP.grids(hw, channels, n_enc)
+    last = a.n_conv - 1
+    out = []
+    for l in range(a.n_conv):
+        H, W, cin, C = a.gh[l], a.gw[l], a.cin(l), a.ch[l]
+        x3f = l < last and l <= n_enc and GP.x3_plan(H, W, cin, C) is not None                # train_generic.hip:277
+        out.append(_generic_conv_launch(f"forward {l}:", H, W, cin, C, l > n_enc, l == last, x3f))
+        if l > 0:                                                                             # channel roles swapped, never upsample-fed
+            x3t = GP.x3_plan(H, W, C, cin) is not None                                        # train_generic.hip:278
+            out.append(_generic_conv_launch(f"backward-data {l}:", H, W, C, cin, False, False, x3t))
+        out.append(wgrad_generic_launch(H, cin, C))
+    return out
+
+
+def generic_train_bytes(hw, channels, n_enc, b):
+    """gen_train_ensure_batch, train_generic.hip:297-322: bytes of the batch buffers."""
+    a = GP.grids(hw, channels, n_enc)
+    npix, last = hw[0] * hw[1], a.n_conv - 1
+    fl = 4 * npix + 8
+    for l in range(last):
+        r = a.gh[l] * a.gw[l] * a.ch[l]
+        fl += 2 * r + 2 * (r // 4 if l < n_enc else r)
+    fl += max((a.gh[l] * a.gw[l] * a.cin(l) for l in range(n_enc + 1, a.n_conv)), default=0)
+    return 4 * fl * b
+
+
+GENERIC_BASE = 3
+
+# as FP32_ORACLE, for the run-time-shaped cases: weights(WSEED + n_enc, shape), mixed_batch(GENERIC_BASE, 40 + position in
+# GENERIC_CASES, hw); the float32 evaluation differed from the float64 one on at most 8.4e-6 of the decisions (the last case)
+GENERIC_CASES = TRAIN_CASES + [CONFIG4 + ("BASELINE.json configs[4]: 128 x 128 crops, a 128-filter bottleneck",)]
+GENERIC_FP32_ORACLE = {
+    ((8, 32), (32, 128, 1)): ((1.3e-06, 2.0e-06, 2.5e-06), (1.8e-06, 1.1e-06)),
+    ((8, 128), (32, 32, 128, 32, 1)): ((1.2e-05, 9.5e-06, 1.1e-05, 1.0e-05, 1.2e-05), (1.2e-05, 8.9e-06, 9.8e-06, 8.3e-06)),
+    ((8, 32), (128, 128, 1)): ((2.0e-06, 3.8e-06, 2.0e-06), (1.5e-06, 1.1e-06)),
+    ((8, 64), (32, 64, 128, 64, 1)): ((7.8e-06, 7.7e-06, 1.0e-05, 5.0e-06, 8.2e-06), (8.6e-06, 6.1e-06, 3.1e-06, 3.3e-06)),
+    ((64, 128), (32, 64, 128, 128, 64, 32, 1)): ((3.2e-05, 5.8e-05, 3.2e-05, 4.1e-05, 5.9e-05, 5.9e-05, 1.5e-04),
+                                                 (3.9e-05, 3.5e-05, 4.3e-05, 4.2e-05, 4.5e-05, 9.1e-05)),
+    ((64, 128), (8, 16, 1)): ((9.9e-05, 7.6e-05, 7.1e-05), (9.2e-05, 2.1e-05)),
+    ((32, 64), (16, 64, 32, 16, 1)): ((1.2e-05, 1.1e-05, 1.0e-05, 1.1e-05, 1.8e-05), (1.0e-05, 6.4e-06, 6.9e-06, 9.9e-06)),
+    ((128, 128), (32, 64, 128, 128, 64, 32, 1)): ((1.5e-04, 1.5e-04, 1.0e-04, 1.5e-04, 1.7e-04, 2.0e-04, 3.7e-04),
+                                                  (1.2e-04, 1.1e-04, 1.7e-04, 1.3e-04, 1.5e-04, 2.1e-04)),
+}
+
+
+def generic_batch(hw, channels, n_enc, least=0):
+    """(base cells, copies): the smallest multiple of GENERIC_BASE cells, at least `least`, at which every launch of
+    generic_launches goes round at least three times and ends ragged."""
+    L = generic_launches(hw, channels, n_enc)
+    k = max(1, -(-least // GENERIC_BASE))
+    while not all(l.rounds(GENERIC_BASE * k, l.caps[0]) >= 3 and l.ragged(GENERIC_BASE * k, l.caps[0]) for l in L):
+        k += 1
+        assert k < 100000, (hw, channels)
+    return GENERIC_BASE, k
+
+
+# ---------------------------------------------------------------- the batches
+def weights(seed, **kw):
+    """synth.random_cae with non-trivial BatchNormalization parameters, every third gamma negative (the pooling then routes
+    through the window's minimum, sign(gamma)) and non-zero conv biases."""
+    from cellscreen import synth
+    w = synth.random_cae(seed=seed, **kw)
+    rng = np.random.default_rng(seed + 1000)
+    for l in range(w.n_conv - 1):
+        w.bn_gamma[l][l % 3::3] *= np.float32(-1.0)
+    for l in range(w.n_conv):
+        w.biases[l][:] = rng.uniform(-0.05, 0.05, w.biases[l].shape).astype(np.float32)
+    return w
+
+
+def mixed_batch(n, seed, hw=(64, 64)):
+    """n cells: blob crops and noise crops interleaved by a seeded shuffle; the input is the target plus noise (the reference trains
+    on an augmented input against the un-augmented target)."""
+    from cellscreen import synth
+    kw = {} if tuple(hw) == (64, 64) else {"hw": hw}
+    y = np.concatenate([synth.blob_crops(seed, n - n // 2, **kw), synth.synth_crops(seed, 0, n // 2, **kw)]) if n > 1 else synth.blob_crops(seed, 1, **kw)
+    rng = np.random.default_rng(seed)
+    y = y[rng.permutation(n)]
+    x = np.clip(y + 0.02 * rng.standard_normal(y.shape).astype(np.float32), 0, 1).astype(np.float32)
+    return x, np.ascontiguousarray(y)
+
+
+def replicate(x, y, k, seed):
+    """Every (input, target) pair k times in a seeded random order: (x_big, y_big, idx) with x_big[i] = x[idx[i]].  The order is a
+    permutation of repeat(arange(b), k), not a tiling: with a periodic order a read of the wrong cell could hit a copy of the right
+    one."""
+    idx = np.random.default_rng(seed).permutation(np.repeat(np.arange(len(x)), k))
+    return np.ascontiguousarray(x[idx]), np.ascontiguousarray(y[idx]), idx
+
+
+def fp32_oracle_figures(w, x, y):
+    """(dz per conv, da per BN layer, share of differing ReLU decisions) of the float32 numpy oracle against the float64 one on the
+    float32 evaluation's activation pattern: max error over the tensor's max.  How FP32_ORACLE and GENERIC_FP32_ORACLE were measured."""
+    import helpers as H
+    from oracle import train_oracle as T
+    nl = w.n_conv - 1
+    f32 = T.forward_backward(T.TrainState(w, dtype=np.float32), x, y)
+    free = T.forward_backward(T.TrainState(w, dtype=np.float64), x, y)
+    masks, args = H.pattern_of_relus(f32["relu"][:nl], w)
+    ref = T.forward_backward(T.TrainState(w, dtype=np.float64), x, y, relu_masks=masks, pool_args=args)
+    mx = lambda a, b: float(np.abs(a.astype(np.float64) - b).max() / max(np.abs(b).max(), 1e-300))
+    flips = sum(int(np.sum(m != (r > 0))) for m, r in zip(masks[:nl], free["relu"][:nl]))
+    return ([mx(f32["dz"][l], ref["dz"][l]) for l in range(nl + 1)], [mx(f32["da"][l], ref["da"][l]) for l in range(nl)],
+            flips / sum(m.size for m in masks[:nl]))
