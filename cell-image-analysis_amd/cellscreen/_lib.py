@@ -54,6 +54,7 @@ class CSDetectorParams(C.Structure):
 
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64)      # cs_allgather_fn
+ALLGATHER_STREAM_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p)      # cs_allgather_stream_fn
 
 
 class CSTrainCfg(C.Structure):
@@ -168,6 +169,7 @@ SIGNATURES = {
     "cs_train_apply": (_I, [_P, C.c_float]),
     "cs_train_set_grad_buffer": (_I, [_P, _P]),
     "cs_train_set_sync_bn": (_I, [_P, _P, _P, _P, _L, _I, _I]),
+    "cs_train_set_sync_bn_stream": (_I, [_P, _P, _P, _P, _L, _I, _I]),
     "cs_train_eval": (_I, [_P, _P, _P, _L, _I, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "cs_train_augment": (_I, [_P, _P, _L, _P, _P, _I]),
     "cs_train_export": (_I, [_P, _P, _P, _P]),

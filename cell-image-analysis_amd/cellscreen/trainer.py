@@ -193,17 +193,26 @@ class Trainer:
         L.order_after_torch(self._lib.cs_train_wait_stream, self._h, self._grad_tensor)
         L.check(self._lib.cs_train_apply(self._h, lr))
 
+    def _sync_buffer(self, world: int):
+        """The exchange buffer: world x 3 x (the largest BatchNormalization layer's filters) floats, what the library asks for."""
+        import torch
+        cmax = max(self.channels[:-1])
+        buf = torch.zeros(world * 3 * cmax, dtype=torch.float32, device=torch.device("cuda", self._device_id))
+        L.order_after_torch(self._lib.cs_train_wait_stream, self._h, buf)      # the fill runs on torch's stream, the slot writes on the handle's
+        return buf
+
+    def _sync_off(self):
+        L.check(self._lib.cs_train_set_sync_bn(self._h, None, None, None, 0, 0, 1))
+        self._sync = None
+
     def set_sync_bn(self, all_gather, rank: int, world: int):
         """cs_train_set_sync_bn: BatchNormalization statistics over the whole batch when it is split over `world` ranks.
         all_gather(buf, floats_per_rank) must fill buf[0 : world * floats_per_rank] (a torch CUDA float32 tensor in which
         this rank's slot [rank * fpr, (rank + 1) * fpr) is already written) and return when that is complete on the device;
-        None switches the synchronisation off."""
+        None switches the synchronisation off.  Every rank steps the same number of cells."""
         if all_gather is None:
-            L.check(self._lib.cs_train_set_sync_bn(self._h, None, None, None, 0, 0, 1))
-            self._sync = None
-            return
-        import torch
-        buf = torch.zeros(world * 3 * 64, dtype=torch.float32, device=torch.device("cuda", self._device_id))
+            return self._sync_off()
+        buf = self._sync_buffer(world)
 
         def hook(_ctx, fpr):
             try:
@@ -216,15 +225,43 @@ class Trainer:
         L.check(self._lib.cs_train_set_sync_bn(self._h, C.cast(cb, C.c_void_p), None, buf.data_ptr(), buf.numel(), rank, world))
         self._sync = (cb, buf)                # keep the callback and the buffer alive as long as the library may call / write them
 
-    def enable_sync_bn(self, dist, rank: int, world: int, group=None):
-        """The same over torch.distributed (backend nccl = RCCL over xGMI): one all_gather_into_tensor per sync point."""
-        import torch
+    def set_sync_bn_stream(self, all_gather, rank: int, world: int):
+        """cs_train_set_sync_bn_stream: the same exchange ordered on the device.  all_gather(buf, floats_per_rank, stream) must
+        ENQUEUE the in-place all-gather of buf[0 : world * floats_per_rank] so that it is ordered on `stream` (the handle's HIP stream
+        as an integer: wrap it in torch.cuda.ExternalStream) and return without waiting for the device; the step then has one host
+        wait, the loss read-back.  Replaces a hook set by set_sync_bn (and the other way round); None switches it off."""
+        if all_gather is None:
+            return self._sync_off()
+        buf = self._sync_buffer(world)
 
-        def all_gather(buf, fpr):
-            mine = buf[rank * fpr:(rank + 1) * fpr].clone()
-            dist.all_gather_into_tensor(buf[:world * fpr], mine, group=group)
-            torch.cuda.current_stream(buf.device).synchronize()
-        self.set_sync_bn(all_gather, rank, world)
+        def hook(_ctx, fpr, stream):
+            try:
+                all_gather(buf, int(fpr), int(stream or 0))
+                return 0
+            except Exception as e:  # noqa: BLE001 - an exception must not unwind through the C frames
+                self._sync_error = e
+                return 1
+        cb = L.ALLGATHER_STREAM_FN(hook)
+        L.check(self._lib.cs_train_set_sync_bn_stream(self._h, C.cast(cb, C.c_void_p), None, buf.data_ptr(), buf.numel(), rank, world))
+        self._sync = (cb, buf)
+
+    def enable_sync_bn(self, dist, rank: int, world: int, group=None, blocking: bool = False):
+        """The same over torch.distributed (backend nccl = RCCL over xGMI): one all_gather_into_tensor per sync point, issued
+        under the handle's stream -- torch orders the collective's own stream against the current stream on both sides, so the
+        host never waits (blocking=True: the earlier form, which synchronises after every collective)."""
+        import torch
+        if blocking:
+            def all_gather(buf, fpr):
+                mine = buf[rank * fpr:(rank + 1) * fpr].clone()
+                dist.all_gather_into_tensor(buf[:world * fpr], mine, group=group)
+                torch.cuda.current_stream(buf.device).synchronize()
+            return self.set_sync_bn(all_gather, rank, world)
+
+        def all_gather_on(buf, fpr, stream):
+            with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=buf.device)):
+                mine = buf[rank * fpr:(rank + 1) * fpr].clone()
+                dist.all_gather_into_tensor(buf[:world * fpr], mine, group=group)
+        self.set_sync_bn_stream(all_gather_on, rank, world)
 
     def use_grad_tensor(self, t):
         """Gradients are written into this torch CUDA float32 tensor (n_trainable elements), so

@@ -23,9 +23,10 @@ e.g. cellscreen.extract.label_cell_extractor), plots and text reports (:153-182,
   -> all-reduce -> cs_train_apply) so every rank holds identical weights.  `sync_bn=True` (the default) makes the
   BatchNormalization batch statistics those of the WHOLE batch of 32, as the reference's single process computes them
   (CAE_improved_modeltrain.py:192-213 with batch_size=32 at :287): the per-rank {n, mean, M2} triples of a layer are
-  all-gathered and merged, and so are the two sums of its backward pass (cellscreen/trainer.py, Trainer.enable_sync_bn);
-  `sync_bn=False` keeps per-rank statistics over the rank's slice (what Keras does under data parallelism without
-  SyncBatchNormalization) -- a deviation from the reference.  Either way the end of every epoch makes the ranks identical
+  all-gathered and merged, and so are the two sums of its backward pass (cellscreen/trainer.py, Trainer.enable_sync_bn), for
+  the reference graph and for every other crop size alike; the all-gathers are ordered on the trainer's stream, so the step's
+  one host wait is its loss read-back.  `sync_bn=False` keeps per-rank statistics over the rank's slice (what Keras does under
+  data parallelism without SyncBatchNormalization) -- a deviation from the reference.  Either way the end of every epoch makes the ranks identical
   before anything is decided: the moving statistics are averaged over the ranks and rank 0's validation loss is what every
   rank's callbacks see, so EarlyStopping and ReduceLROnPlateau fire on the same epoch everywhere.
 * Any instance of the layer grammar trains: `create_improved_autoencoder(input_shape)` is generic in the reference
@@ -169,13 +170,8 @@ class ImprovedAnomalyDetectionTraining:
         if world > 1:
             grad = torch.zeros(tr.n_trainable, dtype=torch.float32, device=dev)
             tr.use_grad_tensor(grad)
-            if self.sync_bn:
-                if tuple(X.shape[1:3]) == tuple(spec.INPUT_HW) and tuple(ae0.channels) == tuple(spec.CHANNELS):
-                    tr.enable_sync_bn(dist, rank, world)
-                else:       # cs_train_set_sync_bn serves the reference graph only (CS_ERR_UNSUPPORTED for run-time shapes)
-                    import warnings
-                    warnings.warn(f"sync_bn is available for the reference 64x64 graph only; training {tuple(X.shape[1:3])} / {tuple(ae0.channels)} "
-                                  f"with per-rank BatchNormalization statistics (pass sync_bn=False to silence this)")
+            if self.sync_bn:                                                        # any crop size: the exchange is sized by the handle
+                tr.enable_sync_bn(dist, rank, world)
         augment = self.augment
         # one GPU, the reference's generator (or none): a fit() batch is ONE library call -- gather, the batch's keyed augmentation
         # draws, forward + backward + Adam (cs_train_fit_step); a caller-supplied hook and the data-parallel step keep the

@@ -74,6 +74,59 @@ int reduce_gradient(cs_trainer* t, int64_t B, const float* errpart)
     return CS_OK;
 }
 
+// this rank's values are in its slot of the exchange buffer (enqueued).  Blocking hook: drain the stream, let the caller all-gather.
+// Stream-ordered hook: the caller enqueues the all-gather behind that work on the handle's stream; the host does not wait
+static int sync_gather(cs_trainer* t, int64_t floats_per_rank)
+{
+    if (t->sync_stream_fn) {
+        const int rc = t->sync_stream_fn(t->sync_ctx, floats_per_rank, (void*)t->stream);
+        if (rc) return fail(CS_ERR_INVALID, "the all-gather hook of cs_train_set_sync_bn_stream returned %d", rc);
+        return CS_OK;
+    }
+    HIPCHK(hipStreamSynchronize(t->stream));
+    const int rc = t->sync_fn(t->sync_ctx, floats_per_rank);
+    if (rc) return fail(CS_ERR_INVALID, "the all-gather hook of cs_train_set_sync_bn returned %d", rc);
+    return CS_OK;
+}
+
+int bn_forward_finish(cs_trainer* t, int l, int G1)
+{
+    hipStream_t s = t->stream;
+    const int C = t->ch[l];
+    float* MOV = t->MOV.as<float>();
+    const float* part = t->part_stats.as<float>();
+    int G = G1;
+    if (t->sync_on()) {
+        // the local partials -> ONE {count, mean, M2} triple per channel in this rank's slot, all-gather, and the final merge
+        // runs over the ranks' triples: the statistics (and the moving averages) of the whole batch, identical on every rank
+        LCHK(launch_bn_stats_merge(part, G1, C, t->sync_buf + (size_t)t->sync_rank * 3 * C, s));
+        int rc = sync_gather(t, 3 * C);
+        if (rc) return rc;
+        part = t->sync_buf; G = t->sync_world;
+    }
+    LCHK(launch_bn_stats_final(part, G, C, t->cfg.bn_eps, t->cfg.bn_momentum, MOV + t->off_mm[l], MOV + t->off_mv[l], t->stats[l].as<float>(), s));
+    return CS_OK;
+}
+
+int bn_backward_finish(cs_trainer* t, int l, int G2, double local)
+{
+    hipStream_t s = t->stream;
+    const int C = t->ch[l];
+    float* G = t->G;
+    if (t->sync_on()) {
+        // dgamma / dbeta stay this rank's share (the gradient all-reduce averages them like every other gradient); the two
+        // MEANS that dz needs are those of the whole batch: raw local sums -> slot, all-gather, summed in rank order
+        LCHK(launch_bn_bwd_final(t->part_bwd.as<float>(), G2, C, 1.0, t->sync_buf + (size_t)t->sync_rank * 2 * C, G + t->off_g[l],
+                                 G + t->off_be[l], s));
+        int rc = sync_gather(t, 2 * C);
+        if (rc) return rc;
+        LCHK(launch_bn_bwd_final(t->sync_buf, t->sync_world, C, local * t->sync_world, t->bwd_sums.as<float>(), t->sync_scratch.as<float>(),
+                                 t->sync_scratch.as<float>() + C, s));
+    } else
+        LCHK(launch_bn_bwd_final(t->part_bwd.as<float>(), G2, C, local, t->bwd_sums.as<float>(), G + t->off_g[l], G + t->off_be[l], s));
+    return CS_OK;
+}
+
 extern "C" {
 
 int cs_train_param_count(int64_t* n_trainable, int64_t* n_moving)
@@ -263,26 +316,36 @@ int cs_train_set_grad_buffer(cs_trainer* t, float* device_buffer)
     return CS_OK;
 }
 
-int cs_train_set_sync_bn(cs_trainer* t, cs_allgather_fn fn, void* ctx, float* device_buf, int64_t capacity_floats, int rank, int world)
+// both registrations: the exchange buffer holds the largest layer's forward triples of every rank, the scratch one layer's
+// {dgamma, dbeta}-shaped output of the second backward reduction (never read)
+static int set_sync(cs_trainer* t, cs_allgather_fn fn, cs_allgather_stream_fn sfn, void* ctx, float* device_buf, int64_t capacity_floats,
+                    int rank, int world)
 {
     if (!t) return fail(CS_ERR_INVALID, "trainer is NULL");
-    if (!fn) { t->sync_fn = nullptr; t->sync_world = 1; t->sync_rank = 0; return CS_OK; }
-    if (!t->ref) return fail(CS_ERR_UNSUPPORTED, "synchronised BatchNormalization is built for the reference graph's trainer");
-    if (!device_buf || world < 1 || rank < 0 || rank >= world || capacity_floats < (int64_t)world * 3 * 64)
-        return fail(CS_ERR_INVALID, "sync buffer NULL / too small (needs world x 192 floats) or bad rank/world");
-    int rc = t->sync_scratch.ensure(2 * 64 * sizeof(float));
+    if (!fn && !sfn) { t->sync_fn = nullptr; t->sync_stream_fn = nullptr; t->sync_world = 1; t->sync_rank = 0; return CS_OK; }
+    if (!device_buf || world < 1 || rank < 0 || rank >= world) return fail(CS_ERR_INVALID, "sync buffer NULL or bad rank/world (%d of %d)", rank, world);
+    const int cmax = t->bn_cmax();
+    const int64_t need = (int64_t)world * 3 * cmax;
+    if (capacity_floats < need)
+        return fail(CS_ERR_INVALID, "sync buffer too small: %lld floats, needs %lld (world %d x 3 x %d filters)", (long long)capacity_floats,
+                    (long long)need, world, cmax);
+    HIPCHK(hipSetDevice(t->device));
+    int rc = t->sync_scratch.ensure(2 * (size_t)cmax * sizeof(float));
     if (rc) return rc;
-    t->sync_fn = fn; t->sync_ctx = ctx; t->sync_buf = device_buf; t->sync_cap = capacity_floats; t->sync_rank = rank; t->sync_world = world;
+    t->sync_fn = fn; t->sync_stream_fn = sfn; t->sync_ctx = ctx; t->sync_buf = device_buf; t->sync_cap = capacity_floats;
+    t->sync_rank = rank; t->sync_world = world;
     return CS_OK;
 }
 
-// this rank's values are in its slot of the exchange buffer (enqueued): drain the stream, let the caller all-gather
-static int sync_gather(cs_trainer* t, int64_t floats_per_rank)
+int cs_train_set_sync_bn(cs_trainer* t, cs_allgather_fn fn, void* ctx, float* device_buf, int64_t capacity_floats, int rank, int world)
 {
-    HIPCHK(hipStreamSynchronize(t->stream));
-    const int rc = t->sync_fn(t->sync_ctx, floats_per_rank);
-    if (rc) return fail(CS_ERR_INVALID, "the all-gather hook of cs_train_set_sync_bn returned %d", rc);
-    return CS_OK;
+    return set_sync(t, fn, nullptr, ctx, device_buf, capacity_floats, rank, world);
+}
+
+int cs_train_set_sync_bn_stream(cs_trainer* t, cs_allgather_stream_fn fn, void* ctx, float* device_buf, int64_t capacity_floats, int rank,
+                                int world)
+{
+    return set_sync(t, nullptr, fn, ctx, device_buf, capacity_floats, rank, world);
 }
 
 // Everything of forward + backward between the input copies and the loss read-back, as stream work only (no host
@@ -291,8 +354,6 @@ static int ref_fb_enqueue(cs_trainer* t, int64_t B)
 {
     hipStream_t s = t->stream;
     float* P = t->P.as<float>();
-    float* G = t->G;
-    float* MOV = t->MOV.as<float>();
 
     // ---- forward, BatchNormalization in training mode ---------------------------------
     for (int l = 0; l < 6; ++l) {
@@ -301,17 +362,7 @@ static int ref_fb_enqueue(cs_trainer* t, int64_t B)
         // the conv leaves its workgroups' {count, mean, M2} per channel beside the tensor: no statistics pass over r
         int G1 = 0;
         LCHK(launch_conv_train_fwd(l, in, t->wf[l].as<float>(), P + t->off_b[l], t->r[l].as<float>(), B, s, t->part_stats.as<float>(), &G1));
-        if (t->sync_fn) {
-            // the local partials -> ONE {count, mean, M2} triple per channel in this rank's slot, all-gather, and the final merge
-            // runs over the ranks' triples: the statistics (and the moving averages) of the whole batch, identical on every rank
-            LCHK(launch_bn_stats_merge(t->part_stats.as<float>(), G1, C, t->sync_buf + (size_t)t->sync_rank * 3 * C, s));
-            int rc = sync_gather(t, 3 * C);
-            if (rc) return rc;
-            LCHK(launch_bn_stats_final(t->sync_buf, t->sync_world, C, t->cfg.bn_eps, t->cfg.bn_momentum, MOV + t->off_mm[l],
-                                       MOV + t->off_mv[l], t->stats[l].as<float>(), s));
-        } else
-        LCHK(launch_bn_stats_final(t->part_stats.as<float>(), G1, C, t->cfg.bn_eps, t->cfg.bn_momentum, MOV + t->off_mm[l],
-                                   MOV + t->off_mv[l], t->stats[l].as<float>(), s));
+        { int rc = bn_forward_finish(t, l, G1); if (rc) return rc; }
         LCHK(launch_bn_apply(t->r[l].as<float>(), C, P + t->off_g[l], P + t->off_be[l], t->stats[l].as<float>(),
                              t->a[l].as<float>(), B, Hc, Hc, pool, s));
     }
@@ -334,18 +385,7 @@ static int ref_fb_enqueue(cs_trainer* t, int64_t B)
         int G2 = 0;
         LCHK(launch_bn_bwd_reduce(t->da[l].as<float>(), t->r[l].as<float>(), t->stats[l].as<float>(), P + t->off_g[l],
                                   P + t->off_be[l], B, Hc, Hc, C, pool, t->part_bwd.as<float>(), &G2, s));
-        if (t->sync_fn) {
-            // dgamma / dbeta stay this rank's share (the gradient all-reduce averages them like every other gradient); the two
-            // MEANS that dz needs are those of the whole batch: raw local sums -> slot, all-gather, summed in rank order
-            LCHK(launch_bn_bwd_final(t->part_bwd.as<float>(), G2, C, 1.0, t->sync_buf + (size_t)t->sync_rank * 2 * C,
-                                     G + t->off_g[l], G + t->off_be[l], s));
-            int rc = sync_gather(t, 2 * C);
-            if (rc) return rc;
-            LCHK(launch_bn_bwd_final(t->sync_buf, t->sync_world, C, (double)B * t->sync_world * Hc * Hc, t->bwd_sums.as<float>(),
-                                     t->sync_scratch.as<float>(), t->sync_scratch.as<float>() + 64, s));
-        } else
-        LCHK(launch_bn_bwd_final(t->part_bwd.as<float>(), G2, C, (double)B * Hc * Hc, t->bwd_sums.as<float>(),
-                                 G + t->off_g[l], G + t->off_be[l], s));
+        { int rc = bn_backward_finish(t, l, G2, (double)B * Hc * Hc); if (rc) return rc; }
         LCHK(launch_bn_bwd_dz(t->da[l].as<float>(), t->r[l].as<float>(), t->stats[l].as<float>(), P + t->off_g[l],
                               P + t->off_be[l], t->bwd_sums.as<float>(), B, Hc, Hc, C, pool, t->dz[l].as<float>(),
                               t->dzsum_part[l].as<float>(), &t->np_b[l], s));

@@ -322,15 +322,14 @@ int gen_train_ensure_batch(cs_trainer* t, int64_t b)
 }
 
 // Forward + backward of the batch in t->x / t->y as stream work only (no host synchronisation once the reduction descriptors of
-// this batch size are uploaded).  The weight gradient of a layer needs only that layer's dz and input: it runs on a second stream beside the
+// this batch size are uploaded; the blocking all-gather hook of cs_train_set_sync_bn is the one exception, train_api.hip).
+// The weight gradient of a layer needs only that layer's dz and input: it runs on a second stream beside the
 // backward-data conv and the BatchNormalization-backward kernels of the layers below (a third of the step's kernel time at
 // batch 32 of the 128 x 128 variant: profiles/r04_*_train_variant_trace.txt); both streams join before the partial sums are reduced.
 int gen_train_fb_enqueue(cs_trainer* t, int64_t B)
 {
     hipStream_t s = t->stream;
     float* P = t->P.as<float>();
-    float* G = t->G;
-    float* MOV = t->MOV.as<float>();
     const int last = t->n_conv - 1;
     const size_t npix = (size_t)t->H * t->W;
 
@@ -346,8 +345,7 @@ int gen_train_fb_enqueue(cs_trainer* t, int64_t B)
                                      l > t->n_enc, GEN_EPI_RELU, s));
         int G1 = 0;
         LCHK(launch_bn_stats(t->r[l].as<float>(), (long)B * t->gh[l] * t->gw[l], C, t->part_stats.as<float>(), &G1, s));
-        LCHK(launch_bn_stats_final(t->part_stats.as<float>(), G1, C, t->cfg.bn_eps, t->cfg.bn_momentum, MOV + t->off_mm[l],
-                                   MOV + t->off_mv[l], t->stats[l].as<float>(), s));
+        { int rc = bn_forward_finish(t, l, G1); if (rc) return rc; }      // synchronised: the ranks' triples are exchanged here
         LCHK(launch_bn_apply(t->r[l].as<float>(), C, P + t->off_g[l], P + t->off_be[l], t->stats[l].as<float>(), t->a[l].as<float>(), B,
                              t->gh[l], t->gw[l], pool, s));
     }
@@ -364,8 +362,7 @@ int gen_train_fb_enqueue(cs_trainer* t, int64_t B)
             int G2 = 0;
             LCHK(launch_bn_bwd_reduce(t->da[l].as<float>(), t->r[l].as<float>(), t->stats[l].as<float>(), P + t->off_g[l], P + t->off_be[l], B,
                                       t->gh[l], t->gw[l], C, pool, t->part_bwd.as<float>(), &G2, s));
-            LCHK(launch_bn_bwd_final(t->part_bwd.as<float>(), G2, C, (double)B * t->gh[l] * t->gw[l], t->bwd_sums.as<float>(), G + t->off_g[l],
-                                     G + t->off_be[l], s));
+            { int rc = bn_backward_finish(t, l, G2, (double)B * t->gh[l] * t->gw[l]); if (rc) return rc; }
             LCHK(launch_bn_bwd_dz(t->da[l].as<float>(), t->r[l].as<float>(), t->stats[l].as<float>(), P + t->off_g[l], P + t->off_be[l],
                                   t->bwd_sums.as<float>(), B, t->gh[l], t->gw[l], C, pool, t->dz[l].as<float>(), t->dzsum_part[l].as<float>(),
                                   &t->np_b[l], s));

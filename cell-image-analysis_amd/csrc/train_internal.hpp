@@ -86,8 +86,13 @@ struct cs_trainer {
     // host, and the event behind the step's input copies
     cs::DevBuf macc;
     double hacc[3] = {0.0, 0.0, 0.0};
-    // synchronised BatchNormalization under data parallelism (cs_train_set_sync_bn): the caller's all-gather, its exchange buffer
+    // synchronised BatchNormalization under data parallelism: the caller's all-gather in ONE of its two forms -- blocking
+    // (cs_train_set_sync_bn: the library drains its stream before the call) or ordered on the stream
+    // (cs_train_set_sync_bn_stream: the library only enqueues) -- and its exchange buffer
     cs_allgather_fn sync_fn = nullptr;
+    cs_allgather_stream_fn sync_stream_fn = nullptr;
+    bool sync_on() const { return sync_fn || sync_stream_fn; }
+    int bn_cmax() const { int c = 0; for (int l = 0; l < n_conv - 1; ++l) c = ch[l] > c ? ch[l] : c; return c; }   // largest BatchNormalization layer
     void* sync_ctx = nullptr;
     float* sync_buf = nullptr;
     int64_t sync_cap = 0;
@@ -116,6 +121,14 @@ struct cs_trainer {
 // train_api.hip: the backward's two streams join, every partial sum -> the flat gradient t->G in workgroup order; errpart (the
 // reference form) also reduces the forward pass's error partials to the batch's {loss, mae} in t->scal
 int reduce_gradient(cs_trainer* t, int64_t B, const float* errpart);
+
+// train_api.hip: the two points of a BatchNormalization layer at which a batch split over ranks is put together again, written once
+// for both forms.  Without a hook they enqueue exactly the one final kernel of the single-process step.
+//   forward:  the G1 {count, mean, M2} partials of layer l in t->part_stats -> t->stats[l] and the moving averages
+//   backward: the G2 {sum dy, sum dy xhat} partials in t->part_bwd -> the two means in t->bwd_sums (over `local` elements per rank)
+//             and this rank's dgamma / dbeta in t->G
+int bn_forward_finish(cs_trainer* t, int l, int G1);
+int bn_backward_finish(cs_trainer* t, int l, int G2, double local);
 
 // train_generic.hip: the run-time-shaped form of the operations the two forms differ in (train_api.hip dispatches them)
 int gen_train_setup(cs_trainer* t);                      // buffers that depend on the architecture only

@@ -60,8 +60,10 @@
  *   - The library links no communication library.  Multi-GPU is one process and one handle per GPU; every
  *     exchange between processes (the gradient all-reduce, the all-gather of BatchNormalization partials,
  *     the gather of results) happens ABOVE this ABI, in the host's own communicator (RCCL through
- *     torch.distributed in cellscreen/dist.py), on buffers the caller owns: cs_train_set_grad_buffer and
- *     cs_train_set_sync_bn are the two hooks.  Screening has no exchange on its data path.
+ *     torch.distributed in cellscreen/dist.py), on buffers the caller owns: cs_train_set_grad_buffer (the gradient) and
+ *     cs_train_set_sync_bn / cs_train_set_sync_bn_stream (the BatchNormalization partials: a blocking hook, or one the
+ *     caller orders on the handle's stream so that the host never waits) are the hooks.  Screening has no exchange on
+ *     its data path.
  *   - There is NO CPU fallback: without a gfx950 device every compute entry point
  *     returns CS_ERR_NO_DEVICE.
  */
@@ -493,10 +495,25 @@ int cs_train_apply(cs_trainer *t, float lr);
  * fake communicator in tests) and returns 0 once device_buf[0 .. world * floats_per_rank) is complete and visible to the
  * device.  The library merges the `world` triples in rank order (Chan's formula, double), so every rank gets identical
  * statistics, identical moving averages, and -- with the usual mean of the per-rank weight gradients -- the gradient of the
- * single-process step.  capacity_floats >= world * 3 * (largest filter count).  fn == NULL switches it off.  Reference graph
- * only (CS_ERR_UNSUPPORTED otherwise). */
+ * single-process step.  Every handle cs_train_create accepts can be synchronised: capacity_floats >= world * 3 * Cmax, Cmax being the
+ * handle's largest BatchNormalization filter count (64 for the reference graph, up to 256); a smaller buffer is CS_ERR_INVALID and
+ * the message names the floats needed.  fn == NULL switches synchronisation off.  Every rank must step the SAME number of cells: the
+ * backward means divide by batch * world elements per pixel, so unequal per-rank batches are not supported.
+ * A hook that returns non-zero fails the step with CS_ERR_INVALID.  The peers of that rank are then inside a collective that will
+ * never complete: the caller must abort its process group (tear the communicator down), not merely retry the step. */
 typedef int (*cs_allgather_fn)(void *ctx, int64_t floats_per_rank);
 int cs_train_set_sync_bn(cs_trainer *t, cs_allgather_fn fn, void *ctx, float *device_buf, int64_t capacity_floats, int rank, int world);
+/* The same exchange ORDERED ON THE STREAM, so that a synchronised step has one host wait (the loss read-back) as the single-GPU
+ * step has.  fn must ENQUEUE an in-place all-gather of device_buf[0 .. world * floats_per_rank) so that it is ordered on hip_stream
+ * (the handle's stream: run the collective on it, or on another stream tied to it by events in both directions) and return
+ * without waiting for the device.  Work enqueued on hip_stream before the call wrote this rank's slot; work the library enqueues
+ * after the call returns reads all slots.  With this hook the library calls no hipStreamSynchronize (or any other host wait)
+ * between the input copies and the loss read-back of cs_train_forward_backward.  Buffer, rank / world, equal per-rank batches and
+ * the failure contract are those of cs_train_set_sync_bn.  Registering either hook replaces the other; fn == NULL on either entry
+ * point switches synchronisation off. */
+typedef int (*cs_allgather_stream_fn)(void *ctx, int64_t floats_per_rank, void *hip_stream);
+int cs_train_set_sync_bn_stream(cs_trainer *t, cs_allgather_stream_fn fn, void *ctx, float *device_buf, int64_t capacity_floats,
+                                int rank, int world);
 /* Use caller-owned device memory (n_trainable floats, e.g. a torch tensor) as the gradient
  * buffer; NULL restores the internal one. */
 int cs_train_set_grad_buffer(cs_trainer *t, float *device_buffer);
