@@ -97,6 +97,13 @@ class CSQcParams(C.Structure):
                 ("max_eccentricity", C.c_double), ("min_mean", C.c_double), ("min_std", C.c_double), ("clip_limit", C.c_double)]
 
 
+class CSSegmentParams(C.Structure):
+    _fields_ = [("threshold_mode", C.c_int32), ("threshold", C.c_int32), ("connectivity", C.c_int32), ("fill_holes", C.c_int32)]
+
+
+THRESH_OTSU, THRESH_FIXED = 0, 1        # cs_segment_params.threshold_mode
+
+
 # cs_region of include/cellscreen.h as a numpy record (80 bytes)
 REGION_DTYPE = np.dtype([("image", np.int32), ("label", np.int32), ("minr", np.int32), ("minc", np.int32), ("maxr", np.int32),
                          ("maxc", np.int32), ("area", np.int64), ("convex_area", np.int64), ("eccentricity", np.float64),
@@ -135,6 +142,9 @@ SIGNATURES = {
                                 C.POINTER(CSQcParams), C.POINTER(_L), C.POINTER(_L)]),
     "cs_extract_fill": (_I, [_P, _P, _P, _I, _P, _P, _I]),
     "cs_extract_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "cs_segment_threshold": (_I, [_P, _P, _I, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _I, C.POINTER(CSSegmentParams),
+                                  _P, _I, _P, _P]),
+    "cs_segment_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "cs_fit_create": (_I, [_I, C.POINTER(_P)]),
     "cs_fit_free": (None, [_P]),
     "cs_fit_wait_stream": (_I, [_P, _P]),

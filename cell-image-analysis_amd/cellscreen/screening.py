@@ -4,8 +4,10 @@ with the arithmetic of compute_anomaly_scores executed by libcellscreen on the G
 
 Out of scope here: the StarDist segmentation itself (:44, :59-60) -- supply a
 `cell_extractor(image_path) -> (list_of_64x64_arrays, list_of_stat_dicts)`, e.g.
-cellscreen.extract.label_cell_extractor(segment), which runs the rest of :48-115 on the GPU, or pre-extracted
-`.npy` crop files; plots and the text report (:263-403).  For a model of another input size the cells have that size:
+cellscreen.extract.label_cell_extractor(segment), which runs the rest of :48-115 on the GPU behind a segmenter of yours,
+cellscreen.segment.threshold_cell_extractor(), which puts the built-in Otsu + connected-components segmenter (not
+StarDist) in its place and keeps the labels on the device, or pre-extracted `.npy` crop files; plots and the text report
+(:263-403).  For a model of another input size the cells have that size:
 label_cell_extractor(segment, out_hw=(H, W))."""
 from __future__ import annotations
 
@@ -54,7 +56,9 @@ class ProductionMutantScreening:
                     raise ValueError(f"expected (N,{hw[0]},{hw[1]}) crops, got {cells.shape}")
                 stats = [{"mean_intensity": float(np.mean(c)), "std_intensity": float(np.std(c))} for c in cells]
                 return list(cells), stats
-            raise NotImplementedError("StarDist cell extraction is out of scope; pass cell_extractor= or use .npy crop files")
+            raise NotImplementedError("StarDist cell extraction is out of scope; pass cell_extractor= (e.g. "
+                                      "cellscreen.segment.threshold_cell_extractor(), the built-in threshold segmenter, or "
+                                      "cellscreen.extract.label_cell_extractor(segment)) or use .npy crop files")
         except Exception as e:                          # :113-115
             print(f"Error processing {image_path}: {e}")
             return [], []

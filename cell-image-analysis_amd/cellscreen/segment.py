@@ -1,0 +1,190 @@
+"""The built-in segmenter on the GPU (csrc/segment.hip): a global threshold (Otsu's, or a fixed one), optional hole filling
+and connected-component labelling, from the segmentation channel of an image stack to int32 label images that
+cellscreen.extract reads without a copy through the host.
+
+It is NOT StarDist and does not try to be: it is a classical segmenter for bright cells on a dark background.  Cells that
+touch come out as one region, which the extraction's area and eccentricity rules then judge like any other region.
+What it computes is exact: the threshold is scikit-image 0.18.3's threshold_otsu of the channel (an integer), the mask is
+`channel > threshold` (after scipy.ndimage.binary_fill_holes with fill_holes), and the labels are scipy.ndimage.label's
+(= skimage.measure.label's) ids, as restated in tests/segment_reference.py; neither library is a dependency.
+
+    seg = ThresholdSegmenter()
+    labels, n_labels, thresholds = seg.segment_batch(images)          # numpy in, numpy out; CUDA tensors in, CUDA tensor out
+
+    screening = ProductionMutantScreening(model_dir, cell_extractor=threshold_cell_extractor())
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional
+
+import numpy as np
+
+from . import _lib as L
+from .extract import (IMAGE_NO_CELLS, IMAGE_OK, MAX_SIDE, CellExtractor, _is_tensor, qc_params, read_image, region_stats,
+                      split_channels)
+from .preprocess import OUT_SIDE, PIX_U8, PIX_U16, Preprocessor, check_out_hw
+
+MAX_BATCH = 65535
+
+
+def segment_params(threshold="otsu", connectivity: int = 1, fill_holes: bool = True) -> L.CSSegmentParams:
+    """cs_segment_params from the Python arguments; anything out of range raises before a handle exists."""
+    p = L.CSSegmentParams()
+    if isinstance(threshold, str):
+        if threshold != "otsu":
+            raise ValueError(f"threshold must be 'otsu' or an integer, got {threshold!r}")
+        p.threshold_mode, p.threshold = L.THRESH_OTSU, 0
+    else:
+        if isinstance(threshold, bool) or not isinstance(threshold, (int, np.integer)):
+            raise TypeError(f"threshold must be 'otsu' or an integer, got {type(threshold).__name__}")
+        if not 0 <= int(threshold) <= 65535:
+            raise ValueError(f"threshold {threshold} outside 0..65535")
+        p.threshold_mode, p.threshold = L.THRESH_FIXED, int(threshold)
+    if isinstance(connectivity, bool) or connectivity not in (1, 2):
+        raise ValueError(f"connectivity must be 1 (4 neighbours) or 2 (8 neighbours), got {connectivity!r}")
+    p.connectivity = int(connectivity)
+    p.fill_holes = 1 if fill_holes else 0
+    return p
+
+
+class ThresholdSegmenter:
+    """Threshold + connected components on one preprocess handle (one GPU, one stream).  threshold: "otsu" (per image) or an
+    integer; foreground is pixel > threshold.  connectivity: 1 (4 neighbours) or 2 (8).  fill_holes: background enclosed
+    by foreground becomes foreground before labelling.  extractor: a CellExtractor whose handle and stream to share, so
+    that labels left on the device feed its extract_batch in stream order."""
+
+    def __init__(self, device_id: int = 0, threshold="otsu", connectivity: int = 1, fill_holes: bool = True,
+                 extractor: Optional[CellExtractor] = None):
+        self._params = segment_params(threshold, connectivity, fill_holes)
+        if extractor is not None and extractor.device_id != device_id:
+            raise ValueError(f"extractor is on device {extractor.device_id}, the segmenter on {device_id}")
+        self.threshold, self.connectivity, self.fill_holes = threshold, int(connectivity), bool(fill_holes)
+        self._lib = L.load_library()
+        self.device_id = device_id
+        self._ext = extractor
+        self._pre: Optional[Preprocessor] = None        # own handle: created by the first call, after its argument checks
+
+    @property
+    def _handle(self):
+        if self._ext is not None:
+            return self._ext._handle
+        if self._pre is None:
+            self._pre = Preprocessor(self.device_id)
+        return self._pre._h
+
+    def close(self):
+        """Frees the segmenter's own handle (a shared extractor's handle stays the extractor's); a later call makes a new one."""
+        if self._pre is not None:
+            self._pre.close()
+            self._pre = None
+
+    # ---- argument checks: everything is refused before the device is touched ---------------------------------------
+    def _check(self, images, channel):
+        on_dev = _is_tensor(images)
+        if not on_dev and not isinstance(images, np.ndarray):
+            raise TypeError(f"unsupported input type {type(images)}")
+        if images.ndim not in (3, 4):
+            raise ValueError(f"images must be [B,H,W] or [B,H,W,C], got shape {tuple(images.shape)}")
+        B, H, W = (int(x) for x in images.shape[:3])
+        Cn = int(images.shape[3]) if images.ndim == 4 else 1
+        if B < 1 or H < 1 or W < 1 or Cn < 1:
+            raise ValueError(f"empty batch or image: shape {tuple(images.shape)}")
+        if H > MAX_SIDE or W > MAX_SIDE:
+            raise ValueError(f"image sides above {MAX_SIDE} are not supported, got {H}x{W}")
+        if B > MAX_BATCH:
+            raise ValueError(f"at most {MAX_BATCH} images per call, got {B}")
+        if channel is None:
+            if Cn == 1:
+                channel = 0
+            elif Cn >= 3:
+                channel = 2                                         # the segmentation channel, improved_detection.py:55
+            else:
+                raise ValueError(f"{Cn} channels: pass channel= explicitly")
+        if isinstance(channel, bool) or not isinstance(channel, (int, np.integer)) or not 0 <= channel < Cn:
+            raise ValueError(f"channel {channel!r} outside [0, {Cn})")
+        if on_dev:
+            import torch
+            if images.dtype == torch.uint8:
+                ptype = PIX_U8
+            elif images.dtype in (torch.uint16, torch.int16):
+                ptype = PIX_U16
+            else:
+                raise TypeError(f"image tensor dtype {images.dtype}: uint8 or uint16 expected")
+            if not images.is_cuda:
+                raise ValueError("images is a CPU tensor; pass numpy arrays or CUDA tensors")
+            if images.device.index != self.device_id:
+                raise ValueError(f"images is on {images.device}, the segmenter on cuda:{self.device_id}")
+            if not images.is_contiguous():
+                raise ValueError("images is not contiguous")
+        else:
+            if images.dtype == np.uint8:
+                ptype = PIX_U8
+            elif images.dtype == np.uint16:
+                ptype = PIX_U16
+            else:
+                raise TypeError(f"image dtype {images.dtype}: uint8 or uint16 expected")
+            if not images.flags.c_contiguous:
+                raise ValueError("images must be C-contiguous")
+        return B, H, W, Cn, int(channel), ptype, on_dev
+
+    def segment_batch(self, images, channel: Optional[int] = None):
+        """images: [B,H,W] or [B,H,W,C] uint8 / uint16, numpy or CUDA tensors of the segmenter's device; the channel that is
+        segmented is `channel` (default 2 of >= 3 channels as improved_detection.py:55, 0 of one).
+        Returns (labels, n_labels, thresholds): labels int32 [B,H,W] (0 = background, ids 1.. in raster order of each
+        component's first pixel), numpy for numpy input and a CUDA tensor for tensor input; n_labels and thresholds int32
+        numpy [B]."""
+        B, H, W, Cn, channel, ptype, on_dev = self._check(images, channel)
+        n_labels = np.zeros(B, np.int32)
+        thresholds = np.zeros(B, np.int32)
+        if on_dev:
+            import torch
+            labels = torch.empty((B, H, W), dtype=torch.int32, device=images.device)
+            L.order_after_torch(self._lib.cs_preproc_wait_stream, self._handle, images, labels)
+        else:
+            labels = np.empty((B, H, W), np.int32)
+        kind = L.CS_MEM_DEVICE if on_dev else L.CS_MEM_HOST
+        L.check(self._lib.cs_segment_threshold(self._handle, L._ptr(images), ptype, Cn, channel, B, H, W, kind,
+                                               C.byref(self._params), L._ptr(labels), kind, n_labels.ctypes.data,
+                                               thresholds.ctypes.data))
+        return labels, n_labels, thresholds
+
+    def last_timing(self):
+        a, b = C.c_double(), C.c_double()
+        L.check(self._lib.cs_segment_last_timing(self._handle, C.byref(a), C.byref(b)))
+        return {"threshold_ms": a.value, "label_ms": b.value}
+
+
+def threshold_cell_extractor(device_id: int = 0, out_hw=(OUT_SIDE, OUT_SIDE), threshold="otsu", connectivity: int = 1,
+                             fill_holes: bool = True, **qc):
+    """The `cell_extractor(image_path) -> (cells, stats)` that ProductionMutantScreening and create_training_dataset accept,
+    with the built-in segmenter in StarDist's place: the file is read (extract.read_image / split_channels), uploaded once,
+    segmented and extracted on one handle, and the labels never leave the device.  Not StarDist: see the module text.
+    Errors raise as label_cell_extractor's do; the screening driver's try turns them into the reference's "Error processing"
+    line and ([], []).  out_hw and **qc as for label_cell_extractor."""
+    out_hw = check_out_hw(out_hw)
+    segment_params(threshold, connectivity, fill_holes)
+    qc_params(**qc)
+    st = {}
+
+    def cell_extractor(image_path: str):
+        import torch
+        image = read_image(image_path)
+        _, img, ch = split_channels(image)
+        seg_ch = 2 if img.ndim == 3 else 0
+        if img.dtype not in (np.uint8, np.uint16):
+            raise TypeError(f"image dtype {img.dtype}: uint8 or uint16 expected")
+        if "x" not in st:
+            st["x"] = CellExtractor(device_id, out_hw, **qc)
+            st["s"] = ThresholdSegmenter(device_id, threshold, connectivity, fill_holes, extractor=st["x"])
+        host = np.ascontiguousarray(img)[None]
+        dev = torch.from_numpy(host.view(np.int16) if host.dtype == np.uint16 else host).to(torch.device("cuda", device_id))
+        labels, _, _ = st["s"].segment_batch(dev, channel=seg_ch)
+        r = st["x"].extract_batch(dev, labels, channel=ch)
+        status = int(r.status[0])
+        if status != IMAGE_OK:
+            raise ValueError("a passing region has a bounding-box side below 8 px (equalize_adapthist raises)"
+                             if status == IMAGE_NO_CELLS else st["x"]._unsupported_text() + " (beyond the preprocess kernel)")
+        return list(r.cells.cpu().numpy()), region_stats(r.regions)
+
+    return cell_extractor

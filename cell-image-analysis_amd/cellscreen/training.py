@@ -4,7 +4,7 @@ files, with the per-batch arithmetic (fit step, validation pass, reconstruction 
 encoder features, detector fit) executed by libcellscreen on the GPU.
 
 Out of scope: the StarDist segmentation itself (create_training_dataset takes a cell_extractor,
-e.g. cellscreen.extract.label_cell_extractor), plots and text reports (:153-182, 304-326, 345-392, 448-478).
+e.g. cellscreen.extract.label_cell_extractor or cellscreen.segment.threshold_cell_extractor), plots and text reports (:153-182, 304-326, 345-392, 448-478).
 
 * Augmentation (:246-254): the default `augment="reference"` runs the reference's ImageDataGenerator
   settings on the GPU (cellscreen/augment.py + cs_train_augment) -- the reference always trains through
@@ -85,7 +85,8 @@ class ImprovedAnomalyDetectionTraining:
     def create_training_dataset(self, folder_path: str, cell_extractor: Callable[[str], tuple], file_pattern: str = "*.tif"):
         """:113-151 with the cell extraction of :39-111 supplied by the caller: `cell_extractor(image_path) -> (cells, stats)`,
         e.g. cellscreen.extract.label_cell_extractor(segment) (quality rules + crop preprocess on the GPU; the segmenter is
-        the caller's, StarDist in the reference).  Writes cell_statistics.csv and file_summary.csv with the reference's
+        the caller's, StarDist in the reference) or cellscreen.segment.threshold_cell_extractor() (the built-in threshold +
+        connected-components segmenter, not StarDist).  Writes cell_statistics.csv and file_summary.csv with the reference's
         columns and pandas calls, returns (np.array(cells), stats_df).  The text report (:153-182) is out of scope.
         The cells have the extractor's size: for a model that is not 64 x 64, the reference's two edits (the resize at :93
         and input_shape) are label_cell_extractor(segment, out_hw=(H, W)) here and

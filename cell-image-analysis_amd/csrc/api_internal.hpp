@@ -84,6 +84,8 @@ hipError_t launch_preprocess(const void* pix, int pixel_type, const CropDesc* de
                              uint16_t* clahe, float* out, int out_h, int out_w, hipStream_t stream);
 struct ExtractState;                            // extract.hip: the state between cs_extract_measure and cs_extract_fill
 void extract_state_free(ExtractState* s);
+struct SegmentState;                            // segment.hip: the buffers of cs_segment_threshold
+void segment_state_free(SegmentState* s);
 
 int upload(DevBuf& d, const void* src, size_t bytes);
 int check_arch(const cs_cae_weights* w, int expect_convs, const char* what);
@@ -91,7 +93,7 @@ int require_gfx950(int device_id);
 
 }  // namespace cs
 
-// The preprocess handle (include/cellscreen.h); its extraction entry points live in extract.hip.
+// The preprocess handle (include/cellscreen.h); its extraction entry points live in extract.hip, its segmenter in segment.hip.
 struct cs_preproc {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -107,9 +109,11 @@ struct cs_preproc {
     double last_kernel_ms = 0.0;
     int64_t last_pixels = 0;
     cs::ExtractState* ext = nullptr;    // created by the first cs_extract_measure
+    cs::SegmentState* seg = nullptr;    // created by the first cs_segment_threshold
     ~cs_preproc()
     {
         cs::extract_state_free(ext);
+        cs::segment_state_free(seg);
         if (hdesc) (void)hipHostFree(hdesc);
     }
 };

@@ -26,6 +26,9 @@
  *        eccentricity / intensity rules + the bbox crop + the preprocess above
  *                                   improved_detection.py:61-111, CAE_improved_modeltrain.py:54-107
  *        (the StarDist segmentation itself, :59-60 / :52-53, stays with the caller)
+ *   cs_segment_threshold
+ *        the library's own classical segmenter (no reference counterpart, and no StarDist): Otsu or
+ *        fixed threshold, optional hole filling, connected-component labels for the extraction above
  *   cs_fit_scaler / cs_fit_pca_moments / cs_fit_pca_subspace / cs_fit_project / cs_fit_ocsvm
  *        RobustScaler / PCA / OneClassSVM fits of create_anomaly_detector
  *                                                 CAE_improved_modeltrain.py:408-427
@@ -371,6 +374,51 @@ int cs_extract_fill(cs_preproc *p, cs_region *regions, int32_t *image_status, in
                     int cells_kind);
 /* Device time of the last measure + fill: label pass, per-region pass (with the scan), gather + preprocess. */
 int cs_extract_last_timing(const cs_preproc *p, double *label_ms, double *region_ms, double *cells_ms);
+
+/* ---- built-in segmenter: global threshold + connected components ---------------------------
+ * Not StarDist: a classical segmenter of the library's own, for bright cells on a dark background.
+ * Touching cells come out as ONE region (the extraction's area / eccentricity rules then judge it).
+ * Input as for the extraction: one `channel` of a [B][H][W][channels] uint8 / uint16 stack, read in place.
+ *   threshold   CS_THRESH_OTSU: scikit-image 0.18.3's threshold_otsu of that channel of each image (exact
+ *               integer histogram over [min, max], int64 cumulative sums, its float64 operations in its order:
+ *               the same integer); a constant image gives its value.  CS_THRESH_FIXED: `threshold`.
+ *               Foreground is pixel > threshold.
+ *   fill_holes  background components (4-connected) that do not touch the image border become foreground:
+ *               scipy.ndimage.binary_fill_holes with its default structure.
+ *   labels      connected components of the mask, connectivity 1 (4 neighbours) or 2 (8), numbered 1.. in
+ *               raster order of each component's first pixel: scipy.ndimage.label's and skimage.measure.label's
+ *               numbering.  0 = background.
+ * Integer arithmetic and integer atomics only: every output is bit-identical run to run and independent of
+ * the other images of the batch. */
+#define CS_THRESH_OTSU  0
+#define CS_THRESH_FIXED 1
+typedef struct cs_segment_params {
+    int32_t threshold_mode;           /* CS_THRESH_OTSU / CS_THRESH_FIXED */
+    int32_t threshold;                /* FIXED: 0..65535; ignored by OTSU */
+    int32_t connectivity;             /* 1 or 2 */
+    int32_t fill_holes;               /* 0 or 1 */
+} cs_segment_params;                  /* NULL = OTSU, connectivity 1, no hole filling */
+
+/* image:  [batch][height][width][channels] uint8 / uint16 (pixel_type), in_kind.  height, width: 1..4096
+ *         (above: CS_ERR_UNSUPPORTED, as the extraction: a deliberate difference from the CS_ERR_INVALID of the other bad
+ *         arguments); batch: 1..65535 (the launch grid's bound).  Workspace on the device: 5 bytes per pixel (mask and
+ *         parents; 4 more for labels that go to the host), and for CS_THRESH_OTSU the histogram tables: 2 KB per image for
+ *         uint8, 256 KB x (1 + parts) per image for uint16 with parts = min(16, 256 / batch, pixels / 16384) >= 1 -- 2.3 MB
+ *         per image at batch 32, 0.5 MB from batch 256 on.  A batch whose workspace does not fit returns CS_ERR_NOMEM;
+ *         split it (the results do not depend on the batch).
+ * labels: out, [batch][height][width] int32, labels_kind.  Left on the device they are cs_extract_measure's
+ *         `labels` as they are, on the same handle, with max_label = the largest of n_labels (counts beyond the
+ *         extraction's table limits are the extraction's to refuse).
+ * n_labels:   out, host [batch]: components per image.
+ * thresholds: out, host [batch], or NULL: the threshold used per image.
+ * One host synchronisation per call.  Bad arguments: CS_ERR_INVALID before any device work; without a gfx950
+ * device (p == NULL because cs_preproc_create failed): CS_ERR_NO_DEVICE. */
+int cs_segment_threshold(cs_preproc *p, const void *image, int pixel_type, int32_t channels, int32_t channel,
+                         int32_t batch, int32_t height, int32_t width, int in_kind,
+                         const cs_segment_params *params, int32_t *labels, int labels_kind,
+                         int32_t *n_labels, int32_t *thresholds);
+/* Device time of the last cs_segment_threshold: histogram + threshold + mask, and hole filling + labelling. */
+int cs_segment_last_timing(const cs_preproc *p, double *threshold_ms, double *label_ms);
 
 /* ---- detector fitting (create_anomaly_detector, CAE_improved_modeltrain.py:394-446) -------- */
 /* The fit of what cs_screen's tail evaluates, for the training set's encoder features
