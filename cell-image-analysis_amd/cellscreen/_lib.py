@@ -104,6 +104,10 @@ class CSSegmentParams(C.Structure):
 THRESH_OTSU, THRESH_FIXED = 0, 1        # cs_segment_params.threshold_mode
 
 
+class CSSplitParams(C.Structure):
+    _fields_ = [("h", C.c_int32)]
+
+
 # cs_region of include/cellscreen.h as a numpy record (80 bytes)
 REGION_DTYPE = np.dtype([("image", np.int32), ("label", np.int32), ("minr", np.int32), ("minc", np.int32), ("maxr", np.int32),
                          ("maxc", np.int32), ("area", np.int64), ("convex_area", np.int64), ("eccentricity", np.float64),
@@ -145,6 +149,10 @@ SIGNATURES = {
     "cs_segment_threshold": (_I, [_P, _P, _I, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _I, C.POINTER(CSSegmentParams),
                                   _P, _I, _P, _P]),
     "cs_segment_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "cs_segment_split": (_I, [_P, _P, _I, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _I, C.POINTER(CSSegmentParams),
+                              C.POINTER(CSSplitParams), _P, _I, _P, _P, _P]),
+    "cs_segment_split_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                          C.POINTER(C.c_double)]),
     "cs_fit_create": (_I, [_I, C.POINTER(_P)]),
     "cs_fit_free": (None, [_P]),
     "cs_fit_wait_stream": (_I, [_P, _P]),

@@ -2,14 +2,19 @@
 and connected-component labelling, from the segmentation channel of an image stack to int32 label images that
 cellscreen.extract reads without a copy through the host.
 
-It is NOT StarDist and does not try to be: it is a classical segmenter for bright cells on a dark background.  Cells that
-touch come out as one region, which the extraction's area and eccentricity rules then judge like any other region.
+It is NOT StarDist and does not try to be: it is a classical segmenter for bright cells on a dark background.  By default
+cells that touch come out as one region, which the extraction's area and eccentricity rules then judge like any other region.
+With split_touching=True such regions are cut at their necks by an exact integer distance-transform watershed
+(cs_segment_split; tests/split_reference.py restates it): seeds are the maxima of the distance to the background that stand
+split_h half pixels above their saddles.  Cells that overlap without a neck, and cores deeper than 127 px, stay whole; with
+connectivity 2 the cut between two equal cells is skewed, so connectivity 1 stays the default.
 What it computes is exact: the threshold is scikit-image 0.18.3's threshold_otsu of the channel (an integer), the mask is
 `channel > threshold` (after scipy.ndimage.binary_fill_holes with fill_holes), and the labels are scipy.ndimage.label's
 (= skimage.measure.label's) ids, as restated in tests/segment_reference.py; neither library is a dependency.
 
     seg = ThresholdSegmenter()
     labels, n_labels, thresholds = seg.segment_batch(images)          # numpy in, numpy out; CUDA tensors in, CUDA tensor out
+    seg = ThresholdSegmenter(split_touching=True)                      # the same, touching cells apart
 
     screening = ProductionMutantScreening(model_dir, cell_extractor=threshold_cell_extractor())
 """
@@ -48,15 +53,35 @@ def segment_params(threshold="otsu", connectivity: int = 1, fill_holes: bool = T
     return p
 
 
+def split_params(split_touching: bool = False, split_h: int = 3) -> Optional[L.CSSplitParams]:
+    """cs_split_params from the Python arguments, None without split_touching; anything out of range raises before a handle
+    exists (also without split_touching: a bad split_h is a mistake either way)."""
+    if not isinstance(split_touching, (bool, np.bool_)):
+        raise TypeError(f"split_touching must be a bool, got {type(split_touching).__name__}")
+    if isinstance(split_h, bool) or not isinstance(split_h, (int, np.integer)):
+        raise TypeError(f"split_h must be an integer (half pixels), got {type(split_h).__name__}")
+    if not 1 <= int(split_h) <= 255:
+        raise ValueError(f"split_h {split_h} outside 1..255")
+    if not split_touching:
+        return None
+    p = L.CSSplitParams()
+    p.h = int(split_h)
+    return p
+
+
 class ThresholdSegmenter:
     """Threshold + connected components on one preprocess handle (one GPU, one stream).  threshold: "otsu" (per image) or an
     integer; foreground is pixel > threshold.  connectivity: 1 (4 neighbours) or 2 (8).  fill_holes: background enclosed
     by foreground becomes foreground before labelling.  extractor: a CellExtractor whose handle and stream to share, so
-    that labels left on the device feed its extract_batch in stream order."""
+    that labels left on the device feed its extract_batch in stream order.  split_touching: cut touching cells apart
+    (cs_segment_split, see the module text); split_h: the depth in half pixels (1..255) a saddle needs below the lower of
+    its two peaks to separate them."""
 
     def __init__(self, device_id: int = 0, threshold="otsu", connectivity: int = 1, fill_holes: bool = True,
-                 extractor: Optional[CellExtractor] = None):
+                 extractor: Optional[CellExtractor] = None, split_touching: bool = False, split_h: int = 3):
         self._params = segment_params(threshold, connectivity, fill_holes)
+        self._split = split_params(split_touching, split_h)
+        self.split_touching, self.split_h = bool(split_touching), int(split_h)
         if extractor is not None and extractor.device_id != device_id:
             raise ValueError(f"extractor is on device {extractor.device_id}, the segmenter on {device_id}")
         self.threshold, self.connectivity, self.fill_holes = threshold, int(connectivity), bool(fill_holes)
@@ -128,13 +153,16 @@ class ThresholdSegmenter:
                 raise ValueError("images must be C-contiguous")
         return B, H, W, Cn, int(channel), ptype, on_dev
 
-    def segment_batch(self, images, channel: Optional[int] = None):
+    def segment_batch(self, images, channel: Optional[int] = None, return_distance: bool = False):
         """images: [B,H,W] or [B,H,W,C] uint8 / uint16, numpy or CUDA tensors of the segmenter's device; the channel that is
         segmented is `channel` (default 2 of >= 3 channels as improved_detection.py:55, 0 of one).
         Returns (labels, n_labels, thresholds): labels int32 [B,H,W] (0 = background, ids 1.. in raster order of each
         component's first pixel), numpy for numpy input and a CUDA tensor for tensor input; n_labels and thresholds int32
-        numpy [B]."""
+        numpy [B].  return_distance (split_touching only): a fourth result, uint8 [B,H,W] where the labels are: the distance
+        to the background in half pixels, capped at 255."""
         B, H, W, Cn, channel, ptype, on_dev = self._check(images, channel)
+        if return_distance and self._split is None:
+            raise ValueError("return_distance needs split_touching=True: the plain segmenter computes no distances")
         n_labels = np.zeros(B, np.int32)
         thresholds = np.zeros(B, np.int32)
         if on_dev:
@@ -144,26 +172,44 @@ class ThresholdSegmenter:
         else:
             labels = np.empty((B, H, W), np.int32)
         kind = L.CS_MEM_DEVICE if on_dev else L.CS_MEM_HOST
-        L.check(self._lib.cs_segment_threshold(self._handle, L._ptr(images), ptype, Cn, channel, B, H, W, kind,
-                                               C.byref(self._params), L._ptr(labels), kind, n_labels.ctypes.data,
-                                               thresholds.ctypes.data))
-        return labels, n_labels, thresholds
+        if self._split is None:
+            L.check(self._lib.cs_segment_threshold(self._handle, L._ptr(images), ptype, Cn, channel, B, H, W, kind,
+                                                   C.byref(self._params), L._ptr(labels), kind, n_labels.ctypes.data,
+                                                   thresholds.ctypes.data))
+            return labels, n_labels, thresholds
+        dist = None
+        if return_distance:
+            if on_dev:
+                dist = torch.empty((B, H, W), dtype=torch.uint8, device=images.device)
+                L.order_after_torch(self._lib.cs_preproc_wait_stream, self._handle, dist)
+            else:
+                dist = np.empty((B, H, W), np.uint8)
+        L.check(self._lib.cs_segment_split(self._handle, L._ptr(images), ptype, Cn, channel, B, H, W, kind, C.byref(self._params),
+                                           C.byref(self._split), L._ptr(labels), kind, n_labels.ctypes.data,
+                                           thresholds.ctypes.data, L._ptr(dist)))
+        return (labels, n_labels, thresholds, dist) if return_distance else (labels, n_labels, thresholds)
 
     def last_timing(self):
-        a, b = C.c_double(), C.c_double()
-        L.check(self._lib.cs_segment_last_timing(self._handle, C.byref(a), C.byref(b)))
-        return {"threshold_ms": a.value, "label_ms": b.value}
+        """Device milliseconds of the last call's stages; with split_touching the stages of cs_segment_split."""
+        if self._split is None:
+            a, b = C.c_double(), C.c_double()
+            L.check(self._lib.cs_segment_last_timing(self._handle, C.byref(a), C.byref(b)))
+            return {"threshold_ms": a.value, "label_ms": b.value}
+        v = [C.c_double() for _ in range(4)]
+        L.check(self._lib.cs_segment_split_last_timing(self._handle, *(C.byref(x) for x in v)))
+        return dict(zip(("threshold_ms", "distance_ms", "seed_ms", "flood_ms"), (x.value for x in v)))
 
 
 def threshold_cell_extractor(device_id: int = 0, out_hw=(OUT_SIDE, OUT_SIDE), threshold="otsu", connectivity: int = 1,
-                             fill_holes: bool = True, **qc):
+                             fill_holes: bool = True, split_touching: bool = False, split_h: int = 3, **qc):
     """The `cell_extractor(image_path) -> (cells, stats)` that ProductionMutantScreening and create_training_dataset accept,
     with the built-in segmenter in StarDist's place: the file is read (extract.read_image / split_channels), uploaded once,
     segmented and extracted on one handle, and the labels never leave the device.  Not StarDist: see the module text.
     Errors raise as label_cell_extractor's do; the screening driver's try turns them into the reference's "Error processing"
-    line and ([], []).  out_hw and **qc as for label_cell_extractor."""
+    line and ([], []).  out_hw and **qc as for label_cell_extractor; split_touching and split_h as for ThresholdSegmenter."""
     out_hw = check_out_hw(out_hw)
     segment_params(threshold, connectivity, fill_holes)
+    split_params(split_touching, split_h)
     qc_params(**qc)
     st = {}
 
@@ -176,7 +222,8 @@ def threshold_cell_extractor(device_id: int = 0, out_hw=(OUT_SIDE, OUT_SIDE), th
             raise TypeError(f"image dtype {img.dtype}: uint8 or uint16 expected")
         if "x" not in st:
             st["x"] = CellExtractor(device_id, out_hw, **qc)
-            st["s"] = ThresholdSegmenter(device_id, threshold, connectivity, fill_holes, extractor=st["x"])
+            st["s"] = ThresholdSegmenter(device_id, threshold, connectivity, fill_holes, extractor=st["x"],
+                                         split_touching=split_touching, split_h=split_h)
         host = np.ascontiguousarray(img)[None]
         dev = torch.from_numpy(host.view(np.int16) if host.dtype == np.uint16 else host).to(torch.device("cuda", device_id))
         labels, _, _ = st["s"].segment_batch(dev, channel=seg_ch)

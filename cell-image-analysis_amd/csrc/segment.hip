@@ -1,7 +1,9 @@
 // segment.hip -- the project's own classical segmenter on gfx950: a global threshold (Otsu's, as scikit-image 0.18.3 computes
 // it on an integer image, or a fixed one), optional hole filling, and connected-component labelling with scipy.ndimage.label's
-// numbering.  It is NOT StarDist: touching cells come out as one region, which the extraction's area and eccentricity rules
-// then judge.  The labels feed cs_extract_measure on the same handle and stream without leaving the device.
+// numbering.  It is NOT StarDist: by default touching cells come out as one region, which the extraction's area and
+// eccentricity rules then judge; cs_segment_split (below, "split_touching") cuts such regions at their necks with an exact
+// integer distance-transform watershed.  The labels feed cs_extract_measure on the same handle and stream without leaving
+// the device.
 //
 // Kernels, per batch:
 //   sg_hist      exact integer histogram of one channel.  A workgroup owns a contiguous part of one image and one window of
@@ -19,6 +21,7 @@
 //   sg_scan / sg_rank / sg_gather   exclusive scan of the root counts per image, label = rank of the root + 1 in raster order.
 //   sg_edge / sg_fill   (fill_holes) the same labelling on the inverted mask, 4-connected; background components without a
 //                pixel on the image border become foreground (scipy.ndimage.binary_fill_holes, default structure).
+//   sp_*         cs_segment_split only: see "split_touching" further down.
 // The final parents are a function of the mask alone (the minimum index of a component), so the labels do not depend on
 // execution order, on the run, or on the other images of the batch.
 #include "api_internal.hpp"
@@ -218,11 +221,14 @@ __device__ inline void uf_union(int* P, int a, int b)
 
 // grid (ceil(W/64), ceil(H/16), B).  Lane l of wave w owns column l of rows w, w+4, w+8, w+12: the first reads of the
 // left and upper neighbours fall on consecutive LDS banks.
+// EQ: two foreground neighbours are joined only where `val` is equal on them (the plateaus of cs_segment_split's seeds).
+template <bool EQ>
 __global__ __launch_bounds__(SG_THREADS) void sg_tile(const unsigned char* __restrict__ mask, int H, int W, int invert, int conn8,
-                                                      int* __restrict__ P)
+                                                      int* __restrict__ P, const unsigned char* __restrict__ val)
 {
     constexpr int WG = __HIP_MEMORY_SCOPE_WORKGROUP;
     __shared__ int L[SG_TILE];
+    __shared__ unsigned char V[EQ ? SG_TILE : 1];
     const int lx = threadIdx.x & 63, lw = threadIdx.x >> 6;
     const int x0 = blockIdx.x * SG_TW, y0 = blockIdx.y * SG_TH, b = blockIdx.z;
     const unsigned char* m = mask + (size_t)b * H * W;
@@ -234,18 +240,20 @@ __global__ __launch_bounds__(SG_THREADS) void sg_tile(const unsigned char* __res
         const int ly = lw + 4 * k, y = y0 + ly;
         fg[k] = x < W && y < H && ((m[(size_t)y * W + x] != 0) != (invert != 0));
         L[ly * SG_TW + lx] = fg[k] ? ly * SG_TW + lx : -1;
+        if (EQ) V[ly * SG_TW + lx] = fg[k] ? val[(size_t)b * H * W + (size_t)y * W + x] : 0;
     }
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         if (!fg[k]) continue;
         const int ly = lw + 4 * k, idx = ly * SG_TW + lx;
-        if (lx > 0 && uf_load<WG>(L, idx - 1) >= 0) uf_union<WG>(L, idx, idx - 1);
+        auto joins = [&](int n) { return uf_load<WG>(L, n) >= 0 && (!EQ || V[n] == V[idx]); };
+        if (lx > 0 && joins(idx - 1)) uf_union<WG>(L, idx, idx - 1);
         if (ly > 0) {
-            if (uf_load<WG>(L, idx - SG_TW) >= 0) uf_union<WG>(L, idx, idx - SG_TW);
-            else if (conn8) {                           // with the pixel above set, both diagonals already hang on it
-                if (lx > 0 && uf_load<WG>(L, idx - SG_TW - 1) >= 0) uf_union<WG>(L, idx, idx - SG_TW - 1);
-                if (lx < SG_TW - 1 && uf_load<WG>(L, idx - SG_TW + 1) >= 0) uf_union<WG>(L, idx, idx - SG_TW + 1);
+            if (joins(idx - SG_TW)) uf_union<WG>(L, idx, idx - SG_TW);
+            else if (conn8) {                           // with the pixel above joined, both diagonals already hang on it
+                if (lx > 0 && joins(idx - SG_TW - 1)) uf_union<WG>(L, idx, idx - SG_TW - 1);
+                if (lx < SG_TW - 1 && joins(idx - SG_TW + 1)) uf_union<WG>(L, idx, idx - SG_TW + 1);
             }
         }
     }
@@ -265,30 +273,36 @@ __global__ __launch_bounds__(SG_THREADS) void sg_tile(const unsigned char* __res
 
 // Every pair of neighbours that a tile border separates: the pixels of the first row of a tile with the row above, the pixels
 // of the first column of a tile with the column to the left.  grid (ceil(n / 256), B), n = nrb * W + ncb * H.
-__global__ __launch_bounds__(SG_THREADS) void sg_border(int H, int W, int conn8, int* __restrict__ P)
+template <bool EQ>
+__global__ __launch_bounds__(SG_THREADS) void sg_border(int H, int W, int conn8, int* __restrict__ P, const unsigned char* __restrict__ val)
 {
     constexpr int AG = __HIP_MEMORY_SCOPE_AGENT;
     const int nrb = (H - 1) / SG_TH, ncb = (W - 1) / SG_TW;
     int id = blockIdx.x * SG_THREADS + threadIdx.x;
     int* Pb = P + (size_t)blockIdx.y * H * W;
+    const unsigned char* vb = EQ ? val + (size_t)blockIdx.y * H * W : nullptr;
+    int i = 0;
+    auto joins = [&](int n) { return uf_load<AG>(Pb, n) >= 0 && (!EQ || vb[n] == vb[i]); };
     if (id < nrb * W) {
-        const int y = (id / W + 1) * SG_TH, x = id % W, i = y * W + x;
+        const int y = (id / W + 1) * SG_TH, x = id % W;
+        i = y * W + x;
         if (uf_load<AG>(Pb, i) < 0) return;
-        if (uf_load<AG>(Pb, i - W) >= 0) uf_union<AG>(Pb, i, i - W);
+        if (joins(i - W)) uf_union<AG>(Pb, i, i - W);
         else if (conn8) {
-            if (x > 0 && uf_load<AG>(Pb, i - W - 1) >= 0) uf_union<AG>(Pb, i, i - W - 1);
-            if (x < W - 1 && uf_load<AG>(Pb, i - W + 1) >= 0) uf_union<AG>(Pb, i, i - W + 1);
+            if (x > 0 && joins(i - W - 1)) uf_union<AG>(Pb, i, i - W - 1);
+            if (x < W - 1 && joins(i - W + 1)) uf_union<AG>(Pb, i, i - W + 1);
         }
         return;
     }
     id -= nrb * W;
     if (id >= ncb * H) return;
-    const int x = (id / H + 1) * SG_TW, y = id % H, i = y * W + x;
+    const int x = (id / H + 1) * SG_TW, y = id % H;
+    i = y * W + x;
     if (uf_load<AG>(Pb, i) < 0) return;
-    if (uf_load<AG>(Pb, i - 1) >= 0) uf_union<AG>(Pb, i, i - 1);
-    else if (conn8) {                                   // with the left pixel set, the two left diagonals already hang on it
-        if (y > 0 && uf_load<AG>(Pb, i - W - 1) >= 0) uf_union<AG>(Pb, i, i - W - 1);
-        if (y < H - 1 && uf_load<AG>(Pb, i + W - 1) >= 0) uf_union<AG>(Pb, i, i + W - 1);
+    if (joins(i - 1)) uf_union<AG>(Pb, i, i - 1);
+    else if (conn8) {                                   // with the left pixel joined, the two left diagonals already hang on it
+        if (y > 0 && joins(i - W - 1)) uf_union<AG>(Pb, i, i - W - 1);
+        if (y < H - 1 && joins(i + W - 1)) uf_union<AG>(Pb, i, i + W - 1);
     }
 }
 
@@ -376,9 +390,11 @@ __global__ __launch_bounds__(HIST_THREADS) void sg_scan(int* __restrict__ chunk_
     if (t == HIST_THREADS - 1) n_labels[blockIdx.x] = buf[t];
 }
 
-// grid (nchunks, B): roots get their label, background 0; the other foreground pixels are written by sg_gather
+// grid (nchunks, B): roots get their label, background 0; the other foreground pixels are written by sg_gather.
+// SEL: only the roots whose `drop` flag is 0 are numbered, the others get 0 (the seeds among the plateaus of cs_segment_split).
+template <bool SEL>
 __global__ __launch_bounds__(SG_THREADS) void sg_rank(int HW, const int* __restrict__ P, const int* __restrict__ chunk_off, int nchunks,
-                                                      int* __restrict__ labels)
+                                                      int* __restrict__ labels, const int* __restrict__ drop)
 {
     __shared__ int wc[4][SG_WAVES];
     const size_t base = (size_t)blockIdx.y * HW;
@@ -388,7 +404,12 @@ __global__ __launch_bounds__(SG_THREADS) void sg_rank(int HW, const int* __restr
     for (int k = 0; k < 4; ++k) {
         const int i = blockIdx.x * SG_CHUNK + k * SG_THREADS + threadIdx.x;
         par[k] = i < HW ? P[base + i] : -1;
-        const unsigned long long m = __ballot(i < HW && par[k] == i);
+        bool root = i < HW && par[k] == i;
+        if (SEL) {
+            if (root && drop[base + i] != 0) { root = false; par[k] = -1; }
+            else if (!root && par[k] >= 0) par[k] = -2;         // not a root: left to the gather
+        }
+        const unsigned long long m = __ballot(root);
         before[k] = __popcll(m & ((1ull << lane) - 1ull));
         if (lane == 0) wc[k][wave] = __popcll(m);
     }
@@ -404,7 +425,7 @@ __global__ __launch_bounds__(SG_THREADS) void sg_rank(int HW, const int* __restr
             run += wc[k][q];
         }
         if (i < HW) {
-            if (par[k] < 0) labels[base + i] = 0;
+            if (par[k] == -1) labels[base + i] = 0;
             else if (par[k] == i) labels[base + i] = mine + before[k] + 1;
         }
     }
@@ -422,11 +443,363 @@ __global__ __launch_bounds__(SG_THREADS) void sg_gather(int HW, const int* __res
     }
 }
 
+// ---- split_touching (cs_segment_split): an exact integer distance-transform watershed -------------------------------------
+// A function of the mask alone (tests/split_reference.py restates it):
+//   Dq   = min(isqrt(4 * D2), 255), D2 the exact squared Euclidean distance to the nearest background pixel of the image
+//          (outside the image is not background): the distance in half pixels, one byte;
+//   R    = reconstruction by dilation of max(Dq - h, 0) under Dq; seeds = the regional maxima of R inside the mask;
+//   flood: for v = 255 .. 1 the unlabelled pixels of mask & Dq >= v take the label that reaches them with the smallest
+//          (steps, label); regions are renumbered by their first pixel.
+// Kernels:
+//   sp_columns   distance to the nearest background pixel of the column, capped at 128 (one thread per column, two sweeps).
+//   sp_rows      D2 = min over |dx| <= 127 of dx^2 + g^2 from a row strip in LDS (the window ends where dx^2 reaches the best
+//                so far), the integer square root, Dq and the marker max(Dq - h, 0); the batch's largest Dq by atomicMax.
+//                D2 >= 128^2 is not told apart: both 4 * 127.5^2 and everything above give Dq = 255.
+//   sp_recon     one round of R <- min(dilate(R), Dq): a 64 x 16 tile with a one-pixel halo relaxes in LDS until it is
+//                quiet.  R only grows and never passes the fixed point, so a halo read while a neighbour writes is only
+//                late, never wrong; a round in which no tile changed anything is the fixed point.
+//   sg_tile<true> / sg_border<true> / sg_flatten   plateaus: the union-find of the labelling, joining neighbours of equal R.
+//   sp_higher    flags the roots of plateaus with a pixel that has a higher neighbour (plain stores of 1, as sg_edge).
+//   sp_seedcount / sg_scan / sg_rank<true> / sp_seedkey   seed ids = ranks of the unflagged roots; every pixel of a seed
+//                plateau gets the key (level 0, 0 steps, id), every other pixel SP_NONE.
+//   sp_flood     one round of one level: key = [63:56] 255 - level at which the pixel was labelled, [55:32] steps, [31:0] label.
+//                An open pixel (Dq >= v, unlabelled or labelled at this level) takes the minimum over its labelled neighbours
+//                of (this level, steps + 1, label), where a neighbour of an earlier level counts 0 steps; pixels of earlier
+//                levels are final.  Keys only fall towards the one fixed point of the level, whatever the order (min-min).
+//                Tiles with no open pixel at or above the level leave at once (tile_top).
+//   sp_advance_* one thread: the round's "something changed" flag decides whether the reconstruction goes on and whether
+//                the flood stays at its level or goes one down.  The host enqueues rounds in groups and reads one int per group.
+//   sp_first / sp_parent   each region's first pixel (atomicMin per seed id), then parents = that pixel, which is what
+//                sg_scan / sg_rank / sg_gather number.
+// Integer atomics only, no floating point at all.
+static constexpr int SP_CAP = 128;                      // column distances are capped here: only D2 < 128^2 matters
+static constexpr int SP_HALO = SP_CAP - 1;
+static constexpr int SP_ROW = SG_THREADS;               // pixels of one row per workgroup in the row pass
+static constexpr int SP_LW = SG_TW + 2, SP_LH = SG_TH + 2;      // a tile with its halo
+static constexpr unsigned long long SP_NONE = ~0ull;
+enum { CT_VMAX = 0, CT_CHANGED, CT_ACTIVE, CT_LEVEL, CT_ROUNDS, CT_N = 8 };
+static constexpr int SP_RECON_GROUP = 16, SP_FLOOD_GROUP = 64;  // rounds enqueued between two reads of the control word
+
+// grid (ceil(W / 256), B)
+__global__ __launch_bounds__(SG_THREADS) void sp_columns(const unsigned char* __restrict__ mask, int H, int W, unsigned char* __restrict__ g)
+{
+    const int x = blockIdx.x * SG_THREADS + threadIdx.x;
+    if (x >= W) return;
+    const size_t base = (size_t)blockIdx.y * H * W + x;
+    int d = SP_CAP;                                     // nothing above the image: outside is not background
+    for (int y0 = 0; y0 < H; y0 += 16) {
+        unsigned char m[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) m[k] = y0 + k < H ? mask[base + (size_t)(y0 + k) * W] : 0;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            if (y0 + k >= H) continue;
+            d = m[k] ? min(d + 1, SP_CAP) : 0;
+            g[base + (size_t)(y0 + k) * W] = (unsigned char)d;
+        }
+    }
+    d = SP_CAP;
+    for (int y1 = H - 1; y1 >= 0; y1 -= 16) {
+        unsigned char m[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) m[k] = y1 - k >= 0 ? g[base + (size_t)(y1 - k) * W] : 0;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            if (y1 - k < 0) continue;
+            d = m[k] ? min(d + 1, SP_CAP) : 0;
+            if (d < (int)m[k]) g[base + (size_t)(y1 - k) * W] = (unsigned char)d;
+        }
+    }
+}
+
+// grid (ceil(W / 256), H, B)
+__global__ __launch_bounds__(SG_THREADS) void sp_rows(const unsigned char* __restrict__ g, int H, int W, int h, unsigned char* __restrict__ dq,
+                                                      unsigned char* __restrict__ R, int* __restrict__ ctrl)
+{
+    __shared__ unsigned char s[SP_ROW + 2 * SP_HALO];
+    const int t = threadIdx.x, x0 = blockIdx.x * SP_ROW;
+    const size_t row = ((size_t)blockIdx.z * H + blockIdx.y) * W;
+    for (int i = t; i < SP_ROW + 2 * SP_HALO; i += SG_THREADS) {
+        const int xx = x0 - SP_HALO + i;
+        s[i] = xx >= 0 && xx < W ? g[row + xx] : (unsigned char)SP_CAP;
+    }
+    __syncthreads();
+    const int x = x0 + t;
+    int q = 0;
+    if (x < W) {
+        const int c = t + SP_HALO, g0 = s[c];
+        int best = g0 * g0;
+        for (int dx = 1; dx <= SP_HALO && dx * dx < best; ++dx) {         // at most 127 steps; 0 on background
+            const int a = min((int)s[c - dx], (int)s[c + dx]);
+            best = min(best, dx * dx + a * a);
+        }
+        const int n = min(4 * best, 255 * 255);
+#pragma unroll
+        for (int bit = 128; bit >= 1; bit >>= 1) {                        // integer square root, 8 bits
+            const int r = q | bit;
+            if (r * r <= n) q = r;
+        }
+        dq[row + x] = (unsigned char)q;
+        R[row + x] = (unsigned char)max(q - h, 0);
+    }
+    int m = q;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) m = max(m, __shfl_xor(m, d));
+    if ((t & 63) == 0 && m > 0) atomicMax(&ctrl[CT_VMAX], m);
+}
+
+// one thread: sets the control words before the reconstruction (mode 0) and before the flood (mode 1)
+__global__ void sp_start(int* __restrict__ ctrl, int mode)
+{
+    ctrl[CT_CHANGED] = 0;
+    ctrl[CT_ROUNDS] = 0;
+    if (mode == 0) ctrl[CT_ACTIVE] = 1;
+    else ctrl[CT_LEVEL] = ctrl[CT_VMAX];
+}
+
+__global__ void sp_advance_recon(int* __restrict__ ctrl, int cap)
+{
+    if (ctrl[CT_ACTIVE] == 0) return;
+    if (ctrl[CT_CHANGED] == 0 || ++ctrl[CT_ROUNDS] >= cap) ctrl[CT_ACTIVE] = 0;
+    ctrl[CT_CHANGED] = 0;
+}
+
+__global__ void sp_advance_flood(int* __restrict__ ctrl, int cap)
+{
+    const int v = ctrl[CT_LEVEL];
+    if (v < 1) return;
+    if (ctrl[CT_CHANGED] == 0 || ++ctrl[CT_ROUNDS] >= cap) {
+        ctrl[CT_LEVEL] = v - 1;
+        ctrl[CT_ROUNDS] = 0;
+    }
+    ctrl[CT_CHANGED] = 0;
+}
+
+// grid (ceil(W/64), ceil(H/16), B), the thread-to-pixel map of sg_tile
+__global__ __launch_bounds__(SG_THREADS) void sp_recon(const unsigned char* __restrict__ dq, int H, int W, int conn8, unsigned char* R,
+                                                       int* ctrl)
+{
+    if (ctrl[CT_ACTIVE] == 0) return;
+    __shared__ unsigned char sR[SP_LH * SP_LW];
+    volatile unsigned char* v = sR;
+    const int lx = threadIdx.x & 63, lw = threadIdx.x >> 6;
+    const int x0 = blockIdx.x * SG_TW, y0 = blockIdx.y * SG_TH;
+    const size_t base = (size_t)blockIdx.z * H * W;
+    for (int i = threadIdx.x; i < SP_LH * SP_LW; i += SG_THREADS) {
+        const int y = y0 + i / SP_LW - 1, x = x0 + i % SP_LW - 1;
+        sR[i] = y >= 0 && y < H && x >= 0 && x < W ? R[base + (size_t)y * W + x] : 0;
+    }
+    const int x = x0 + lx;
+    int d[4], cur[4], was[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int y = y0 + lw + 4 * k;
+        d[k] = x < W && y < H ? (int)dq[base + (size_t)y * W + x] : 0;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) was[k] = cur[k] = sR[(lw + 4 * k + 1) * SP_LW + lx + 1];
+    for (int it = 0; it < SG_TILE; ++it) {                                  // a path inside the tile has at most SG_TILE pixels
+        int ch = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (cur[k] >= d[k]) continue;
+            const int c = (lw + 4 * k + 1) * SP_LW + lx + 1;
+            int m = max(max((int)v[c - 1], (int)v[c + 1]), max((int)v[c - SP_LW], (int)v[c + SP_LW]));
+            if (conn8) m = max(m, max(max((int)v[c - SP_LW - 1], (int)v[c - SP_LW + 1]), max((int)v[c + SP_LW - 1], (int)v[c + SP_LW + 1])));
+            m = min(m, d[k]);
+            if (m > cur[k]) { cur[k] = m; v[c] = (unsigned char)m; ch = 1; }
+        }
+        if (!__syncthreads_or(ch)) break;
+    }
+    int any = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (cur[k] != was[k]) { R[base + (size_t)(y0 + lw + 4 * k) * W + x] = (unsigned char)cur[k]; any = 1; }
+    any = __syncthreads_or(any);
+    if (threadIdx.x == 0 && any) atomicOr(&ctrl[CT_CHANGED], 1);
+}
+
+// grid (nchunks, B): a pixel with a higher neighbour disqualifies its plateau
+__global__ __launch_bounds__(SG_THREADS) void sp_higher(int H, int W, int conn8, const unsigned char* __restrict__ R, const int* __restrict__ P,
+                                                        int* __restrict__ drop)
+{
+    const size_t base = (size_t)blockIdx.y * H * W;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = blockIdx.x * SG_CHUNK + k * SG_THREADS + threadIdx.x;
+        if (i >= H * W) continue;
+        const int r = P[base + i];
+        if (r < 0) continue;
+        const int y = i / W, x = i % W, me = R[base + i];
+        bool hi = false;
+        for (int dy = -1; dy <= 1; ++dy)
+            for (int dx = -1; dx <= 1; ++dx) {
+                if ((dy == 0 && dx == 0) || (!conn8 && dy != 0 && dx != 0)) continue;
+                const int yy = y + dy, xx = x + dx;
+                if (yy >= 0 && yy < H && xx >= 0 && xx < W && (int)R[base + (size_t)yy * W + xx] > me) hi = true;
+            }
+        if (hi) drop[base + r] = 1;
+    }
+}
+
+// grid (nchunks, B): seeds (roots that are not flagged) per chunk
+__global__ __launch_bounds__(SG_THREADS) void sp_seedcount(int HW, const int* __restrict__ P, const int* __restrict__ drop,
+                                                           int* __restrict__ chunk_cnt, int nchunks)
+{
+    __shared__ int wc[SG_WAVES];
+    const size_t base = (size_t)blockIdx.y * HW;
+    int cnt = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = blockIdx.x * SG_CHUNK + k * SG_THREADS + threadIdx.x;
+        if (i < HW && P[base + i] == i && drop[base + i] == 0) ++cnt;
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) cnt += __shfl_xor(cnt, m);
+    if ((threadIdx.x & 63) == 0) wc[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) chunk_cnt[(size_t)blockIdx.y * nchunks + blockIdx.x] = wc[0] + wc[1] + wc[2] + wc[3];
+}
+
+// grid (nchunks, B): seed_id holds the id at seed roots and 0 at the other roots
+__global__ __launch_bounds__(SG_THREADS) void sp_seedkey(int HW, const int* __restrict__ P, const int* __restrict__ seed_id,
+                                                         unsigned long long* __restrict__ key)
+{
+    const size_t base = (size_t)blockIdx.y * HW;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = blockIdx.x * SG_CHUNK + k * SG_THREADS + threadIdx.x;
+        if (i >= HW) continue;
+        const int r = P[base + i];
+        const int id = r >= 0 ? seed_id[base + r] : 0;
+        key[base + i] = id > 0 ? (unsigned long long)id : SP_NONE;
+    }
+}
+
+// grid (ceil(W/64), ceil(H/16), B), the thread-to-pixel map of sg_tile
+__global__ __launch_bounds__(SG_THREADS) void sp_flood(const unsigned char* __restrict__ dq, int H, int W, int conn8, unsigned long long* key,
+                                                       unsigned char* tile_top, int* ctrl)
+{
+    constexpr int WG = __HIP_MEMORY_SCOPE_WORKGROUP, AG = __HIP_MEMORY_SCOPE_AGENT;
+    const int v = ctrl[CT_LEVEL];
+    if (v < 1) return;
+    const size_t tile = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+    if ((int)tile_top[tile] < v) return;
+    __shared__ unsigned long long sK[SP_LH * SP_LW];
+    __shared__ int s_top;
+    const unsigned long long code = (unsigned long long)(255 - v);
+    const int lx = threadIdx.x & 63, lw = threadIdx.x >> 6;
+    const int x0 = blockIdx.x * SG_TW, y0 = blockIdx.y * SG_TH;
+    const size_t base = (size_t)blockIdx.z * H * W;
+    if (threadIdx.x == 0) s_top = 0;
+    for (int i = threadIdx.x; i < SP_LH * SP_LW; i += SG_THREADS) {
+        const int y = y0 + i / SP_LW - 1, x = x0 + i % SP_LW - 1;
+        sK[i] = y >= 0 && y < H && x >= 0 && x < W ? __hip_atomic_load(key + base + (size_t)y * W + x, __ATOMIC_RELAXED, AG) : SP_NONE;
+    }
+    const int x = x0 + lx;
+    int d[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int y = y0 + lw + 4 * k;
+        d[k] = x < W && y < H ? (int)dq[base + (size_t)y * W + x] : 0;
+    }
+    __syncthreads();
+    unsigned long long cur[4], was[4];
+    bool open[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        was[k] = cur[k] = sK[(lw + 4 * k + 1) * SP_LW + lx + 1];
+        open[k] = d[k] >= v && (cur[k] == SP_NONE || (cur[k] >> 56) == code);
+    }
+    for (int it = 0; it < SG_TILE; ++it) {
+        int ch = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (!open[k]) continue;
+            const int c = (lw + 4 * k + 1) * SP_LW + lx + 1;
+            unsigned long long best = cur[k];
+            auto look = [&](int n) {
+                const unsigned long long kn = __hip_atomic_load(&sK[n], __ATOMIC_RELAXED, WG);
+                if (kn == SP_NONE) return;
+                const unsigned long long steps = (kn >> 56) == code ? ((kn >> 32) & 0xffffffull) : 0ull;
+                const unsigned long long cand = (code << 56) | ((steps + 1ull) << 32) | (kn & 0xffffffffull);
+                if (cand < best) best = cand;
+            };
+            look(c - 1); look(c + 1); look(c - SP_LW); look(c + SP_LW);
+            if (conn8) { look(c - SP_LW - 1); look(c - SP_LW + 1); look(c + SP_LW - 1); look(c + SP_LW + 1); }
+            if (best < cur[k]) {
+                cur[k] = best;
+                __hip_atomic_store(&sK[c], best, __ATOMIC_RELAXED, WG);
+                ch = 1;
+            }
+        }
+        if (!__syncthreads_or(ch)) break;
+    }
+    int any = 0, top = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (cur[k] != was[k]) {
+            __hip_atomic_store(key + base + (size_t)(y0 + lw + 4 * k) * W + x, cur[k], __ATOMIC_RELAXED, AG);
+            any = 1;
+        }
+        if (d[k] > 0 && (cur[k] == SP_NONE || (cur[k] >> 56) == code)) top = max(top, d[k]);     // still open at this level or below
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) top = max(top, __shfl_xor(top, m));
+    if ((threadIdx.x & 63) == 0 && top > 0) atomicMax(&s_top, top);
+    any = __syncthreads_or(any);
+    if (threadIdx.x == 0) {
+        tile_top[tile] = (unsigned char)s_top;
+        if (any) atomicOr(&ctrl[CT_CHANGED], 1);
+    }
+}
+
+// grid (nchunks, B): first[id - 1] = the smallest linear index with that seed id (first was filled with 0x7f7f7f7f)
+__global__ __launch_bounds__(SG_THREADS) void sp_first(int HW, const unsigned long long* __restrict__ key, int* first)
+{
+    const size_t base = (size_t)blockIdx.y * HW;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = blockIdx.x * SG_CHUNK + k * SG_THREADS + threadIdx.x;
+        if (i >= HW) continue;
+        const unsigned long long kk = key[base + i];
+        if (kk == SP_NONE) continue;
+        int* f = first + base + ((int)(kk & 0xffffffffull) - 1);
+        if (i < __hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(f, i);
+    }
+}
+
+// grid (nchunks, B): parents = the region's first pixel, and the root counts per chunk as sg_flatten leaves them
+__global__ __launch_bounds__(SG_THREADS) void sp_parent(int HW, const unsigned long long* __restrict__ key, const int* __restrict__ first,
+                                                        int* __restrict__ P, int* __restrict__ chunk_cnt, int nchunks)
+{
+    __shared__ int wc[SG_WAVES];
+    const size_t base = (size_t)blockIdx.y * HW;
+    int cnt = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = blockIdx.x * SG_CHUNK + k * SG_THREADS + threadIdx.x;
+        if (i >= HW) continue;
+        const unsigned long long kk = key[base + i];
+        const int r = kk == SP_NONE ? -1 : first[base + ((int)(kk & 0xffffffffull) - 1)];
+        P[base + i] = r;
+        cnt += r == i;
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) cnt += __shfl_xor(cnt, m);
+    if ((threadIdx.x & 63) == 0) wc[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) chunk_cnt[(size_t)blockIdx.y * nchunks + blockIdx.x] = wc[0] + wc[1] + wc[2] + wc[3];
+}
+
 // ---- host state ---------------------------------------------------------------------------------------------------------------
 struct SegmentState {
     DevBuf img, lab, mask, parent, slab, hist, thr, chunks, counts;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    DevBuf dq, rec, key, ttop, ctrl;                    // cs_segment_split only
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     double threshold_ms = 0.0, label_ms = 0.0;
+    double sp_threshold_ms = 0.0, sp_distance_ms = 0.0, sp_seed_ms = 0.0, sp_flood_ms = 0.0;
     ~SegmentState()
     {
         for (hipEvent_t e : ev)
@@ -436,16 +809,20 @@ struct SegmentState {
 
 void segment_state_free(SegmentState* s) { delete s; }
 
-// tile union-find, border merge, path compression (with the root counts when chunk_cnt is given)
+// tile union-find, border merge, path compression (with the root counts when chunk_cnt is given); with `val` only neighbours
+// of equal val are joined
 static hipError_t label_mask(const unsigned char* mask, int batch, int H, int W, int invert, int conn8, int* parent, int* chunk_cnt,
-                             int nchunks, hipStream_t st)
+                             int nchunks, hipStream_t st, const unsigned char* val = nullptr)
 {
     const dim3 tgrid((unsigned)((W + SG_TW - 1) / SG_TW), (unsigned)((H + SG_TH - 1) / SG_TH), (unsigned)batch);
-    hipLaunchKernelGGL(sg_tile, tgrid, dim3(SG_THREADS), 0, st, mask, H, W, invert, conn8, parent);
+    if (val) hipLaunchKernelGGL(sg_tile<true>, tgrid, dim3(SG_THREADS), 0, st, mask, H, W, invert, conn8, parent, val);
+    else hipLaunchKernelGGL(sg_tile<false>, tgrid, dim3(SG_THREADS), 0, st, mask, H, W, invert, conn8, parent, val);
     const int nb = ((H - 1) / SG_TH) * W + ((W - 1) / SG_TW) * H;
-    if (nb > 0)
-        hipLaunchKernelGGL(sg_border, dim3((unsigned)((nb + SG_THREADS - 1) / SG_THREADS), (unsigned)batch), dim3(SG_THREADS), 0, st, H, W,
-                           conn8, parent);
+    if (nb > 0) {
+        const dim3 bgrid((unsigned)((nb + SG_THREADS - 1) / SG_THREADS), (unsigned)batch);
+        if (val) hipLaunchKernelGGL(sg_border<true>, bgrid, dim3(SG_THREADS), 0, st, H, W, conn8, parent, val);
+        else hipLaunchKernelGGL(sg_border<false>, bgrid, dim3(SG_THREADS), 0, st, H, W, conn8, parent, val);
+    }
     hipLaunchKernelGGL(sg_flatten, dim3((unsigned)nchunks, (unsigned)batch), dim3(SG_THREADS), 0, st, H * W, parent, chunk_cnt, nchunks);
     return hipGetLastError();
 }
@@ -470,14 +847,10 @@ static int otsu_thresholds(const PIX* img, int C, int ch, int batch, int HW, Seg
     return CS_OK;
 }
 
-}  // namespace cs
-
-// ---- C ABI ----------------------------------------------------------------------------------
-using namespace cs;
-
-int cs_segment_threshold(cs_preproc* p, const void* image, int pixel_type, int32_t channels, int32_t channel, int32_t batch, int32_t height,
-                         int32_t width, int in_kind, const cs_segment_params* params, int32_t* labels, int labels_kind, int32_t* n_labels,
-                         int32_t* thresholds)
+// The argument rules that cs_segment_threshold and cs_segment_split share; sp receives the parameters in force.
+static int segment_check(const void* image, int pixel_type, int32_t channels, int32_t channel, int32_t batch, int32_t height, int32_t width,
+                         int in_kind, const cs_segment_params* params, const int32_t* labels, int labels_kind, const int32_t* n_labels,
+                         cs_segment_params& sp)
 {
     if (!image || !labels || !n_labels) return fail(CS_ERR_INVALID, "NULL argument");
     if (pixel_type != CS_PIX_U8 && pixel_type != CS_PIX_U16) return fail(CS_ERR_INVALID, "pixel_type must be CS_PIX_U8 or CS_PIX_U16");
@@ -490,7 +863,7 @@ int cs_segment_threshold(cs_preproc* p, const void* image, int pixel_type, int32
     if (height > kSegMaxSide || width > kSegMaxSide)
         return fail(CS_ERR_UNSUPPORTED, "image %dx%d: sides above %d are not supported", (int)height, (int)width, kSegMaxSide);
     if (batch > kSegMaxBatch) return fail(CS_ERR_UNSUPPORTED, "batch %d: at most %d images per call", (int)batch, kSegMaxBatch);
-    cs_segment_params sp{CS_THRESH_OTSU, 0, 1, 0};
+    sp = cs_segment_params{CS_THRESH_OTSU, 0, 1, 0};
     if (params) {
         sp = *params;
         if (sp.threshold_mode != CS_THRESH_OTSU && sp.threshold_mode != CS_THRESH_FIXED)
@@ -500,10 +873,21 @@ int cs_segment_threshold(cs_preproc* p, const void* image, int pixel_type, int32
         if (sp.connectivity != 1 && sp.connectivity != 2) return fail(CS_ERR_INVALID, "connectivity %d: 1 or 2", (int)sp.connectivity);
         if (sp.fill_holes != 0 && sp.fill_holes != 1) return fail(CS_ERR_INVALID, "fill_holes %d: 0 or 1", (int)sp.fill_holes);
     }
-    if (!p) {
-        const int rc = require_gfx950(0);
-        return rc ? rc : fail(CS_ERR_INVALID, "handle is NULL");
-    }
+    return CS_OK;
+}
+
+// What both entry points do up to the mask: the state, the uploads, the common workspace, the thresholds, the mask (between
+// ev[0] and ev[1]) and the hole filling.  d_img / d_lab are where the image and the labels are on the device.
+struct SegmentCall {
+    int batch, H, W, HW, nchunks;
+    size_t npx;
+    int* d_lab;
+    dim3 pgrid;
+};
+
+static int segment_mask(cs_preproc* p, const void* image, int pixel_type, int32_t channels, int32_t channel, int32_t batch, int32_t height,
+                        int32_t width, int in_kind, const cs_segment_params& sp, int32_t* labels, int labels_kind, SegmentCall& c)
+{
     HIPCHK(hipSetDevice(p->device));
     if (!p->seg) p->seg = new SegmentState();
     SegmentState& S = *p->seg;
@@ -559,15 +943,46 @@ int cs_segment_threshold(cs_preproc* p, const void* image, int pixel_type, int32
         hipLaunchKernelGGL(sg_fill, pgrid, dim3(SG_THREADS), 0, st, HW, S.parent.as<int>(), d_lab, S.mask.as<unsigned char>());
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(label_mask(S.mask.as<unsigned char>(), batch, H, W, 0, sp.connectivity == 2, S.parent.as<int>(), S.chunks.as<int>(), nchunks, st));
-    hipLaunchKernelGGL(sg_scan, dim3((unsigned)batch), dim3(HIST_THREADS), 0, st, S.chunks.as<int>(), nchunks, S.counts.as<int>());
-    hipLaunchKernelGGL(sg_rank, pgrid, dim3(SG_THREADS), 0, st, HW, S.parent.as<int>(), S.chunks.as<int>(), nchunks, d_lab);
-    hipLaunchKernelGGL(sg_gather, pgrid, dim3(SG_THREADS), 0, st, HW, S.parent.as<int>(), d_lab);
-    HIPCHK(hipGetLastError());
+    c = SegmentCall{(int)batch, H, W, HW, nchunks, npx, d_lab, pgrid};
+    return CS_OK;
+}
+
+// scan of the root counts, labels of the roots, labels of the rest: from parents that point to each region's first pixel
+static hipError_t number_regions(SegmentState& S, const SegmentCall& c, hipStream_t st)
+{
+    hipLaunchKernelGGL(sg_scan, dim3((unsigned)c.batch), dim3(HIST_THREADS), 0, st, S.chunks.as<int>(), c.nchunks, S.counts.as<int>());
+    hipLaunchKernelGGL(sg_rank<false>, c.pgrid, dim3(SG_THREADS), 0, st, c.HW, S.parent.as<int>(), S.chunks.as<int>(), c.nchunks, c.d_lab,
+                       (const int*)nullptr);
+    hipLaunchKernelGGL(sg_gather, c.pgrid, dim3(SG_THREADS), 0, st, c.HW, S.parent.as<int>(), c.d_lab);
+    return hipGetLastError();
+}
+
+}  // namespace cs
+
+// ---- C ABI ----------------------------------------------------------------------------------
+using namespace cs;
+
+int cs_segment_threshold(cs_preproc* p, const void* image, int pixel_type, int32_t channels, int32_t channel, int32_t batch, int32_t height,
+                         int32_t width, int in_kind, const cs_segment_params* params, int32_t* labels, int labels_kind, int32_t* n_labels,
+                         int32_t* thresholds)
+{
+    cs_segment_params sp;
+    int rc = segment_check(image, pixel_type, channels, channel, batch, height, width, in_kind, params, labels, labels_kind, n_labels, sp);
+    if (rc) return rc;
+    if (!p) {
+        rc = require_gfx950(0);
+        return rc ? rc : fail(CS_ERR_INVALID, "handle is NULL");
+    }
+    SegmentCall c;
+    if ((rc = segment_mask(p, image, pixel_type, channels, channel, batch, height, width, in_kind, sp, labels, labels_kind, c))) return rc;
+    SegmentState& S = *p->seg;
+    hipStream_t st = p->stream;
+    HIPCHK(label_mask(S.mask.as<unsigned char>(), batch, c.H, c.W, 0, sp.connectivity == 2, S.parent.as<int>(), S.chunks.as<int>(), c.nchunks, st));
+    HIPCHK(number_regions(S, c, st));
     HIPCHK(hipEventRecord(S.ev[2], st));
     HIPCHK(hipMemcpyAsync(n_labels, S.counts.p, batch * sizeof(int), hipMemcpyDeviceToHost, st));
     if (thresholds) HIPCHK(hipMemcpyAsync(thresholds, S.thr.p, batch * sizeof(int), hipMemcpyDeviceToHost, st));
-    if (labels_kind == CS_MEM_HOST) HIPCHK(hipMemcpyAsync(labels, d_lab, npx * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (labels_kind == CS_MEM_HOST) HIPCHK(hipMemcpyAsync(labels, c.d_lab, c.npx * sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));                     // the one host synchronisation: the counts
     float ms = 0.f;
     HIPCHK(hipEventElapsedTime(&ms, S.ev[0], S.ev[1]));
@@ -583,5 +998,111 @@ int cs_segment_last_timing(const cs_preproc* p, double* threshold_ms, double* la
     const SegmentState* S = p->seg;
     if (threshold_ms) *threshold_ms = S ? S->threshold_ms : 0.0;
     if (label_ms) *label_ms = S ? S->label_ms : 0.0;
+    return CS_OK;
+}
+
+int cs_segment_split(cs_preproc* p, const void* image, int pixel_type, int32_t channels, int32_t channel, int32_t batch, int32_t height,
+                     int32_t width, int in_kind, const cs_segment_params* params, const cs_split_params* split, int32_t* labels,
+                     int labels_kind, int32_t* n_labels, int32_t* thresholds, uint8_t* dist)
+{
+    cs_segment_params sp;
+    int rc = segment_check(image, pixel_type, channels, channel, batch, height, width, in_kind, params, labels, labels_kind, n_labels, sp);
+    if (rc) return rc;
+    const int h = split ? (int)split->h : 3;
+    if (h < 1 || h > 255) return fail(CS_ERR_INVALID, "split h %d outside 1..255 (half pixels)", h);
+    if (!p) {
+        rc = require_gfx950(0);
+        return rc ? rc : fail(CS_ERR_INVALID, "handle is NULL");
+    }
+    SegmentCall c;
+    if ((rc = segment_mask(p, image, pixel_type, channels, channel, batch, height, width, in_kind, sp, labels, labels_kind, c))) return rc;
+    SegmentState& S = *p->seg;
+    hipStream_t st = p->stream;
+    const int H = c.H, W = c.W, HW = c.HW, conn8 = sp.connectivity == 2;
+    const dim3 tgrid((unsigned)((W + SG_TW - 1) / SG_TW), (unsigned)((H + SG_TH - 1) / SG_TH), (unsigned)batch);
+    const size_t ntiles = (size_t)tgrid.x * tgrid.y * tgrid.z;
+    if ((rc = S.dq.ensure(c.npx)) || (rc = S.rec.ensure(c.npx)) || (rc = S.key.ensure(c.npx * sizeof(unsigned long long))) ||
+        (rc = S.ttop.ensure(ntiles)) || (rc = S.ctrl.ensure(CT_N * sizeof(int))))
+        return rc;
+    unsigned char *mask = S.mask.as<unsigned char>(), *dq = S.dq.as<unsigned char>(), *rec = S.rec.as<unsigned char>();
+    unsigned long long* key = S.key.as<unsigned long long>();
+    int *ctrl = S.ctrl.as<int>(), *parent = S.parent.as<int>();
+    const dim3 one(1);
+
+    // distances: the column distances live in the key buffer, which the flood fills only later
+    HIPCHK(hipMemsetAsync(ctrl, 0, CT_N * sizeof(int), st));
+    hipLaunchKernelGGL(sp_columns, dim3((unsigned)((W + SG_THREADS - 1) / SG_THREADS), (unsigned)batch), dim3(SG_THREADS), 0, st, mask, H, W,
+                       (unsigned char*)key);
+    hipLaunchKernelGGL(sp_rows, dim3((unsigned)((W + SP_ROW - 1) / SP_ROW), (unsigned)H, (unsigned)batch), dim3(SG_THREADS), 0, st,
+                       (const unsigned char*)key, H, W, h, dq, rec, ctrl);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(S.ev[2], st));
+
+    // h-maxima: reconstruction in rounds, read back once per group of rounds; the bound of HW rounds never binds in practice
+    hipLaunchKernelGGL(sp_start, one, one, 0, st, ctrl, 0);
+    for (int active = 1; active;) {
+        for (int r = 0; r < SP_RECON_GROUP; ++r) {
+            hipLaunchKernelGGL(sp_recon, tgrid, dim3(SG_THREADS), 0, st, dq, H, W, conn8, rec, ctrl);
+            hipLaunchKernelGGL(sp_advance_recon, one, one, 0, st, ctrl, HW);
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(&active, ctrl + CT_ACTIVE, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    // seeds: plateaus of equal R, those without a higher neighbour, ranked; the flags live in the key buffer, the ids in the labels
+    int* drop = (int*)key;
+    HIPCHK(hipMemsetAsync(drop, 0, c.npx * sizeof(int), st));
+    HIPCHK(label_mask(mask, batch, H, W, 0, conn8, parent, nullptr, c.nchunks, st, rec));
+    hipLaunchKernelGGL(sp_higher, c.pgrid, dim3(SG_THREADS), 0, st, H, W, conn8, rec, parent, drop);
+    hipLaunchKernelGGL(sp_seedcount, c.pgrid, dim3(SG_THREADS), 0, st, HW, parent, drop, S.chunks.as<int>(), c.nchunks);
+    hipLaunchKernelGGL(sg_scan, dim3((unsigned)batch), dim3(HIST_THREADS), 0, st, S.chunks.as<int>(), c.nchunks, S.counts.as<int>());
+    hipLaunchKernelGGL(sg_rank<true>, c.pgrid, dim3(SG_THREADS), 0, st, HW, parent, S.chunks.as<int>(), c.nchunks, c.d_lab, (const int*)drop);
+    hipLaunchKernelGGL(sp_seedkey, c.pgrid, dim3(SG_THREADS), 0, st, HW, parent, c.d_lab, key);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(S.ev[3], st));
+
+    // flood, level by level from the batch's largest Dq; then each region's first pixel and the numbering
+    HIPCHK(hipMemsetAsync(S.ttop.p, 0xff, ntiles, st));
+    hipLaunchKernelGGL(sp_start, one, one, 0, st, ctrl, 1);
+    for (int level = 1; level >= 1;) {
+        for (int r = 0; r < SP_FLOOD_GROUP; ++r) {
+            hipLaunchKernelGGL(sp_flood, tgrid, dim3(SG_THREADS), 0, st, dq, H, W, conn8, key, S.ttop.as<unsigned char>(), ctrl);
+            hipLaunchKernelGGL(sp_advance_flood, one, one, 0, st, ctrl, HW);
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(&level, ctrl + CT_LEVEL, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    HIPCHK(hipMemsetAsync(c.d_lab, 0x7f, c.npx * sizeof(int), st));
+    hipLaunchKernelGGL(sp_first, c.pgrid, dim3(SG_THREADS), 0, st, HW, key, c.d_lab);
+    hipLaunchKernelGGL(sp_parent, c.pgrid, dim3(SG_THREADS), 0, st, HW, key, c.d_lab, parent, S.chunks.as<int>(), c.nchunks);
+    HIPCHK(hipGetLastError());
+    HIPCHK(number_regions(S, c, st));
+    HIPCHK(hipEventRecord(S.ev[4], st));
+    HIPCHK(hipMemcpyAsync(n_labels, S.counts.p, batch * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (thresholds) HIPCHK(hipMemcpyAsync(thresholds, S.thr.p, batch * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (labels_kind == CS_MEM_HOST) HIPCHK(hipMemcpyAsync(labels, c.d_lab, c.npx * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (dist) HIPCHK(hipMemcpyAsync(dist, dq, c.npx, labels_kind == CS_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, S.ev[0], S.ev[1]));
+    S.sp_threshold_ms = ms;
+    HIPCHK(hipEventElapsedTime(&ms, S.ev[1], S.ev[2]));
+    S.sp_distance_ms = ms;
+    HIPCHK(hipEventElapsedTime(&ms, S.ev[2], S.ev[3]));
+    S.sp_seed_ms = ms;
+    HIPCHK(hipEventElapsedTime(&ms, S.ev[3], S.ev[4]));
+    S.sp_flood_ms = ms;
+    return CS_OK;
+}
+
+int cs_segment_split_last_timing(const cs_preproc* p, double* threshold_ms, double* distance_ms, double* seed_ms, double* flood_ms)
+{
+    if (!p) return fail(CS_ERR_INVALID, "handle is NULL");
+    const SegmentState* S = p->seg;
+    if (threshold_ms) *threshold_ms = S ? S->sp_threshold_ms : 0.0;
+    if (distance_ms) *distance_ms = S ? S->sp_distance_ms : 0.0;
+    if (seed_ms) *seed_ms = S ? S->sp_seed_ms : 0.0;
+    if (flood_ms) *flood_ms = S ? S->sp_flood_ms : 0.0;
     return CS_OK;
 }

@@ -26,7 +26,7 @@
  *        eccentricity / intensity rules + the bbox crop + the preprocess above
  *                                   improved_detection.py:61-111, CAE_improved_modeltrain.py:54-107
  *        (the StarDist segmentation itself, :59-60 / :52-53, stays with the caller)
- *   cs_segment_threshold
+ *   cs_segment_threshold / cs_segment_split
  *        the library's own classical segmenter (no reference counterpart, and no StarDist): Otsu or
  *        fixed threshold, optional hole filling, connected-component labels for the extraction above
  *   cs_fit_scaler / cs_fit_pca_moments / cs_fit_pca_subspace / cs_fit_project / cs_fit_ocsvm
@@ -377,7 +377,8 @@ int cs_extract_last_timing(const cs_preproc *p, double *label_ms, double *region
 
 /* ---- built-in segmenter: global threshold + connected components ---------------------------
  * Not StarDist: a classical segmenter of the library's own, for bright cells on a dark background.
- * Touching cells come out as ONE region (the extraction's area / eccentricity rules then judge it).
+ * Touching cells come out as ONE region (the extraction's area / eccentricity rules then judge it) unless
+ * cs_segment_split is called in its place, which cuts them apart at their necks.
  * Input as for the extraction: one `channel` of a [B][H][W][channels] uint8 / uint16 stack, read in place.
  *   threshold   CS_THRESH_OTSU: scikit-image 0.18.3's threshold_otsu of that channel of each image (exact
  *               integer histogram over [min, max], int64 cumulative sums, its float64 operations in its order:
@@ -419,6 +420,37 @@ int cs_segment_threshold(cs_preproc *p, const void *image, int pixel_type, int32
                          int32_t *n_labels, int32_t *thresholds);
 /* Device time of the last cs_segment_threshold: histogram + threshold + mask, and hole filling + labelling. */
 int cs_segment_last_timing(const cs_preproc *p, double *threshold_ms, double *label_ms);
+
+/* cs_segment_threshold with touching cells split: a distance-transform watershed on the same mask (after the threshold and
+ * the optional hole filling), exact and all integers.  The result is a function of the mask alone:
+ *   Dq     min(isqrt(4 * D2), 255): D2 the exact squared Euclidean distance of a foreground pixel to the nearest
+ *          background pixel of the same image (scipy.ndimage.distance_transform_edt squared), so Dq is the distance in half
+ *          pixels; 0 on background.  Outside the image is not background; an image without background is 255 everywhere.
+ *   seeds  R = morphological reconstruction by dilation of max(Dq - h, 0) under Dq; the seeds are the regional maxima of R
+ *          inside the mask (the h-maxima of Dq), numbered in raster order of their first pixels.
+ *   flood  for v = 255 .. 1: an unlabelled pixel with Dq >= v takes the label that reaches it through unlabelled pixels
+ *          with Dq >= v with the smallest (number of steps, label); the step count restarts at every level.
+ *   labels the regions, renumbered 1.. in raster order of each region's first pixel.  Where every component holds one
+ *          seed they equal cs_segment_threshold's labels bit for bit.
+ * The segmenter's connectivity is the neighbourhood of the dilation, the plateaus and the steps.  With connectivity 2 the
+ * chessboard step count skews the cut between two equal cells; connectivity 1 is the default.  Not split: cells that
+ * overlap without a neck (one maximum), and cores deeper than 127 px (one plateau of Dq = 255).
+ * Workspace on the device beyond cs_segment_threshold's: 10 bytes per pixel and 1 byte per 64 x 16 tile.  Host
+ * synchronisations: one per 16 rounds of the reconstruction, one per 64 rounds of the flood and the final one -- 3 for
+ * isolated small cells, a handful for crowded fields.  Arguments, errors and outputs as cs_segment_threshold; h outside 1..255:
+ * CS_ERR_INVALID.
+ * dist: optional out, [batch][height][width] uint8: Dq, on the device or the host as labels_kind; NULL: not wanted. */
+typedef struct cs_split_params {
+    int32_t h;                        /* half pixels, 1..255: how much lower than its peak a saddle must be to separate two cells */
+} cs_split_params;                    /* NULL = h 3 */
+int cs_segment_split(cs_preproc *p, const void *image, int pixel_type, int32_t channels, int32_t channel,
+                     int32_t batch, int32_t height, int32_t width, int in_kind,
+                     const cs_segment_params *params, const cs_split_params *split, int32_t *labels, int labels_kind,
+                     int32_t *n_labels, int32_t *thresholds, uint8_t *dist);
+/* Device time of the last cs_segment_split: histogram + threshold + mask; hole filling + distances; reconstruction + seeds;
+ * flood + numbering. */
+int cs_segment_split_last_timing(const cs_preproc *p, double *threshold_ms, double *distance_ms, double *seed_ms,
+                                 double *flood_ms);
 
 /* ---- detector fitting (create_anomaly_detector, CAE_improved_modeltrain.py:394-446) -------- */
 /* The fit of what cs_screen's tail evaluates, for the training set's encoder features

@@ -12,7 +12,14 @@ writes it to profiles/segment_bench.json:
   host_segment_images_per_s             its segmentation part alone
 The device and the host path are compared on their outputs first: equal labels, equal region tables.
 
-Usage: python tools/bench_segment.py [--images 32] [--side 2048] [--cells 1000] [--reps 10] [--warmup 2] [--host-images 4]"""
+--split measures the split_touching option (cs_segment_split) in its place and writes profiles/segment_split_bench.json: per
+workload -- the one above, and one with --split-cells cells per image, where most cells touch another -- the unsplit
+segmenter's images/s of the same run, the split's images/s and its four stage times (threshold, distance, seeds, flood), the
+split + extraction images/s, the ratio of the split's time to the unsplit one's, and the time of the host restatement
+(tests/split_reference.py) on one image, whose labels the device's are compared with first.
+
+Usage: python tools/bench_segment.py [--images 32] [--side 2048] [--cells 1000] [--reps 10] [--warmup 2] [--host-images 4]
+                                     [--split [--split-cells 3000] [--split-h 3]]"""
 import argparse
 import json
 import os
@@ -27,6 +34,74 @@ for p in (os.path.join(ROOT, "cell-image-analysis_amd"), ROOT, os.path.join(ROOT
         sys.path.insert(0, p)
 
 
+def split_leg(a):
+    import torch
+    import split_reference as SR
+    from build import source_hash
+    from cellscreen import extract as X
+    from cellscreen import segment as S
+    from cellscreen import synth
+
+    fill = not a.no_fill_holes
+    dev = torch.device("cuda", 0)
+    med = lambda v: float(np.median(v))
+    res = {"tool": "bench_segment --split", "source_hash": source_hash(), "images": a.images, "side": a.side,
+           "connectivity": a.connectivity, "fill_holes": fill, "split_h": a.split_h, "reps": a.reps, "warmup": a.warmup, "workloads": []}
+    for name, cells in (("cells", a.cells), ("touching", a.split_cells)):
+        imgs, _ = synth.label_images(2024, a.images, hw=(a.side, a.side), n_cells=cells)
+        ti = torch.from_numpy(imgs.view(np.int16)).to(dev)
+        torch.cuda.synchronize()
+        ext = X.CellExtractor(0)
+        plain = S.ThresholdSegmenter(0, "otsu", a.connectivity, fill, extractor=ext)
+        split = S.ThresholdSegmenter(0, "otsu", a.connectivity, fill, extractor=ext, split_touching=True, split_h=a.split_h)
+
+        def timed(fn, seg):
+            walls, stages = [], []
+            for k in range(a.warmup + a.reps):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                out = fn()
+                torch.cuda.synchronize()
+                if k >= a.warmup:
+                    walls.append(time.perf_counter() - t0)
+                    stages.append(seg.last_timing())
+            return out, walls, stages
+
+        (_, n_plain, _), plain_walls, _ = timed(lambda: plain.segment_batch(ti), plain)
+        (labels, n_split, _), split_walls, stages = timed(lambda: split.segment_batch(ti), split)
+        _, plain_chain, _ = timed(lambda: ext.extract_batch(ti, plain.segment_batch(ti)[0]), plain)
+        r, split_chain, _ = timed(lambda: ext.extract_batch(ti, split.segment_batch(ti)[0]), split)
+        t0 = time.perf_counter()
+        hl, hn, _, _ = SR.split(np.ascontiguousarray(imgs[0, ..., 2]), "otsu", a.connectivity, fill, a.split_h)
+        host_s = time.perf_counter() - t0
+        assert hn == int(n_split[0]) and np.array_equal(labels[0].cpu().numpy(), hl), "device labels differ from the host restatement"
+        spread = lambda k: [round(med([t[k] for t in stages]), 4), round(min(t[k] for t in stages), 4), round(max(t[k] for t in stages), 4)]
+        res["workloads"].append({
+            "name": name, "cells_painted_per_image": cells, "components": int(n_plain.sum()), "regions_split": int(n_split.sum()),
+            "cells_extracted_split": int(r.cells.shape[0]),
+            "unsplit_images_per_s": round(a.images / med(plain_walls), 2), "split_images_per_s": round(a.images / med(split_walls), 2),
+            "split_wall_ms": [round(med(split_walls) * 1e3, 3), round(min(split_walls) * 1e3, 3), round(max(split_walls) * 1e3, 3)],
+            "threshold_ms": spread("threshold_ms"), "distance_ms": spread("distance_ms"), "seed_ms": spread("seed_ms"),
+            "flood_ms": spread("flood_ms"),
+            "split_over_unsplit_time": round(med(split_walls) / med(plain_walls), 2),
+            "unsplit_extract_images_per_s": round(a.images / med(plain_chain), 2),
+            "split_extract_images_per_s": round(a.images / med(split_chain), 2),
+            "host_restatement_s_per_image": round(host_s, 2),
+            "speedup_over_host_restatement": round(host_s / (med(split_walls) / a.images), 1), "outputs_equal": True})
+        ext.close()
+        del ti
+    line = json.dumps(res)
+    out = a.out if a.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "segment_split_bench.json")
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            f.write(line + "\n")
+    print(line)
+
+
+DEFAULT_OUT = os.path.join(ROOT, "profiles", "segment_bench.json")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=32)
@@ -37,8 +112,13 @@ def main():
     ap.add_argument("--host-images", type=int, default=4)
     ap.add_argument("--connectivity", type=int, default=1)
     ap.add_argument("--no-fill-holes", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "segment_bench.json"))
+    ap.add_argument("--out", default=DEFAULT_OUT)
+    ap.add_argument("--split", action="store_true", help="measure the split_touching option (profiles/segment_split_bench.json)")
+    ap.add_argument("--split-cells", type=int, default=3000)
+    ap.add_argument("--split-h", type=int, default=3)
     a = ap.parse_args()
+    if a.split:
+        return split_leg(a)
 
     import torch
     import segment_reference as R
