@@ -12,9 +12,18 @@ What it computes is exact: the threshold is scikit-image 0.18.3's threshold_otsu
 `channel > threshold` (after scipy.ndimage.binary_fill_holes with fill_holes), and the labels are scipy.ndimage.label's
 (= skimage.measure.label's) ids, as restated in tests/segment_reference.py; neither library is a dependency.
 
+One global threshold needs a flat background.  Where the illumination is uneven (vignetting, a tilted coverslip, haze: a
+background slope larger than the cells' own contrast) pass background_radius=r: the channel is first corrected on the device by
+a white top-hat with the flat square of side 2r + 1 (cs_segment_background; scipy.ndimage.white_tophat bit for bit, restated in
+tests/background_reference.py), after an optional 3 x 3 median (denoise=True), and the threshold, the labels and the split see
+the corrected plane.  r must exceed half the width of the widest cell (r >= 51 for cells up to the extraction's 8000 px area
+limit); a smaller r eats the cores of the cells.  Off by default, and only the segmentation channel is corrected: the
+extraction's intensity rules and crops read the raw analysis channel.
+
     seg = ThresholdSegmenter()
     labels, n_labels, thresholds = seg.segment_batch(images)          # numpy in, numpy out; CUDA tensors in, CUDA tensor out
     seg = ThresholdSegmenter(split_touching=True)                      # the same, touching cells apart
+    seg = ThresholdSegmenter(background_radius=51)                     # uneven illumination flattened before the threshold
 
     screening = ProductionMutantScreening(model_dir, cell_extractor=threshold_cell_extractor())
 """
@@ -69,18 +78,41 @@ def split_params(split_touching: bool = False, split_h: int = 3) -> Optional[L.C
     return p
 
 
+def background_params(background_radius=None, denoise: bool = False) -> Optional[L.CSBackgroundParams]:
+    """cs_background_params from the Python arguments, None without a radius (no correction); anything out of range raises
+    before a handle exists.  denoise (the 3 x 3 median) is part of the correction: without a radius it is an error."""
+    if not isinstance(denoise, (bool, np.bool_)):
+        raise TypeError(f"denoise must be a bool, got {type(denoise).__name__}")
+    if background_radius is None:
+        if denoise:
+            raise ValueError("denoise=True needs background_radius: the median is a step of the background correction")
+        return None
+    if isinstance(background_radius, bool) or not isinstance(background_radius, (int, np.integer)):
+        raise TypeError(f"background_radius must be None or an integer (pixels), got {type(background_radius).__name__}")
+    if not 1 <= int(background_radius) <= 255:
+        raise ValueError(f"background_radius {background_radius} outside 1..255")
+    p = L.CSBackgroundParams()
+    p.radius, p.median = int(background_radius), 1 if denoise else 0
+    return p
+
+
 class ThresholdSegmenter:
     """Threshold + connected components on one preprocess handle (one GPU, one stream).  threshold: "otsu" (per image) or an
     integer; foreground is pixel > threshold.  connectivity: 1 (4 neighbours) or 2 (8).  fill_holes: background enclosed
     by foreground becomes foreground before labelling.  extractor: a CellExtractor whose handle and stream to share, so
     that labels left on the device feed its extract_batch in stream order.  split_touching: cut touching cells apart
     (cs_segment_split, see the module text); split_h: the depth in half pixels (1..255) a saddle needs below the lower of
-    its two peaks to separate them."""
+    its two peaks to separate them.  background_radius: None, or the radius r (1..255) of the white top-hat that flattens the
+    channel before the threshold (see the module text); denoise: a 3 x 3 median before the top-hat.  With numpy input the
+    corrected plane makes one extra round trip through the host; CUDA tensors are the fast path."""
 
     def __init__(self, device_id: int = 0, threshold="otsu", connectivity: int = 1, fill_holes: bool = True,
-                 extractor: Optional[CellExtractor] = None, split_touching: bool = False, split_h: int = 3):
+                 extractor: Optional[CellExtractor] = None, split_touching: bool = False, split_h: int = 3,
+                 background_radius: Optional[int] = None, denoise: bool = False):
         self._params = segment_params(threshold, connectivity, fill_holes)
         self._split = split_params(split_touching, split_h)
+        self._background = background_params(background_radius, denoise)
+        self.background_radius, self.denoise = (None if background_radius is None else int(background_radius)), bool(denoise)
         self.split_touching, self.split_h = bool(split_touching), int(split_h)
         if extractor is not None and extractor.device_id != device_id:
             raise ValueError(f"extractor is on device {extractor.device_id}, the segmenter on {device_id}")
@@ -153,6 +185,35 @@ class ThresholdSegmenter:
                 raise ValueError("images must be C-contiguous")
         return B, H, W, Cn, int(channel), ptype, on_dev
 
+    def _correct(self, images, B, H, W, Cn, channel, ptype, on_dev):
+        """The corrected plane [B,H,W] where the images are; a device plane is complete in the handle's stream order only."""
+        if on_dev:
+            import torch
+            plane = torch.empty((B, H, W), dtype=images.dtype, device=images.device)
+            L.order_after_torch(self._lib.cs_preproc_wait_stream, self._handle, images, plane)
+        else:
+            plane = np.empty((B, H, W), images.dtype)
+        kind = L.CS_MEM_DEVICE if on_dev else L.CS_MEM_HOST
+        L.check(self._lib.cs_segment_background(self._handle, L._ptr(images), ptype, Cn, channel, B, H, W, kind,
+                                                C.byref(self._background), L._ptr(plane), kind))
+        return plane
+
+    def _background_timing(self):
+        a, b = C.c_double(), C.c_double()
+        L.check(self._lib.cs_segment_background_last_timing(self._handle, C.byref(a), C.byref(b)))
+        return {"median_ms": a.value, "background_ms": b.value}
+
+    def correct_batch(self, images, channel: Optional[int] = None):
+        """The background-corrected plane of `channel` that segment_batch thresholds: [B,H,W] of the images' dtype, numpy for
+        numpy input, a CUDA tensor for tensor input (complete when this returns).  Needs background_radius."""
+        B, H, W, Cn, channel, ptype, on_dev = self._check(images, channel)
+        if self._background is None:
+            raise ValueError("correct_batch needs background_radius: this segmenter corrects nothing")
+        plane = self._correct(images, B, H, W, Cn, channel, ptype, on_dev)
+        if on_dev:
+            self._background_timing()                               # reads the times, which waits for the plane: torch may use it
+        return plane
+
     def segment_batch(self, images, channel: Optional[int] = None, return_distance: bool = False):
         """images: [B,H,W] or [B,H,W,C] uint8 / uint16, numpy or CUDA tensors of the segmenter's device; the channel that is
         segmented is `channel` (default 2 of >= 3 channels as improved_detection.py:55, 0 of one).
@@ -163,6 +224,11 @@ class ThresholdSegmenter:
         B, H, W, Cn, channel, ptype, on_dev = self._check(images, channel)
         if return_distance and self._split is None:
             raise ValueError("return_distance needs split_touching=True: the plain segmenter computes no distances")
+        if self._background is not None:
+            # threshold, label and split the corrected plane in the channel's place; the library's final synchronisation
+            # comes after everything that reads the plane
+            images = self._correct(images, B, H, W, Cn, channel, ptype, on_dev)
+            Cn, channel = 1, 0
         n_labels = np.zeros(B, np.int32)
         thresholds = np.zeros(B, np.int32)
         if on_dev:
@@ -190,26 +256,32 @@ class ThresholdSegmenter:
         return (labels, n_labels, thresholds, dist) if return_distance else (labels, n_labels, thresholds)
 
     def last_timing(self):
-        """Device milliseconds of the last call's stages; with split_touching the stages of cs_segment_split."""
+        """Device milliseconds of the last call's stages; with split_touching the stages of cs_segment_split; with
+        background_radius also median_ms and background_ms (the top-hat) of the last correction."""
+        extra = self._background_timing() if self._background is not None else {}
         if self._split is None:
             a, b = C.c_double(), C.c_double()
             L.check(self._lib.cs_segment_last_timing(self._handle, C.byref(a), C.byref(b)))
-            return {"threshold_ms": a.value, "label_ms": b.value}
+            return dict({"threshold_ms": a.value, "label_ms": b.value}, **extra)
         v = [C.c_double() for _ in range(4)]
         L.check(self._lib.cs_segment_split_last_timing(self._handle, *(C.byref(x) for x in v)))
-        return dict(zip(("threshold_ms", "distance_ms", "seed_ms", "flood_ms"), (x.value for x in v)))
+        return dict(zip(("threshold_ms", "distance_ms", "seed_ms", "flood_ms"), (x.value for x in v)), **extra)
 
 
 def threshold_cell_extractor(device_id: int = 0, out_hw=(OUT_SIDE, OUT_SIDE), threshold="otsu", connectivity: int = 1,
-                             fill_holes: bool = True, split_touching: bool = False, split_h: int = 3, **qc):
+                             fill_holes: bool = True, split_touching: bool = False, split_h: int = 3,
+                             background_radius: Optional[int] = None, denoise: bool = False, **qc):
     """The `cell_extractor(image_path) -> (cells, stats)` that ProductionMutantScreening and create_training_dataset accept,
     with the built-in segmenter in StarDist's place: the file is read (extract.read_image / split_channels), uploaded once,
     segmented and extracted on one handle, and the labels never leave the device.  Not StarDist: see the module text.
     Errors raise as label_cell_extractor's do; the screening driver's try turns them into the reference's "Error processing"
-    line and ([], []).  out_hw and **qc as for label_cell_extractor; split_touching and split_h as for ThresholdSegmenter."""
+    line and ([], []).  out_hw and **qc as for label_cell_extractor; split_touching, split_h, background_radius and denoise as
+    for ThresholdSegmenter: with background_radius the segmentation channel is corrected before the threshold, while the
+    extraction still reads the raw analysis channel, so the intensity rules and the crops are what they are without it."""
     out_hw = check_out_hw(out_hw)
     segment_params(threshold, connectivity, fill_holes)
     split_params(split_touching, split_h)
+    background_params(background_radius, denoise)
     qc_params(**qc)
     st = {}
 
@@ -223,7 +295,8 @@ def threshold_cell_extractor(device_id: int = 0, out_hw=(OUT_SIDE, OUT_SIDE), th
         if "x" not in st:
             st["x"] = CellExtractor(device_id, out_hw, **qc)
             st["s"] = ThresholdSegmenter(device_id, threshold, connectivity, fill_holes, extractor=st["x"],
-                                         split_touching=split_touching, split_h=split_h)
+                                         split_touching=split_touching, split_h=split_h, background_radius=background_radius,
+                                         denoise=denoise)
         host = np.ascontiguousarray(img)[None]
         dev = torch.from_numpy(host.view(np.int16) if host.dtype == np.uint16 else host).to(torch.device("cuda", device_id))
         labels, _, _ = st["s"].segment_batch(dev, channel=seg_ch)

@@ -109,7 +109,7 @@ struct cs_preproc {
     double last_kernel_ms = 0.0;
     int64_t last_pixels = 0;
     cs::ExtractState* ext = nullptr;    // created by the first cs_extract_measure
-    cs::SegmentState* seg = nullptr;    // created by the first cs_segment_threshold
+    cs::SegmentState* seg = nullptr;    // created by the first cs_segment_* call
     ~cs_preproc()
     {
         cs::extract_state_free(ext);

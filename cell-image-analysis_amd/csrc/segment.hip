@@ -22,6 +22,8 @@
 //   sg_edge / sg_fill   (fill_holes) the same labelling on the inverted mask, 4-connected; background components without a
 //                pixel on the image border become foreground (scipy.ndimage.binary_fill_holes, default structure).
 //   sp_*         cs_segment_split only: see "split_touching" further down.
+//   bg_*         cs_segment_background only: the optional correction of the channel BEFORE all of the above (3x3 median, white
+//                top-hat); see "background correction" further down.  Its plane then stands in the channel's place.
 // The final parents are a function of the mask alone (the minimum index of a component), so the labels do not depend on
 // execution order, on the run, or on the other images of the batch.
 #include "api_internal.hpp"
@@ -793,16 +795,178 @@ __global__ __launch_bounds__(SG_THREADS) void sp_parent(int HW, const unsigned l
     if (threadIdx.x == 0) chunk_cnt[(size_t)blockIdx.y * nchunks + blockIdx.x] = wc[0] + wc[1] + wc[2] + wc[3];
 }
 
+// ---- background correction (cs_segment_background): 3x3 median, white top-hat by a flat square ------------------------------
+// out = x - dilate(erode(x)) with the square of side w = 2r + 1, windows clipped to the image (DESIGN 3l;
+// tests/background_reference.py restates it).  The square is separable and min / max passes commute across axes:
+//   bg_rows<min>  ->  bg_cols<min>  ->  bg_cols<max>  ->  bg_rows<max, fused>: out = x - opening, in the pixel type.
+// A pass puts its lines with a halo of r on either side into LDS as 16-bit values (outside the image: the operation's
+// identity, which is what clipping the window means), then doubles in place: after step j an element holds the min / max over
+// the 2^j elements from itself on, and with 2^K <= w < 2^(K+1) a window is two overlapping spans of 2^K: K = floor(log2 w)
+// <= 8 steps whatever r, no per-r template.  Doubling in place: a chunk of BG_E elements per thread is read (with its partners
+// further on), a barrier, then written; chunks ascend, so a later chunk never reads what an earlier one wrote.
+//   bg_rows   256 threads, 4 rows x up to 1024 pixels; wave k owns row k, lanes run along the row.
+//   bg_cols   1024 threads, 64 columns x TR rows (TR = 2r rounded up to 64, within 128..512: the halo is never more than the
+//             tile itself); LDS is [row][64 columns], lanes run across the columns, so a wave's 64 accesses are 64 consecutive
+//             16-bit values of one row at every step: no bank is hit twice.  Dynamic LDS, (TR + 2r) * 128 bytes <= 130,816.
+//   bg_median 3x3 median with the edge pixel repeated (scipy.ndimage.median_filter's default "reflect" at size 3), one thread
+//             per pixel, reads the selected channel of the stack in place.
+// min, max and subtract on integers only, no atomics: the plane is a function of its own image alone.
+static constexpr int BG_E = 8;                          // elements a thread holds across the barrier of a doubling chunk
+static constexpr int BG_MAX_R = 255;
+static constexpr int BG_ROW_SEG = 1024, BG_ROW_LINES = SG_THREADS / 64;
+static constexpr int BG_ROW_LEN = BG_ROW_SEG + 2 * BG_MAX_R;
+static constexpr int BG_COL_THREADS = 1024, BG_COL_W = 64;
+static constexpr int BG_COL_TR_MIN = 128, BG_COL_TR_MAX = 512;
+
+static inline int bg_col_rows(int r) { return std::min(BG_COL_TR_MAX, std::max(BG_COL_TR_MIN, (2 * r + 63) / 64 * 64)); }
+static inline int bg_levels(int r)
+{
+    int k = 0;
+    while ((2 << k) <= 2 * r + 1) ++k;
+    return k;                                           // 2^k <= 2r + 1 < 2^(k+1)
+}
+
+template <bool IS_MAX>
+__device__ inline int bg_op(int a, int b) { return IS_MAX ? max(a, b) : min(a, b); }
+
+// s: this thread's line (element `pos` at s[pos * es]); the thread owns positions tp, tp + pstep, ...  Called by the whole
+// workgroup with the same len and levels.
+template <bool IS_MAX>
+__device__ inline void bg_double(unsigned short* s, int es, int len, int tp, int pstep, int levels)
+{
+    for (int j = 0; j < levels; ++j) {
+        const int d = 1 << j;
+        for (int p0 = 0; p0 < len; p0 += BG_E * pstep) {
+            int v[BG_E];
+#pragma unroll
+            for (int e = 0; e < BG_E; ++e) {
+                const int pos = p0 + e * pstep + tp;
+                v[e] = 0;
+                if (pos < len) {
+                    v[e] = s[pos * es];
+                    if (pos + d < len) v[e] = bg_op<IS_MAX>(v[e], (int)s[(pos + d) * es]);
+                }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int e = 0; e < BG_E; ++e) {
+                const int pos = p0 + e * pstep + tp;
+                if (pos < len) s[pos * es] = (unsigned short)v[e];
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// grid (ceil(W / BG_ROW_SEG), ceil(H / BG_ROW_LINES), B).  in: pixel (b, y, x) at in[b * in_img + (y * W + x) * in_pix].
+// FUSE: out = orig - result, orig addressed the same way.
+template <typename PIX, bool IS_MAX, bool FUSE>
+__global__ __launch_bounds__(SG_THREADS) void bg_rows(const PIX* __restrict__ in, size_t in_img, int in_pix, int H, int W, int r, int levels,
+                                                      const PIX* __restrict__ orig, size_t orig_img, int orig_pix, PIX* __restrict__ out)
+{
+    __shared__ unsigned short sm[BG_ROW_LINES * BG_ROW_LEN];
+    const int tp = threadIdx.x & 63, line = threadIdx.x >> 6;
+    const int x0 = blockIdx.x * BG_ROW_SEG, y = blockIdx.y * BG_ROW_LINES + line, b = blockIdx.z;
+    const int seg = min(BG_ROW_SEG, W - x0), len = seg + 2 * r;
+    constexpr unsigned short ident = IS_MAX ? 0 : 0xffff;
+    unsigned short* s = sm + line * BG_ROW_LEN;
+    const PIX* src = in + (size_t)b * in_img + (size_t)(y < H ? y : 0) * W * in_pix;
+    for (int pos = tp; pos < len; pos += 64) {
+        const int x = x0 - r + pos;
+        s[pos] = y < H && x >= 0 && x < W ? (unsigned short)src[(size_t)x * in_pix] : ident;
+    }
+    __syncthreads();
+    bg_double<IS_MAX>(s, 1, len, tp, 64, levels);
+    if (y >= H) return;
+    const int off = 2 * r + 1 - (1 << levels);
+    for (int pos = tp; pos < seg; pos += 64) {
+        int v = bg_op<IS_MAX>((int)s[pos], (int)s[pos + off]);
+        const size_t px = (size_t)y * W + x0 + pos;
+        if (FUSE) v = (int)orig[(size_t)b * orig_img + px * orig_pix] - v;
+        out[(size_t)b * H * W + px] = (PIX)v;
+    }
+}
+
+// grid (ceil(W / 64), ceil(H / TR), B), planes in and out; dynamic LDS (min(TR, H) + 2r) * 64 * 2 bytes
+template <typename PIX, bool IS_MAX>
+__global__ __launch_bounds__(BG_COL_THREADS) void bg_cols(const PIX* __restrict__ in, int H, int W, int r, int levels, int TR,
+                                                          PIX* __restrict__ out)
+{
+    extern __shared__ unsigned short bg_sm[];
+    const int col = threadIdx.x & 63, tp = threadIdx.x >> 6;
+    constexpr int PS = BG_COL_THREADS / BG_COL_W;
+    const int x = blockIdx.x * BG_COL_W + col, y0 = blockIdx.y * TR;
+    const int rows = min(TR, H - y0), len = rows + 2 * r;
+    constexpr unsigned short ident = IS_MAX ? 0 : 0xffff;
+    const size_t base = (size_t)blockIdx.z * H * W;
+    unsigned short* s = bg_sm + col;
+    for (int pos = tp; pos < len; pos += PS) {
+        const int y = y0 - r + pos;
+        s[pos * BG_COL_W] = x < W && y >= 0 && y < H ? (unsigned short)in[base + (size_t)y * W + x] : ident;
+    }
+    __syncthreads();
+    bg_double<IS_MAX>(s, BG_COL_W, len, tp, PS, levels);
+    if (x >= W) return;
+    const int off = 2 * r + 1 - (1 << levels);
+    for (int pos = tp; pos < rows; pos += PS)
+        out[base + (size_t)(y0 + pos) * W + x] = (PIX)bg_op<IS_MAX>((int)s[pos * BG_COL_W], (int)s[(pos + off) * BG_COL_W]);
+}
+
+__device__ inline void bg_sort3(int& a, int& b, int& c)
+{
+    const int lo = min(a, b), hi = max(a, b);
+    a = min(lo, c);
+    const int m = max(lo, c);
+    b = min(m, hi);
+    c = max(m, hi);
+}
+
+// grid (ceil(HW / SG_CHUNK), B).  The median of nine from the three sorted columns: the largest of their minima, the median of
+// their medians and the smallest of their maxima hold it between them.
+template <typename PIX>
+__global__ __launch_bounds__(SG_THREADS) void bg_median(const PIX* __restrict__ image, int C, int ch, int H, int W, PIX* __restrict__ out)
+{
+    const int HW = H * W;
+    const PIX* img = image + (size_t)blockIdx.y * HW * C + ch;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = blockIdx.x * SG_CHUNK + k * SG_THREADS + threadIdx.x;
+        if (i >= HW) continue;
+        const int y = i / W, x = i % W;
+        const int ys[3] = {max(y - 1, 0), y, min(y + 1, H - 1)}, xs[3] = {max(x - 1, 0), x, min(x + 1, W - 1)};
+        int lo[3], mid[3], hi[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            lo[c] = img[((size_t)ys[0] * W + xs[c]) * C];
+            mid[c] = img[((size_t)ys[1] * W + xs[c]) * C];
+            hi[c] = img[((size_t)ys[2] * W + xs[c]) * C];
+            bg_sort3(lo[c], mid[c], hi[c]);
+        }
+        int a = max(max(lo[0], lo[1]), lo[2]), c = min(min(hi[0], hi[1]), hi[2]);
+        bg_sort3(mid[0], mid[1], mid[2]);
+        int m = mid[1];
+        bg_sort3(a, m, c);
+        out[(size_t)blockIdx.y * HW + i] = (PIX)m;
+    }
+}
+
 // ---- host state ---------------------------------------------------------------------------------------------------------------
 struct SegmentState {
     DevBuf img, lab, mask, parent, slab, hist, thr, chunks, counts;
     DevBuf dq, rec, key, ttop, ctrl;                    // cs_segment_split only
+    DevBuf bg_in, bg_med, bg_a, bg_b, bg_out;           // cs_segment_background only: upload, median, two planes, host staging
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t bev[3] = {nullptr, nullptr, nullptr};
+    bool bg_pending = false;                            // bev of a call that left its plane on the device: not read yet
+    bool bg_median = false;                             // that call ran the median
+    double bg_median_ms = 0.0, bg_tophat_ms = 0.0;
     double threshold_ms = 0.0, label_ms = 0.0;
     double sp_threshold_ms = 0.0, sp_distance_ms = 0.0, sp_seed_ms = 0.0, sp_flood_ms = 0.0;
     ~SegmentState()
     {
         for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : bev)
             if (e) (void)hipEventDestroy(e);
     }
 };
@@ -957,6 +1121,59 @@ static hipError_t number_regions(SegmentState& S, const SegmentCall& c, hipStrea
     return hipGetLastError();
 }
 
+// median (optional) and the four passes of the top-hat on the stream; d_out is a [B][H][W] plane on the device
+template <typename PIX>
+static int background_launch(SegmentState& S, const PIX* d_img, int C, int ch, int batch, int H, int W, int r, bool median, PIX* d_out,
+                             hipStream_t st)
+{
+    const int HW = H * W, levels = bg_levels(r), TR = bg_col_rows(r);
+    const size_t plane = (size_t)batch * HW * sizeof(PIX);
+    int rc;
+    if ((rc = S.bg_a.ensure(plane)) || (rc = S.bg_b.ensure(plane))) return rc;
+    const PIX* x = d_img + ch;                          // what the opening is subtracted from
+    size_t x_img = (size_t)HW * C;
+    int x_pix = C;
+    HIPCHK(hipEventRecord(S.bev[0], st));
+    S.bg_median = median;
+    if (median) {
+        if ((rc = S.bg_med.ensure(plane))) return rc;
+        hipLaunchKernelGGL(bg_median<PIX>, dim3((unsigned)((HW + SG_CHUNK - 1) / SG_CHUNK), (unsigned)batch), dim3(SG_THREADS), 0, st, d_img, C,
+                           ch, H, W, S.bg_med.as<PIX>());
+        HIPCHK(hipGetLastError());
+        x = S.bg_med.as<PIX>();
+        x_img = (size_t)HW;
+        x_pix = 1;
+    }
+    HIPCHK(hipEventRecord(S.bev[1], st));
+    PIX *A = S.bg_a.as<PIX>(), *B = S.bg_b.as<PIX>();
+    const dim3 rgrid((unsigned)((W + BG_ROW_SEG - 1) / BG_ROW_SEG), (unsigned)((H + BG_ROW_LINES - 1) / BG_ROW_LINES), (unsigned)batch);
+    const dim3 cgrid((unsigned)((W + BG_COL_W - 1) / BG_COL_W), (unsigned)((H + TR - 1) / TR), (unsigned)batch);
+    const size_t lds = (size_t)(std::min(TR, H) + 2 * r) * BG_COL_W * sizeof(unsigned short);
+    HIPCHK(hipFuncSetAttribute((const void*)bg_cols<PIX, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIPCHK(hipFuncSetAttribute((const void*)bg_cols<PIX, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((bg_rows<PIX, false, false>), rgrid, dim3(SG_THREADS), 0, st, x, x_img, x_pix, H, W, r, levels, (const PIX*)nullptr,
+                       (size_t)0, 0, A);
+    hipLaunchKernelGGL((bg_cols<PIX, false>), cgrid, dim3(BG_COL_THREADS), lds, st, (const PIX*)A, H, W, r, levels, TR, B);
+    hipLaunchKernelGGL((bg_cols<PIX, true>), cgrid, dim3(BG_COL_THREADS), lds, st, (const PIX*)B, H, W, r, levels, TR, A);
+    hipLaunchKernelGGL((bg_rows<PIX, true, true>), rgrid, dim3(SG_THREADS), 0, st, (const PIX*)A, (size_t)HW, 1, H, W, r, levels, x, x_img,
+                       x_pix, d_out);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(S.bev[2], st));
+    return CS_OK;
+}
+
+static int background_times(SegmentState& S)
+{
+    float ms = 0.f;
+    HIPCHK(hipEventSynchronize(S.bev[2]));
+    S.bg_pending = false;
+    HIPCHK(hipEventElapsedTime(&ms, S.bev[0], S.bev[1]));
+    S.bg_median_ms = S.bg_median ? ms : 0.0;            // without it the two records are back to back
+    HIPCHK(hipEventElapsedTime(&ms, S.bev[1], S.bev[2]));
+    S.bg_tophat_ms = ms;
+    return CS_OK;
+}
+
 }  // namespace cs
 
 // ---- C ABI ----------------------------------------------------------------------------------
@@ -1104,5 +1321,76 @@ int cs_segment_split_last_timing(const cs_preproc* p, double* threshold_ms, doub
     if (distance_ms) *distance_ms = S ? S->sp_distance_ms : 0.0;
     if (seed_ms) *seed_ms = S ? S->sp_seed_ms : 0.0;
     if (flood_ms) *flood_ms = S ? S->sp_flood_ms : 0.0;
+    return CS_OK;
+}
+
+int cs_segment_background(cs_preproc* p, const void* image, int pixel_type, int32_t channels, int32_t channel, int32_t batch, int32_t height,
+                          int32_t width, int in_kind, const cs_background_params* params, void* out, int out_kind)
+{
+    if (!image || !params || !out) return fail(CS_ERR_INVALID, "NULL argument");
+    if (pixel_type != CS_PIX_U8 && pixel_type != CS_PIX_U16) return fail(CS_ERR_INVALID, "pixel_type must be CS_PIX_U8 or CS_PIX_U16");
+    if ((in_kind != CS_MEM_HOST && in_kind != CS_MEM_DEVICE) || (out_kind != CS_MEM_HOST && out_kind != CS_MEM_DEVICE))
+        return fail(CS_ERR_INVALID, "in_kind / out_kind must be CS_MEM_HOST or CS_MEM_DEVICE");
+    if (channels < 1 || channel < 0 || channel >= channels)
+        return fail(CS_ERR_INVALID, "channel %d of %d: need 0 <= channel < channels", (int)channel, (int)channels);
+    if (batch < 1 || height < 1 || width < 1) return fail(CS_ERR_INVALID, "batch %d, height %d, width %d: all must be >= 1", (int)batch,
+                                                          (int)height, (int)width);
+    if (params->radius < 1 || params->radius > BG_MAX_R) return fail(CS_ERR_INVALID, "background radius %d outside 1..%d", (int)params->radius, BG_MAX_R);
+    if (params->median != 0 && params->median != 1) return fail(CS_ERR_INVALID, "median %d: 0 or 1", (int)params->median);
+    if (height > kSegMaxSide || width > kSegMaxSide)
+        return fail(CS_ERR_UNSUPPORTED, "image %dx%d: sides above %d are not supported", (int)height, (int)width, kSegMaxSide);
+    if (batch > kSegMaxBatch) return fail(CS_ERR_UNSUPPORTED, "batch %d: at most %d images per call", (int)batch, kSegMaxBatch);
+    if (!p) {
+        const int rc = require_gfx950(0);
+        return rc ? rc : fail(CS_ERR_INVALID, "handle is NULL");
+    }
+    HIPCHK(hipSetDevice(p->device));
+    if (!p->seg) p->seg = new SegmentState();
+    SegmentState& S = *p->seg;
+    for (hipEvent_t& e : S.bev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    hipStream_t st = p->stream;
+    const size_t esz = pixel_type == CS_PIX_U8 ? 1 : 2;
+    const size_t npx = (size_t)batch * height * width;
+    int rc;
+    const void* d_img = image;
+    if (in_kind == CS_MEM_HOST) {
+        if ((rc = S.bg_in.ensure(npx * channels * esz))) return rc;
+        HIPCHK(hipMemcpyAsync(S.bg_in.p, image, npx * channels * esz, hipMemcpyHostToDevice, st));
+        d_img = S.bg_in.p;
+    }
+    void* d_out = out;
+    if (out_kind == CS_MEM_HOST) {
+        if ((rc = S.bg_out.ensure(npx * esz))) return rc;
+        d_out = S.bg_out.p;
+    }
+    S.bg_pending = false;
+    if (pixel_type == CS_PIX_U8)
+        rc = background_launch<unsigned char>(S, (const unsigned char*)d_img, channels, channel, batch, height, width, params->radius,
+                                              params->median != 0, (unsigned char*)d_out, st);
+    else
+        rc = background_launch<unsigned short>(S, (const unsigned short*)d_img, channels, channel, batch, height, width, params->radius,
+                                               params->median != 0, (unsigned short*)d_out, st);
+    if (rc) return rc;
+    if (out_kind == CS_MEM_DEVICE && in_kind == CS_MEM_DEVICE) {
+        S.bg_pending = true;                            // no host synchronisation: the times are read when they are asked for
+        return CS_OK;
+    }
+    if (out_kind == CS_MEM_HOST) HIPCHK(hipMemcpyAsync(out, d_out, npx * esz, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));                     // the one host synchronisation: the caller's host buffers are free / filled
+    return background_times(S);
+}
+
+int cs_segment_background_last_timing(const cs_preproc* p, double* median_ms, double* tophat_ms)
+{
+    if (!p) return fail(CS_ERR_INVALID, "handle is NULL");
+    SegmentState* S = p->seg;
+    if (S && S->bg_pending) {
+        HIPCHK(hipSetDevice(p->device));
+        const int rc = background_times(*S);
+        if (rc) return rc;
+    }
+    if (median_ms) *median_ms = S ? S->bg_median_ms : 0.0;
+    if (tophat_ms) *tophat_ms = S ? S->bg_tophat_ms : 0.0;
     return CS_OK;
 }

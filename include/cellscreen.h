@@ -452,6 +452,37 @@ int cs_segment_split(cs_preproc *p, const void *image, int pixel_type, int32_t c
 int cs_segment_split_last_timing(const cs_preproc *p, double *threshold_ms, double *distance_ms, double *seed_ms,
                                  double *flood_ms);
 
+/* Background correction of the segmentation channel before the threshold: for images whose illumination is not flat
+ * (vignetting, a tilted coverslip, out-of-focus haze), where one global threshold cuts the field in two instead of finding
+ * cells.  Integer arithmetic in the pixel type, each image on its own:
+ *   median   (optional) the 3 x 3 median with the edge pixel repeated: scipy.ndimage.median_filter(x, size=3), default mode.
+ *   top-hat  out = x - dilate(erode(x)) with the flat square of side 2 * radius + 1, erosion and dilation being the minimum
+ *            and maximum over the window [i - r, i + r] x [j - r, j + r] clipped to the image:
+ *            scipy.ndimage.white_tophat(x, size=(2r + 1, 2r + 1)) bit for bit, also where r exceeds a side.  The opening is
+ *            never above x, so the subtraction cannot wrap.
+ * radius must exceed half the width of the widest cell, or the opening eats the cell's core: the extraction's area limit of
+ * 8000 px (a disk of diameter 101) asks for radius >= 51 where cells get that large.  The cost does not grow with the radius
+ * beyond the halo a tile reads (at most the tile again).
+ * image, pixel_type, channels, channel, batch, height, width, in_kind: as cs_segment_threshold; the channel is read in place.
+ * out: [batch][height][width] of the same pixel type, out_kind.  Left on the device it is cs_segment_threshold's or
+ *      cs_segment_split's `image` with channels = 1, channel = 0, on the same handle (the same stream: no ordering needed).
+ * Workspace on the device: 2 planes of the pixel type (2 or 4 bytes per pixel), one more with the median, one more for an
+ * `out` on the host, and the image itself when it comes from the host.
+ * Host synchronisations: none when image and out are both on the device (the plane is complete in stream order; the times
+ * are read when cs_segment_background_last_timing asks for them, which waits for the plane), else one.
+ * Bad arguments (NULL params among them, radius outside 1..255, median not 0 or 1): CS_ERR_INVALID before any device work;
+ * sides above 4096, batches above 65535: CS_ERR_UNSUPPORTED; without a gfx950 device (p == NULL): CS_ERR_NO_DEVICE. */
+typedef struct cs_background_params {
+    int32_t radius;                   /* 1..255: the square has side 2 * radius + 1 */
+    int32_t median;                   /* 0 or 1: 3 x 3 median first */
+} cs_background_params;
+int cs_segment_background(cs_preproc *p, const void *image, int pixel_type, int32_t channels, int32_t channel,
+                          int32_t batch, int32_t height, int32_t width, int in_kind,
+                          const cs_background_params *params /* not NULL */, void *out, int out_kind);
+/* Device time of the last cs_segment_background: the median (0 without it) and the four passes of the top-hat.  Waits for
+ * that call's plane if it was left on the device. */
+int cs_segment_background_last_timing(const cs_preproc *p, double *median_ms, double *tophat_ms);
+
 /* ---- detector fitting (create_anomaly_detector, CAE_improved_modeltrain.py:394-446) -------- */
 /* The fit of what cs_screen's tail evaluates, for the training set's encoder features
  * (cs_encode output, [n][n_features] fp32, host or device).  Own handle, own stream.

@@ -18,8 +18,14 @@ segmenter's images/s of the same run, the split's images/s and its four stage ti
 split + extraction images/s, the ratio of the split's time to the unsplit one's, and the time of the host restatement
 (tests/split_reference.py) on one image, whose labels the device's are compared with first.
 
+--background R [--denoise] measures the background correction (cs_segment_background, ThresholdSegmenter(background_radius=R))
+in its place and writes profiles/segment_background_bench.json: one image's corrected plane and labels are compared with the
+host restatement (tests/background_reference.py) first; then the images/s of the segmenter without and with the correction in
+the same run, their ratio, and the two new stage times (median, top-hat) at R and at the radii 8, 32 and 128 side by side,
+which show whether the cost is flat in the radius.  No time is a pass condition.
+
 Usage: python tools/bench_segment.py [--images 32] [--side 2048] [--cells 1000] [--reps 10] [--warmup 2] [--host-images 4]
-                                     [--split [--split-cells 3000] [--split-h 3]]"""
+                                     [--split [--split-cells 3000] [--split-h 3]] [--background R [--denoise]]"""
 import argparse
 import json
 import os
@@ -99,6 +105,74 @@ def split_leg(a):
     print(line)
 
 
+def background_leg(a):
+    import torch
+    import background_reference as BR
+    from build import source_hash
+    from cellscreen import segment as S
+    from cellscreen import synth
+
+    fill = not a.no_fill_holes
+    dev = torch.device("cuda", 0)
+    med = lambda v: float(np.median(v))
+    imgs, _ = synth.label_images(2024, a.images, hw=(a.side, a.side), n_cells=a.cells)
+    ti = torch.from_numpy(imgs.view(np.int16)).to(dev)
+    torch.cuda.synchronize()
+
+    def timed(seg, fn):
+        walls, stages = [], []
+        for k in range(a.warmup + a.reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = fn(seg)
+            torch.cuda.synchronize()
+            if k >= a.warmup:
+                walls.append(time.perf_counter() - t0)
+                stages.append(seg.last_timing())
+        return out, walls, stages
+
+    spread = lambda stages, k: [round(med([t[k] for t in stages]), 4), round(min(t[k] for t in stages), 4),
+                                round(max(t[k] for t in stages), 4)]
+    plain = S.ThresholdSegmenter(0, "otsu", a.connectivity, fill)
+    (_, n_plain, _), plain_walls, _ = timed(plain, lambda s: s.segment_batch(ti))
+    plain.close()
+    res = {"tool": "bench_segment --background", "source_hash": source_hash(), "images": a.images, "side": a.side,
+           "connectivity": a.connectivity, "fill_holes": fill, "denoise": bool(a.denoise), "reps": a.reps, "warmup": a.warmup,
+           "components_uncorrected": int(n_plain.sum()), "uncorrected_images_per_s": round(a.images / med(plain_walls), 2),
+           "uncorrected_wall_ms": [round(med(plain_walls) * 1e3, 3), round(min(plain_walls) * 1e3, 3), round(max(plain_walls) * 1e3, 3)],
+           "radii": []}
+    for r in sorted({a.background, 8, 32, 128}):
+        seg = S.ThresholdSegmenter(0, "otsu", a.connectivity, fill, background_radius=r, denoise=a.denoise)
+        entry = {"radius": r}
+        if r == a.background:
+            # outputs first: one image's plane and labels against the host restatement
+            plane = seg.correct_batch(ti[:1].contiguous())
+            labels, n, thr = seg.segment_batch(ti[:1].contiguous())
+            chan = np.ascontiguousarray(imgs[0, ..., 2])
+            assert np.array_equal(plane[0].cpu().numpy().view(np.uint16), BR.correct(chan, r, a.denoise)), "plane differs from the restatement"
+            hl, hn, ht = BR.segment(chan, r, a.denoise, "otsu", a.connectivity, fill)
+            assert hn == int(n[0]) and ht == int(thr[0]) and np.array_equal(labels[0].cpu().numpy(), hl), "labels differ from the restatement"
+            entry["outputs_equal"] = True
+        (_, n_corr, _), walls, stages = timed(seg, lambda s: s.segment_batch(ti))
+        _, plane_walls, _ = timed(seg, lambda s: s.correct_batch(ti))
+        seg.close()
+        entry.update({
+            "components": int(n_corr.sum()), "corrected_images_per_s": round(a.images / med(walls), 2),
+            "corrected_wall_ms": [round(med(walls) * 1e3, 3), round(min(walls) * 1e3, 3), round(max(walls) * 1e3, 3)],
+            "corrected_over_uncorrected_time": round(med(walls) / med(plain_walls), 3),
+            "correct_batch_wall_ms": [round(med(plane_walls) * 1e3, 3), round(min(plane_walls) * 1e3, 3), round(max(plane_walls) * 1e3, 3)],
+            "median_ms": spread(stages, "median_ms"), "background_ms": spread(stages, "background_ms"),
+            "threshold_ms": spread(stages, "threshold_ms"), "label_ms": spread(stages, "label_ms")})
+        res["radii"].append(entry)
+    line = json.dumps(res)
+    out = a.out if a.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "segment_background_bench.json")
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            f.write(line + "\n")
+    print(line)
+
+
 DEFAULT_OUT = os.path.join(ROOT, "profiles", "segment_bench.json")
 
 
@@ -116,9 +190,16 @@ def main():
     ap.add_argument("--split", action="store_true", help="measure the split_touching option (profiles/segment_split_bench.json)")
     ap.add_argument("--split-cells", type=int, default=3000)
     ap.add_argument("--split-h", type=int, default=3)
+    ap.add_argument("--background", type=int, default=None, metavar="R",
+                    help="measure the background correction of radius R (profiles/segment_background_bench.json)")
+    ap.add_argument("--denoise", action="store_true", help="with --background: the 3 x 3 median first")
     a = ap.parse_args()
+    if a.denoise and a.background is None:
+        ap.error("--denoise needs --background R")
     if a.split:
         return split_leg(a)
+    if a.background is not None:
+        return background_leg(a)
 
     import torch
     import segment_reference as R
