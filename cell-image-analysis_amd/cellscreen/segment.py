@@ -20,10 +20,23 @@ the corrected plane.  r must exceed half the width of the widest cell (r >= 51 f
 limit); a smaller r eats the cores of the cells.  Off by default, and only the segmentation channel is corrected: the
 extraction's intensity rules and crops read the raw analysis channel.
 
+One global threshold also needs cells of one brightness.  Where bright and dim cells share a field, Otsu's threshold settles
+between the background and the bright ones and the dim cells are never found.  threshold="local" with local_radius=r cuts every
+pixel against the mean of its own (2r + 1)^2 neighbourhood instead (cs_segment_local; tests/local_reference.py restates it):
+foreground is  n * x - S - n * local_delta > 0  and  x > local_floor, S the window's sum with the image reflected about its
+edges, n = (2r + 1)^2.  That is x > skimage.filters.threshold_local(x, 2r + 1, method='mean', offset=-local_delta) decided in
+integers; the one difference is an exact tie, n * (x - local_delta) = S, which is background here while the library's float64
+mean may fall on either side.  The window must be wider than the widest cell, as the top-hat's square, or a cell's core sits
+near its own mean and drops out.  Noise on empty background passes a small local_delta as speckle: the extraction's area rule
+drops it, but the label count rises towards the extraction's limit (batch * max_label <= 2^22); denoise=True and a
+local_delta of a few noise sigmas keep it down.  The mask feeds the same hole filling, labelling and split; with
+background_radius the local rule runs on the corrected plane.
+
     seg = ThresholdSegmenter()
     labels, n_labels, thresholds = seg.segment_batch(images)          # numpy in, numpy out; CUDA tensors in, CUDA tensor out
     seg = ThresholdSegmenter(split_touching=True)                      # the same, touching cells apart
     seg = ThresholdSegmenter(background_radius=51)                     # uneven illumination flattened before the threshold
+    seg = ThresholdSegmenter(threshold="local", local_radius=25, local_delta=60)      # bright and dim cells in one field
 
     screening = ProductionMutantScreening(model_dir, cell_extractor=threshold_cell_extractor())
 """
@@ -96,6 +109,42 @@ def background_params(background_radius=None, denoise: bool = False) -> Optional
     return p
 
 
+def local_params(local_radius=None, local_delta: int = 0, local_floor: int = -1, denoise: bool = False) -> L.CSLocalParams:
+    """cs_local_params from the Python arguments of threshold="local"; anything out of range (a missing radius among them)
+    raises before a handle exists.  denoise: the 3 x 3 median before the sums."""
+    if not isinstance(denoise, (bool, np.bool_)):
+        raise TypeError(f"denoise must be a bool, got {type(denoise).__name__}")
+    if local_radius is None:
+        raise ValueError("threshold='local' needs local_radius: the window has side 2 * local_radius + 1")
+    for name, v in (("local_radius", local_radius), ("local_delta", local_delta), ("local_floor", local_floor)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError(f"{name} must be an integer, got {type(v).__name__}")
+    if not 1 <= int(local_radius) <= 255:
+        raise ValueError(f"local_radius {local_radius} outside 1..255")
+    if not -65535 <= int(local_delta) <= 65535:
+        raise ValueError(f"local_delta {local_delta} outside -65535..65535")
+    if not -1 <= int(local_floor) <= 65535:
+        raise ValueError(f"local_floor {local_floor} outside -1..65535 (-1: off)")
+    p = L.CSLocalParams()
+    p.radius, p.delta, p.floor, p.median = int(local_radius), int(local_delta), int(local_floor), 1 if denoise else 0
+    return p
+
+
+def _threshold_mode(threshold, connectivity, fill_holes, local_radius, local_delta, local_floor, background_radius, denoise):
+    """(cs_segment_params, cs_local_params or None, cs_background_params or None) of a segmenter's arguments.  In local mode the
+    labelling sees a 0 / 1 plane, so its parameters are a fixed threshold of 0; the median runs once: inside the correction
+    when there is one, else inside the local rule."""
+    if isinstance(threshold, str) and threshold == "local":
+        if not isinstance(denoise, (bool, np.bool_)):
+            raise TypeError(f"denoise must be a bool, got {type(denoise).__name__}")
+        background = background_params(background_radius, bool(denoise) and background_radius is not None)
+        local = local_params(local_radius, local_delta, local_floor, bool(denoise) and background is None)
+        return segment_params(0, connectivity, fill_holes), local, background
+    if local_radius is not None or local_delta != 0 or local_floor != -1:
+        raise ValueError("local_radius, local_delta and local_floor belong to threshold='local'")
+    return segment_params(threshold, connectivity, fill_holes), None, background_params(background_radius, denoise)
+
+
 class ThresholdSegmenter:
     """Threshold + connected components on one preprocess handle (one GPU, one stream).  threshold: "otsu" (per image) or an
     integer; foreground is pixel > threshold.  connectivity: 1 (4 neighbours) or 2 (8).  fill_holes: background enclosed
@@ -104,14 +153,21 @@ class ThresholdSegmenter:
     (cs_segment_split, see the module text); split_h: the depth in half pixels (1..255) a saddle needs below the lower of
     its two peaks to separate them.  background_radius: None, or the radius r (1..255) of the white top-hat that flattens the
     channel before the threshold (see the module text); denoise: a 3 x 3 median before the top-hat.  With numpy input the
-    corrected plane makes one extra round trip through the host; CUDA tensors are the fast path."""
+    corrected plane makes one extra round trip through the host; CUDA tensors are the fast path.
+    threshold="local": the local mean threshold of the module text in the global one's place, with local_radius (1..255,
+    required), local_delta (counts above the local mean, -65535..65535) and local_floor (pixel > local_floor as well; -1:
+    off); these three belong to "local" alone.  denoise then needs no background_radius: the median runs before the sums.  The
+    thresholds it reports are -1: there is no single number.  With numpy input the mask makes one more round trip."""
 
     def __init__(self, device_id: int = 0, threshold="otsu", connectivity: int = 1, fill_holes: bool = True,
                  extractor: Optional[CellExtractor] = None, split_touching: bool = False, split_h: int = 3,
-                 background_radius: Optional[int] = None, denoise: bool = False):
-        self._params = segment_params(threshold, connectivity, fill_holes)
+                 background_radius: Optional[int] = None, denoise: bool = False, local_radius: Optional[int] = None,
+                 local_delta: int = 0, local_floor: int = -1):
+        self._params, self._local, self._background = _threshold_mode(threshold, connectivity, fill_holes, local_radius, local_delta,
+                                                                      local_floor, background_radius, denoise)
         self._split = split_params(split_touching, split_h)
-        self._background = background_params(background_radius, denoise)
+        self.local_radius, self.local_delta, self.local_floor = (None if local_radius is None else int(local_radius)), int(local_delta), \
+            int(local_floor)
         self.background_radius, self.denoise = (None if background_radius is None else int(background_radius)), bool(denoise)
         self.split_touching, self.split_h = bool(split_touching), int(split_h)
         if extractor is not None and extractor.device_id != device_id:
@@ -214,6 +270,39 @@ class ThresholdSegmenter:
             self._background_timing()                               # reads the times, which waits for the plane: torch may use it
         return plane
 
+    def _local_mask(self, images, B, H, W, Cn, channel, ptype, on_dev):
+        """The 0 / 1 plane [B,H,W] uint8 where the images are; a device plane is complete in the handle's stream order only."""
+        if on_dev:
+            import torch
+            mask = torch.empty((B, H, W), dtype=torch.uint8, device=images.device)
+            L.order_after_torch(self._lib.cs_preproc_wait_stream, self._handle, images, mask)
+        else:
+            mask = np.empty((B, H, W), np.uint8)
+        kind = L.CS_MEM_DEVICE if on_dev else L.CS_MEM_HOST
+        L.check(self._lib.cs_segment_local(self._handle, L._ptr(images), ptype, Cn, channel, B, H, W, kind, C.byref(self._local),
+                                           L._ptr(mask), kind))
+        return mask
+
+    def _local_timing(self):
+        a, b = C.c_double(), C.c_double()
+        L.check(self._lib.cs_segment_local_last_timing(self._handle, C.byref(a), C.byref(b)))
+        return {"local_median_ms": a.value, "local_ms": b.value}
+
+    def local_mask_batch(self, images, channel: Optional[int] = None):
+        """The mask of the local mean threshold that segment_batch fills and labels: [B,H,W] uint8, 1 = foreground, numpy for
+        numpy input, a CUDA tensor for tensor input (complete when this returns).  Needs threshold="local"; with
+        background_radius it is the mask of the corrected plane."""
+        B, H, W, Cn, channel, ptype, on_dev = self._check(images, channel)
+        if self._local is None:
+            raise ValueError("local_mask_batch needs threshold='local'")
+        if self._background is not None:
+            images = self._correct(images, B, H, W, Cn, channel, ptype, on_dev)
+            Cn, channel = 1, 0
+        mask = self._local_mask(images, B, H, W, Cn, channel, ptype, on_dev)
+        if on_dev:
+            self._local_timing()                                    # reads the times, which waits for the plane: torch may use it
+        return mask
+
     def segment_batch(self, images, channel: Optional[int] = None, return_distance: bool = False):
         """images: [B,H,W] or [B,H,W,C] uint8 / uint16, numpy or CUDA tensors of the segmenter's device; the channel that is
         segmented is `channel` (default 2 of >= 3 channels as improved_detection.py:55, 0 of one).
@@ -229,6 +318,10 @@ class ThresholdSegmenter:
             # comes after everything that reads the plane
             images = self._correct(images, B, H, W, Cn, channel, ptype, on_dev)
             Cn, channel = 1, 0
+        if self._local is not None:
+            # the 0 / 1 plane in the channel's place, cut at the fixed threshold 0: hole filling, labels and the split as they are
+            images = self._local_mask(images, B, H, W, Cn, channel, ptype, on_dev)
+            Cn, channel, ptype = 1, 0, PIX_U8
         n_labels = np.zeros(B, np.int32)
         thresholds = np.zeros(B, np.int32)
         if on_dev:
@@ -242,6 +335,8 @@ class ThresholdSegmenter:
             L.check(self._lib.cs_segment_threshold(self._handle, L._ptr(images), ptype, Cn, channel, B, H, W, kind,
                                                    C.byref(self._params), L._ptr(labels), kind, n_labels.ctypes.data,
                                                    thresholds.ctypes.data))
+            if self._local is not None:
+                thresholds[:] = -1                                  # no single number
             return labels, n_labels, thresholds
         dist = None
         if return_distance:
@@ -253,12 +348,17 @@ class ThresholdSegmenter:
         L.check(self._lib.cs_segment_split(self._handle, L._ptr(images), ptype, Cn, channel, B, H, W, kind, C.byref(self._params),
                                            C.byref(self._split), L._ptr(labels), kind, n_labels.ctypes.data,
                                            thresholds.ctypes.data, L._ptr(dist)))
+        if self._local is not None:
+            thresholds[:] = -1
         return (labels, n_labels, thresholds, dist) if return_distance else (labels, n_labels, thresholds)
 
     def last_timing(self):
         """Device milliseconds of the last call's stages; with split_touching the stages of cs_segment_split; with
-        background_radius also median_ms and background_ms (the top-hat) of the last correction."""
+        background_radius also median_ms and background_ms (the top-hat) of the last correction; with threshold="local" also
+        local_median_ms and local_ms (the sums and the comparison) of the last mask."""
         extra = self._background_timing() if self._background is not None else {}
+        if self._local is not None:
+            extra.update(self._local_timing())
         if self._split is None:
             a, b = C.c_double(), C.c_double()
             L.check(self._lib.cs_segment_last_timing(self._handle, C.byref(a), C.byref(b)))
@@ -270,18 +370,18 @@ class ThresholdSegmenter:
 
 def threshold_cell_extractor(device_id: int = 0, out_hw=(OUT_SIDE, OUT_SIDE), threshold="otsu", connectivity: int = 1,
                              fill_holes: bool = True, split_touching: bool = False, split_h: int = 3,
-                             background_radius: Optional[int] = None, denoise: bool = False, **qc):
+                             background_radius: Optional[int] = None, denoise: bool = False, local_radius: Optional[int] = None,
+                             local_delta: int = 0, local_floor: int = -1, **qc):
     """The `cell_extractor(image_path) -> (cells, stats)` that ProductionMutantScreening and create_training_dataset accept,
     with the built-in segmenter in StarDist's place: the file is read (extract.read_image / split_channels), uploaded once,
     segmented and extracted on one handle, and the labels never leave the device.  Not StarDist: see the module text.
     Errors raise as label_cell_extractor's do; the screening driver's try turns them into the reference's "Error processing"
     line and ([], []).  out_hw and **qc as for label_cell_extractor; split_touching, split_h, background_radius and denoise as
-    for ThresholdSegmenter: with background_radius the segmentation channel is corrected before the threshold, while the
+    for ThresholdSegmenter, and threshold="local" with local_radius, local_delta and local_floor too: with background_radius the segmentation channel is corrected before the threshold, while the
     extraction still reads the raw analysis channel, so the intensity rules and the crops are what they are without it."""
     out_hw = check_out_hw(out_hw)
-    segment_params(threshold, connectivity, fill_holes)
+    _threshold_mode(threshold, connectivity, fill_holes, local_radius, local_delta, local_floor, background_radius, denoise)
     split_params(split_touching, split_h)
-    background_params(background_radius, denoise)
     qc_params(**qc)
     st = {}
 
@@ -296,7 +396,8 @@ def threshold_cell_extractor(device_id: int = 0, out_hw=(OUT_SIDE, OUT_SIDE), th
             st["x"] = CellExtractor(device_id, out_hw, **qc)
             st["s"] = ThresholdSegmenter(device_id, threshold, connectivity, fill_holes, extractor=st["x"],
                                          split_touching=split_touching, split_h=split_h, background_radius=background_radius,
-                                         denoise=denoise)
+                                         denoise=denoise, local_radius=local_radius, local_delta=local_delta,
+                                         local_floor=local_floor)
         host = np.ascontiguousarray(img)[None]
         dev = torch.from_numpy(host.view(np.int16) if host.dtype == np.uint16 else host).to(torch.device("cuda", device_id))
         labels, _, _ = st["s"].segment_batch(dev, channel=seg_ch)

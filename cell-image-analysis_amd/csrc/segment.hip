@@ -950,13 +950,123 @@ __global__ __launch_bounds__(SG_THREADS) void bg_median(const PIX* __restrict__ 
     }
 }
 
+// ---- local mean threshold (cs_segment_local) -----------------------------------------------------------------------------------
+// fg = n * x - S - n * delta > 0 and x > floor, with S the sum of x over the window [i - r, i + r] x [j - r, j + r] of side
+// w = 2r + 1 (n = w * w), indices outside the image reflected about the edge (d c b a | a b c d, period 2 * side, so r may exceed
+// a side): x > skimage.filters.threshold_local(x, w, 'mean', offset=-delta) decided in integers, an exact tie being background
+// (tests/local_reference.py restates it).  The square is separable: row sums, then column sums of the row sums.
+//   lt_rows   256 threads, 4 rows x up to 1024 pixels; wave k owns row k.  The row with a halo of r on either side goes into
+//             LDS as 32-bit values; lane l sums its own run of CH consecutive values (CH odd, so the 64 lanes of an access are
+//             on 64 different banks), the wave scans the 64 totals, and each lane turns its run into inclusive prefix sums in
+//             place.  A window is the difference of two prefixes; lanes run along the row for the loads and the stores.  A
+//             prefix is at most 1534 * 65535 and a row sum at most 511 * 65535: both fit 32 bits.
+//   lt_cols   256 threads, 64 columns x 4 row tiles of TR rows (TR as bg_cols': 2r rounded up to 64, within 128..512, so the
+//             2r halo rows are never more than the tile); lanes run across the columns, every access of a wave is 64 consecutive
+//             values of one row.  A thread walks down its column with the window's sum in a 64-bit register (n * x and S reach
+//             1.7e10): 2r + 1 row sums to start, then one in and one out per pixel, compared and written as 0 / 1.  No LDS:
+//             the row that leaves was read 2r + 1 rows earlier by the same wave and comes from the cache.
+// Integer sums do not depend on their order and there are no atomics: the plane is a function of its own image alone.
+static constexpr int LT_MAX_R = 255;
+static constexpr int LT_ROW_SEG = 1024, LT_ROW_LINES = SG_THREADS / 64;
+static constexpr int LT_ROW_LEN = LT_ROW_SEG + 2 * LT_MAX_R;
+static constexpr int LT_COL_W = 64, LT_COL_TILES = SG_THREADS / 64;
+static constexpr int LT_COL_U = 8;                      // rows a thread of lt_cols loads before it uses the first
+
+// index i of a line of n reflected about the edges: ... 2 1 0 | 0 1 2 ... n-1 | n-1 n-2 ..., period 2n; any i
+__device__ inline int lt_fold(int i, int n)
+{
+    if ((unsigned)i < (unsigned)n) return i;
+    const int p = 2 * n;
+    int m = i % p;
+    if (m < 0) m += p;
+    return m < n ? m : p - 1 - m;
+}
+
+// grid (ceil(W / LT_ROW_SEG), ceil(H / LT_ROW_LINES), B).  in: pixel (b, y, x) at in[b * in_img + (y * W + x) * in_pix].
+// sums: [B][H][W] uint32, the sum over [x - r, x + r] of row y.
+template <typename PIX>
+__global__ __launch_bounds__(SG_THREADS) void lt_rows(const PIX* __restrict__ in, size_t in_img, int in_pix, int H, int W, int r,
+                                                      unsigned int* __restrict__ sums)
+{
+    __shared__ unsigned int sm[LT_ROW_LINES * LT_ROW_LEN];
+    const int tp = threadIdx.x & 63, line = threadIdx.x >> 6;
+    const int x0 = blockIdx.x * LT_ROW_SEG, y = blockIdx.y * LT_ROW_LINES + line, b = blockIdx.z;
+    const int seg = min(LT_ROW_SEG, W - x0), len = seg + 2 * r;
+    unsigned int* s = sm + line * LT_ROW_LEN;
+    const PIX* src = in + (size_t)b * in_img + (size_t)(y < H ? y : 0) * W * in_pix;
+    for (int pos = tp; pos < len; pos += 64) s[pos] = y < H ? (unsigned int)src[(size_t)lt_fold(x0 - r + pos, W) * in_pix] : 0u;
+    __syncthreads();
+    const int ch = ((len + 63) / 64) | 1;               // >= len / 64 and odd
+    const int p0 = min(tp * ch, len), p1 = min(p0 + ch, len);
+    unsigned int total = 0;
+    for (int pos = p0; pos < p1; ++pos) total += s[pos];
+    unsigned int before = total;                        // inclusive scan of the lanes' totals
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const unsigned int up = __shfl_up(before, d, 64);
+        if (tp >= d) before += up;
+    }
+    before -= total;
+    for (int pos = p0; pos < p1; ++pos) {
+        before += s[pos];
+        s[pos] = before;
+    }
+    __syncthreads();
+    if (y >= H) return;
+    unsigned int* dst = sums + ((size_t)b * H + y) * W + x0;
+    for (int pos = tp; pos < seg; pos += 64) dst[pos] = s[pos + 2 * r] - (pos ? s[pos - 1] : 0u);
+}
+
+// grid (ceil(W / LT_COL_W), ceil(H / (LT_COL_TILES * TR)), B).  x: the pixels, addressed as lt_rows' in; out: [B][H][W] 0 / 1.
+template <typename PIX>
+__global__ __launch_bounds__(SG_THREADS) void lt_cols(const unsigned int* __restrict__ sums, const PIX* __restrict__ x, size_t x_img,
+                                                      int x_pix, int H, int W, int r, int TR, long long n, long long n_delta, int floor,
+                                                      unsigned char* __restrict__ out)
+{
+    const int col = blockIdx.x * LT_COL_W + (threadIdx.x & 63);
+    const int y0 = (blockIdx.y * LT_COL_TILES + (threadIdx.x >> 6)) * TR, y1 = min(y0 + TR, H);
+    if (col >= W || y0 >= H) return;
+    const unsigned int* sc = sums + (size_t)blockIdx.z * H * W + col;
+    const PIX* xc = x + (size_t)blockIdx.z * x_img + (size_t)col * x_pix;
+    unsigned char* oc = out + (size_t)blockIdx.z * H * W + col;
+    long long S = 0;
+#pragma unroll 8
+    for (int k = -r; k <= r; ++k) S += sc[(size_t)lt_fold(y0 + k, H) * W];
+    int y = y0;
+    for (; y + LT_COL_U <= y1; y += LT_COL_U) {         // the loads of LT_COL_U rows in flight before the first is used
+        int v[LT_COL_U];
+        unsigned int in[LT_COL_U], gone[LT_COL_U];
+#pragma unroll
+        for (int u = 0; u < LT_COL_U; ++u) {
+            v[u] = xc[(size_t)(y + u) * W * x_pix];
+            in[u] = sc[(size_t)lt_fold(y + u + r + 1, H) * W];
+            gone[u] = sc[(size_t)lt_fold(y + u - r, H) * W];
+        }
+#pragma unroll
+        for (int u = 0; u < LT_COL_U; ++u) {
+            oc[(size_t)(y + u) * W] = (n * v[u] - S - n_delta > 0 && v[u] > floor) ? 1 : 0;
+            S += (long long)in[u] - (long long)gone[u];
+        }
+    }
+    for (; y < y1; ++y) {
+        const int v = xc[(size_t)y * W * x_pix];
+        oc[(size_t)y * W] = (n * v - S - n_delta > 0 && v > floor) ? 1 : 0;
+        S += (long long)sc[(size_t)lt_fold(y + r + 1, H) * W] - (long long)sc[(size_t)lt_fold(y - r, H) * W];
+    }
+}
+
 // ---- host state ---------------------------------------------------------------------------------------------------------------
 struct SegmentState {
     DevBuf img, lab, mask, parent, slab, hist, thr, chunks, counts;
     DevBuf dq, rec, key, ttop, ctrl;                    // cs_segment_split only
     DevBuf bg_in, bg_med, bg_a, bg_b, bg_out;           // cs_segment_background only: upload, median, two planes, host staging
+    DevBuf lt_in, lt_med, lt_sum, lt_out;               // cs_segment_local only: upload, median, row sums, host staging
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     hipEvent_t bev[3] = {nullptr, nullptr, nullptr};
+    hipEvent_t lev[3] = {nullptr, nullptr, nullptr};
+    bool lt_pending = false;                            // lev of a call that left its plane on the device: not read yet
+    bool lt_median = false;                             // that call ran the median
+    double lt_median_ms = 0.0, lt_sum_ms = 0.0;
     bool bg_pending = false;                            // bev of a call that left its plane on the device: not read yet
     bool bg_median = false;                             // that call ran the median
     double bg_median_ms = 0.0, bg_tophat_ms = 0.0;
@@ -967,6 +1077,8 @@ struct SegmentState {
         for (hipEvent_t e : ev)
             if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : bev)
+            if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : lev)
             if (e) (void)hipEventDestroy(e);
     }
 };
@@ -1171,6 +1283,52 @@ static int background_times(SegmentState& S)
     S.bg_median_ms = S.bg_median ? ms : 0.0;            // without it the two records are back to back
     HIPCHK(hipEventElapsedTime(&ms, S.bev[1], S.bev[2]));
     S.bg_tophat_ms = ms;
+    return CS_OK;
+}
+
+// median (optional), row sums, column sums + compare on the stream; d_out is a [B][H][W] uint8 plane on the device
+template <typename PIX>
+static int local_launch(SegmentState& S, const PIX* d_img, int C, int ch, int batch, int H, int W, const cs_local_params& lp,
+                        unsigned char* d_out, hipStream_t st)
+{
+    const int HW = H * W, r = lp.radius, TR = bg_col_rows(r);
+    int rc;
+    if ((rc = S.lt_sum.ensure((size_t)batch * HW * sizeof(unsigned int)))) return rc;
+    const PIX* x = d_img + ch;                          // both sides of the comparison read this
+    size_t x_img = (size_t)HW * C;
+    int x_pix = C;
+    HIPCHK(hipEventRecord(S.lev[0], st));
+    S.lt_median = lp.median != 0;
+    if (lp.median) {
+        if ((rc = S.lt_med.ensure((size_t)batch * HW * sizeof(PIX)))) return rc;
+        hipLaunchKernelGGL(bg_median<PIX>, dim3((unsigned)((HW + SG_CHUNK - 1) / SG_CHUNK), (unsigned)batch), dim3(SG_THREADS), 0, st, d_img, C,
+                           ch, H, W, S.lt_med.as<PIX>());
+        HIPCHK(hipGetLastError());
+        x = S.lt_med.as<PIX>();
+        x_img = (size_t)HW;
+        x_pix = 1;
+    }
+    HIPCHK(hipEventRecord(S.lev[1], st));
+    const dim3 rgrid((unsigned)((W + LT_ROW_SEG - 1) / LT_ROW_SEG), (unsigned)((H + LT_ROW_LINES - 1) / LT_ROW_LINES), (unsigned)batch);
+    const dim3 cgrid((unsigned)((W + LT_COL_W - 1) / LT_COL_W), (unsigned)((H + LT_COL_TILES * TR - 1) / (LT_COL_TILES * TR)), (unsigned)batch);
+    const long long n = (long long)(2 * r + 1) * (2 * r + 1);
+    hipLaunchKernelGGL(lt_rows<PIX>, rgrid, dim3(SG_THREADS), 0, st, x, x_img, x_pix, H, W, r, S.lt_sum.as<unsigned int>());
+    hipLaunchKernelGGL(lt_cols<PIX>, cgrid, dim3(SG_THREADS), 0, st, (const unsigned int*)S.lt_sum.as<unsigned int>(), x, x_img, x_pix, H, W, r,
+                       TR, n, n * lp.delta, (int)lp.floor, d_out);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(S.lev[2], st));
+    return CS_OK;
+}
+
+static int local_times(SegmentState& S)
+{
+    float ms = 0.f;
+    HIPCHK(hipEventSynchronize(S.lev[2]));
+    S.lt_pending = false;
+    HIPCHK(hipEventElapsedTime(&ms, S.lev[0], S.lev[1]));
+    S.lt_median_ms = S.lt_median ? ms : 0.0;            // without it the two records are back to back
+    HIPCHK(hipEventElapsedTime(&ms, S.lev[1], S.lev[2]));
+    S.lt_sum_ms = ms;
     return CS_OK;
 }
 
@@ -1392,5 +1550,76 @@ int cs_segment_background_last_timing(const cs_preproc* p, double* median_ms, do
     }
     if (median_ms) *median_ms = S ? S->bg_median_ms : 0.0;
     if (tophat_ms) *tophat_ms = S ? S->bg_tophat_ms : 0.0;
+    return CS_OK;
+}
+
+int cs_segment_local(cs_preproc* p, const void* image, int pixel_type, int32_t channels, int32_t channel, int32_t batch, int32_t height,
+                     int32_t width, int in_kind, const cs_local_params* params, uint8_t* out, int out_kind)
+{
+    if (!image || !params || !out) return fail(CS_ERR_INVALID, "NULL argument");
+    if (pixel_type != CS_PIX_U8 && pixel_type != CS_PIX_U16) return fail(CS_ERR_INVALID, "pixel_type must be CS_PIX_U8 or CS_PIX_U16");
+    if ((in_kind != CS_MEM_HOST && in_kind != CS_MEM_DEVICE) || (out_kind != CS_MEM_HOST && out_kind != CS_MEM_DEVICE))
+        return fail(CS_ERR_INVALID, "in_kind / out_kind must be CS_MEM_HOST or CS_MEM_DEVICE");
+    if (channels < 1 || channel < 0 || channel >= channels)
+        return fail(CS_ERR_INVALID, "channel %d of %d: need 0 <= channel < channels", (int)channel, (int)channels);
+    if (batch < 1 || height < 1 || width < 1) return fail(CS_ERR_INVALID, "batch %d, height %d, width %d: all must be >= 1", (int)batch,
+                                                          (int)height, (int)width);
+    if (params->radius < 1 || params->radius > LT_MAX_R) return fail(CS_ERR_INVALID, "local radius %d outside 1..%d", (int)params->radius, LT_MAX_R);
+    if (params->delta < -65535 || params->delta > 65535) return fail(CS_ERR_INVALID, "local delta %d outside -65535..65535", (int)params->delta);
+    if (params->floor < -1 || params->floor > 65535) return fail(CS_ERR_INVALID, "local floor %d outside -1..65535", (int)params->floor);
+    if (params->median != 0 && params->median != 1) return fail(CS_ERR_INVALID, "median %d: 0 or 1", (int)params->median);
+    if (height > kSegMaxSide || width > kSegMaxSide)
+        return fail(CS_ERR_UNSUPPORTED, "image %dx%d: sides above %d are not supported", (int)height, (int)width, kSegMaxSide);
+    if (batch > kSegMaxBatch) return fail(CS_ERR_UNSUPPORTED, "batch %d: at most %d images per call", (int)batch, kSegMaxBatch);
+    if (!p) {
+        const int rc = require_gfx950(0);
+        return rc ? rc : fail(CS_ERR_INVALID, "handle is NULL");
+    }
+    HIPCHK(hipSetDevice(p->device));
+    if (!p->seg) p->seg = new SegmentState();
+    SegmentState& S = *p->seg;
+    for (hipEvent_t& e : S.lev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    hipStream_t st = p->stream;
+    const size_t esz = pixel_type == CS_PIX_U8 ? 1 : 2;
+    const size_t npx = (size_t)batch * height * width;
+    int rc;
+    const void* d_img = image;
+    if (in_kind == CS_MEM_HOST) {
+        if ((rc = S.lt_in.ensure(npx * channels * esz))) return rc;
+        HIPCHK(hipMemcpyAsync(S.lt_in.p, image, npx * channels * esz, hipMemcpyHostToDevice, st));
+        d_img = S.lt_in.p;
+    }
+    unsigned char* d_out = out;
+    if (out_kind == CS_MEM_HOST) {
+        if ((rc = S.lt_out.ensure(npx))) return rc;
+        d_out = S.lt_out.as<unsigned char>();
+    }
+    S.lt_pending = false;
+    if (pixel_type == CS_PIX_U8)
+        rc = local_launch<unsigned char>(S, (const unsigned char*)d_img, channels, channel, batch, height, width, *params, d_out, st);
+    else
+        rc = local_launch<unsigned short>(S, (const unsigned short*)d_img, channels, channel, batch, height, width, *params, d_out, st);
+    if (rc) return rc;
+    if (out_kind == CS_MEM_DEVICE && in_kind == CS_MEM_DEVICE) {
+        S.lt_pending = true;                            // no host synchronisation: the times are read when they are asked for
+        return CS_OK;
+    }
+    if (out_kind == CS_MEM_HOST) HIPCHK(hipMemcpyAsync(out, d_out, npx, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));                     // the one host synchronisation: the caller's host buffers are free / filled
+    return local_times(S);
+}
+
+int cs_segment_local_last_timing(const cs_preproc* p, double* median_ms, double* sum_ms)
+{
+    if (!p) return fail(CS_ERR_INVALID, "handle is NULL");
+    SegmentState* S = p->seg;
+    if (S && S->lt_pending) {
+        HIPCHK(hipSetDevice(p->device));
+        const int rc = local_times(*S);
+        if (rc) return rc;
+    }
+    if (median_ms) *median_ms = S ? S->lt_median_ms : 0.0;
+    if (sum_ms) *sum_ms = S ? S->lt_sum_ms : 0.0;
     return CS_OK;
 }

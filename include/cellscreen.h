@@ -483,6 +483,44 @@ int cs_segment_background(cs_preproc *p, const void *image, int pixel_type, int3
  * that call's plane if it was left on the device. */
 int cs_segment_background_last_timing(const cs_preproc *p, double *median_ms, double *tophat_ms);
 
+/* Local mean threshold: a mask from each pixel's own neighbourhood instead of one global number, for fields that hold bright
+ * and dim cells side by side (Otsu settles between the background and the bright population, and the dim cells fall under
+ * it; the top-hat above removes an additive background, not a difference in brightness).  Integers only, each image on its own:
+ *   median  (optional) the 3 x 3 median of cs_segment_background first; both sides of the comparison then see its plane.
+ *   S(i,j)  the sum of x over the window [i - r, i + r] x [j - r, j + r] (side w = 2 * radius + 1, n = w * w pixels), indices
+ *           outside the image reflected about the edge (d c b a | a b c d: scipy's mode='reflect', numpy.pad's 'symmetric',
+ *           period 2 * side, so radius may exceed a side).
+ *   out     1 where n * x - S - n * delta > 0 and x > floor, else 0 (64-bit arithmetic: n * x reaches 1.7e10).
+ * This is x > skimage.filters.threshold_local(x, w, method='mean', offset=-delta), decided exactly.  The one deliberate
+ * difference: where n * (x - delta) = S the pixel is background, while the library's float64 mean may fall on either side of
+ * such a tie.  Everywhere else the two agree (the mean's rounding error is far below the smallest non-zero gap, 1 / n).
+ * The window must be wider than the widest cell (as the top-hat's square), or a cell's core sits near its own mean and drops
+ * out.  Noise on empty background passes a small delta as speckle: a delta of a few noise sigmas and median = 1 keep it down.
+ * image, pixel_type, channels, channel, batch, height, width, in_kind: as cs_segment_threshold; the channel is read in place.
+ *      The output of cs_segment_background is a valid image (channels = 1, channel = 0): the local rule after the top-hat.
+ * out: [batch][height][width] uint8, out_kind.  Left on the device it is cs_segment_threshold's or cs_segment_split's `image`
+ *      with pixel_type CS_PIX_U8, channels = 1, channel = 0, CS_THRESH_FIXED and threshold = 0, on the same handle (the same
+ *      stream: no ordering needed); hole filling, labels and the split follow unchanged.
+ * Workspace on the device: 4 bytes per pixel (the row sums), one plane of the pixel type more with the median (1 or 2 bytes
+ * per pixel), 1 byte per pixel for an `out` on the host, and the image itself when it comes from the host.
+ * Host synchronisations: none when image and out are both on the device (the plane is complete in stream order; the times
+ * are read when cs_segment_local_last_timing asks for them, which waits for the plane), else one.
+ * Bad arguments (NULL params among them, radius outside 1..255, delta outside -65535..65535, floor outside -1..65535, median
+ * not 0 or 1): CS_ERR_INVALID before any device work; sides above 4096, batches above 65535: CS_ERR_UNSUPPORTED; without a
+ * gfx950 device (p == NULL): CS_ERR_NO_DEVICE. */
+typedef struct cs_local_params {
+    int32_t radius;                   /* 1..255: the window has side 2 * radius + 1 */
+    int32_t delta;                    /* -65535..65535: counts above the local mean */
+    int32_t floor;                    /* -1..65535: pixel > floor as well; -1 = off */
+    int32_t median;                   /* 0 or 1: 3 x 3 median first */
+} cs_local_params;
+int cs_segment_local(cs_preproc *p, const void *image, int pixel_type, int32_t channels, int32_t channel,
+                     int32_t batch, int32_t height, int32_t width, int in_kind,
+                     const cs_local_params *params /* not NULL */, uint8_t *out, int out_kind);
+/* Device time of the last cs_segment_local: the median (0 without it), and the two sum passes with the comparison.  Waits for
+ * that call's plane if it was left on the device. */
+int cs_segment_local_last_timing(const cs_preproc *p, double *median_ms, double *sum_ms);
+
 /* ---- detector fitting (create_anomaly_detector, CAE_improved_modeltrain.py:394-446) -------- */
 /* The fit of what cs_screen's tail evaluates, for the training set's encoder features
  * (cs_encode output, [n][n_features] fp32, host or device).  Own handle, own stream.

@@ -24,8 +24,15 @@ host restatement (tests/background_reference.py) first; then the images/s of the
 the same run, their ratio, and the two new stage times (median, top-hat) at R and at the radii 8, 32 and 128 side by side,
 which show whether the cost is flat in the radius.  No time is a pass condition.
 
+--local R [--delta D] [--denoise] measures the local mean threshold (cs_segment_local, ThresholdSegmenter(threshold="local",
+local_radius=R, local_delta=D)) in its place and writes profiles/segment_local_bench.json: one image's mask and labels are
+compared with the host restatement (tests/local_reference.py) first; then, in the same run, the images/s of the plain Otsu
+segmenter, of the segmenter with the top-hat of radius 51 (--background 51's figure) and of the local segmenter, the stage times
+of each, and the local stage's time as a ratio to the top-hat's.  No time is a pass condition.
+
 Usage: python tools/bench_segment.py [--images 32] [--side 2048] [--cells 1000] [--reps 10] [--warmup 2] [--host-images 4]
-                                     [--split [--split-cells 3000] [--split-h 3]] [--background R [--denoise]]"""
+                                     [--split [--split-cells 3000] [--split-h 3]] [--background R [--denoise]]
+                                     [--local R [--delta D] [--denoise]]"""
 import argparse
 import json
 import os
@@ -173,7 +180,84 @@ def background_leg(a):
     print(line)
 
 
+def local_leg(a):
+    import torch
+    import local_reference as LR
+    from build import source_hash
+    from cellscreen import segment as S
+    from cellscreen import synth
+
+    fill = not a.no_fill_holes
+    dev = torch.device("cuda", 0)
+    med = lambda v: float(np.median(v))
+    imgs, _ = synth.label_images(2024, a.images, hw=(a.side, a.side), n_cells=a.cells)
+    ti = torch.from_numpy(imgs.view(np.int16)).to(dev)
+    torch.cuda.synchronize()
+
+    def timed(seg, fn):
+        walls, stages = [], []
+        for k in range(a.warmup + a.reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = fn(seg)
+            torch.cuda.synchronize()
+            if k >= a.warmup:
+                walls.append(time.perf_counter() - t0)
+                stages.append(seg.last_timing())
+        return out, walls, stages
+
+    spread = lambda stages, k: [round(med([t[k] for t in stages]), 4), round(min(t[k] for t in stages), 4),
+                                round(max(t[k] for t in stages), 4)]
+    wall3 = lambda walls: [round(med(walls) * 1e3, 3), round(min(walls) * 1e3, 3), round(max(walls) * 1e3, 3)]
+    res = {"tool": "bench_segment --local", "source_hash": source_hash(), "images": a.images, "side": a.side,
+           "connectivity": a.connectivity, "fill_holes": fill, "local_radius": a.local, "local_delta": a.delta,
+           "denoise": bool(a.denoise), "reps": a.reps, "warmup": a.warmup}
+
+    plain = S.ThresholdSegmenter(0, "otsu", a.connectivity, fill)
+    (_, n_plain, _), plain_walls, plain_stages = timed(plain, lambda s: s.segment_batch(ti))
+    plain.close()
+    res["otsu"] = {"components": int(n_plain.sum()), "images_per_s": round(a.images / med(plain_walls), 2), "wall_ms": wall3(plain_walls),
+                   "threshold_ms": spread(plain_stages, "threshold_ms"), "label_ms": spread(plain_stages, "label_ms")}
+
+    tophat = S.ThresholdSegmenter(0, "otsu", a.connectivity, fill, background_radius=TOPHAT_RADIUS)
+    (_, n_top, _), top_walls, top_stages = timed(tophat, lambda s: s.segment_batch(ti))
+    tophat.close()
+    res["background"] = {"radius": TOPHAT_RADIUS, "components": int(n_top.sum()), "images_per_s": round(a.images / med(top_walls), 2),
+                         "wall_ms": wall3(top_walls), "background_ms": spread(top_stages, "background_ms"),
+                         "threshold_ms": spread(top_stages, "threshold_ms"), "label_ms": spread(top_stages, "label_ms")}
+
+    seg = S.ThresholdSegmenter(0, "local", a.connectivity, fill, local_radius=a.local, local_delta=a.delta, denoise=a.denoise)
+    # outputs first: one image's mask and labels against the host restatement
+    one = ti[:1].contiguous()
+    mask = seg.local_mask_batch(one)
+    labels, n, thr = seg.segment_batch(one)
+    chan = np.ascontiguousarray(imgs[0, ..., 2])
+    assert np.array_equal(mask[0].cpu().numpy(), LR.local_mask(chan, a.local, a.delta, -1, a.denoise)), "mask differs from the restatement"
+    hl, hn, _ = LR.segment(chan, a.local, a.delta, -1, a.denoise, a.connectivity, fill)
+    assert hn == int(n[0]) and int(thr[0]) == -1 and np.array_equal(labels[0].cpu().numpy(), hl), "labels differ from the restatement"
+    (_, n_loc, _), walls, stages = timed(seg, lambda s: s.segment_batch(ti))
+    _, mask_walls, _ = timed(seg, lambda s: s.local_mask_batch(ti))
+    seg.close()
+    px = a.images * a.side * a.side
+    local_ms, top_ms = med([t["local_ms"] for t in stages]), med([t["background_ms"] for t in top_stages])
+    res["local"] = {"outputs_equal": True, "components": int(n_loc.sum()), "images_per_s": round(a.images / med(walls), 2),
+                    "wall_ms": wall3(walls), "local_mask_batch_wall_ms": wall3(mask_walls),
+                    "local_median_ms": spread(stages, "local_median_ms"), "local_ms": spread(stages, "local_ms"),
+                    "threshold_ms": spread(stages, "threshold_ms"), "label_ms": spread(stages, "label_ms"),
+                    "local_ns_per_pixel": round(local_ms * 1e6 / px, 4)}
+    res["local_over_tophat_stage_time"] = round(local_ms / top_ms, 3)
+    res["local_over_otsu_wall_time"] = round(med(walls) / med(plain_walls), 3)
+    line = json.dumps(res)
+    out = a.out if a.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "segment_local_bench.json")
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            f.write(line + "\n")
+    print(line)
+
+
 DEFAULT_OUT = os.path.join(ROOT, "profiles", "segment_bench.json")
+TOPHAT_RADIUS = 51                                      # the top-hat that --local is set beside: --background 51's figure
 
 
 def main():
@@ -192,14 +276,23 @@ def main():
     ap.add_argument("--split-h", type=int, default=3)
     ap.add_argument("--background", type=int, default=None, metavar="R",
                     help="measure the background correction of radius R (profiles/segment_background_bench.json)")
-    ap.add_argument("--denoise", action="store_true", help="with --background: the 3 x 3 median first")
+    ap.add_argument("--denoise", action="store_true", help="with --background or --local: the 3 x 3 median first")
+    ap.add_argument("--local", type=int, default=None, metavar="R",
+                    help="measure the local mean threshold of radius R (profiles/segment_local_bench.json)")
+    ap.add_argument("--delta", type=int, default=0, metavar="D", help="with --local: counts above the local mean")
     a = ap.parse_args()
-    if a.denoise and a.background is None:
-        ap.error("--denoise needs --background R")
+    if a.denoise and a.background is None and a.local is None:
+        ap.error("--denoise needs --background R or --local R")
+    if a.delta and a.local is None:
+        ap.error("--delta needs --local R")
+    if a.local is not None and (a.split or a.background is not None):
+        ap.error("--local is measured on its own")
     if a.split:
         return split_leg(a)
     if a.background is not None:
         return background_leg(a)
+    if a.local is not None:
+        return local_leg(a)
 
     import torch
     import segment_reference as R
