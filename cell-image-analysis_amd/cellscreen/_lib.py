@@ -116,6 +116,10 @@ class CSLocalParams(C.Structure):
     _fields_ = [("radius", C.c_int32), ("delta", C.c_int32), ("floor", C.c_int32), ("median", C.c_int32)]
 
 
+class CSCleanParams(C.Structure):
+    _fields_ = [("open_radius", C.c_int32), ("open_connectivity", C.c_int32), ("min_area", C.c_int32)]
+
+
 # cs_region of include/cellscreen.h as a numpy record (80 bytes)
 REGION_DTYPE = np.dtype([("image", np.int32), ("label", np.int32), ("minr", np.int32), ("minc", np.int32), ("maxr", np.int32),
                          ("maxc", np.int32), ("area", np.int64), ("convex_area", np.int64), ("eccentricity", np.float64),
@@ -166,6 +170,9 @@ SIGNATURES = {
     "cs_segment_background_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "cs_segment_local": (_I, [_P, _P, _I, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _I, C.POINTER(CSLocalParams), _P, _I]),
     "cs_segment_local_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "cs_segment_clean": (_I, [_P, _P, _I, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _I, C.POINTER(CSSegmentParams),
+                              C.POINTER(CSCleanParams), _P, _I, _P]),
+    "cs_segment_clean_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "cs_fit_create": (_I, [_I, C.POINTER(_P)]),
     "cs_fit_free": (None, [_P]),
     "cs_fit_wait_stream": (_I, [_P, _P]),

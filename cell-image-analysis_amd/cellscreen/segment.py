@@ -27,16 +27,25 @@ foreground is  n * x - S - n * local_delta > 0  and  x > local_floor, S the wind
 edges, n = (2r + 1)^2.  That is x > skimage.filters.threshold_local(x, 2r + 1, method='mean', offset=-local_delta) decided in
 integers; the one difference is an exact tie, n * (x - local_delta) = S, which is background here while the library's float64
 mean may fall on either side.  The window must be wider than the widest cell, as the top-hat's square, or a cell's core sits
-near its own mean and drops out.  Noise on empty background passes a small local_delta as speckle: the extraction's area rule
-drops it, but the label count rises towards the extraction's limit (batch * max_label <= 2^22); denoise=True and a
-local_delta of a few noise sigmas keep it down.  The mask feeds the same hole filling, labelling and split; with
-background_radius the local rule runs on the corrected plane.
+near its own mean and drops out.  Noise on empty background passes a small local_delta as speckle: hundreds of regions of a
+few pixels per field, each labelled, numbered and measured before the extraction's area rule drops it, and the label count
+rises towards the extraction's limit (batch * max_label <= 2^22).  min_area (below) removes them before the labelling;
+denoise=True and a local_delta of a few noise sigmas make fewer of them.  The mask feeds the same hole filling, labelling and
+split; with background_radius the local rule runs on the corrected plane.
+
+Mask cleanup, between the hole filling and the labels (cs_segment_clean; tests/clean_reference.py restates it), off by default:
+open_radius=r (1..15) opens the mask, r erosions then r dilations by the 3 x 3 square (open_connectivity=2, the default) or
+cross (1), which is scipy.ndimage.binary_opening(mask, generate_binary_structure(2, k), iterations=r) bit for bit: speckle and
+bridges thinner than 2r + 1 pixels go, and the square rounds a disk's diagonal edge by about 0.4 * r px.  min_area=a then turns
+components (under the segmenter's connectivity) of fewer than a pixels into background, as
+skimage.morphology.remove_small_objects(mask, min_size=a) does.  The labels, the split and the distances see the cleaned mask.
 
     seg = ThresholdSegmenter()
     labels, n_labels, thresholds = seg.segment_batch(images)          # numpy in, numpy out; CUDA tensors in, CUDA tensor out
     seg = ThresholdSegmenter(split_touching=True)                      # the same, touching cells apart
     seg = ThresholdSegmenter(background_radius=51)                     # uneven illumination flattened before the threshold
     seg = ThresholdSegmenter(threshold="local", local_radius=25, local_delta=60)      # bright and dim cells in one field
+    seg = ThresholdSegmenter(threshold="local", local_radius=25, local_delta=40, min_area=50)         # ... without the speckle
 
     screening = ProductionMutantScreening(model_dir, cell_extractor=threshold_cell_extractor())
 """
@@ -130,6 +139,30 @@ def local_params(local_radius=None, local_delta: int = 0, local_floor: int = -1,
     return p
 
 
+MAX_OPEN_RADIUS, MAX_MIN_AREA = 15, 1 << 24
+
+
+def clean_params(open_radius=None, open_connectivity: int = 2, min_area=None) -> Optional[L.CSCleanParams]:
+    """cs_clean_params from the Python arguments, None with neither step (no cleanup); anything out of range raises before a
+    handle exists.  open_connectivity is checked also without open_radius: alone it is a default, not a request."""
+    for name, v in (("open_radius", open_radius), ("min_area", min_area)):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, (int, np.integer))):
+            raise TypeError(f"{name} must be None or an integer, got {type(v).__name__}")
+    if isinstance(open_connectivity, bool) or not isinstance(open_connectivity, (int, np.integer)):
+        raise TypeError(f"open_connectivity must be 1 (cross) or 2 (square), got {type(open_connectivity).__name__}")
+    if open_connectivity not in (1, 2):
+        raise ValueError(f"open_connectivity must be 1 (cross) or 2 (square), got {open_connectivity!r}")
+    if open_radius is not None and not 1 <= int(open_radius) <= MAX_OPEN_RADIUS:
+        raise ValueError(f"open_radius {open_radius} outside 1..{MAX_OPEN_RADIUS}")
+    if min_area is not None and not 1 <= int(min_area) <= MAX_MIN_AREA:
+        raise ValueError(f"min_area {min_area} outside 1..{MAX_MIN_AREA}")
+    if open_radius is None and min_area is None:
+        return None
+    p = L.CSCleanParams()
+    p.open_radius, p.open_connectivity, p.min_area = int(open_radius or 0), int(open_connectivity), int(min_area or 0)
+    return p
+
+
 def _threshold_mode(threshold, connectivity, fill_holes, local_radius, local_delta, local_floor, background_radius, denoise):
     """(cs_segment_params, cs_local_params or None, cs_background_params or None) of a segmenter's arguments.  In local mode the
     labelling sees a 0 / 1 plane, so its parameters are a fixed threshold of 0; the median runs once: inside the correction
@@ -157,15 +190,24 @@ class ThresholdSegmenter:
     threshold="local": the local mean threshold of the module text in the global one's place, with local_radius (1..255,
     required), local_delta (counts above the local mean, -65535..65535) and local_floor (pixel > local_floor as well; -1:
     off); these three belong to "local" alone.  denoise then needs no background_radius: the median runs before the sums.  The
-    thresholds it reports are -1: there is no single number.  With numpy input the mask makes one more round trip."""
+    thresholds it reports are -1: there is no single number.  With numpy input the mask makes one more round trip.
+    open_radius (None or 1..15), open_connectivity (1 cross, 2 square) and min_area (None or 1..2^24): the mask cleanup of the
+    module text, after the hole filling; the labels and the split then see the cleaned mask.  With numpy input the cleaned
+    mask makes one more round trip."""
 
     def __init__(self, device_id: int = 0, threshold="otsu", connectivity: int = 1, fill_holes: bool = True,
                  extractor: Optional[CellExtractor] = None, split_touching: bool = False, split_h: int = 3,
                  background_radius: Optional[int] = None, denoise: bool = False, local_radius: Optional[int] = None,
-                 local_delta: int = 0, local_floor: int = -1):
+                 local_delta: int = 0, local_floor: int = -1, open_radius: Optional[int] = None, open_connectivity: int = 2,
+                 min_area: Optional[int] = None):
         self._params, self._local, self._background = _threshold_mode(threshold, connectivity, fill_holes, local_radius, local_delta,
                                                                       local_floor, background_radius, denoise)
         self._split = split_params(split_touching, split_h)
+        self._clean = clean_params(open_radius, open_connectivity, min_area)
+        # what labels the cleaned 0 / 1 plane: the fixed threshold 0 and no second hole filling
+        self._after_clean = segment_params(0, connectivity, False)
+        self.open_radius, self.open_connectivity, self.min_area = (None if open_radius is None else int(open_radius)), \
+            int(open_connectivity), (None if min_area is None else int(min_area))
         self.local_radius, self.local_delta, self.local_floor = (None if local_radius is None else int(local_radius)), int(local_delta), \
             int(local_floor)
         self.background_radius, self.denoise = (None if background_radius is None else int(background_radius)), bool(denoise)
@@ -303,6 +345,44 @@ class ThresholdSegmenter:
             self._local_timing()                                    # reads the times, which waits for the plane: torch may use it
         return mask
 
+    def _clean_mask(self, images, B, H, W, Cn, channel, ptype, on_dev, thresholds=None):
+        """The cleaned 0 / 1 plane [B,H,W] uint8 where the images are; a device plane is complete in the handle's stream order
+        only.  thresholds: an int32 [B] array for the thresholds of the mask, which costs a device plane its one wait."""
+        if on_dev:
+            import torch
+            mask = torch.empty((B, H, W), dtype=torch.uint8, device=images.device)
+            L.order_after_torch(self._lib.cs_preproc_wait_stream, self._handle, images, mask)
+        else:
+            mask = np.empty((B, H, W), np.uint8)
+        kind = L.CS_MEM_DEVICE if on_dev else L.CS_MEM_HOST
+        L.check(self._lib.cs_segment_clean(self._handle, L._ptr(images), ptype, Cn, channel, B, H, W, kind, C.byref(self._params),
+                                           C.byref(self._clean), L._ptr(mask), kind,
+                                           None if thresholds is None else thresholds.ctypes.data))
+        return mask
+
+    def _clean_timing(self):
+        v = [C.c_double() for _ in range(3)]
+        L.check(self._lib.cs_segment_clean_last_timing(self._handle, *(C.byref(x) for x in v)))
+        return {"open_ms": v[1].value, "min_area_ms": v[2].value}
+
+    def clean_mask_batch(self, images, channel: Optional[int] = None):
+        """The cleaned mask that segment_batch labels: [B,H,W] uint8, 1 = foreground, numpy for numpy input, a CUDA tensor for
+        tensor input (complete when this returns).  Needs open_radius or min_area; with background_radius and threshold="local"
+        it is the cleaned mask of what they make."""
+        B, H, W, Cn, channel, ptype, on_dev = self._check(images, channel)
+        if self._clean is None:
+            raise ValueError("clean_mask_batch needs open_radius or min_area: this segmenter cleans nothing")
+        if self._background is not None:
+            images = self._correct(images, B, H, W, Cn, channel, ptype, on_dev)
+            Cn, channel = 1, 0
+        if self._local is not None:
+            images = self._local_mask(images, B, H, W, Cn, channel, ptype, on_dev)
+            Cn, channel, ptype = 1, 0, PIX_U8
+        mask = self._clean_mask(images, B, H, W, Cn, channel, ptype, on_dev)
+        if on_dev:
+            self._clean_timing()                                    # reads the times, which waits for the plane: torch may use it
+        return mask
+
     def segment_batch(self, images, channel: Optional[int] = None, return_distance: bool = False):
         """images: [B,H,W] or [B,H,W,C] uint8 / uint16, numpy or CUDA tensors of the segmenter's device; the channel that is
         segmented is `channel` (default 2 of >= 3 channels as improved_detection.py:55, 0 of one).
@@ -324,6 +404,16 @@ class ThresholdSegmenter:
             Cn, channel, ptype = 1, 0, PIX_U8
         n_labels = np.zeros(B, np.int32)
         thresholds = np.zeros(B, np.int32)
+        params, reported = self._params, None
+        if self._clean is not None:
+            # the cleaned 0 / 1 plane in the channel's place, cut at the fixed threshold 0 and not filled again; the thresholds
+            # are the cleanup's (Otsu's are computed there; a fixed one and local mode's -1 need no reading)
+            reported = np.zeros(B, np.int32)
+            otsu = self._params.threshold_mode == L.THRESH_OTSU
+            images = self._clean_mask(images, B, H, W, Cn, channel, ptype, on_dev, reported if otsu else None)
+            if not otsu:
+                reported[:] = self._params.threshold
+            Cn, channel, ptype, params = 1, 0, PIX_U8, self._after_clean
         if on_dev:
             import torch
             labels = torch.empty((B, H, W), dtype=torch.int32, device=images.device)
@@ -333,8 +423,10 @@ class ThresholdSegmenter:
         kind = L.CS_MEM_DEVICE if on_dev else L.CS_MEM_HOST
         if self._split is None:
             L.check(self._lib.cs_segment_threshold(self._handle, L._ptr(images), ptype, Cn, channel, B, H, W, kind,
-                                                   C.byref(self._params), L._ptr(labels), kind, n_labels.ctypes.data,
+                                                   C.byref(params), L._ptr(labels), kind, n_labels.ctypes.data,
                                                    thresholds.ctypes.data))
+            if reported is not None:
+                thresholds = reported
             if self._local is not None:
                 thresholds[:] = -1                                  # no single number
             return labels, n_labels, thresholds
@@ -345,9 +437,11 @@ class ThresholdSegmenter:
                 L.order_after_torch(self._lib.cs_preproc_wait_stream, self._handle, dist)
             else:
                 dist = np.empty((B, H, W), np.uint8)
-        L.check(self._lib.cs_segment_split(self._handle, L._ptr(images), ptype, Cn, channel, B, H, W, kind, C.byref(self._params),
+        L.check(self._lib.cs_segment_split(self._handle, L._ptr(images), ptype, Cn, channel, B, H, W, kind, C.byref(params),
                                            C.byref(self._split), L._ptr(labels), kind, n_labels.ctypes.data,
                                            thresholds.ctypes.data, L._ptr(dist)))
+        if reported is not None:
+            thresholds = reported
         if self._local is not None:
             thresholds[:] = -1
         return (labels, n_labels, thresholds, dist) if return_distance else (labels, n_labels, thresholds)
@@ -355,10 +449,14 @@ class ThresholdSegmenter:
     def last_timing(self):
         """Device milliseconds of the last call's stages; with split_touching the stages of cs_segment_split; with
         background_radius also median_ms and background_ms (the top-hat) of the last correction; with threshold="local" also
-        local_median_ms and local_ms (the sums and the comparison) of the last mask."""
+        local_median_ms and local_ms (the sums and the comparison) of the last mask; with open_radius or min_area also open_ms
+        and min_area_ms of the last cleanup (0 for a step that is off), and threshold_ms is then the labelling call's cut of the
+        cleaned plane."""
         extra = self._background_timing() if self._background is not None else {}
         if self._local is not None:
             extra.update(self._local_timing())
+        if self._clean is not None:
+            extra.update(self._clean_timing())
         if self._split is None:
             a, b = C.c_double(), C.c_double()
             L.check(self._lib.cs_segment_last_timing(self._handle, C.byref(a), C.byref(b)))
@@ -371,17 +469,21 @@ class ThresholdSegmenter:
 def threshold_cell_extractor(device_id: int = 0, out_hw=(OUT_SIDE, OUT_SIDE), threshold="otsu", connectivity: int = 1,
                              fill_holes: bool = True, split_touching: bool = False, split_h: int = 3,
                              background_radius: Optional[int] = None, denoise: bool = False, local_radius: Optional[int] = None,
-                             local_delta: int = 0, local_floor: int = -1, **qc):
+                             local_delta: int = 0, local_floor: int = -1, open_radius: Optional[int] = None,
+                             open_connectivity: int = 2, mask_min_area: Optional[int] = None, **qc):
     """The `cell_extractor(image_path) -> (cells, stats)` that ProductionMutantScreening and create_training_dataset accept,
     with the built-in segmenter in StarDist's place: the file is read (extract.read_image / split_channels), uploaded once,
     segmented and extracted on one handle, and the labels never leave the device.  Not StarDist: see the module text.
     Errors raise as label_cell_extractor's do; the screening driver's try turns them into the reference's "Error processing"
     line and ([], []).  out_hw and **qc as for label_cell_extractor; split_touching, split_h, background_radius and denoise as
     for ThresholdSegmenter, and threshold="local" with local_radius, local_delta and local_floor too: with background_radius the segmentation channel is corrected before the threshold, while the
-    extraction still reads the raw analysis channel, so the intensity rules and the crops are what they are without it."""
+    extraction still reads the raw analysis channel, so the intensity rules and the crops are what they are without it.
+    open_radius and open_connectivity as for ThresholdSegmenter, and mask_min_area for its min_area: the mask cleanup before
+    the labels.  The name differs here because min_area is, and stays, the extraction's own area rule among **qc."""
     out_hw = check_out_hw(out_hw)
     _threshold_mode(threshold, connectivity, fill_holes, local_radius, local_delta, local_floor, background_radius, denoise)
     split_params(split_touching, split_h)
+    clean_params(open_radius, open_connectivity, mask_min_area)
     qc_params(**qc)
     st = {}
 
@@ -397,7 +499,8 @@ def threshold_cell_extractor(device_id: int = 0, out_hw=(OUT_SIDE, OUT_SIDE), th
             st["s"] = ThresholdSegmenter(device_id, threshold, connectivity, fill_holes, extractor=st["x"],
                                          split_touching=split_touching, split_h=split_h, background_radius=background_radius,
                                          denoise=denoise, local_radius=local_radius, local_delta=local_delta,
-                                         local_floor=local_floor)
+                                         local_floor=local_floor, open_radius=open_radius, open_connectivity=open_connectivity,
+                                         min_area=mask_min_area)
         host = np.ascontiguousarray(img)[None]
         dev = torch.from_numpy(host.view(np.int16) if host.dtype == np.uint16 else host).to(torch.device("cuda", device_id))
         labels, _, _ = st["s"].segment_batch(dev, channel=seg_ch)

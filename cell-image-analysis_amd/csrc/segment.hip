@@ -24,6 +24,10 @@
 //   sp_*         cs_segment_split only: see "split_touching" further down.
 //   bg_*         cs_segment_background only: the optional correction of the channel BEFORE all of the above (3x3 median, white
 //                top-hat); see "background correction" further down.  Its plane then stands in the channel's place.
+//   lt_*         cs_segment_local only: the local mean threshold in the global one's place; see "local mean threshold".
+//   cl_*         cs_segment_clean only: the optional cleanup of the mask BEFORE the labelling (binary opening on a bit-packed
+//                tile in LDS, minimum area by pixel counts per union-find root); see "mask cleanup" further down.  Its plane
+//                then stands in the channel's place, cut at the fixed threshold 0.
 // The final parents are a function of the mask alone (the minimum index of a component), so the labels do not depend on
 // execution order, on the run, or on the other images of the batch.
 #include "api_internal.hpp"
@@ -1055,15 +1059,151 @@ __global__ __launch_bounds__(SG_THREADS) void lt_cols(const unsigned int* __rest
     }
 }
 
+// ---- mask cleanup (cs_segment_clean): binary opening, minimum area -------------------------------------------------------------
+// Between the hole filling and the labelling, on the 0 / 1 mask alone (tests/clean_reference.py restates it):
+//   opening   r erosions then r dilations by the 3 x 3 cross (connectivity 1) or square (2), outside the image background for
+//             the erosion: scipy.ndimage.binary_opening(mask, generate_binary_structure(2, k), iterations=r).
+//   min area  components (under the segmenter's connectivity) of fewer than `a` pixels become background.
+//   cl_open   one workgroup opens a tile of 256 x 32 pixels.  The mask is packed one pixel per bit: a wave reads 64 consecutive
+//             bytes of a row and its ballot is the 64-bit word of that row segment (bit i = pixel x + i).  The tile sits in LDS
+//             with a halo of one word (64 >= 2r pixels) left and right and 2r rows above and below: r pixels for the erosion,
+//             r more for the dilation of what it leaves.  Pixels outside the image are loaded as 0, which is all the erosion's
+//             border rule needs; the dilation may grow into them, and nothing there finds a way back in that a path inside the
+//             image would not have (the structures are convex).  An elementary step is shifts, ANDs and ORs of a word, its two
+//             row neighbours and the carried-in bits of the words left and right, from one LDS buffer to the other; a frame of
+//             zero words around the two buffers stands for what is beyond them, and whatever creeps in from there moves one
+//             pixel per step and has 2r pixels to go.  The mask crosses HBM once each way however large r is.
+//   cl_count  pixels per component at the root's slot of a per-pixel int table: one atomicAdd per run of equal roots among the
+//             first rounds' leaders of a wave (a row segment inside one component is one add), as hist_add.  Integer sums do
+//             not depend on their order.
+//   cl_drop   out = 1 where the pixel's root counts at least `a`.
+// Components come from label_mask (tile union-find, border merge, flatten), so a component spread over many tiles is counted
+// as one.  Shifts, ANDs, ORs and integer adds only: the plane is a function of the mask alone.
+static constexpr int CL_MAX_R = 15;
+static constexpr int CL_MAX_AREA = 1 << 24;             // kSegMaxSide^2: no component is larger
+static constexpr int CL_TWW = 4, CL_TW = 64 * CL_TWW;   // words and pixels of a tile's row
+static constexpr int CL_TH = 32;                        // rows of a tile
+static constexpr int CL_LW = CL_TWW + 2;                // words of a row in LDS: the tile and one halo word on either side
+static constexpr int CL_SW = CL_LW + 2;                 // with the frame of zero words
+static constexpr int CL_ROWS = CL_TH + 4 * CL_MAX_R;    // rows in LDS at the largest radius
+static constexpr int CL_LOAD_U = 4;                     // row segments a wave loads before its first ballot
+
+// grid (ceil(W / CL_TW), ceil(H / CL_TH), B)
+__global__ __launch_bounds__(SG_THREADS) void cl_open(const unsigned char* __restrict__ mask, int H, int W, int r, int square,
+                                                      unsigned char* __restrict__ out)
+{
+    __shared__ unsigned long long buf[2][(CL_ROWS + 2) * CL_SW];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int x0 = blockIdx.x * CL_TW, y0 = blockIdx.y * CL_TH;
+    const int rows = CL_TH + 4 * r, nseg = rows * CL_LW;
+    const unsigned char* m = mask + (size_t)blockIdx.z * H * W;
+    for (int i = threadIdx.x; i < (rows + 2) * CL_SW; i += SG_THREADS) buf[0][i] = buf[1][i] = 0ull;        // the frame stays
+    __syncthreads();
+    for (int s0 = wave; s0 < nseg; s0 += SG_WAVES * CL_LOAD_U) {
+        unsigned char v[CL_LOAD_U];
+#pragma unroll
+        for (int u = 0; u < CL_LOAD_U; ++u) {
+            const int s = s0 + u * SG_WAVES;
+            const int y = y0 - 2 * r + s / CL_LW, x = x0 + (s % CL_LW - 1) * 64 + lane;
+            v[u] = s < nseg && y >= 0 && y < H && x >= 0 && x < W ? m[(size_t)y * W + x] : 0;
+        }
+#pragma unroll
+        for (int u = 0; u < CL_LOAD_U; ++u) {
+            const int s = s0 + u * SG_WAVES;
+            const unsigned long long bits = __ballot(v[u] != 0);
+            if (lane == 0 && s < nseg) buf[0][(s / CL_LW + 1) * CL_SW + s % CL_LW + 1] = bits;
+        }
+    }
+    __syncthreads();
+    int cur = 0;
+    for (int step = 0; step < 2 * r; ++step, cur ^= 1) {
+        const unsigned long long* a = buf[cur];
+        unsigned long long* b = buf[cur ^ 1];
+        const bool erode = step < r;
+        for (int s = threadIdx.x; s < nseg; s += SG_THREADS) {
+            const int c = (s / CL_LW + 1) * CL_SW + s % CL_LW + 1;
+            unsigned long long res;
+            if (square) {                               // the row's own 1 x 3 step on the three rows, then across them
+                unsigned long long h[3];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const int q = c + (k - 1) * CL_SW;
+                    const unsigned long long w = a[q], lt = (w << 1) | (a[q - 1] >> 63), rt = (w >> 1) | (a[q + 1] << 63);
+                    h[k] = erode ? (w & lt & rt) : (w | lt | rt);
+                }
+                res = erode ? (h[0] & h[1] & h[2]) : (h[0] | h[1] | h[2]);
+            } else {
+                const unsigned long long w = a[c], lt = (w << 1) | (a[c - 1] >> 63), rt = (w >> 1) | (a[c + 1] << 63);
+                const unsigned long long up = a[c - CL_SW], dn = a[c + CL_SW];
+                res = erode ? (w & lt & rt & up & dn) : (w | lt | rt | up | dn);
+            }
+            b[c] = res;
+        }
+        __syncthreads();
+    }
+    unsigned char* o = out + (size_t)blockIdx.z * H * W;
+    for (int s = wave; s < CL_TH * CL_TWW; s += SG_WAVES) {
+        const int ly = s / CL_TWW, lw = s % CL_TWW;
+        const int y = y0 + ly, x = x0 + lw * 64 + lane;
+        if (y >= H || x >= W) continue;
+        const unsigned long long w = buf[cur][(2 * r + ly + 1) * CL_SW + lw + 2];
+        o[(size_t)y * W + x] = (unsigned char)((w >> lane) & 1ull);
+    }
+}
+
+// grid (nchunks, B); cnt: [B][HW], zero before
+__global__ __launch_bounds__(SG_THREADS) void cl_count(int HW, const int* __restrict__ P, int* __restrict__ cnt)
+{
+    const size_t base = (size_t)blockIdx.y * HW;
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = blockIdx.x * SG_CHUNK + k * SG_THREADS + threadIdx.x;
+        const int root = i < HW ? P[base + i] : -1;
+        bool pend = root >= 0;
+#pragma unroll
+        for (int round = 0; round < 2; ++round) {
+            const unsigned long long m = __ballot(pend);
+            if (m == 0ull) break;
+            const int leader = __ffsll((long long)m) - 1;
+            const int rl = __shfl(root, leader);
+            const bool mine = pend && root == rl;
+            const unsigned long long mm = __ballot(mine);
+            if (lane == leader) atomicAdd(&cnt[base + rl], __popcll(mm));
+            if (mine) pend = false;
+        }
+        if (pend) atomicAdd(&cnt[base + root], 1);
+    }
+}
+
+// grid (nchunks, B); out may be the mask that P was made from
+__global__ __launch_bounds__(SG_THREADS) void cl_drop(int HW, const int* __restrict__ P, const int* __restrict__ cnt, int min_area,
+                                                      unsigned char* __restrict__ out)
+{
+    const size_t base = (size_t)blockIdx.y * HW;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = blockIdx.x * SG_CHUNK + k * SG_THREADS + threadIdx.x;
+        if (i >= HW) continue;
+        const int root = P[base + i];
+        out[base + i] = root >= 0 && cnt[base + root] >= min_area ? 1 : 0;
+    }
+}
+
 // ---- host state ---------------------------------------------------------------------------------------------------------------
 struct SegmentState {
     DevBuf img, lab, mask, parent, slab, hist, thr, chunks, counts;
     DevBuf dq, rec, key, ttop, ctrl;                    // cs_segment_split only
     DevBuf bg_in, bg_med, bg_a, bg_b, bg_out;           // cs_segment_background only: upload, median, two planes, host staging
     DevBuf lt_in, lt_med, lt_sum, lt_out;               // cs_segment_local only: upload, median, row sums, host staging
+    DevBuf cl_out;                                      // cs_segment_clean only: host staging
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     hipEvent_t bev[3] = {nullptr, nullptr, nullptr};
     hipEvent_t lev[3] = {nullptr, nullptr, nullptr};
+    hipEvent_t cev[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool cl_pending = false;                            // cev of a call that left its plane on the device: not read yet
+    bool cl_opened = false, cl_dropped = false;         // the steps that call ran
+    double cl_mask_ms = 0.0, cl_open_ms = 0.0, cl_area_ms = 0.0;
     bool lt_pending = false;                            // lev of a call that left its plane on the device: not read yet
     bool lt_median = false;                             // that call ran the median
     double lt_median_ms = 0.0, lt_sum_ms = 0.0;
@@ -1079,6 +1219,8 @@ struct SegmentState {
         for (hipEvent_t e : bev)
             if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : lev)
+            if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : cev)
             if (e) (void)hipEventDestroy(e);
     }
 };
@@ -1329,6 +1471,20 @@ static int local_times(SegmentState& S)
     S.lt_median_ms = S.lt_median ? ms : 0.0;            // without it the two records are back to back
     HIPCHK(hipEventElapsedTime(&ms, S.lev[1], S.lev[2]));
     S.lt_sum_ms = ms;
+    return CS_OK;
+}
+
+static int clean_times(SegmentState& S)
+{
+    float ms = 0.f;
+    HIPCHK(hipEventSynchronize(S.cev[3]));
+    S.cl_pending = false;
+    HIPCHK(hipEventElapsedTime(&ms, S.cev[0], S.cev[1]));
+    S.cl_mask_ms = ms;
+    HIPCHK(hipEventElapsedTime(&ms, S.cev[1], S.cev[2]));
+    S.cl_open_ms = S.cl_opened ? ms : 0.0;              // without a step its two records are back to back
+    HIPCHK(hipEventElapsedTime(&ms, S.cev[2], S.cev[3]));
+    S.cl_area_ms = S.cl_dropped ? ms : 0.0;
     return CS_OK;
 }
 
@@ -1621,5 +1777,86 @@ int cs_segment_local_last_timing(const cs_preproc* p, double* median_ms, double*
     }
     if (median_ms) *median_ms = S ? S->lt_median_ms : 0.0;
     if (sum_ms) *sum_ms = S ? S->lt_sum_ms : 0.0;
+    return CS_OK;
+}
+
+int cs_segment_clean(cs_preproc* p, const void* image, int pixel_type, int32_t channels, int32_t channel, int32_t batch, int32_t height,
+                     int32_t width, int in_kind, const cs_segment_params* params, const cs_clean_params* clean, uint8_t* out, int out_kind,
+                     int32_t* thresholds)
+{
+    if (!clean || !out) return fail(CS_ERR_INVALID, "NULL argument");
+    cs_segment_params sp;
+    // segment_check's rules with the plane in the labels' place: it looks at no more of them than NULL and the kind
+    int rc = segment_check(image, pixel_type, channels, channel, batch, height, width, in_kind, params, (const int32_t*)out, out_kind,
+                           (const int32_t*)out, sp);
+    if (rc) return rc;
+    const int r = clean->open_radius, k = clean->open_connectivity, a = clean->min_area;
+    if (r < 0 || r > CL_MAX_R) return fail(CS_ERR_INVALID, "open_radius %d outside 0..%d (0: no opening)", r, CL_MAX_R);
+    if (k != 1 && k != 2) return fail(CS_ERR_INVALID, "open_connectivity %d: 1 (cross) or 2 (square)", k);
+    if (a < 0 || a > CL_MAX_AREA) return fail(CS_ERR_INVALID, "min_area %d outside 0..%d (0: no area step)", a, CL_MAX_AREA);
+    if (r == 0 && a == 0) return fail(CS_ERR_INVALID, "open_radius and min_area are both 0: nothing to clean");
+    if (!p) {
+        rc = require_gfx950(0);
+        return rc ? rc : fail(CS_ERR_INVALID, "handle is NULL");
+    }
+    HIPCHK(hipSetDevice(p->device));
+    if (!p->seg) p->seg = new SegmentState();
+    SegmentState& S = *p->seg;
+    for (hipEvent_t& e : S.cev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    hipStream_t st = p->stream;
+    const size_t npx = (size_t)batch * height * width;
+    unsigned char* d_out = out;
+    if (out_kind == CS_MEM_HOST) {
+        if ((rc = S.cl_out.ensure(npx))) return rc;
+        d_out = S.cl_out.as<unsigned char>();
+    }
+    S.cl_pending = false;
+    S.cl_opened = r > 0;
+    S.cl_dropped = a > 0;
+    HIPCHK(hipEventRecord(S.cev[0], st));
+    // the mask as the segmenter makes it; its workspace for labels that go to the host (4 bytes per pixel) holds the hole
+    // filling's flags and then the pixel counts
+    SegmentCall c;
+    if ((rc = segment_mask(p, image, pixel_type, channels, channel, batch, height, width, in_kind, sp, nullptr, CS_MEM_HOST, c))) return rc;
+    HIPCHK(hipEventRecord(S.cev[1], st));
+    const unsigned char* cur = S.mask.as<unsigned char>();
+    if (r > 0) {
+        const dim3 ogrid((unsigned)((c.W + CL_TW - 1) / CL_TW), (unsigned)((c.H + CL_TH - 1) / CL_TH), (unsigned)batch);
+        hipLaunchKernelGGL(cl_open, ogrid, dim3(SG_THREADS), 0, st, cur, c.H, c.W, r, (int)(k == 2), d_out);
+        HIPCHK(hipGetLastError());
+        cur = d_out;
+    }
+    HIPCHK(hipEventRecord(S.cev[2], st));
+    if (a > 0) {
+        HIPCHK(hipMemsetAsync(c.d_lab, 0, c.npx * sizeof(int), st));
+        HIPCHK(label_mask(cur, batch, c.H, c.W, 0, sp.connectivity == 2, S.parent.as<int>(), nullptr, c.nchunks, st));
+        hipLaunchKernelGGL(cl_count, c.pgrid, dim3(SG_THREADS), 0, st, c.HW, (const int*)S.parent.as<int>(), c.d_lab);
+        hipLaunchKernelGGL(cl_drop, c.pgrid, dim3(SG_THREADS), 0, st, c.HW, (const int*)S.parent.as<int>(), (const int*)c.d_lab, a, d_out);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(S.cev[3], st));
+    if (out_kind == CS_MEM_DEVICE && in_kind == CS_MEM_DEVICE && !thresholds) {
+        S.cl_pending = true;                            // no host synchronisation: the times are read when they are asked for
+        return CS_OK;
+    }
+    if (thresholds) HIPCHK(hipMemcpyAsync(thresholds, S.thr.p, batch * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (out_kind == CS_MEM_HOST) HIPCHK(hipMemcpyAsync(out, d_out, npx, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));                     // the one host synchronisation: host buffers are free / filled
+    return clean_times(S);
+}
+
+int cs_segment_clean_last_timing(const cs_preproc* p, double* mask_ms, double* open_ms, double* area_ms)
+{
+    if (!p) return fail(CS_ERR_INVALID, "handle is NULL");
+    SegmentState* S = p->seg;
+    if (S && S->cl_pending) {
+        HIPCHK(hipSetDevice(p->device));
+        const int rc = clean_times(*S);
+        if (rc) return rc;
+    }
+    if (mask_ms) *mask_ms = S ? S->cl_mask_ms : 0.0;
+    if (open_ms) *open_ms = S ? S->cl_open_ms : 0.0;
+    if (area_ms) *area_ms = S ? S->cl_area_ms : 0.0;
     return CS_OK;
 }

@@ -29,6 +29,7 @@
  *   cs_segment_threshold / cs_segment_split
  *        the library's own classical segmenter (no reference counterpart, and no StarDist): Otsu or
  *        fixed threshold, optional hole filling, connected-component labels for the extraction above
+ *        (cs_segment_background, cs_segment_local, cs_segment_clean: optional stages before the labels)
  *   cs_fit_scaler / cs_fit_pca_moments / cs_fit_pca_subspace / cs_fit_project / cs_fit_ocsvm
  *        RobustScaler / PCA / OneClassSVM fits of create_anomaly_detector
  *                                                 CAE_improved_modeltrain.py:408-427
@@ -520,6 +521,44 @@ int cs_segment_local(cs_preproc *p, const void *image, int pixel_type, int32_t c
 /* Device time of the last cs_segment_local: the median (0 without it), and the two sum passes with the comparison.  Waits for
  * that call's plane if it was left on the device. */
 int cs_segment_local_last_timing(const cs_preproc *p, double *median_ms, double *sum_ms);
+
+/* Mask cleanup between the hole filling and the labelling: speckle that passes the threshold (noise under a small local delta,
+ * above all) and bridges of a few pixels between cells leave the mask before anything is labelled, flooded or measured.
+ * Integers only, each image on its own, in this order:
+ *   mask      cs_segment_threshold's: pixel > threshold (Otsu's or the fixed one) of the channel, hole-filled with fill_holes.
+ *   opening   open_radius erosions, then as many dilations, by the 3 x 3 cross (open_connectivity 1: a diamond of that radius
+ *             in all) or the 3 x 3 square (2: the square of side 2 * open_radius + 1); outside the image is background for the
+ *             erosion: scipy.ndimage.binary_opening(mask, generate_binary_structure(2, open_connectivity),
+ *             iterations=open_radius) bit for bit.  The square rounds a disk's diagonal edge by about 0.4 * open_radius px.
+ *   min area  components of the opened mask under params->connectivity with fewer than min_area pixels become background:
+ *             skimage.morphology.remove_small_objects(mask, min_size=min_area, connectivity=params->connectivity); a component
+ *             of exactly min_area pixels stays.
+ * image, pixel_type, channels, channel, batch, height, width, in_kind, params: as cs_segment_threshold.  The outputs of
+ *      cs_segment_background and cs_segment_local are valid images (channels = 1, channel = 0; the latter with pixel_type
+ *      CS_PIX_U8, CS_THRESH_FIXED and threshold = 0).
+ * out: [batch][height][width] uint8, 0 / 1, out_kind.  Left on the device it is cs_segment_threshold's or cs_segment_split's
+ *      `image` with pixel_type CS_PIX_U8, channels = 1, channel = 0, CS_THRESH_FIXED, threshold = 0 and fill_holes = 0, on the
+ *      same handle (the same stream: no ordering needed).
+ * thresholds: out, host [batch], or NULL: the threshold used per image.
+ * Workspace on the device: cs_segment_threshold's with labels that go to the host (9 bytes per pixel, and the histogram tables
+ * for CS_THRESH_OTSU), 1 byte per pixel more for an `out` on the host, and the image itself when it comes from the host.
+ * Host synchronisations: none when image and out are both on the device and thresholds is NULL (the plane is complete in
+ * stream order; the times are read when cs_segment_clean_last_timing asks for them, which waits for the plane), else one.
+ * Bad arguments (NULL clean among them, open_radius outside 0..15, open_connectivity not 1 or 2, min_area outside 0..2^24, both
+ * steps off): CS_ERR_INVALID before any device work; sides above 4096, batches above 65535: CS_ERR_UNSUPPORTED; without a
+ * gfx950 device (p == NULL): CS_ERR_NO_DEVICE. */
+typedef struct cs_clean_params {
+    int32_t open_radius;              /* 0 = none, 1..15 */
+    int32_t open_connectivity;        /* 1 cross, 2 square */
+    int32_t min_area;                 /* 0 = none, 1..16777216 */
+} cs_clean_params;
+int cs_segment_clean(cs_preproc *p, const void *image, int pixel_type, int32_t channels, int32_t channel,
+                     int32_t batch, int32_t height, int32_t width, int in_kind,
+                     const cs_segment_params *params, const cs_clean_params *clean /* not NULL */,
+                     uint8_t *out, int out_kind, int32_t *thresholds /* may be NULL */);
+/* Device time of the last cs_segment_clean: threshold + mask + hole filling, the opening (0 without it), and the labelling,
+ * counting and dropping of the area step (0 without it).  Waits for that call's plane if it was left on the device. */
+int cs_segment_clean_last_timing(const cs_preproc *p, double *mask_ms, double *open_ms, double *area_ms);
 
 /* ---- detector fitting (create_anomaly_detector, CAE_improved_modeltrain.py:394-446) -------- */
 /* The fit of what cs_screen's tail evaluates, for the training set's encoder features

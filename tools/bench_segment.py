@@ -30,9 +30,19 @@ compared with the host restatement (tests/local_reference.py) first; then, in th
 segmenter, of the segmenter with the top-hat of radius 51 (--background 51's figure) and of the local segmenter, the stage times
 of each, and the local stage's time as a ratio to the top-hat's.  No time is a pass condition.
 
+--clean [--open R] [--min-area A] [--delta D] measures the mask cleanup (cs_segment_clean, ThresholdSegmenter(open_radius=R,
+min_area=A); --min-area 50 when neither is given) and writes profiles/segment_clean_bench.json.  The scene is speckled: every
+image is 16 fields of tests/test_local_cpu.py's dim_cell_scene (512 x 512, 40 bright and dim cells, noise sigma 25) side by side,
+cut by the local threshold of radius 25 and --delta D (60 by default).  One image's cleaned mask and labels are compared with
+the host restatement (tests/clean_reference.py) first; then, in the same run, the segmenter without cleanup (what it was before
+the option) and with it: images/s of segment_batch and of segment + extract, the label counts, the stage times, open_ms and
+min_area_ms per image, and the ratios of the cleaned figures to the uncleaned ones; with --min-area up to the extraction's own
+bound and no opening, the extracted cells are compared too.  Then open_ms alone at the radii 1, 3, 7 and 15 with both
+structures, which shows what the radius costs.  No time is a pass condition.
+
 Usage: python tools/bench_segment.py [--images 32] [--side 2048] [--cells 1000] [--reps 10] [--warmup 2] [--host-images 4]
                                      [--split [--split-cells 3000] [--split-h 3]] [--background R [--denoise]]
-                                     [--local R [--delta D] [--denoise]]"""
+                                     [--local R [--delta D] [--denoise]] [--clean [--open R] [--min-area A] [--delta D]]"""
 import argparse
 import json
 import os
@@ -256,6 +266,107 @@ def local_leg(a):
     print(line)
 
 
+def clean_leg(a):
+    import torch
+    import clean_reference as CR
+    import local_reference as LR
+    import segment_reference as R
+    from build import source_hash
+    from cellscreen import extract as X
+    from cellscreen import segment as S
+    from test_local_cpu import dim_cell_scene
+
+    fill = not a.no_fill_holes
+    dev = torch.device("cuda", 0)
+    med = lambda v: float(np.median(v))
+    tiles = a.side // 512
+    if tiles < 1 or a.side % 512:
+        raise SystemExit("--clean needs --side a multiple of 512: the scene is made of 512 x 512 fields")
+    fields = [dim_cell_scene(seed)[0] for seed in range(tiles * tiles)]
+    base = np.block([[fields[i * tiles + j] for j in range(tiles)] for i in range(tiles)])
+    variants = [base, base[::-1], base[:, ::-1], base[::-1, ::-1]]          # four distinct images from one painting
+    imgs = np.ascontiguousarray(np.stack([variants[b % 4] for b in range(a.images)]))
+    ti = torch.from_numpy(imgs.view(np.int16)).to(dev)
+    torch.cuda.synchronize()
+    radius, delta = 25, a.delta or 60
+    open_r, min_area = a.open, a.min_area
+    if open_r is None and min_area is None:
+        min_area = 50
+    local = dict(threshold="local", connectivity=a.connectivity, fill_holes=fill, local_radius=radius, local_delta=delta)
+    ext = X.CellExtractor(0)
+    plain = S.ThresholdSegmenter(0, extractor=ext, **local)
+    clean = S.ThresholdSegmenter(0, extractor=ext, open_radius=open_r, min_area=min_area, **local)
+
+    def timed(fn, seg):
+        walls, stages = [], []
+        for k in range(a.warmup + a.reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = fn()
+            torch.cuda.synchronize()
+            if k >= a.warmup:
+                walls.append(time.perf_counter() - t0)
+                stages.append(seg.last_timing())
+        return out, walls, stages
+
+    # outputs first: one image's cleaned mask and labels against the host restatement
+    one = ti[:1].contiguous()
+    mask = clean.clean_mask_batch(one)
+    labels, n, _ = clean.segment_batch(one)
+    m = LR.local_mask(imgs[0], radius, delta) > 0
+    want = CR.clean(R.ndimage.binary_fill_holes(m) if fill else m, open_r, 2, min_area, a.connectivity)
+    hl, hn = R.label_mask(want, a.connectivity)
+    assert np.array_equal(mask[0].cpu().numpy(), want), "cleaned mask differs from the restatement"
+    assert hn == int(n[0]) and np.array_equal(labels[0].cpu().numpy(), hl), "labels differ from the restatement"
+
+    spread = lambda stages, k: [round(med([t[k] for t in stages]), 4), round(min(t[k] for t in stages), 4),
+                                round(max(t[k] for t in stages), 4)]
+    wall3 = lambda walls: [round(med(walls) * 1e3, 3), round(min(walls) * 1e3, 3), round(max(walls) * 1e3, 3)]
+    res = {"tool": "bench_segment --clean", "source_hash": source_hash(), "images": a.images, "side": a.side,
+           "connectivity": a.connectivity, "fill_holes": fill, "local_radius": radius, "local_delta": delta, "open_radius": open_r,
+           "open_connectivity": 2, "min_area": min_area, "cells_painted_per_image": 40 * tiles * tiles, "reps": a.reps,
+           "warmup": a.warmup, "outputs_equal": True}
+    legs = {}
+    for name, seg in (("uncleaned", plain), ("cleaned", clean)):
+        (_, n_lab, _), walls, stages = timed(lambda: seg.segment_batch(ti), seg)
+        r, chain, _ = timed(lambda: ext.extract_batch(ti, seg.segment_batch(ti)[0]), seg)
+        legs[name] = dict(walls=walls, chain=chain, cells=r.cells.cpu().numpy(), stats=X.region_stats(r.regions))
+        res[name] = {"labels_per_image": round(float(n_lab.mean()), 1), "regions_measured": len(r.regions),
+                     "cells_extracted": int(r.cells.shape[0]), "segment_images_per_s": round(a.images / med(walls), 2),
+                     "segment_wall_ms": wall3(walls), "segment_extract_images_per_s": round(a.images / med(chain), 2),
+                     "segment_extract_wall_ms": wall3(chain),
+                     **{k: spread(stages, k) for k in sorted(stages[0])}}
+    st = res["cleaned"]
+    res["open_ms_per_image"] = round(st["open_ms"][0] / a.images, 5)
+    res["min_area_ms_per_image"] = round(st["min_area_ms"][0] / a.images, 5)
+    res["cleaned_over_uncleaned_segment_time"] = round(med(legs["cleaned"]["walls"]) / med(legs["uncleaned"]["walls"]), 3)
+    res["cleaned_over_uncleaned_segment_extract_time"] = round(med(legs["cleaned"]["chain"]) / med(legs["uncleaned"]["chain"]), 3)
+    res["cleaned_over_uncleaned_segment_extract_images_per_s"] = round(
+        res["cleaned"]["segment_extract_images_per_s"] / res["uncleaned"]["segment_extract_images_per_s"], 3)
+    if open_r is None and min_area <= X.REFERENCE_QC["min_area"]:
+        assert legs["cleaned"]["stats"] == legs["uncleaned"]["stats"] and np.array_equal(legs["cleaned"]["cells"], legs["uncleaned"]["cells"]), \
+            "the extraction changed under a min_area within its own area bound"
+        res["extraction_equal"] = True
+    plain_ms = med(legs["uncleaned"]["walls"]) * 1e3 / a.images
+    res["open_radius_sweep"] = []
+    for k in (1, 2):
+        for r_ in (1, 3, 7, 15):
+            seg = S.ThresholdSegmenter(0, extractor=ext, open_radius=r_, open_connectivity=k, **local)
+            _, _, stages = timed(lambda: seg.clean_mask_batch(ti), seg)
+            per = med([t["open_ms"] for t in stages]) / a.images
+            res["open_radius_sweep"].append({"open_connectivity": k, "open_radius": r_, "open_ms_per_image": round(per, 5),
+                                             "open_ns_per_pixel": round(per * 1e6 / (a.side * a.side), 4),
+                                             "over_uncleaned_segment_time": round(per / plain_ms, 4)})
+    ext.close()
+    line = json.dumps(res)
+    out = a.out if a.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "segment_clean_bench.json")
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            f.write(line + "\n")
+    print(line)
+
+
 DEFAULT_OUT = os.path.join(ROOT, "profiles", "segment_bench.json")
 TOPHAT_RADIUS = 51                                      # the top-hat that --local is set beside: --background 51's figure
 
@@ -279,12 +390,21 @@ def main():
     ap.add_argument("--denoise", action="store_true", help="with --background or --local: the 3 x 3 median first")
     ap.add_argument("--local", type=int, default=None, metavar="R",
                     help="measure the local mean threshold of radius R (profiles/segment_local_bench.json)")
-    ap.add_argument("--delta", type=int, default=0, metavar="D", help="with --local: counts above the local mean")
+    ap.add_argument("--delta", type=int, default=0, metavar="D", help="with --local or --clean: counts above the local mean")
+    ap.add_argument("--clean", action="store_true", help="measure the mask cleanup on a speckled scene (profiles/segment_clean_bench.json)")
+    ap.add_argument("--open", type=int, default=None, metavar="R", help="with --clean: open_radius")
+    ap.add_argument("--min-area", type=int, default=None, metavar="A", help="with --clean: min_area (50 when --open is not given either)")
     a = ap.parse_args()
+    if (a.open is not None or a.min_area is not None) and not a.clean:
+        ap.error("--open and --min-area need --clean")
+    if a.clean:
+        if a.split or a.background is not None or a.local is not None or a.denoise:
+            ap.error("--clean is measured on its own")
+        return clean_leg(a)
     if a.denoise and a.background is None and a.local is None:
         ap.error("--denoise needs --background R or --local R")
     if a.delta and a.local is None:
-        ap.error("--delta needs --local R")
+        ap.error("--delta needs --local R or --clean")
     if a.local is not None and (a.split or a.background is not None):
         ap.error("--local is measured on its own")
     if a.split:
