@@ -120,6 +120,13 @@ class CSCleanParams(C.Structure):
     _fields_ = [("open_radius", C.c_int32), ("open_connectivity", C.c_int32), ("min_area", C.c_int32)]
 
 
+SMOOTH_MAX_RADIUS = 64                  # cs_smooth_params.weights holds 65 taps
+
+
+class CSSmoothParams(C.Structure):
+    _fields_ = [("radius", C.c_int32), ("median", C.c_int32), ("weights", C.c_int32 * (SMOOTH_MAX_RADIUS + 1)), ("reserved", C.c_int32)]
+
+
 # cs_region of include/cellscreen.h as a numpy record (80 bytes)
 REGION_DTYPE = np.dtype([("image", np.int32), ("label", np.int32), ("minr", np.int32), ("minc", np.int32), ("maxr", np.int32),
                          ("maxc", np.int32), ("area", np.int64), ("convex_area", np.int64), ("eccentricity", np.float64),
@@ -173,6 +180,8 @@ SIGNATURES = {
     "cs_segment_clean": (_I, [_P, _P, _I, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _I, C.POINTER(CSSegmentParams),
                               C.POINTER(CSCleanParams), _P, _I, _P]),
     "cs_segment_clean_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "cs_segment_smooth": (_I, [_P, _P, _I, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _I, C.POINTER(CSSmoothParams), _P, _I]),
+    "cs_segment_smooth_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "cs_fit_create": (_I, [_I, C.POINTER(_P)]),
     "cs_fit_free": (None, [_P]),
     "cs_fit_wait_stream": (_I, [_P, _P]),

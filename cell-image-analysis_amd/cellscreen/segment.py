@@ -40,18 +40,29 @@ bridges thinner than 2r + 1 pixels go, and the square rounds a disk's diagonal e
 components (under the segmenter's connectivity) of fewer than a pixels into background, as
 skimage.morphology.remove_small_objects(mask, min_size=a) does.  The labels, the split and the distances see the cleaned mask.
 
+Smoothing, before everything else (cs_segment_smooth; tests/smooth_reference.py restates it), off by default: smooth_sigma=s
+(0.25..15.875) replaces the channel by its Gaussian, for noisy fields where the threshold shatters a faint cell into fragments
+that no cleanup of the mask puts together again.  Integers only: a separable kernel of radius int(4 s + 0.5) with 16-bit
+fixed-point weights that sum to 2^16 (smooth_weights), the image reflected about its edges, one rounding to nearest at the very
+end.  That is scipy.ndimage.gaussian_filter(x, s, mode='reflect', truncate=4.0) in float64 to within 0.5 + top * (2 eps + eps^2),
+eps the summed quantisation error of the taps; the library's own integer output truncates and is not reproduced bit for bit.
+denoise=True then runs the 3 x 3 median before the Gaussian (hot pixels go before they are smeared) and nowhere else; the
+correction, the threshold, the cleanup, the labels and the split see the smoothed plane, the extraction the raw channel.
+
     seg = ThresholdSegmenter()
     labels, n_labels, thresholds = seg.segment_batch(images)          # numpy in, numpy out; CUDA tensors in, CUDA tensor out
     seg = ThresholdSegmenter(split_touching=True)                      # the same, touching cells apart
     seg = ThresholdSegmenter(background_radius=51)                     # uneven illumination flattened before the threshold
     seg = ThresholdSegmenter(threshold="local", local_radius=25, local_delta=60)      # bright and dim cells in one field
     seg = ThresholdSegmenter(threshold="local", local_radius=25, local_delta=40, min_area=50)         # ... without the speckle
+    seg = ThresholdSegmenter(smooth_sigma=2)                           # faint cells in noise: Gaussian first
 
     screening = ProductionMutantScreening(model_dir, cell_extractor=threshold_cell_extractor())
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Optional
 
 import numpy as np
@@ -163,10 +174,57 @@ def clean_params(open_radius=None, open_connectivity: int = 2, min_area=None) ->
     return p
 
 
-def _threshold_mode(threshold, connectivity, fill_holes, local_radius, local_delta, local_floor, background_radius, denoise):
+SMOOTH_SIGMA_MIN, SMOOTH_SIGMA_MAX = 0.25, 15.875         # radius int(4 sigma + 0.5) = 1..64
+
+
+def smooth_weights(sigma: float, truncate: float = 4.0):
+    """The fixed-point Gaussian table w[0..r] of cs_smooth_params, r = int(truncate * sigma + 0.5): w_k = floor(e_k) with
+    e_k = 65536 * g_k / (g_0 + 2 * sum g_k), g_k = exp(-k^2 / (2 sigma^2)) in float64; the deficit 65536 - w_0 - 2 * sum w_k
+    is handed out by largest remainder over k >= 1 (ties to the smaller k; +1 each, which costs 2) and the centre takes the
+    last 0 or 1.  w_0 + 2 * sum_{k >= 1} w_k == 65536, non-increasing from the centre.  tests/smooth_reference.py has an
+    identical copy."""
+    r = int(truncate * sigma + 0.5)
+    g = [math.exp(-(k * k) / (2.0 * sigma * sigma)) for k in range(r + 1)]
+    norm = g[0] + 2.0 * sum(g[1:])
+    e = [65536.0 * gk / norm for gk in g]
+    w = [int(math.floor(ek)) for ek in e]
+    deficit = 65536 - w[0] - 2 * sum(w[1:])
+    for k in sorted(range(1, r + 1), key=lambda k: (-(e[k] - w[k]), k)):
+        if deficit < 2:
+            break
+        w[k] += 1
+        deficit -= 2
+    w[0] += deficit
+    return w
+
+
+def smooth_params(smooth_sigma=None, denoise: bool = False) -> Optional[L.CSSmoothParams]:
+    """cs_smooth_params from the Python arguments, None without a sigma (no smoothing); anything out of range raises before a
+    handle exists.  denoise: the 3 x 3 median before the Gaussian."""
+    if not isinstance(denoise, (bool, np.bool_)):
+        raise TypeError(f"denoise must be a bool, got {type(denoise).__name__}")
+    if smooth_sigma is None:
+        return None
+    if isinstance(smooth_sigma, (bool, np.bool_)) or not isinstance(smooth_sigma, (int, float, np.integer, np.floating)):
+        raise TypeError(f"smooth_sigma must be None or a number (pixels), got {type(smooth_sigma).__name__}")
+    if not SMOOTH_SIGMA_MIN <= float(smooth_sigma) <= SMOOTH_SIGMA_MAX:                  # NaN fails both
+        raise ValueError(f"smooth_sigma {smooth_sigma} outside {SMOOTH_SIGMA_MIN}..{SMOOTH_SIGMA_MAX}")
+    w = smooth_weights(float(smooth_sigma))
+    p = L.CSSmoothParams()
+    p.radius, p.median, p.reserved = len(w) - 1, 1 if denoise else 0, 0
+    for k, v in enumerate(w):
+        p.weights[k] = v
+    return p
+
+
+def _threshold_mode(threshold, connectivity, fill_holes, local_radius, local_delta, local_floor, background_radius, denoise,
+                    smooth_sigma=None):
     """(cs_segment_params, cs_local_params or None, cs_background_params or None) of a segmenter's arguments.  In local mode the
-    labelling sees a 0 / 1 plane, so its parameters are a fixed threshold of 0; the median runs once: inside the correction
-    when there is one, else inside the local rule."""
+    labelling sees a 0 / 1 plane, so its parameters are a fixed threshold of 0; the median runs once, inside the first stage
+    that exists: the smoothing (smooth_params has it then, and the stages here get none), else the correction, else the local
+    rule."""
+    if smooth_params(smooth_sigma, denoise) is not None:
+        denoise = False
     if isinstance(threshold, str) and threshold == "local":
         if not isinstance(denoise, (bool, np.bool_)):
             raise TypeError(f"denoise must be a bool, got {type(denoise).__name__}")
@@ -193,15 +251,20 @@ class ThresholdSegmenter:
     thresholds it reports are -1: there is no single number.  With numpy input the mask makes one more round trip.
     open_radius (None or 1..15), open_connectivity (1 cross, 2 square) and min_area (None or 1..2^24): the mask cleanup of the
     module text, after the hole filling; the labels and the split then see the cleaned mask.  With numpy input the cleaned
-    mask makes one more round trip."""
+    mask makes one more round trip.
+    smooth_sigma (None or 0.25..15.875): the Gaussian smoothing of the module text, before everything else; denoise then runs
+    the median before the Gaussian and needs no background_radius.  With numpy input the smoothed plane makes one more round
+    trip."""
 
     def __init__(self, device_id: int = 0, threshold="otsu", connectivity: int = 1, fill_holes: bool = True,
                  extractor: Optional[CellExtractor] = None, split_touching: bool = False, split_h: int = 3,
                  background_radius: Optional[int] = None, denoise: bool = False, local_radius: Optional[int] = None,
                  local_delta: int = 0, local_floor: int = -1, open_radius: Optional[int] = None, open_connectivity: int = 2,
-                 min_area: Optional[int] = None):
+                 min_area: Optional[int] = None, smooth_sigma: Optional[float] = None):
         self._params, self._local, self._background = _threshold_mode(threshold, connectivity, fill_holes, local_radius, local_delta,
-                                                                      local_floor, background_radius, denoise)
+                                                                      local_floor, background_radius, denoise, smooth_sigma)
+        self._smooth = smooth_params(smooth_sigma, denoise)
+        self.smooth_sigma = None if smooth_sigma is None else float(smooth_sigma)
         self._split = split_params(split_touching, split_h)
         self._clean = clean_params(open_radius, open_connectivity, min_area)
         # what labels the cleaned 0 / 1 plane: the fixed threshold 0 and no second hole filling
@@ -283,6 +346,38 @@ class ThresholdSegmenter:
                 raise ValueError("images must be C-contiguous")
         return B, H, W, Cn, int(channel), ptype, on_dev
 
+    def _smoothed(self, images, B, H, W, Cn, channel, ptype, on_dev):
+        """The smoothed plane [B,H,W] where the images are; a device plane is complete in the handle's stream order only."""
+        if on_dev:
+            import torch
+            plane = torch.empty((B, H, W), dtype=images.dtype, device=images.device)
+            L.order_after_torch(self._lib.cs_preproc_wait_stream, self._handle, images, plane)
+        else:
+            plane = np.empty((B, H, W), images.dtype)
+        kind = L.CS_MEM_DEVICE if on_dev else L.CS_MEM_HOST
+        L.check(self._lib.cs_segment_smooth(self._handle, L._ptr(images), ptype, Cn, channel, B, H, W, kind, C.byref(self._smooth),
+                                            L._ptr(plane), kind))
+        return plane
+
+    def _smooth_timing(self):
+        a, b = C.c_double(), C.c_double()
+        L.check(self._lib.cs_segment_smooth_last_timing(self._handle, C.byref(a), C.byref(b)))
+        t = {"smooth_ms": b.value}
+        if self._smooth.median:
+            t["smooth_median_ms"] = a.value
+        return t
+
+    def smooth_batch(self, images, channel: Optional[int] = None):
+        """The smoothed plane of `channel` that every later stage starts from: [B,H,W] of the images' dtype, numpy for numpy
+        input, a CUDA tensor for tensor input (complete when this returns).  Needs smooth_sigma."""
+        B, H, W, Cn, channel, ptype, on_dev = self._check(images, channel)
+        if self._smooth is None:
+            raise ValueError("smooth_batch needs smooth_sigma: this segmenter smooths nothing")
+        plane = self._smoothed(images, B, H, W, Cn, channel, ptype, on_dev)
+        if on_dev:
+            self._smooth_timing()                                   # reads the times, which waits for the plane: torch may use it
+        return plane
+
     def _correct(self, images, B, H, W, Cn, channel, ptype, on_dev):
         """The corrected plane [B,H,W] where the images are; a device plane is complete in the handle's stream order only."""
         if on_dev:
@@ -307,6 +402,9 @@ class ThresholdSegmenter:
         B, H, W, Cn, channel, ptype, on_dev = self._check(images, channel)
         if self._background is None:
             raise ValueError("correct_batch needs background_radius: this segmenter corrects nothing")
+        if self._smooth is not None:
+            images = self._smoothed(images, B, H, W, Cn, channel, ptype, on_dev)
+            Cn, channel = 1, 0
         plane = self._correct(images, B, H, W, Cn, channel, ptype, on_dev)
         if on_dev:
             self._background_timing()                               # reads the times, which waits for the plane: torch may use it
@@ -337,6 +435,9 @@ class ThresholdSegmenter:
         B, H, W, Cn, channel, ptype, on_dev = self._check(images, channel)
         if self._local is None:
             raise ValueError("local_mask_batch needs threshold='local'")
+        if self._smooth is not None:
+            images = self._smoothed(images, B, H, W, Cn, channel, ptype, on_dev)
+            Cn, channel = 1, 0
         if self._background is not None:
             images = self._correct(images, B, H, W, Cn, channel, ptype, on_dev)
             Cn, channel = 1, 0
@@ -372,6 +473,9 @@ class ThresholdSegmenter:
         B, H, W, Cn, channel, ptype, on_dev = self._check(images, channel)
         if self._clean is None:
             raise ValueError("clean_mask_batch needs open_radius or min_area: this segmenter cleans nothing")
+        if self._smooth is not None:
+            images = self._smoothed(images, B, H, W, Cn, channel, ptype, on_dev)
+            Cn, channel = 1, 0
         if self._background is not None:
             images = self._correct(images, B, H, W, Cn, channel, ptype, on_dev)
             Cn, channel = 1, 0
@@ -393,6 +497,10 @@ class ThresholdSegmenter:
         B, H, W, Cn, channel, ptype, on_dev = self._check(images, channel)
         if return_distance and self._split is None:
             raise ValueError("return_distance needs split_touching=True: the plain segmenter computes no distances")
+        if self._smooth is not None:
+            # every later stage takes the smoothed plane in the channel's place
+            images = self._smoothed(images, B, H, W, Cn, channel, ptype, on_dev)
+            Cn, channel = 1, 0
         if self._background is not None:
             # threshold, label and split the corrected plane in the channel's place; the library's final synchronisation
             # comes after everything that reads the plane
@@ -451,8 +559,11 @@ class ThresholdSegmenter:
         background_radius also median_ms and background_ms (the top-hat) of the last correction; with threshold="local" also
         local_median_ms and local_ms (the sums and the comparison) of the last mask; with open_radius or min_area also open_ms
         and min_area_ms of the last cleanup (0 for a step that is off), and threshold_ms is then the labelling call's cut of the
-        cleaned plane."""
-        extra = self._background_timing() if self._background is not None else {}
+        cleaned plane; with smooth_sigma also smooth_ms (the two passes) of the last smoothing, and smooth_median_ms when the
+        median ran there."""
+        extra = self._smooth_timing() if self._smooth is not None else {}
+        if self._background is not None:
+            extra.update(self._background_timing())
         if self._local is not None:
             extra.update(self._local_timing())
         if self._clean is not None:
@@ -470,7 +581,8 @@ def threshold_cell_extractor(device_id: int = 0, out_hw=(OUT_SIDE, OUT_SIDE), th
                              fill_holes: bool = True, split_touching: bool = False, split_h: int = 3,
                              background_radius: Optional[int] = None, denoise: bool = False, local_radius: Optional[int] = None,
                              local_delta: int = 0, local_floor: int = -1, open_radius: Optional[int] = None,
-                             open_connectivity: int = 2, mask_min_area: Optional[int] = None, **qc):
+                             open_connectivity: int = 2, mask_min_area: Optional[int] = None,
+                             smooth_sigma: Optional[float] = None, **qc):
     """The `cell_extractor(image_path) -> (cells, stats)` that ProductionMutantScreening and create_training_dataset accept,
     with the built-in segmenter in StarDist's place: the file is read (extract.read_image / split_channels), uploaded once,
     segmented and extracted on one handle, and the labels never leave the device.  Not StarDist: see the module text.
@@ -479,9 +591,11 @@ def threshold_cell_extractor(device_id: int = 0, out_hw=(OUT_SIDE, OUT_SIDE), th
     for ThresholdSegmenter, and threshold="local" with local_radius, local_delta and local_floor too: with background_radius the segmentation channel is corrected before the threshold, while the
     extraction still reads the raw analysis channel, so the intensity rules and the crops are what they are without it.
     open_radius and open_connectivity as for ThresholdSegmenter, and mask_min_area for its min_area: the mask cleanup before
-    the labels.  The name differs here because min_area is, and stays, the extraction's own area rule among **qc."""
+    the labels.  The name differs here because min_area is, and stays, the extraction's own area rule among **qc.
+    smooth_sigma as for ThresholdSegmenter: the segmentation channel is smoothed first, the extraction reads the raw one."""
     out_hw = check_out_hw(out_hw)
-    _threshold_mode(threshold, connectivity, fill_holes, local_radius, local_delta, local_floor, background_radius, denoise)
+    _threshold_mode(threshold, connectivity, fill_holes, local_radius, local_delta, local_floor, background_radius, denoise,
+                    smooth_sigma)
     split_params(split_touching, split_h)
     clean_params(open_radius, open_connectivity, mask_min_area)
     qc_params(**qc)
@@ -500,7 +614,7 @@ def threshold_cell_extractor(device_id: int = 0, out_hw=(OUT_SIDE, OUT_SIDE), th
                                          split_touching=split_touching, split_h=split_h, background_radius=background_radius,
                                          denoise=denoise, local_radius=local_radius, local_delta=local_delta,
                                          local_floor=local_floor, open_radius=open_radius, open_connectivity=open_connectivity,
-                                         min_area=mask_min_area)
+                                         min_area=mask_min_area, smooth_sigma=smooth_sigma)
         host = np.ascontiguousarray(img)[None]
         dev = torch.from_numpy(host.view(np.int16) if host.dtype == np.uint16 else host).to(torch.device("cuda", device_id))
         labels, _, _ = st["s"].segment_batch(dev, channel=seg_ch)

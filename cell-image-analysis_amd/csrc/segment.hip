@@ -28,6 +28,8 @@
 //   cl_*         cs_segment_clean only: the optional cleanup of the mask BEFORE the labelling (binary opening on a bit-packed
 //                tile in LDS, minimum area by pixel counts per union-find root); see "mask cleanup" further down.  Its plane
 //                then stands in the channel's place, cut at the fixed threshold 0.
+//   sm_*         cs_segment_smooth only: the optional Gaussian smoothing of the channel BEFORE all of the above, the background
+//                correction included (separable, 16-bit fixed-point weights, one rounding); see "Gaussian smoothing".
 // The final parents are a function of the mask alone (the minimum index of a component), so the labels do not depend on
 // execution order, on the run, or on the other images of the batch.
 #include "api_internal.hpp"
@@ -1059,6 +1061,136 @@ __global__ __launch_bounds__(SG_THREADS) void lt_cols(const unsigned int* __rest
     }
 }
 
+// ---- Gaussian smoothing (cs_segment_smooth) ------------------------------------------------------------------------------------
+// y = (A + 2^31) >> 32 with T(i, j) = sum_k w[|k|] x(i, fold(j + k, W)) and A(i, j) = sum_k w[|k|] T(fold(i + k, H), j), k = -r..r,
+// fold being lt_fold (scipy's mode='reflect'; r may exceed a side) and w[0] + 2 * sum_{k >= 1} w[k] = 2^16 (DESIGN 3o;
+// tests/smooth_reference.py restates it).  The table comes with the call (cs_smooth_params): the kernels are exact for any table
+// that passes smooth_check.  x <= 65535, so T <= 65535 * 2^16 fits 32 bits and A < 2^48; a constant image is a fixed point.
+//   sm_rows   256 threads, 4 rows x up to 768 pixels; wave k owns row k.  The row with a halo of r on either side goes into LDS
+//             as 16-bit values.  A lane produces SM_ROW_E = 6 adjacent outputs at a time from two sliding windows of registers,
+//             x[j - k ..] and x[j + k ..]: one step of k costs it two LDS reads (the value that enters each window) and six
+//             (left + right) * w[k], 17 bits times at most 17, accumulated in 32 bits.  Lanes are 6 halfwords = 3 words apart
+//             in LDS: an odd stride, so the 32 lanes of an access are on 32 different banks.  Writes T, 4 bytes per pixel.
+//   sm_cols   256 threads, 64 columns x 128 rows; LDS is [rows + 2r][64 columns] of T (dynamic, at most 66,560 bytes), lanes run
+//             across the columns, so every access of a wave is 64 consecutive words of one row.  A thread produces SM_COL_E = 4
+//             adjacent rows of its column, again from two sliding windows.  The 48-bit sum without a 64-bit multiply: T is split
+//             into its high and low 16 bits, each half has a 32-bit accumulator (at most 65535 * 2^16 < 2^32, as the weights
+//             sum to 2^16), and the two meet once: A = (hi << 16) + lo, plus 2^31, shifted by 32.
+// The weights are a kernel argument by value, indexed by the uniform k: scalar loads, no vector register holds them.  Integer
+// multiplies and adds only, no atomics: the plane is a function of its own image and the table alone.
+static constexpr int SM_MAX_R = 64;
+static constexpr int SM_ROW_E = 6, SM_ROW_SEG = 2 * 64 * SM_ROW_E, SM_ROW_LINES = SG_THREADS / 64;
+static constexpr int SM_ROW_LEN = SM_ROW_SEG + 2 * SM_MAX_R + SM_ROW_E;          // a last lane's windows run up to E - 2 past the halo
+static constexpr int SM_COL_W = 64, SM_COL_WAVES = SG_THREADS / 64, SM_COL_E = 4, SM_COL_TR = 128;
+
+struct SmWeights {
+    int r;
+    unsigned int w[SM_MAX_R + 1];
+};
+
+// grid (ceil(W / SM_ROW_SEG), ceil(H / SM_ROW_LINES), B).  in: pixel (b, y, x) at in[b * in_img + (y * W + x) * in_pix].
+// T: [B][H][W] uint32.
+template <typename PIX>
+__global__ __launch_bounds__(SG_THREADS) void sm_rows(const PIX* __restrict__ in, size_t in_img, int in_pix, int H, int W, const SmWeights wt,
+                                                      unsigned int* __restrict__ T)
+{
+    __shared__ unsigned short sm[SM_ROW_LINES * SM_ROW_LEN];
+    constexpr int E = SM_ROW_E;
+    const int tp = threadIdx.x & 63, line = threadIdx.x >> 6;
+    const int x0 = blockIdx.x * SM_ROW_SEG, y = blockIdx.y * SM_ROW_LINES + line, b = blockIdx.z;
+    const int r = wt.r, seg = min(SM_ROW_SEG, W - x0), len = seg + 2 * r;
+    unsigned short* s = sm + line * SM_ROW_LEN;
+    const PIX* src = in + (size_t)b * in_img + (size_t)(y < H ? y : 0) * W * in_pix;
+    for (int pos = tp; pos < len + E; pos += 64)
+        s[pos] = y < H && pos < len ? (unsigned short)src[(size_t)lt_fold(x0 - r + pos, W) * in_pix] : (unsigned short)0;
+    __syncthreads();
+    if (y >= H) return;
+    unsigned int* dst = T + ((size_t)b * H + y) * W + x0;
+    const unsigned int w0 = wt.w[0];
+    for (int j = tp * E; j < seg; j += 64 * E) {
+        const unsigned short* c = s + r + j;            // c[d]: the pixel x0 + j + d
+        unsigned int lo[E], hi[E], acc[E];
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            lo[e] = hi[e] = c[e];
+            acc[e] = w0 * lo[e];
+        }
+        for (int k = 1; k <= r; ++k) {                  // lo[e] = c[e - k], hi[e] = c[e + k]
+            const unsigned int w = wt.w[k];
+#pragma unroll
+            for (int e = E - 1; e > 0; --e) lo[e] = lo[e - 1];
+#pragma unroll
+            for (int e = 0; e < E - 1; ++e) hi[e] = hi[e + 1];
+            lo[0] = c[-k];
+            hi[E - 1] = c[E - 1 + k];
+#pragma unroll
+            for (int e = 0; e < E; ++e) acc[e] += w * (lo[e] + hi[e]);
+        }
+#pragma unroll
+        for (int e = 0; e < E; ++e)
+            if (j + e < seg) dst[j + e] = acc[e];
+    }
+}
+
+// grid (ceil(W / SM_COL_W), ceil(H / SM_COL_TR), B); dynamic LDS (min(SM_COL_TR, H) + 2r + SM_COL_E) * 64 * 4 bytes.
+// out: [B][H][W] of the pixel type.
+template <typename PIX>
+__global__ __launch_bounds__(SG_THREADS) void sm_cols(const unsigned int* __restrict__ T, int H, int W, const SmWeights wt, PIX* __restrict__ out)
+{
+    extern __shared__ unsigned int sm_tile[];
+    constexpr int E = SM_COL_E;
+    const int col = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int x = blockIdx.x * SM_COL_W + col, y0 = blockIdx.y * SM_COL_TR;
+    const int r = wt.r, rows = min(SM_COL_TR, H - y0), len = rows + 2 * r;
+    const size_t base = (size_t)blockIdx.z * H * W;
+    for (int pos = wv; pos < len + E; pos += SM_COL_WAVES)
+        sm_tile[pos * SM_COL_W + col] = x < W && pos < len ? T[base + (size_t)lt_fold(y0 - r + pos, H) * W + x] : 0u;
+    __syncthreads();
+    if (x >= W) return;
+    const unsigned int w0 = wt.w[0];
+    for (int j = wv * E; j < rows; j += SM_COL_WAVES * E) {
+        const unsigned int* c = sm_tile + (r + j) * SM_COL_W + col;      // c[d * 64]: T of row y0 + j + d
+        unsigned int lh[E], ll[E], hh[E], hl[E], ah[E], al[E];  // the two windows and the sums, high and low halves
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            const unsigned int t = c[e * SM_COL_W];
+            lh[e] = hh[e] = t >> 16;
+            ll[e] = hl[e] = t & 0xffffu;
+            ah[e] = w0 * lh[e];
+            al[e] = w0 * ll[e];
+        }
+        for (int k = 1; k <= r; ++k) {
+            const unsigned int w = wt.w[k];
+            const unsigned int a = c[-k * SM_COL_W], z = c[(E - 1 + k) * SM_COL_W];
+#pragma unroll
+            for (int e = E - 1; e > 0; --e) {
+                lh[e] = lh[e - 1];
+                ll[e] = ll[e - 1];
+            }
+#pragma unroll
+            for (int e = 0; e < E - 1; ++e) {
+                hh[e] = hh[e + 1];
+                hl[e] = hl[e + 1];
+            }
+            lh[0] = a >> 16;
+            ll[0] = a & 0xffffu;
+            hh[E - 1] = z >> 16;
+            hl[E - 1] = z & 0xffffu;
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                ah[e] += w * (lh[e] + hh[e]);
+                al[e] += w * (ll[e] + hl[e]);
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < E; ++e)
+            if (j + e < rows) {
+                const unsigned long long A = ((unsigned long long)ah[e] << 16) + al[e] + (1ull << 31);
+                out[base + (size_t)(y0 + j + e) * W + x] = (PIX)(A >> 32);
+            }
+    }
+}
+
 // ---- mask cleanup (cs_segment_clean): binary opening, minimum area -------------------------------------------------------------
 // Between the hole filling and the labelling, on the 0 / 1 mask alone (tests/clean_reference.py restates it):
 //   opening   r erosions then r dilations by the 3 x 3 cross (connectivity 1) or square (2), outside the image background for
@@ -1197,10 +1329,15 @@ struct SegmentState {
     DevBuf bg_in, bg_med, bg_a, bg_b, bg_out;           // cs_segment_background only: upload, median, two planes, host staging
     DevBuf lt_in, lt_med, lt_sum, lt_out;               // cs_segment_local only: upload, median, row sums, host staging
     DevBuf cl_out;                                      // cs_segment_clean only: host staging
+    DevBuf sm_in, sm_med, sm_t, sm_out;                 // cs_segment_smooth only: upload, median, row pass, host staging
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     hipEvent_t bev[3] = {nullptr, nullptr, nullptr};
     hipEvent_t lev[3] = {nullptr, nullptr, nullptr};
     hipEvent_t cev[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t sev[3] = {nullptr, nullptr, nullptr};
+    bool sm_pending = false;                            // sev of a call that left its plane on the device: not read yet
+    bool sm_median = false;                             // that call ran the median
+    double sm_median_ms = 0.0, sm_smooth_ms = 0.0;
     bool cl_pending = false;                            // cev of a call that left its plane on the device: not read yet
     bool cl_opened = false, cl_dropped = false;         // the steps that call ran
     double cl_mask_ms = 0.0, cl_open_ms = 0.0, cl_area_ms = 0.0;
@@ -1221,6 +1358,8 @@ struct SegmentState {
         for (hipEvent_t e : lev)
             if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : cev)
+            if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : sev)
             if (e) (void)hipEventDestroy(e);
     }
 };
@@ -1471,6 +1610,72 @@ static int local_times(SegmentState& S)
     S.lt_median_ms = S.lt_median ? ms : 0.0;            // without it the two records are back to back
     HIPCHK(hipEventElapsedTime(&ms, S.lev[1], S.lev[2]));
     S.lt_sum_ms = ms;
+    return CS_OK;
+}
+
+// median (optional), row pass, column pass on the stream; d_out is a [B][H][W] plane on the device
+template <typename PIX>
+static int smooth_launch(SegmentState& S, const PIX* d_img, int C, int ch, int batch, int H, int W, const SmWeights& wt, bool median,
+                         PIX* d_out, hipStream_t st)
+{
+    const int HW = H * W, r = wt.r;
+    int rc;
+    if ((rc = S.sm_t.ensure((size_t)batch * HW * sizeof(unsigned int)))) return rc;
+    const PIX* x = d_img + ch;
+    size_t x_img = (size_t)HW * C;
+    int x_pix = C;
+    HIPCHK(hipEventRecord(S.sev[0], st));
+    S.sm_median = median;
+    if (median) {
+        if ((rc = S.sm_med.ensure((size_t)batch * HW * sizeof(PIX)))) return rc;
+        hipLaunchKernelGGL(bg_median<PIX>, dim3((unsigned)((HW + SG_CHUNK - 1) / SG_CHUNK), (unsigned)batch), dim3(SG_THREADS), 0, st, d_img, C,
+                           ch, H, W, S.sm_med.as<PIX>());
+        HIPCHK(hipGetLastError());
+        x = S.sm_med.as<PIX>();
+        x_img = (size_t)HW;
+        x_pix = 1;
+    }
+    HIPCHK(hipEventRecord(S.sev[1], st));
+    const dim3 rgrid((unsigned)((W + SM_ROW_SEG - 1) / SM_ROW_SEG), (unsigned)((H + SM_ROW_LINES - 1) / SM_ROW_LINES), (unsigned)batch);
+    const dim3 cgrid((unsigned)((W + SM_COL_W - 1) / SM_COL_W), (unsigned)((H + SM_COL_TR - 1) / SM_COL_TR), (unsigned)batch);
+    const size_t lds = (size_t)(std::min(SM_COL_TR, H) + 2 * r + SM_COL_E) * SM_COL_W * sizeof(unsigned int);
+    HIPCHK(hipFuncSetAttribute((const void*)sm_cols<PIX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(sm_rows<PIX>, rgrid, dim3(SG_THREADS), 0, st, x, x_img, x_pix, H, W, wt, S.sm_t.as<unsigned int>());
+    hipLaunchKernelGGL(sm_cols<PIX>, cgrid, dim3(SG_THREADS), lds, st, (const unsigned int*)S.sm_t.as<unsigned int>(), H, W, wt, d_out);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(S.sev[2], st));
+    return CS_OK;
+}
+
+static int smooth_times(SegmentState& S)
+{
+    float ms = 0.f;
+    HIPCHK(hipEventSynchronize(S.sev[2]));
+    S.sm_pending = false;
+    HIPCHK(hipEventElapsedTime(&ms, S.sev[0], S.sev[1]));
+    S.sm_median_ms = S.sm_median ? ms : 0.0;            // without it the two records are back to back
+    HIPCHK(hipEventElapsedTime(&ms, S.sev[1], S.sev[2]));
+    S.sm_smooth_ms = ms;
+    return CS_OK;
+}
+
+// the table rules of cs_smooth_params; wt receives the table in force
+static int smooth_check(const cs_smooth_params& sp, SmWeights& wt)
+{
+    if (sp.radius < 1 || sp.radius > SM_MAX_R) return fail(CS_ERR_INVALID, "smooth radius %d outside 1..%d", (int)sp.radius, SM_MAX_R);
+    if (sp.median != 0 && sp.median != 1) return fail(CS_ERR_INVALID, "median %d: 0 or 1", (int)sp.median);
+    if (sp.reserved != 0) return fail(CS_ERR_INVALID, "cs_smooth_params.reserved must be 0");
+    long long sum = 0;
+    for (int k = 0; k <= SM_MAX_R; ++k) {
+        const int32_t w = sp.weights[k];
+        if (w < 0) return fail(CS_ERR_INVALID, "weights[%d] = %d: negative", k, (int)w);
+        if (k > sp.radius && w != 0) return fail(CS_ERR_INVALID, "weights[%d] = %d beyond radius %d", k, (int)w, (int)sp.radius);
+        sum += k ? 2ll * w : (long long)w;
+        wt.w[k] = (unsigned int)w;
+    }
+    if (sp.weights[0] < 1) return fail(CS_ERR_INVALID, "weights[0] = %d: the centre tap must be at least 1", (int)sp.weights[0]);
+    if (sum != 65536) return fail(CS_ERR_INVALID, "weights[0] + 2 * sum(weights[1..radius]) = %lld, not 65536", sum);
+    wt.r = sp.radius;
     return CS_OK;
 }
 
@@ -1858,5 +2063,76 @@ int cs_segment_clean_last_timing(const cs_preproc* p, double* mask_ms, double* o
     if (mask_ms) *mask_ms = S ? S->cl_mask_ms : 0.0;
     if (open_ms) *open_ms = S ? S->cl_open_ms : 0.0;
     if (area_ms) *area_ms = S ? S->cl_area_ms : 0.0;
+    return CS_OK;
+}
+
+int cs_segment_smooth(cs_preproc* p, const void* image, int pixel_type, int32_t channels, int32_t channel, int32_t batch, int32_t height,
+                      int32_t width, int in_kind, const cs_smooth_params* params, void* plane, int plane_kind)
+{
+    if (!image || !params || !plane) return fail(CS_ERR_INVALID, "NULL argument");
+    if (pixel_type != CS_PIX_U8 && pixel_type != CS_PIX_U16) return fail(CS_ERR_INVALID, "pixel_type must be CS_PIX_U8 or CS_PIX_U16");
+    if ((in_kind != CS_MEM_HOST && in_kind != CS_MEM_DEVICE) || (plane_kind != CS_MEM_HOST && plane_kind != CS_MEM_DEVICE))
+        return fail(CS_ERR_INVALID, "in_kind / plane_kind must be CS_MEM_HOST or CS_MEM_DEVICE");
+    if (channels < 1 || channel < 0 || channel >= channels)
+        return fail(CS_ERR_INVALID, "channel %d of %d: need 0 <= channel < channels", (int)channel, (int)channels);
+    if (batch < 1 || height < 1 || width < 1) return fail(CS_ERR_INVALID, "batch %d, height %d, width %d: all must be >= 1", (int)batch,
+                                                          (int)height, (int)width);
+    SmWeights wt;
+    int rc = smooth_check(*params, wt);
+    if (rc) return rc;
+    if (height > kSegMaxSide || width > kSegMaxSide)
+        return fail(CS_ERR_UNSUPPORTED, "image %dx%d: sides above %d are not supported", (int)height, (int)width, kSegMaxSide);
+    if (batch > kSegMaxBatch) return fail(CS_ERR_UNSUPPORTED, "batch %d: at most %d images per call", (int)batch, kSegMaxBatch);
+    if (!p) {
+        rc = require_gfx950(0);
+        return rc ? rc : fail(CS_ERR_INVALID, "handle is NULL");
+    }
+    HIPCHK(hipSetDevice(p->device));
+    if (!p->seg) p->seg = new SegmentState();
+    SegmentState& S = *p->seg;
+    for (hipEvent_t& e : S.sev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    hipStream_t st = p->stream;
+    const size_t esz = pixel_type == CS_PIX_U8 ? 1 : 2;
+    const size_t npx = (size_t)batch * height * width;
+    const void* d_img = image;
+    if (in_kind == CS_MEM_HOST) {
+        if ((rc = S.sm_in.ensure(npx * channels * esz))) return rc;
+        HIPCHK(hipMemcpyAsync(S.sm_in.p, image, npx * channels * esz, hipMemcpyHostToDevice, st));
+        d_img = S.sm_in.p;
+    }
+    void* d_out = plane;
+    if (plane_kind == CS_MEM_HOST) {
+        if ((rc = S.sm_out.ensure(npx * esz))) return rc;
+        d_out = S.sm_out.p;
+    }
+    S.sm_pending = false;
+    if (pixel_type == CS_PIX_U8)
+        rc = smooth_launch<unsigned char>(S, (const unsigned char*)d_img, channels, channel, batch, height, width, wt, params->median != 0,
+                                          (unsigned char*)d_out, st);
+    else
+        rc = smooth_launch<unsigned short>(S, (const unsigned short*)d_img, channels, channel, batch, height, width, wt, params->median != 0,
+                                           (unsigned short*)d_out, st);
+    if (rc) return rc;
+    if (plane_kind == CS_MEM_DEVICE && in_kind == CS_MEM_DEVICE) {
+        S.sm_pending = true;                            // no host synchronisation: the times are read when they are asked for
+        return CS_OK;
+    }
+    if (plane_kind == CS_MEM_HOST) HIPCHK(hipMemcpyAsync(plane, d_out, npx * esz, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));                     // the one host synchronisation: the caller's host buffers are free / filled
+    return smooth_times(S);
+}
+
+int cs_segment_smooth_last_timing(const cs_preproc* p, double* median_ms, double* smooth_ms)
+{
+    if (!p) return fail(CS_ERR_INVALID, "handle is NULL");
+    SegmentState* S = p->seg;
+    if (S && S->sm_pending) {
+        HIPCHK(hipSetDevice(p->device));
+        const int rc = smooth_times(*S);
+        if (rc) return rc;
+    }
+    if (median_ms) *median_ms = S ? S->sm_median_ms : 0.0;
+    if (smooth_ms) *smooth_ms = S ? S->sm_smooth_ms : 0.0;
     return CS_OK;
 }

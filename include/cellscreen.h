@@ -29,7 +29,7 @@
  *   cs_segment_threshold / cs_segment_split
  *        the library's own classical segmenter (no reference counterpart, and no StarDist): Otsu or
  *        fixed threshold, optional hole filling, connected-component labels for the extraction above
- *        (cs_segment_background, cs_segment_local, cs_segment_clean: optional stages before the labels)
+ *        (cs_segment_smooth, cs_segment_background, cs_segment_local, cs_segment_clean: optional stages before the labels)
  *   cs_fit_scaler / cs_fit_pca_moments / cs_fit_pca_subspace / cs_fit_project / cs_fit_ocsvm
  *        RobustScaler / PCA / OneClassSVM fits of create_anomaly_detector
  *                                                 CAE_improved_modeltrain.py:408-427
@@ -559,6 +559,43 @@ int cs_segment_clean(cs_preproc *p, const void *image, int pixel_type, int32_t c
 /* Device time of the last cs_segment_clean: threshold + mask + hole filling, the opening (0 without it), and the labelling,
  * counting and dropping of the area step (0 without it).  Waits for that call's plane if it was left on the device. */
 int cs_segment_clean_last_timing(const cs_preproc *p, double *mask_ms, double *open_ms, double *area_ms);
+
+/* Gaussian smoothing of the segmentation channel, before everything else: for noisy fields, where the threshold shatters a
+ * faint cell into fragments that no cleanup of the mask can put together again.  Integers only, each image on its own:
+ *   median  (optional) the 3 x 3 median of cs_segment_background first: hot pixels go before they are smeared.
+ *   T(i,j)  sum over k = -radius..radius of weights[|k|] * x(i, fold(j + k, width))      (fits 32 bits)
+ *   A(i,j)  sum over k of weights[|k|] * T(fold(i + k, height), j)                       (below 2^48)
+ *   plane   (A + 2^31) >> 32: one rounding to nearest, at the very end.
+ * fold reflects an index about the edges (d c b a | a b c d: scipy's mode='reflect', as cs_segment_local; period 2 * side, so
+ * radius may exceed a side).  The table is part of the input: any non-negative weights with weights[0] >= 1 and weights[0] +
+ * 2 * (weights[1] + ... + weights[radius]) == 65536 are applied exactly; a constant image maps to itself and nothing can
+ * overflow.  cellscreen.segment.smooth_weights(sigma) builds the table of a Gaussian: radius = int(4 * sigma + 0.5), taps
+ * proportional to exp(-k^2 / (2 sigma^2)), rounded down, the rest handed out by largest remainder.  With it the plane is
+ * scipy.ndimage.gaussian_filter(x, sigma, mode='reflect', truncate=4.0) computed in float64, to within 0.5 + top * (2 eps + eps^2),
+ * eps being the summed quantisation error of the taps; the library's own integer output truncates and is not
+ * reproduced bit for bit.
+ * image, pixel_type, channels, channel, batch, height, width, in_kind: as cs_segment_threshold; the channel is read in place.
+ * plane: [batch][height][width] of the same pixel type, plane_kind.  Left on the device it is the `image` of every other
+ *      cs_segment_* call with channels = 1, channel = 0, on the same handle (the same stream: no ordering needed).
+ * Workspace on the device: 4 bytes per pixel (the row pass), one plane of the pixel type more with the median, one more for a
+ * `plane` on the host, and the image itself when it comes from the host; CS_ERR_NOMEM when it does not fit.
+ * Host synchronisations: none when image and plane are both on the device (the plane is complete in stream order; the times
+ * are read when cs_segment_smooth_last_timing asks for them, which waits for the plane), else one.
+ * Bad arguments (NULL params among them, radius outside 1..64, median not 0 or 1, reserved not 0, a negative weight,
+ * weights[0] < 1, a non-zero weight beyond radius, a sum other than 65536): CS_ERR_INVALID before any device work; sides above
+ * 4096, batches above 65535: CS_ERR_UNSUPPORTED; without a gfx950 device (p == NULL): CS_ERR_NO_DEVICE. */
+typedef struct cs_smooth_params {
+    int32_t radius;                   /* 1..64 */
+    int32_t median;                   /* 0 or 1: 3 x 3 median first */
+    int32_t weights[65];              /* weights[k]: the tap at distance k, k = 0..radius; beyond radius: 0 */
+    int32_t reserved;                 /* must be 0 */
+} cs_smooth_params;
+int cs_segment_smooth(cs_preproc *p, const void *image, int pixel_type, int32_t channels, int32_t channel,
+                      int32_t batch, int32_t height, int32_t width, int in_kind,
+                      const cs_smooth_params *params /* not NULL */, void *plane, int plane_kind);
+/* Device time of the last cs_segment_smooth: the median (0 without it) and the two passes.  Waits for that call's plane if it
+ * was left on the device. */
+int cs_segment_smooth_last_timing(const cs_preproc *p, double *median_ms, double *smooth_ms);
 
 /* ---- detector fitting (create_anomaly_detector, CAE_improved_modeltrain.py:394-446) -------- */
 /* The fit of what cs_screen's tail evaluates, for the training set's encoder features

@@ -40,9 +40,18 @@ min_area_ms per image, and the ratios of the cleaned figures to the uncleaned on
 bound and no opening, the extracted cells are compared too.  Then open_ms alone at the radii 1, 3, 7 and 15 with both
 structures, which shows what the radius costs.  No time is a pass condition.
 
+--smooth SIGMA [--denoise] measures the Gaussian smoothing (cs_segment_smooth, ThresholdSegmenter(smooth_sigma=SIGMA)) and writes
+profiles/segment_smooth_bench.json.  The scene is faint cells in noise: every image is 16 fields of
+tests/test_smooth_cpu.py's faint_cell_scene (512 x 512, 40 cells of peak 250 over noise of sigma 100) side by side, cut by
+Otsu's threshold.  One image's smoothed plane and labels are compared with the host restatement (tests/smooth_reference.py)
+first; then, in the same run, the segmenter without smoothing (what it was before the option) and with it: images/s of
+segment_batch and of segment + extract, the label counts, the stage times, smooth_ms per image, and the ratios of the smoothed
+figures to the unsmoothed ones.  Then smooth_ms alone at the sigmas 0.25, 1, 2, 4, 8 and 15.875 (radii 1 to 64), which shows
+what the radius costs.  No time is a pass condition.
+
 Usage: python tools/bench_segment.py [--images 32] [--side 2048] [--cells 1000] [--reps 10] [--warmup 2] [--host-images 4]
                                      [--split [--split-cells 3000] [--split-h 3]] [--background R [--denoise]]
-                                     [--local R [--delta D] [--denoise]] [--clean [--open R] [--min-area A] [--delta D]]"""
+                                     [--local R [--delta D] [--denoise]] [--clean [--open R] [--min-area A] [--delta D]] [--smooth SIGMA [--denoise]]"""
 import argparse
 import json
 import os
@@ -367,6 +376,95 @@ def clean_leg(a):
     print(line)
 
 
+def smooth_leg(a):
+    import torch
+    import segment_reference as R
+    import smooth_reference as SM
+    from build import source_hash
+    from cellscreen import extract as X
+    from cellscreen import segment as S
+    from test_smooth_cpu import faint_cell_scene
+
+    fill = not a.no_fill_holes
+    dev = torch.device("cuda", 0)
+    med = lambda v: float(np.median(v))
+    tiles = a.side // 512
+    if tiles < 1 or a.side % 512:
+        raise SystemExit("--smooth needs --side a multiple of 512: the scene is made of 512 x 512 fields")
+    fields = [faint_cell_scene(seed)[0] for seed in range(tiles * tiles)]
+    base = np.block([[fields[i * tiles + j] for j in range(tiles)] for i in range(tiles)])
+    variants = [base, base[::-1], base[:, ::-1], base[::-1, ::-1]]          # four distinct images from one painting
+    imgs = np.ascontiguousarray(np.stack([variants[b % 4] for b in range(a.images)]))
+    ti = torch.from_numpy(imgs.view(np.int16)).to(dev)
+    torch.cuda.synchronize()
+    common = dict(threshold="otsu", connectivity=a.connectivity, fill_holes=fill)
+    ext = X.CellExtractor(0)
+    plain = S.ThresholdSegmenter(0, extractor=ext, **common)
+    smooth = S.ThresholdSegmenter(0, extractor=ext, smooth_sigma=a.smooth, denoise=a.denoise, **common)
+
+    def timed(fn, seg):
+        walls, stages = [], []
+        for k in range(a.warmup + a.reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = fn()
+            torch.cuda.synchronize()
+            if k >= a.warmup:
+                walls.append(time.perf_counter() - t0)
+                stages.append(seg.last_timing())
+        return out, walls, stages
+
+    # outputs first: one image's smoothed plane and labels against the host restatement
+    one = ti[:1].contiguous()
+    plane = smooth.smooth_batch(one)
+    labels, n, thr = smooth.segment_batch(one)
+    want = SM.smooth_sigma(imgs[0], a.smooth, median=a.denoise)
+    assert np.array_equal(plane[0].cpu().numpy().view(np.uint16), want), "smoothed plane differs from the restatement"
+    hl, hn, ht = R.segment(want, "otsu", a.connectivity, fill)
+    assert hn == int(n[0]) and ht == int(thr[0]) and np.array_equal(labels[0].cpu().numpy(), hl), "labels differ from the restatement"
+
+    spread = lambda stages, k: [round(med([t[k] for t in stages]), 4), round(min(t[k] for t in stages), 4),
+                                round(max(t[k] for t in stages), 4)]
+    wall3 = lambda walls: [round(med(walls) * 1e3, 3), round(min(walls) * 1e3, 3), round(max(walls) * 1e3, 3)]
+    res = {"tool": "bench_segment --smooth", "source_hash": source_hash(), "images": a.images, "side": a.side,
+           "connectivity": a.connectivity, "fill_holes": fill, "smooth_sigma": a.smooth, "smooth_radius": len(S.smooth_weights(a.smooth)) - 1,
+           "denoise": bool(a.denoise), "cells_painted_per_image": 40 * tiles * tiles, "reps": a.reps, "warmup": a.warmup,
+           "outputs_equal": True}
+    legs = {}
+    for name, seg in (("unsmoothed", plain), ("smoothed", smooth)):
+        (_, n_lab, _), walls, stages = timed(lambda: seg.segment_batch(ti), seg)
+        r, chain, _ = timed(lambda: ext.extract_batch(ti, seg.segment_batch(ti)[0]), seg)
+        legs[name] = dict(walls=walls, chain=chain)
+        res[name] = {"labels_per_image": round(float(n_lab.mean()), 1), "regions_measured": len(r.regions),
+                     "cells_extracted": int(r.cells.shape[0]), "segment_images_per_s": round(a.images / med(walls), 2),
+                     "segment_wall_ms": wall3(walls), "segment_extract_images_per_s": round(a.images / med(chain), 2),
+                     "segment_extract_wall_ms": wall3(chain),
+                     **{k: spread(stages, k) for k in sorted(stages[0])}}
+    px = a.side * a.side
+    res["smooth_ms_per_image"] = round(res["smoothed"]["smooth_ms"][0] / a.images, 5)
+    res["smooth_ns_per_pixel"] = round(res["smoothed"]["smooth_ms"][0] * 1e6 / (a.images * px), 4)
+    res["smoothed_over_unsmoothed_segment_time"] = round(med(legs["smoothed"]["walls"]) / med(legs["unsmoothed"]["walls"]), 3)
+    res["smoothed_over_unsmoothed_segment_extract_time"] = round(med(legs["smoothed"]["chain"]) / med(legs["unsmoothed"]["chain"]), 3)
+    plain_ms = med(legs["unsmoothed"]["walls"]) * 1e3 / a.images
+    res["sigma_sweep"] = []
+    for sigma in (0.25, 1, 2, 4, 8, 15.875):
+        seg = S.ThresholdSegmenter(0, extractor=ext, smooth_sigma=sigma, **common)
+        _, _, stages = timed(lambda: seg.smooth_batch(ti), seg)
+        per = med([t["smooth_ms"] for t in stages]) / a.images
+        res["sigma_sweep"].append({"smooth_sigma": sigma, "radius": len(S.smooth_weights(sigma)) - 1, "smooth_ms_per_image": round(per, 5),
+                                   "smooth_ns_per_pixel": round(per * 1e6 / px, 4),
+                                   "effective_gb_per_s": round(12.0 * px / (per * 1e-3) / 1e9, 1),       # 2 + 4 + 4 + 2 bytes per pixel
+                                   "over_unsmoothed_segment_time": round(per / plain_ms, 4)})
+    ext.close()
+    line = json.dumps(res)
+    out = a.out if a.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "segment_smooth_bench.json")
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            f.write(line + "\n")
+    print(line)
+
+
 DEFAULT_OUT = os.path.join(ROOT, "profiles", "segment_bench.json")
 TOPHAT_RADIUS = 51                                      # the top-hat that --local is set beside: --background 51's figure
 
@@ -387,14 +485,20 @@ def main():
     ap.add_argument("--split-h", type=int, default=3)
     ap.add_argument("--background", type=int, default=None, metavar="R",
                     help="measure the background correction of radius R (profiles/segment_background_bench.json)")
-    ap.add_argument("--denoise", action="store_true", help="with --background or --local: the 3 x 3 median first")
+    ap.add_argument("--denoise", action="store_true", help="with --background, --local or --smooth: the 3 x 3 median first")
     ap.add_argument("--local", type=int, default=None, metavar="R",
                     help="measure the local mean threshold of radius R (profiles/segment_local_bench.json)")
     ap.add_argument("--delta", type=int, default=0, metavar="D", help="with --local or --clean: counts above the local mean")
     ap.add_argument("--clean", action="store_true", help="measure the mask cleanup on a speckled scene (profiles/segment_clean_bench.json)")
     ap.add_argument("--open", type=int, default=None, metavar="R", help="with --clean: open_radius")
     ap.add_argument("--min-area", type=int, default=None, metavar="A", help="with --clean: min_area (50 when --open is not given either)")
+    ap.add_argument("--smooth", type=float, default=None, metavar="SIGMA",
+                    help="measure the Gaussian smoothing on a field of faint cells in noise (profiles/segment_smooth_bench.json)")
     a = ap.parse_args()
+    if a.smooth is not None:
+        if a.split or a.background is not None or a.local is not None or a.clean or a.delta:
+            ap.error("--smooth is measured on its own")
+        return smooth_leg(a)
     if (a.open is not None or a.min_area is not None) and not a.clean:
         ap.error("--open and --min-area need --clean")
     if a.clean:
