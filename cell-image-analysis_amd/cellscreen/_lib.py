@@ -108,6 +108,10 @@ class CSSplitParams(C.Structure):
     _fields_ = [("h", C.c_int32)]
 
 
+class CSSplitIntensityParams(C.Structure):
+    _fields_ = [("depth", C.c_int32), ("min_contrast", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 class CSBackgroundParams(C.Structure):
     _fields_ = [("radius", C.c_int32), ("median", C.c_int32)]
 
@@ -172,6 +176,12 @@ SIGNATURES = {
                               C.POINTER(CSSplitParams), _P, _I, _P, _P, _P]),
     "cs_segment_split_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                           C.POINTER(C.c_double)]),
+    "cs_segment_split_intensity": (_I, [_P, _P, _I, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _I,
+                                        C.POINTER(CSSegmentParams), C.POINTER(CSSplitIntensityParams), _P, _I, C.c_int32, C.c_int32,
+                                        _P, _I, _P, _P, _P]),
+    "cs_segment_split_intensity_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                    C.POINTER(C.c_double)]),
+    "cs_segment_split_last_syncs": (_I, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "cs_segment_background": (_I, [_P, _P, _I, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _I,
                                    C.POINTER(CSBackgroundParams), _P, _I]),
     "cs_segment_background_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),

@@ -6,8 +6,18 @@ It is NOT StarDist and does not try to be: it is a classical segmenter for brigh
 cells that touch come out as one region, which the extraction's area and eccentricity rules then judge like any other region.
 With split_touching=True such regions are cut at their necks by an exact integer distance-transform watershed
 (cs_segment_split; tests/split_reference.py restates it): seeds are the maxima of the distance to the background that stand
-split_h half pixels above their saddles.  Cells that overlap without a neck, and cores deeper than 127 px, stay whole; with
-connectivity 2 the cut between two equal cells is skewed, so connectivity 1 stays the default.
+split_h half pixels above their saddles.  Cells that overlap without a neck, and cores deeper than 127 px, stay whole under
+that rule (it sees the mask alone); with connectivity 2 the cut between two equal cells is skewed, so connectivity 1 stays the
+default.
+split_by="intensity" (with split_touching=True) is for the cells without a neck: the same watershed on heights taken from the
+image (cs_segment_split_intensity; tests/split_intensity_reference.py restates it).  Each component's own range of the plane
+the threshold saw (after smooth_sigma and background_radius) is stretched to 254 levels, Hq = 1 + (G - lo) * 254 // max(hi - lo,
+split_contrast, 1), and two bright cores are cut apart along the valley between them when it lies split_depth levels below the
+lower core.  The scale is per component, so a dim cell beside a bright field keeps its own 254 levels and nothing depends on
+the rest of the batch; a component flatter than split_contrast counts is not stretched, the guard against splitting on noise.
+It needs a smoothed plane: pass smooth_sigma (1.5 on the scene it was specified on), because on a noisy plane every noise peak
+deeper than split_depth is a seed and a cell shatters into dozens of regions.  And cells that overlap in projection add up,
+so the lens between two cores can be the brightest spot and come out as a third region.
 What it computes is exact: the threshold is scikit-image 0.18.3's threshold_otsu of the channel (an integer), the mask is
 `channel > threshold` (after scipy.ndimage.binary_fill_holes with fill_holes), and the labels are scipy.ndimage.label's
 (= skimage.measure.label's) ids, as restated in tests/segment_reference.py; neither library is a dependency.
@@ -52,6 +62,7 @@ correction, the threshold, the cleanup, the labels and the split see the smoothe
     seg = ThresholdSegmenter()
     labels, n_labels, thresholds = seg.segment_batch(images)          # numpy in, numpy out; CUDA tensors in, CUDA tensor out
     seg = ThresholdSegmenter(split_touching=True)                      # the same, touching cells apart
+    seg = ThresholdSegmenter(split_touching=True, split_by="intensity", smooth_sigma=1.5)     # ... cells without a neck too
     seg = ThresholdSegmenter(background_radius=51)                     # uneven illumination flattened before the threshold
     seg = ThresholdSegmenter(threshold="local", local_radius=25, local_delta=60)      # bright and dim cells in one field
     seg = ThresholdSegmenter(threshold="local", local_radius=25, local_delta=40, min_area=50)         # ... without the speckle
@@ -108,6 +119,38 @@ def split_params(split_touching: bool = False, split_h: int = 3) -> Optional[L.C
         return None
     p = L.CSSplitParams()
     p.h = int(split_h)
+    return p
+
+
+SPLIT_DEPTH, SPLIT_CONTRAST = 16, 0                       # the defaults of split_by="intensity"
+
+
+def split_intensity_params(split_touching: bool = False, split_by="distance", split_h: int = 3, split_depth: int = SPLIT_DEPTH,
+                           split_contrast: int = SPLIT_CONTRAST) -> Optional[L.CSSplitIntensityParams]:
+    """cs_split_intensity_params from the Python arguments, None with split_by="distance"; anything out of range raises before
+    a handle exists.  split_depth and split_contrast belong to "intensity" alone, split_h to "distance" alone, and "intensity"
+    needs split_touching=True: it is a way of splitting, not a switch of its own."""
+    if not isinstance(split_by, str):
+        raise TypeError(f"split_by must be 'distance' or 'intensity', got {type(split_by).__name__}")
+    if split_by not in ("distance", "intensity"):
+        raise ValueError(f"split_by must be 'distance' or 'intensity', got {split_by!r}")
+    for name, v in (("split_depth", split_depth), ("split_contrast", split_contrast)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError(f"{name} must be an integer, got {type(v).__name__}")
+    if not 1 <= int(split_depth) <= 254:
+        raise ValueError(f"split_depth {split_depth} outside 1..254")
+    if not 0 <= int(split_contrast) <= 65535:
+        raise ValueError(f"split_contrast {split_contrast} outside 0..65535")
+    if split_by == "distance":
+        if int(split_depth) != SPLIT_DEPTH or int(split_contrast) != SPLIT_CONTRAST:
+            raise ValueError("split_depth and split_contrast belong to split_by='intensity'")
+        return None
+    if not split_touching:
+        raise ValueError("split_by='intensity' needs split_touching=True")
+    if split_h != 3:
+        raise ValueError("split_h belongs to split_by='distance'; the intensity split takes split_depth")
+    p = L.CSSplitIntensityParams()
+    p.depth, p.min_contrast = int(split_depth), int(split_contrast)
     return p
 
 
@@ -242,7 +285,11 @@ class ThresholdSegmenter:
     by foreground becomes foreground before labelling.  extractor: a CellExtractor whose handle and stream to share, so
     that labels left on the device feed its extract_batch in stream order.  split_touching: cut touching cells apart
     (cs_segment_split, see the module text); split_h: the depth in half pixels (1..255) a saddle needs below the lower of
-    its two peaks to separate them.  background_radius: None, or the radius r (1..255) of the white top-hat that flattens the
+    its two peaks to separate them.  split_by: "distance" (that rule) or "intensity" (split_touching=True still switches the
+    split on): the heights come from the plane the threshold saw, see the module text; split_depth (1..254 of a component's 254
+    levels, default 16: on the specifying scene 8 to 20 give the same regions) is how far below the lower core a valley must lie,
+    split_contrast (0..65535 counts) the range below which a component is not stretched.  These two belong to "intensity" alone
+    and split_h to "distance" alone.  background_radius: None, or the radius r (1..255) of the white top-hat that flattens the
     channel before the threshold (see the module text); denoise: a 3 x 3 median before the top-hat.  With numpy input the
     corrected plane makes one extra round trip through the host; CUDA tensors are the fast path.
     threshold="local": the local mean threshold of the module text in the global one's place, with local_radius (1..255,
@@ -260,12 +307,15 @@ class ThresholdSegmenter:
                  extractor: Optional[CellExtractor] = None, split_touching: bool = False, split_h: int = 3,
                  background_radius: Optional[int] = None, denoise: bool = False, local_radius: Optional[int] = None,
                  local_delta: int = 0, local_floor: int = -1, open_radius: Optional[int] = None, open_connectivity: int = 2,
-                 min_area: Optional[int] = None, smooth_sigma: Optional[float] = None):
+                 min_area: Optional[int] = None, smooth_sigma: Optional[float] = None, split_by: str = "distance",
+                 split_depth: int = SPLIT_DEPTH, split_contrast: int = SPLIT_CONTRAST):
         self._params, self._local, self._background = _threshold_mode(threshold, connectivity, fill_holes, local_radius, local_delta,
                                                                       local_floor, background_radius, denoise, smooth_sigma)
         self._smooth = smooth_params(smooth_sigma, denoise)
         self.smooth_sigma = None if smooth_sigma is None else float(smooth_sigma)
         self._split = split_params(split_touching, split_h)
+        self._split_intensity = split_intensity_params(split_touching, split_by, split_h, split_depth, split_contrast)
+        self.split_by, self.split_depth, self.split_contrast = split_by, int(split_depth), int(split_contrast)
         self._clean = clean_params(open_radius, open_connectivity, min_area)
         # what labels the cleaned 0 / 1 plane: the fixed threshold 0 and no second hole filling
         self._after_clean = segment_params(0, connectivity, False)
@@ -493,7 +543,7 @@ class ThresholdSegmenter:
         Returns (labels, n_labels, thresholds): labels int32 [B,H,W] (0 = background, ids 1.. in raster order of each
         component's first pixel), numpy for numpy input and a CUDA tensor for tensor input; n_labels and thresholds int32
         numpy [B].  return_distance (split_touching only): a fourth result, uint8 [B,H,W] where the labels are: the distance
-        to the background in half pixels, capped at 255."""
+        to the background in half pixels, capped at 255; with split_by="intensity" the heights Hq the split used instead."""
         B, H, W, Cn, channel, ptype, on_dev = self._check(images, channel)
         if return_distance and self._split is None:
             raise ValueError("return_distance needs split_touching=True: the plain segmenter computes no distances")
@@ -506,6 +556,8 @@ class ThresholdSegmenter:
             # comes after everything that reads the plane
             images = self._correct(images, B, H, W, Cn, channel, ptype, on_dev)
             Cn, channel = 1, 0
+        # what split_by="intensity" takes its heights from: the plane the threshold stage sees, never a 0 / 1 plane
+        guide, guide_cn, guide_channel, guide_ptype = images, Cn, channel, ptype
         if self._local is not None:
             # the 0 / 1 plane in the channel's place, cut at the fixed threshold 0: hole filling, labels and the split as they are
             images = self._local_mask(images, B, H, W, Cn, channel, ptype, on_dev)
@@ -545,9 +597,15 @@ class ThresholdSegmenter:
                 L.order_after_torch(self._lib.cs_preproc_wait_stream, self._handle, dist)
             else:
                 dist = np.empty((B, H, W), np.uint8)
-        L.check(self._lib.cs_segment_split(self._handle, L._ptr(images), ptype, Cn, channel, B, H, W, kind, C.byref(params),
-                                           C.byref(self._split), L._ptr(labels), kind, n_labels.ctypes.data,
-                                           thresholds.ctypes.data, L._ptr(dist)))
+        if self._split_intensity is not None:
+            L.check(self._lib.cs_segment_split_intensity(self._handle, L._ptr(images), ptype, Cn, channel, B, H, W, kind,
+                                                         C.byref(params), C.byref(self._split_intensity), L._ptr(guide), guide_ptype,
+                                                         guide_cn, guide_channel, L._ptr(labels), kind, n_labels.ctypes.data,
+                                                         thresholds.ctypes.data, L._ptr(dist)))
+        else:
+            L.check(self._lib.cs_segment_split(self._handle, L._ptr(images), ptype, Cn, channel, B, H, W, kind, C.byref(params),
+                                               C.byref(self._split), L._ptr(labels), kind, n_labels.ctypes.data,
+                                               thresholds.ctypes.data, L._ptr(dist)))
         if reported is not None:
             thresholds = reported
         if self._local is not None:
@@ -555,7 +613,8 @@ class ThresholdSegmenter:
         return (labels, n_labels, thresholds, dist) if return_distance else (labels, n_labels, thresholds)
 
     def last_timing(self):
-        """Device milliseconds of the last call's stages; with split_touching the stages of cs_segment_split; with
+        """Device milliseconds of the last call's stages; with split_touching the stages of cs_segment_split (with
+        split_by="intensity" those of cs_segment_split_intensity: height_ms where the other has distance_ms); with
         background_radius also median_ms and background_ms (the top-hat) of the last correction; with threshold="local" also
         local_median_ms and local_ms (the sums and the comparison) of the last mask; with open_radius or min_area also open_ms
         and min_area_ms of the last cleanup (0 for a step that is off), and threshold_ms is then the labelling call's cut of the
@@ -573,8 +632,21 @@ class ThresholdSegmenter:
             L.check(self._lib.cs_segment_last_timing(self._handle, C.byref(a), C.byref(b)))
             return dict({"threshold_ms": a.value, "label_ms": b.value}, **extra)
         v = [C.c_double() for _ in range(4)]
+        if self._split_intensity is not None:
+            L.check(self._lib.cs_segment_split_intensity_last_timing(self._handle, *(C.byref(x) for x in v)))
+            return dict(zip(("threshold_ms", "height_ms", "seed_ms", "flood_ms"), (x.value for x in v)), **extra)
         L.check(self._lib.cs_segment_split_last_timing(self._handle, *(C.byref(x) for x in v)))
         return dict(zip(("threshold_ms", "distance_ms", "seed_ms", "flood_ms"), (x.value for x in v)), **extra)
+
+
+    def last_host_syncs(self) -> int:
+        """Host synchronisations of the last split_touching call (either split_by): the reads of the control word between
+        groups of reconstruction and flood rounds, and the final one."""
+        if self._split is None:
+            raise ValueError("last_host_syncs needs split_touching=True: the plain segmenter synchronises once")
+        a, b = C.c_int32(), C.c_int32()
+        L.check(self._lib.cs_segment_split_last_syncs(self._handle, C.byref(a), C.byref(b)))
+        return a.value + b.value + 1
 
 
 def threshold_cell_extractor(device_id: int = 0, out_hw=(OUT_SIDE, OUT_SIDE), threshold="otsu", connectivity: int = 1,
@@ -582,7 +654,8 @@ def threshold_cell_extractor(device_id: int = 0, out_hw=(OUT_SIDE, OUT_SIDE), th
                              background_radius: Optional[int] = None, denoise: bool = False, local_radius: Optional[int] = None,
                              local_delta: int = 0, local_floor: int = -1, open_radius: Optional[int] = None,
                              open_connectivity: int = 2, mask_min_area: Optional[int] = None,
-                             smooth_sigma: Optional[float] = None, **qc):
+                             smooth_sigma: Optional[float] = None, split_by: str = "distance", split_depth: int = SPLIT_DEPTH,
+                             split_contrast: int = SPLIT_CONTRAST, **qc):
     """The `cell_extractor(image_path) -> (cells, stats)` that ProductionMutantScreening and create_training_dataset accept,
     with the built-in segmenter in StarDist's place: the file is read (extract.read_image / split_channels), uploaded once,
     segmented and extracted on one handle, and the labels never leave the device.  Not StarDist: see the module text.
@@ -592,11 +665,13 @@ def threshold_cell_extractor(device_id: int = 0, out_hw=(OUT_SIDE, OUT_SIDE), th
     extraction still reads the raw analysis channel, so the intensity rules and the crops are what they are without it.
     open_radius and open_connectivity as for ThresholdSegmenter, and mask_min_area for its min_area: the mask cleanup before
     the labels.  The name differs here because min_area is, and stays, the extraction's own area rule among **qc.
-    smooth_sigma as for ThresholdSegmenter: the segmentation channel is smoothed first, the extraction reads the raw one."""
+    smooth_sigma as for ThresholdSegmenter: the segmentation channel is smoothed first, the extraction reads the raw one.
+    split_by, split_depth and split_contrast as for ThresholdSegmenter; split_by="intensity" wants smooth_sigma."""
     out_hw = check_out_hw(out_hw)
     _threshold_mode(threshold, connectivity, fill_holes, local_radius, local_delta, local_floor, background_radius, denoise,
                     smooth_sigma)
     split_params(split_touching, split_h)
+    split_intensity_params(split_touching, split_by, split_h, split_depth, split_contrast)
     clean_params(open_radius, open_connectivity, mask_min_area)
     qc_params(**qc)
     st = {}
@@ -614,7 +689,8 @@ def threshold_cell_extractor(device_id: int = 0, out_hw=(OUT_SIDE, OUT_SIDE), th
                                          split_touching=split_touching, split_h=split_h, background_radius=background_radius,
                                          denoise=denoise, local_radius=local_radius, local_delta=local_delta,
                                          local_floor=local_floor, open_radius=open_radius, open_connectivity=open_connectivity,
-                                         min_area=mask_min_area, smooth_sigma=smooth_sigma)
+                                         min_area=mask_min_area, smooth_sigma=smooth_sigma, split_by=split_by,
+                                         split_depth=split_depth, split_contrast=split_contrast)
         host = np.ascontiguousarray(img)[None]
         dev = torch.from_numpy(host.view(np.int16) if host.dtype == np.uint16 else host).to(torch.device("cuda", device_id))
         labels, _, _ = st["s"].segment_batch(dev, channel=seg_ch)

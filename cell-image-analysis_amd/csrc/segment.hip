@@ -2,8 +2,8 @@
 // it on an integer image, or a fixed one), optional hole filling, and connected-component labelling with scipy.ndimage.label's
 // numbering.  It is NOT StarDist: by default touching cells come out as one region, which the extraction's area and
 // eccentricity rules then judge; cs_segment_split (below, "split_touching") cuts such regions at their necks with an exact
-// integer distance-transform watershed.  The labels feed cs_extract_measure on the same handle and stream without leaving
-// the device.
+// integer distance-transform watershed, cs_segment_split_intensity along the intensity valleys between their cores.  The
+// labels feed cs_extract_measure on the same handle and stream without leaving the device.
 //
 // Kernels, per batch:
 //   sg_hist      exact integer histogram of one channel.  A workgroup owns a contiguous part of one image and one window of
@@ -22,6 +22,8 @@
 //   sg_edge / sg_fill   (fill_holes) the same labelling on the inverted mask, 4-connected; background components without a
 //                pixel on the image border become foreground (scipy.ndimage.binary_fill_holes, default structure).
 //   sp_*         cs_segment_split only: see "split_touching" further down.
+//   si_*         cs_segment_split_intensity only: the same watershed on heights made from the image (each component's own
+//                intensity range stretched to 254 levels) instead of from the mask; see "split_by intensity".
 //   bg_*         cs_segment_background only: the optional correction of the channel BEFORE all of the above (3x3 median, white
 //                top-hat); see "background correction" further down.  Its plane then stands in the channel's place.
 //   lt_*         cs_segment_local only: the local mean threshold in the global one's place; see "local mean threshold".
@@ -801,6 +803,92 @@ __global__ __launch_bounds__(SG_THREADS) void sp_parent(int HW, const unsigned l
     if (threadIdx.x == 0) chunk_cnt[(size_t)blockIdx.y * nchunks + blockIdx.x] = wc[0] + wc[1] + wc[2] + wc[3];
 }
 
+// ---- split_by intensity (cs_segment_split_intensity): the same watershed on a height plane made from the image ---------------------
+// A function of the mask and the guide plane G alone (tests/split_intensity_reference.py restates it):
+//   lo_c, hi_c  the smallest and largest G over the pixels of component c of the mask (filled holes included);
+//   Hq   = 1 + ((G - lo_c) * 254) / max(hi_c - lo_c, min_contrast, 1) on the mask, a byte in 1..255 (65535 * 254 fits 32 bits),
+//          0 on background: every component has its own 254 levels, and one flatter than min_contrast is not stretched;
+//   then R, the seeds, the flood and the numbering of the distance split, with Hq in Dq's place and depth in h's.
+// Kernels:
+//   si_range     lo / hi per component at the root's slot of two per-pixel int planes (they live in the key buffer, which the
+//                flood fills only later): atomicMin / atomicMax per run of equal roots among the first rounds' leaders of a wave,
+//                as cl_count -- the lanes that share the leader's root reduce their minimum and maximum across the wave first.
+//                A minimum does not depend on the order it is taken in.
+//   si_height    Hq and the marker max(Hq - depth, 0); the batch's largest Hq by one atomicMax per wave, as sp_rows.
+// Components come from label_mask, so one spread over many tiles has one root.  Integer atomics only, no floating point.
+static constexpr int SI_NONE = 0x7f7f7f7f;              // lo before the first pixel: what a memset of 0x7f leaves
+
+template <typename PIX>
+__device__ inline int si_pixel(const PIX* __restrict__ guide, int C, int ch, size_t px) { return (int)guide[px * C + ch]; }
+
+// grid (nchunks, B); lo: [B][HW] filled with SI_NONE, hi: [B][HW] zero before
+template <typename PIX>
+__global__ __launch_bounds__(SG_THREADS) void si_range(int HW, const int* __restrict__ P, const PIX* __restrict__ guide, int C, int ch,
+                                                       int* __restrict__ lo, int* __restrict__ hi)
+{
+    constexpr int AG = __HIP_MEMORY_SCOPE_AGENT;
+    const size_t base = (size_t)blockIdx.y * HW;
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = blockIdx.x * SG_CHUNK + k * SG_THREADS + threadIdx.x;
+        const int root = i < HW ? P[base + i] : -1;
+        const int g = root >= 0 ? si_pixel(guide, C, ch, base + i) : 0;
+        bool pend = root >= 0;
+#pragma unroll
+        for (int round = 0; round < 2; ++round) {
+            const unsigned long long m = __ballot(pend);
+            if (m == 0ull) break;
+            const int leader = __ffsll((long long)m) - 1;
+            const int rl = __shfl(root, leader);
+            const bool mine = pend && root == rl;
+            int mn = mine ? g : SI_NONE, mx = mine ? g : 0;
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) {
+                mn = min(mn, __shfl_xor(mn, d));
+                mx = max(mx, __shfl_xor(mx, d));
+            }
+            if (lane == leader) {
+                if (mn < __hip_atomic_load(lo + base + rl, __ATOMIC_RELAXED, AG)) atomicMin(&lo[base + rl], mn);
+                if (mx > __hip_atomic_load(hi + base + rl, __ATOMIC_RELAXED, AG)) atomicMax(&hi[base + rl], mx);
+            }
+            if (mine) pend = false;
+        }
+        if (pend) {
+            if (g < __hip_atomic_load(lo + base + root, __ATOMIC_RELAXED, AG)) atomicMin(&lo[base + root], g);
+            if (g > __hip_atomic_load(hi + base + root, __ATOMIC_RELAXED, AG)) atomicMax(&hi[base + root], g);
+        }
+    }
+}
+
+// grid (nchunks, B)
+template <typename PIX>
+__global__ __launch_bounds__(SG_THREADS) void si_height(int HW, const int* __restrict__ P, const PIX* __restrict__ guide, int C, int ch,
+                                                        const int* __restrict__ lo, const int* __restrict__ hi, int depth, int min_contrast,
+                                                        unsigned char* __restrict__ hq, unsigned char* __restrict__ R, int* __restrict__ ctrl)
+{
+    const size_t base = (size_t)blockIdx.y * HW;
+    int top = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = blockIdx.x * SG_CHUNK + k * SG_THREADS + threadIdx.x;
+        if (i >= HW) continue;
+        const int root = P[base + i];
+        int q = 0;
+        if (root >= 0) {
+            const int l = lo[base + root];
+            const unsigned int span = (unsigned int)max(max(hi[base + root] - l, min_contrast), 1);
+            q = 1 + (int)((unsigned int)(si_pixel(guide, C, ch, base + i) - l) * 254u / span);
+        }
+        hq[base + i] = (unsigned char)q;
+        R[base + i] = (unsigned char)max(q - depth, 0);
+        top = max(top, q);
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) top = max(top, __shfl_xor(top, d));
+    if ((threadIdx.x & 63) == 0 && top > 0) atomicMax(&ctrl[CT_VMAX], top);
+}
+
 // ---- background correction (cs_segment_background): 3x3 median, white top-hat by a flat square ------------------------------
 // out = x - dilate(erode(x)) with the square of side w = 2r + 1, windows clipped to the image (DESIGN 3l;
 // tests/background_reference.py restates it).  The square is separable and min / max passes commute across axes:
@@ -1325,7 +1413,8 @@ __global__ __launch_bounds__(SG_THREADS) void cl_drop(int HW, const int* __restr
 // ---- host state ---------------------------------------------------------------------------------------------------------------
 struct SegmentState {
     DevBuf img, lab, mask, parent, slab, hist, thr, chunks, counts;
-    DevBuf dq, rec, key, ttop, ctrl;                    // cs_segment_split only
+    DevBuf dq, rec, key, ttop, ctrl;                    // cs_segment_split and cs_segment_split_intensity only
+    DevBuf si_guide;                                    // cs_segment_split_intensity only: a guide uploaded from the host
     DevBuf bg_in, bg_med, bg_a, bg_b, bg_out;           // cs_segment_background only: upload, median, two planes, host staging
     DevBuf lt_in, lt_med, lt_sum, lt_out;               // cs_segment_local only: upload, median, row sums, host staging
     DevBuf cl_out;                                      // cs_segment_clean only: host staging
@@ -1349,6 +1438,8 @@ struct SegmentState {
     double bg_median_ms = 0.0, bg_tophat_ms = 0.0;
     double threshold_ms = 0.0, label_ms = 0.0;
     double sp_threshold_ms = 0.0, sp_distance_ms = 0.0, sp_seed_ms = 0.0, sp_flood_ms = 0.0;
+    double si_threshold_ms = 0.0, si_height_ms = 0.0, si_seed_ms = 0.0, si_flood_ms = 0.0;
+    int sp_recon_reads = 0, sp_flood_reads = 0;         // control-word reads (one host synchronisation each) of the last split of either kind
     ~SegmentState()
     {
         for (hipEvent_t e : ev)
@@ -1693,6 +1784,106 @@ static int clean_times(SegmentState& S)
     return CS_OK;
 }
 
+// The workspace of the two splits beyond segment_mask's: heights, reconstruction, keys, tile tops, control words.
+struct SplitCall {
+    dim3 tgrid;
+    size_t ntiles;
+};
+
+static int split_workspace(SegmentState& S, const SegmentCall& c, SplitCall& w)
+{
+    w.tgrid = dim3((unsigned)((c.W + SG_TW - 1) / SG_TW), (unsigned)((c.H + SG_TH - 1) / SG_TH), (unsigned)c.batch);
+    w.ntiles = (size_t)w.tgrid.x * w.tgrid.y * w.tgrid.z;
+    int rc;
+    if ((rc = S.dq.ensure(c.npx)) || (rc = S.rec.ensure(c.npx)) || (rc = S.key.ensure(c.npx * sizeof(unsigned long long))) ||
+        (rc = S.ttop.ensure(w.ntiles)) || (rc = S.ctrl.ensure(CT_N * sizeof(int))))
+        return rc;
+    return CS_OK;
+}
+
+// What cs_segment_split and cs_segment_split_intensity share once the height plane (S.dq), the marker (S.rec) and the batch's
+// largest height (ctrl[CT_VMAX]) are on the stream: ev[2], the reconstruction, the seeds, the flood, the numbering, the copies
+// out and the one final synchronisation.  times_ms: the four spans between ev[0] .. ev[4].  dist: the optional copy of S.dq.
+static int split_watershed(SegmentState& S, const SegmentCall& c, const SplitCall& w, int conn8, hipStream_t st, int32_t* labels,
+                           int labels_kind, int32_t* n_labels, int32_t* thresholds, uint8_t* dist, double* times_ms)
+{
+    const int H = c.H, W = c.W, HW = c.HW;
+    const dim3 tgrid = w.tgrid;
+    const size_t ntiles = w.ntiles;
+    unsigned char *mask = S.mask.as<unsigned char>(), *dq = S.dq.as<unsigned char>(), *rec = S.rec.as<unsigned char>();
+    unsigned long long* key = S.key.as<unsigned long long>();
+    int *ctrl = S.ctrl.as<int>(), *parent = S.parent.as<int>();
+    const dim3 one(1);
+    HIPCHK(hipEventRecord(S.ev[2], st));
+
+    // h-maxima: reconstruction in rounds, read back once per group of rounds; the bound of HW rounds never binds in practice
+    hipLaunchKernelGGL(sp_start, one, one, 0, st, ctrl, 0);
+    S.sp_recon_reads = S.sp_flood_reads = 0;
+    for (int active = 1; active; ++S.sp_recon_reads) {
+        for (int r = 0; r < SP_RECON_GROUP; ++r) {
+            hipLaunchKernelGGL(sp_recon, tgrid, dim3(SG_THREADS), 0, st, dq, H, W, conn8, rec, ctrl);
+            hipLaunchKernelGGL(sp_advance_recon, one, one, 0, st, ctrl, HW);
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(&active, ctrl + CT_ACTIVE, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    // seeds: plateaus of equal R, those without a higher neighbour, ranked; the flags live in the key buffer, the ids in the labels
+    int* drop = (int*)key;
+    HIPCHK(hipMemsetAsync(drop, 0, c.npx * sizeof(int), st));
+    HIPCHK(label_mask(mask, c.batch, H, W, 0, conn8, parent, nullptr, c.nchunks, st, rec));
+    hipLaunchKernelGGL(sp_higher, c.pgrid, dim3(SG_THREADS), 0, st, H, W, conn8, rec, parent, drop);
+    hipLaunchKernelGGL(sp_seedcount, c.pgrid, dim3(SG_THREADS), 0, st, HW, parent, drop, S.chunks.as<int>(), c.nchunks);
+    hipLaunchKernelGGL(sg_scan, dim3((unsigned)c.batch), dim3(HIST_THREADS), 0, st, S.chunks.as<int>(), c.nchunks, S.counts.as<int>());
+    hipLaunchKernelGGL(sg_rank<true>, c.pgrid, dim3(SG_THREADS), 0, st, HW, parent, S.chunks.as<int>(), c.nchunks, c.d_lab, (const int*)drop);
+    hipLaunchKernelGGL(sp_seedkey, c.pgrid, dim3(SG_THREADS), 0, st, HW, parent, c.d_lab, key);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(S.ev[3], st));
+
+    // flood, level by level from the batch's largest Dq; then each region's first pixel and the numbering
+    HIPCHK(hipMemsetAsync(S.ttop.p, 0xff, ntiles, st));
+    hipLaunchKernelGGL(sp_start, one, one, 0, st, ctrl, 1);
+    for (int level = 1; level >= 1; ++S.sp_flood_reads) {
+        for (int r = 0; r < SP_FLOOD_GROUP; ++r) {
+            hipLaunchKernelGGL(sp_flood, tgrid, dim3(SG_THREADS), 0, st, dq, H, W, conn8, key, S.ttop.as<unsigned char>(), ctrl);
+            hipLaunchKernelGGL(sp_advance_flood, one, one, 0, st, ctrl, HW);
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(&level, ctrl + CT_LEVEL, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    HIPCHK(hipMemsetAsync(c.d_lab, 0x7f, c.npx * sizeof(int), st));
+    hipLaunchKernelGGL(sp_first, c.pgrid, dim3(SG_THREADS), 0, st, HW, key, c.d_lab);
+    hipLaunchKernelGGL(sp_parent, c.pgrid, dim3(SG_THREADS), 0, st, HW, key, c.d_lab, parent, S.chunks.as<int>(), c.nchunks);
+    HIPCHK(hipGetLastError());
+    HIPCHK(number_regions(S, c, st));
+    HIPCHK(hipEventRecord(S.ev[4], st));
+    HIPCHK(hipMemcpyAsync(n_labels, S.counts.p, c.batch * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (thresholds) HIPCHK(hipMemcpyAsync(thresholds, S.thr.p, c.batch * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (labels_kind == CS_MEM_HOST) HIPCHK(hipMemcpyAsync(labels, c.d_lab, c.npx * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (dist) HIPCHK(hipMemcpyAsync(dist, dq, c.npx, labels_kind == CS_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int k = 0; k < 4; ++k) {
+        float ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&ms, S.ev[k], S.ev[k + 1]));
+        times_ms[k] = ms;
+    }
+    return CS_OK;
+}
+
+// component ranges and heights of the mask in S.mask under the guide, on the stream: S.dq, S.rec and ctrl[CT_VMAX] as sp_rows
+// leaves them.  The two range planes are the halves of the key buffer.
+template <typename PIX>
+static hipError_t heights_launch(SegmentState& S, const SegmentCall& c, const PIX* d_guide, int C, int ch, int depth, int min_contrast,
+                                 hipStream_t st)
+{
+    int *lo = S.key.as<int>(), *hi = lo + c.npx;
+    hipLaunchKernelGGL(si_range<PIX>, c.pgrid, dim3(SG_THREADS), 0, st, c.HW, S.parent.as<const int>(), d_guide, C, ch, lo, hi);
+    hipLaunchKernelGGL(si_height<PIX>, c.pgrid, dim3(SG_THREADS), 0, st, c.HW, S.parent.as<const int>(), d_guide, C, ch, (const int*)lo,
+                       (const int*)hi, depth, min_contrast, S.dq.as<unsigned char>(), S.rec.as<unsigned char>(), S.ctrl.as<int>());
+    return hipGetLastError();
+}
+
 }  // namespace cs
 
 // ---- C ABI ----------------------------------------------------------------------------------
@@ -1754,81 +1945,23 @@ int cs_segment_split(cs_preproc* p, const void* image, int pixel_type, int32_t c
     if ((rc = segment_mask(p, image, pixel_type, channels, channel, batch, height, width, in_kind, sp, labels, labels_kind, c))) return rc;
     SegmentState& S = *p->seg;
     hipStream_t st = p->stream;
-    const int H = c.H, W = c.W, HW = c.HW, conn8 = sp.connectivity == 2;
-    const dim3 tgrid((unsigned)((W + SG_TW - 1) / SG_TW), (unsigned)((H + SG_TH - 1) / SG_TH), (unsigned)batch);
-    const size_t ntiles = (size_t)tgrid.x * tgrid.y * tgrid.z;
-    if ((rc = S.dq.ensure(c.npx)) || (rc = S.rec.ensure(c.npx)) || (rc = S.key.ensure(c.npx * sizeof(unsigned long long))) ||
-        (rc = S.ttop.ensure(ntiles)) || (rc = S.ctrl.ensure(CT_N * sizeof(int))))
-        return rc;
-    unsigned char *mask = S.mask.as<unsigned char>(), *dq = S.dq.as<unsigned char>(), *rec = S.rec.as<unsigned char>();
-    unsigned long long* key = S.key.as<unsigned long long>();
-    int *ctrl = S.ctrl.as<int>(), *parent = S.parent.as<int>();
-    const dim3 one(1);
+    const int H = c.H, W = c.W;
+    SplitCall w;
+    if ((rc = split_workspace(S, c, w))) return rc;
 
     // distances: the column distances live in the key buffer, which the flood fills only later
-    HIPCHK(hipMemsetAsync(ctrl, 0, CT_N * sizeof(int), st));
-    hipLaunchKernelGGL(sp_columns, dim3((unsigned)((W + SG_THREADS - 1) / SG_THREADS), (unsigned)batch), dim3(SG_THREADS), 0, st, mask, H, W,
-                       (unsigned char*)key);
+    HIPCHK(hipMemsetAsync(S.ctrl.p, 0, CT_N * sizeof(int), st));
+    hipLaunchKernelGGL(sp_columns, dim3((unsigned)((W + SG_THREADS - 1) / SG_THREADS), (unsigned)batch), dim3(SG_THREADS), 0, st,
+                       S.mask.as<unsigned char>(), H, W, S.key.as<unsigned char>());
     hipLaunchKernelGGL(sp_rows, dim3((unsigned)((W + SP_ROW - 1) / SP_ROW), (unsigned)H, (unsigned)batch), dim3(SG_THREADS), 0, st,
-                       (const unsigned char*)key, H, W, h, dq, rec, ctrl);
+                       S.key.as<const unsigned char>(), H, W, h, S.dq.as<unsigned char>(), S.rec.as<unsigned char>(), S.ctrl.as<int>());
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(S.ev[2], st));
-
-    // h-maxima: reconstruction in rounds, read back once per group of rounds; the bound of HW rounds never binds in practice
-    hipLaunchKernelGGL(sp_start, one, one, 0, st, ctrl, 0);
-    for (int active = 1; active;) {
-        for (int r = 0; r < SP_RECON_GROUP; ++r) {
-            hipLaunchKernelGGL(sp_recon, tgrid, dim3(SG_THREADS), 0, st, dq, H, W, conn8, rec, ctrl);
-            hipLaunchKernelGGL(sp_advance_recon, one, one, 0, st, ctrl, HW);
-        }
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(&active, ctrl + CT_ACTIVE, sizeof(int), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    }
-    // seeds: plateaus of equal R, those without a higher neighbour, ranked; the flags live in the key buffer, the ids in the labels
-    int* drop = (int*)key;
-    HIPCHK(hipMemsetAsync(drop, 0, c.npx * sizeof(int), st));
-    HIPCHK(label_mask(mask, batch, H, W, 0, conn8, parent, nullptr, c.nchunks, st, rec));
-    hipLaunchKernelGGL(sp_higher, c.pgrid, dim3(SG_THREADS), 0, st, H, W, conn8, rec, parent, drop);
-    hipLaunchKernelGGL(sp_seedcount, c.pgrid, dim3(SG_THREADS), 0, st, HW, parent, drop, S.chunks.as<int>(), c.nchunks);
-    hipLaunchKernelGGL(sg_scan, dim3((unsigned)batch), dim3(HIST_THREADS), 0, st, S.chunks.as<int>(), c.nchunks, S.counts.as<int>());
-    hipLaunchKernelGGL(sg_rank<true>, c.pgrid, dim3(SG_THREADS), 0, st, HW, parent, S.chunks.as<int>(), c.nchunks, c.d_lab, (const int*)drop);
-    hipLaunchKernelGGL(sp_seedkey, c.pgrid, dim3(SG_THREADS), 0, st, HW, parent, c.d_lab, key);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(S.ev[3], st));
-
-    // flood, level by level from the batch's largest Dq; then each region's first pixel and the numbering
-    HIPCHK(hipMemsetAsync(S.ttop.p, 0xff, ntiles, st));
-    hipLaunchKernelGGL(sp_start, one, one, 0, st, ctrl, 1);
-    for (int level = 1; level >= 1;) {
-        for (int r = 0; r < SP_FLOOD_GROUP; ++r) {
-            hipLaunchKernelGGL(sp_flood, tgrid, dim3(SG_THREADS), 0, st, dq, H, W, conn8, key, S.ttop.as<unsigned char>(), ctrl);
-            hipLaunchKernelGGL(sp_advance_flood, one, one, 0, st, ctrl, HW);
-        }
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(&level, ctrl + CT_LEVEL, sizeof(int), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    }
-    HIPCHK(hipMemsetAsync(c.d_lab, 0x7f, c.npx * sizeof(int), st));
-    hipLaunchKernelGGL(sp_first, c.pgrid, dim3(SG_THREADS), 0, st, HW, key, c.d_lab);
-    hipLaunchKernelGGL(sp_parent, c.pgrid, dim3(SG_THREADS), 0, st, HW, key, c.d_lab, parent, S.chunks.as<int>(), c.nchunks);
-    HIPCHK(hipGetLastError());
-    HIPCHK(number_regions(S, c, st));
-    HIPCHK(hipEventRecord(S.ev[4], st));
-    HIPCHK(hipMemcpyAsync(n_labels, S.counts.p, batch * sizeof(int), hipMemcpyDeviceToHost, st));
-    if (thresholds) HIPCHK(hipMemcpyAsync(thresholds, S.thr.p, batch * sizeof(int), hipMemcpyDeviceToHost, st));
-    if (labels_kind == CS_MEM_HOST) HIPCHK(hipMemcpyAsync(labels, c.d_lab, c.npx * sizeof(int), hipMemcpyDeviceToHost, st));
-    if (dist) HIPCHK(hipMemcpyAsync(dist, dq, c.npx, labels_kind == CS_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, S.ev[0], S.ev[1]));
-    S.sp_threshold_ms = ms;
-    HIPCHK(hipEventElapsedTime(&ms, S.ev[1], S.ev[2]));
-    S.sp_distance_ms = ms;
-    HIPCHK(hipEventElapsedTime(&ms, S.ev[2], S.ev[3]));
-    S.sp_seed_ms = ms;
-    HIPCHK(hipEventElapsedTime(&ms, S.ev[3], S.ev[4]));
-    S.sp_flood_ms = ms;
+    double t[4];
+    if ((rc = split_watershed(S, c, w, sp.connectivity == 2, st, labels, labels_kind, n_labels, thresholds, dist, t))) return rc;
+    S.sp_threshold_ms = t[0];
+    S.sp_distance_ms = t[1];
+    S.sp_seed_ms = t[2];
+    S.sp_flood_ms = t[3];
     return CS_OK;
 }
 
@@ -1840,6 +1973,85 @@ int cs_segment_split_last_timing(const cs_preproc* p, double* threshold_ms, doub
     if (distance_ms) *distance_ms = S ? S->sp_distance_ms : 0.0;
     if (seed_ms) *seed_ms = S ? S->sp_seed_ms : 0.0;
     if (flood_ms) *flood_ms = S ? S->sp_flood_ms : 0.0;
+    return CS_OK;
+}
+
+int cs_segment_split_intensity(cs_preproc* p, const void* image, int pixel_type, int32_t channels, int32_t channel, int32_t batch,
+                               int32_t height_px, int32_t width, int in_kind, const cs_segment_params* params,
+                               const cs_split_intensity_params* split, const void* guide, int guide_pixel_type, int32_t guide_channels,
+                               int32_t guide_channel, int32_t* labels, int labels_kind, int32_t* n_labels, int32_t* thresholds,
+                               uint8_t* height)
+{
+    cs_segment_params sp;
+    int rc = segment_check(image, pixel_type, channels, channel, batch, height_px, width, in_kind, params, labels, labels_kind, n_labels, sp);
+    if (rc) return rc;
+    if (!split || !guide) return fail(CS_ERR_INVALID, "NULL argument");
+    if (split->depth < 1 || split->depth > 254) return fail(CS_ERR_INVALID, "split depth %d outside 1..254 (levels)", (int)split->depth);
+    if (split->min_contrast < 0 || split->min_contrast > 65535)
+        return fail(CS_ERR_INVALID, "split min_contrast %d outside 0..65535 (counts)", (int)split->min_contrast);
+    if (split->reserved[0] != 0 || split->reserved[1] != 0) return fail(CS_ERR_INVALID, "reserved must be 0");
+    if (guide_pixel_type != CS_PIX_U8 && guide_pixel_type != CS_PIX_U16)
+        return fail(CS_ERR_INVALID, "guide_pixel_type must be CS_PIX_U8 or CS_PIX_U16");
+    if (guide_channels < 1 || guide_channel < 0 || guide_channel >= guide_channels)
+        return fail(CS_ERR_INVALID, "guide channel %d of %d: need 0 <= channel < channels", (int)guide_channel, (int)guide_channels);
+    if (!p) {
+        rc = require_gfx950(0);
+        return rc ? rc : fail(CS_ERR_INVALID, "handle is NULL");
+    }
+    SegmentCall c;
+    if ((rc = segment_mask(p, image, pixel_type, channels, channel, batch, height_px, width, in_kind, sp, labels, labels_kind, c))) return rc;
+    SegmentState& S = *p->seg;
+    hipStream_t st = p->stream;
+    SplitCall w;
+    if ((rc = split_workspace(S, c, w))) return rc;
+    const void* d_guide = guide;
+    if (in_kind == CS_MEM_HOST) {
+        if (guide == image && guide_pixel_type == pixel_type && guide_channels == channels) d_guide = S.img.p;     // uploaded already
+        else {
+            const size_t bytes = c.npx * guide_channels * (guide_pixel_type == CS_PIX_U8 ? 1 : 2);
+            if ((rc = S.si_guide.ensure(bytes))) return rc;
+            HIPCHK(hipMemcpyAsync(S.si_guide.p, guide, bytes, hipMemcpyHostToDevice, st));
+            d_guide = S.si_guide.p;
+        }
+    }
+    // components of the mask (no numbering yet: the parents are free again before the plateaus need them), their ranges, heights
+    const int conn8 = sp.connectivity == 2;
+    HIPCHK(hipMemsetAsync(S.ctrl.p, 0, CT_N * sizeof(int), st));
+    HIPCHK(hipMemsetAsync(S.key.p, 0x7f, c.npx * sizeof(int), st));
+    HIPCHK(hipMemsetAsync(S.key.as<int>() + c.npx, 0, c.npx * sizeof(int), st));
+    HIPCHK(label_mask(S.mask.as<unsigned char>(), batch, c.H, c.W, 0, conn8, S.parent.as<int>(), nullptr, c.nchunks, st));
+    if (guide_pixel_type == CS_PIX_U8)
+        HIPCHK(heights_launch(S, c, (const unsigned char*)d_guide, (int)guide_channels, (int)guide_channel, (int)split->depth,
+                              (int)split->min_contrast, st));
+    else
+        HIPCHK(heights_launch(S, c, (const unsigned short*)d_guide, (int)guide_channels, (int)guide_channel, (int)split->depth,
+                              (int)split->min_contrast, st));
+    double t[4];
+    if ((rc = split_watershed(S, c, w, conn8, st, labels, labels_kind, n_labels, thresholds, height, t))) return rc;
+    S.si_threshold_ms = t[0];
+    S.si_height_ms = t[1];
+    S.si_seed_ms = t[2];
+    S.si_flood_ms = t[3];
+    return CS_OK;
+}
+
+int cs_segment_split_intensity_last_timing(const cs_preproc* p, double* threshold_ms, double* height_ms, double* seed_ms, double* flood_ms)
+{
+    if (!p) return fail(CS_ERR_INVALID, "handle is NULL");
+    const SegmentState* S = p->seg;
+    if (threshold_ms) *threshold_ms = S ? S->si_threshold_ms : 0.0;
+    if (height_ms) *height_ms = S ? S->si_height_ms : 0.0;
+    if (seed_ms) *seed_ms = S ? S->si_seed_ms : 0.0;
+    if (flood_ms) *flood_ms = S ? S->si_flood_ms : 0.0;
+    return CS_OK;
+}
+
+int cs_segment_split_last_syncs(const cs_preproc* p, int32_t* reconstruction, int32_t* flood)
+{
+    if (!p) return fail(CS_ERR_INVALID, "handle is NULL");
+    const SegmentState* S = p->seg;
+    if (reconstruction) *reconstruction = S ? S->sp_recon_reads : 0;
+    if (flood) *flood = S ? S->sp_flood_reads : 0;
     return CS_OK;
 }
 

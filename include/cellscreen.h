@@ -26,7 +26,7 @@
  *        eccentricity / intensity rules + the bbox crop + the preprocess above
  *                                   improved_detection.py:61-111, CAE_improved_modeltrain.py:54-107
  *        (the StarDist segmentation itself, :59-60 / :52-53, stays with the caller)
- *   cs_segment_threshold / cs_segment_split
+ *   cs_segment_threshold / cs_segment_split / cs_segment_split_intensity
  *        the library's own classical segmenter (no reference counterpart, and no StarDist): Otsu or
  *        fixed threshold, optional hole filling, connected-component labels for the extraction above
  *        (cs_segment_smooth, cs_segment_background, cs_segment_local, cs_segment_clean: optional stages before the labels)
@@ -379,7 +379,8 @@ int cs_extract_last_timing(const cs_preproc *p, double *label_ms, double *region
 /* ---- built-in segmenter: global threshold + connected components ---------------------------
  * Not StarDist: a classical segmenter of the library's own, for bright cells on a dark background.
  * Touching cells come out as ONE region (the extraction's area / eccentricity rules then judge it) unless
- * cs_segment_split is called in its place, which cuts them apart at their necks.
+ * cs_segment_split is called in its place, which cuts them apart at their necks, or cs_segment_split_intensity, which cuts
+ * them along the intensity valleys between their cores.
  * Input as for the extraction: one `channel` of a [B][H][W][channels] uint8 / uint16 stack, read in place.
  *   threshold   CS_THRESH_OTSU: scikit-image 0.18.3's threshold_otsu of that channel of each image (exact
  *               integer histogram over [min, max], int64 cumulative sums, its float64 operations in its order:
@@ -452,6 +453,46 @@ int cs_segment_split(cs_preproc *p, const void *image, int pixel_type, int32_t c
  * flood + numbering. */
 int cs_segment_split_last_timing(const cs_preproc *p, double *threshold_ms, double *distance_ms, double *seed_ms,
                                  double *flood_ms);
+
+/* cs_segment_split with the heights taken from the image instead of from the mask: cells that overlap without a neck, which the
+ * distance split leaves whole, are cut along the darker valley between their bright cores.  Exact and all integers; the result is
+ * a function of the mask (after the threshold and the optional hole filling) and of the guide plane G alone:
+ *   lo_c, hi_c   the smallest and largest G over the pixels of component c of the mask (under the connectivity; filled holes
+ *                count);
+ *   Hq     1 + ((G - lo_c) * 254) / max(hi_c - lo_c, min_contrast, 1) on the mask, a byte in 1..255; 0 on background.  The scale
+ *          is per component: a dim cell beside a bright field keeps its own 254 levels, and the result does not depend on the
+ *          rest of the batch.  A component flatter than min_contrast is not stretched to the full range (the guard against
+ *          splitting on noise); a constant component is 1 everywhere.
+ *   R, seeds, flood, labels   as cs_segment_split, with Hq in Dq's place and depth in h's: two cores are separated when the
+ *          valley between them lies at least `depth` of the component's 254 levels below the lower core.
+ * With depth 254 every component holds one seed and the labels equal cs_segment_threshold's bit for bit; adding a constant to G
+ * changes nothing.  G must be smooth (cs_segment_smooth's plane): on a noisy plane every noise peak deeper than `depth` is a
+ * seed.  Cells that overlap in projection add up, so the lens between two cores can be the brightest spot: a third region.
+ * guide: the plane G, [batch][height][width][guide_channels] of guide_pixel_type, where `image` is (in_kind); channel
+ *        guide_channel is read in place.  It may be `image` itself; with cs_segment_local or cs_segment_clean in front, `image`
+ *        is their 0 / 1 plane and `guide` the plane they were made from.
+ * height: optional out, [batch][height][width] uint8: Hq, on the device or the host as labels_kind; NULL: not wanted.
+ * Workspace and host synchronisations as cs_segment_split (the component ranges live in the flood's key buffer), and a copy of
+ * a guide that comes from the host.  NULL split or guide, depth outside 1..254, min_contrast outside 0..65535, non-zero reserved,
+ * a bad guide pixel type or channel: CS_ERR_INVALID before any device work; everything else as cs_segment_split. */
+typedef struct cs_split_intensity_params {
+    int32_t depth;                    /* 1..254 levels: how much lower than its peak a valley must be to separate two cores */
+    int32_t min_contrast;             /* 0..65535 counts: a component's range is stretched over at least this much */
+    int32_t reserved[2];              /* 0 */
+} cs_split_intensity_params;
+int cs_segment_split_intensity(cs_preproc *p, const void *image, int pixel_type, int32_t channels, int32_t channel,
+                               int32_t batch, int32_t height_px, int32_t width, int in_kind,
+                               const cs_segment_params *params, const cs_split_intensity_params *split,
+                               const void *guide, int guide_pixel_type, int32_t guide_channels, int32_t guide_channel,
+                               int32_t *labels, int labels_kind, int32_t *n_labels, int32_t *thresholds, uint8_t *height);
+/* Device time of the last cs_segment_split_intensity: histogram + threshold + mask; hole filling + components + heights;
+ * reconstruction + seeds; flood + numbering. */
+int cs_segment_split_intensity_last_timing(const cs_preproc *p, double *threshold_ms, double *height_ms, double *seed_ms,
+                                           double *flood_ms);
+
+/* Host synchronisations of the last cs_segment_split or cs_segment_split_intensity on this handle beyond the final one: the
+ * reads of the control word after a group of 16 reconstruction rounds and after a group of 64 flood rounds. */
+int cs_segment_split_last_syncs(const cs_preproc *p, int32_t *reconstruction, int32_t *flood);
 
 /* Background correction of the segmentation channel before the threshold: for images whose illumination is not flat
  * (vignetting, a tilted coverslip, out-of-focus haze), where one global threshold cuts the field in two instead of finding

@@ -49,9 +49,18 @@ segment_batch and of segment + extract, the label counts, the stage times, smoot
 figures to the unsmoothed ones.  Then smooth_ms alone at the sigmas 0.25, 1, 2, 4, 8 and 15.875 (radii 1 to 64), which shows
 what the radius costs.  No time is a pass condition.
 
+--split-intensity measures split_by="intensity" (cs_segment_split_intensity) beside the distance split and writes
+profiles/segment_split_intensity_bench.json.  The scene is a field of touching cells with bright cores: every image is
+tests/split_intensity_reference.py's scene (170 x 260, 11 Gaussian cells that overlap without a neck, 5 components) tiled to
+the image's size, with Gaussian noise of 60 counts, smoothed with sigma 1.5 and cut by Otsu's threshold.  One scene's labels and
+heights are compared with the host restatement first (and the distance split's labels with tests/split_reference.py); then, in
+the same run, split_by="distance" (--split's mode) and split_by="intensity": images/s of segment_batch and of segment + extract,
+the regions found, the stage times and the host synchronisations per call.  No time is a pass condition.
+
 Usage: python tools/bench_segment.py [--images 32] [--side 2048] [--cells 1000] [--reps 10] [--warmup 2] [--host-images 4]
                                      [--split [--split-cells 3000] [--split-h 3]] [--background R [--denoise]]
-                                     [--local R [--delta D] [--denoise]] [--clean [--open R] [--min-area A] [--delta D]] [--smooth SIGMA [--denoise]]"""
+                                     [--local R [--delta D] [--denoise]] [--clean [--open R] [--min-area A] [--delta D]] [--smooth SIGMA [--denoise]]
+                                     [--split-intensity [--split-depth 16] [--split-contrast 0]]"""
 import argparse
 import json
 import os
@@ -124,6 +133,85 @@ def split_leg(a):
         del ti
     line = json.dumps(res)
     out = a.out if a.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "segment_split_bench.json")
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            f.write(line + "\n")
+    print(line)
+
+
+def split_intensity_leg(a):
+    import torch
+    import smooth_reference as SM
+    import split_intensity_reference as IR
+    import split_reference as SR
+    from build import source_hash
+    from cellscreen import extract as X
+    from cellscreen import segment as S
+
+    fill = not a.no_fill_holes
+    dev = torch.device("cuda", 0)
+    med = lambda v: float(np.median(v))
+    sigma, noise = 1.5, 60.0
+    sh, sw = IR.SCENE_SHAPE                                                 # the scene's own margins are background: it tiles seamlessly
+    field = np.tile(IR.scene(0.0).astype(np.float64), (-(-a.side // sh), -(-a.side // sw)))[:a.side, :a.side]
+    base = field + np.random.default_rng(2024).normal(0.0, noise, (a.side, a.side))
+    base = np.rint(np.clip(base, 0, 65535)).astype(np.uint16)
+    variants = [base, base[::-1], base[:, ::-1], base[::-1, ::-1]]          # four distinct images from one painting
+    imgs = np.ascontiguousarray(np.stack([variants[b % 4] for b in range(a.images)]))
+    ti = torch.from_numpy(imgs.view(np.int16)).to(dev)
+    torch.cuda.synchronize()
+    common = dict(threshold="otsu", connectivity=a.connectivity, fill_holes=fill, smooth_sigma=sigma, split_touching=True)
+    ext = X.CellExtractor(0)
+    dist = S.ThresholdSegmenter(0, extractor=ext, split_h=a.split_h, **common)
+    inten = S.ThresholdSegmenter(0, extractor=ext, split_by="intensity", split_depth=a.split_depth, split_contrast=a.split_contrast, **common)
+
+    # outputs first: one scene's labels and heights against the host restatements
+    one = np.ascontiguousarray(IR.scene(noise)[None])
+    t1 = torch.from_numpy(one.view(np.int16)).to(dev)
+    labels, n, thr, hq = inten.segment_batch(t1, return_distance=True)
+    el, en, et, eh, _ = IR.segment_batch(one, threshold="otsu", connectivity=a.connectivity, fill_holes=fill, depth=a.split_depth,
+                                         min_contrast=a.split_contrast, smooth_sigma=sigma)
+    assert np.array_equal(n, en) and np.array_equal(thr, et) and np.array_equal(labels.cpu().numpy(), el) and \
+        np.array_equal(hq.cpu().numpy(), eh), "intensity split differs from the restatement"
+    dl, dn, _ = dist.segment_batch(t1)
+    hl, hn, _, _ = SR.split(SM.smooth_sigma(one[0], sigma), "otsu", a.connectivity, fill, a.split_h)
+    assert hn == int(dn[0]) and np.array_equal(dl[0].cpu().numpy(), hl), "distance split differs from the restatement"
+
+    def timed(fn, seg):
+        walls, stages, syncs = [], [], []
+        for k in range(a.warmup + a.reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = fn()
+            torch.cuda.synchronize()
+            if k >= a.warmup:
+                walls.append(time.perf_counter() - t0)
+                stages.append(seg.last_timing())
+                syncs.append(seg.last_host_syncs())
+        return out, walls, stages, syncs
+
+    spread = lambda stages, k: [round(med([t[k] for t in stages]), 4), round(min(t[k] for t in stages), 4),
+                                round(max(t[k] for t in stages), 4)]
+    wall3 = lambda walls: [round(med(walls) * 1e3, 3), round(min(walls) * 1e3, 3), round(max(walls) * 1e3, 3)]
+    res = {"tool": "bench_segment --split-intensity", "source_hash": source_hash(), "images": a.images, "side": a.side,
+           "connectivity": a.connectivity, "fill_holes": fill, "smooth_sigma": sigma, "noise_sigma": noise, "split_h": a.split_h,
+           "split_depth": a.split_depth, "split_contrast": a.split_contrast, "whole_scenes_per_image": (a.side // sh) * (a.side // sw), "cells_per_scene": len(IR.CELLS),
+           "scene_regions": {"distance": int(dn[0]), "intensity": int(n[0])}, "reps": a.reps, "warmup": a.warmup, "outputs_equal": True}
+    legs = {}
+    for name, seg in (("distance", dist), ("intensity", inten)):
+        (_, n_lab, _), walls, stages, syncs = timed(lambda: seg.segment_batch(ti), seg)
+        r, chain, _, _ = timed(lambda: ext.extract_batch(ti, seg.segment_batch(ti)[0]), seg)
+        legs[name] = walls
+        res[name] = {"regions_per_image": round(float(n_lab.mean()), 1), "cells_extracted": int(r.cells.shape[0]),
+                     "segment_images_per_s": round(a.images / med(walls), 2), "segment_wall_ms": wall3(walls),
+                     "segment_extract_images_per_s": round(a.images / med(chain), 2), "segment_extract_wall_ms": wall3(chain),
+                     "host_syncs_per_call": [int(med(syncs)), int(min(syncs)), int(max(syncs))],
+                     **{k: spread(stages, k) for k in sorted(stages[0])}}
+    res["intensity_over_distance_segment_time"] = round(med(legs["intensity"]) / med(legs["distance"]), 3)
+    ext.close()
+    line = json.dumps(res)
+    out = a.out if a.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "segment_split_intensity_bench.json")
     if out:
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
         with open(out, "w") as f:
@@ -483,6 +571,10 @@ def main():
     ap.add_argument("--split", action="store_true", help="measure the split_touching option (profiles/segment_split_bench.json)")
     ap.add_argument("--split-cells", type=int, default=3000)
     ap.add_argument("--split-h", type=int, default=3)
+    ap.add_argument("--split-intensity", action="store_true",
+                    help="measure split_by='intensity' beside the distance split (profiles/segment_split_intensity_bench.json)")
+    ap.add_argument("--split-depth", type=int, default=16)
+    ap.add_argument("--split-contrast", type=int, default=0)
     ap.add_argument("--background", type=int, default=None, metavar="R",
                     help="measure the background correction of radius R (profiles/segment_background_bench.json)")
     ap.add_argument("--denoise", action="store_true", help="with --background, --local or --smooth: the 3 x 3 median first")
@@ -495,6 +587,10 @@ def main():
     ap.add_argument("--smooth", type=float, default=None, metavar="SIGMA",
                     help="measure the Gaussian smoothing on a field of faint cells in noise (profiles/segment_smooth_bench.json)")
     a = ap.parse_args()
+    if a.split_intensity:
+        if a.split or a.background is not None or a.local is not None or a.clean or a.delta or a.smooth is not None or a.denoise:
+            ap.error("--split-intensity is measured on its own")
+        return split_intensity_leg(a)
     if a.smooth is not None:
         if a.split or a.background is not None or a.local is not None or a.clean or a.delta:
             ap.error("--smooth is measured on its own")
