@@ -124,6 +124,13 @@ class CSCleanParams(C.Structure):
     _fields_ = [("open_radius", C.c_int32), ("open_connectivity", C.c_int32), ("min_area", C.c_int32)]
 
 
+class CSHysteresisParams(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("weak", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+WEAK_ABSOLUTE, WEAK_FRACTION, WEAK_LOCAL = 0, 1, 2      # cs_hysteresis_params.mode
+
+
 SMOOTH_MAX_RADIUS = 64                  # cs_smooth_params.weights holds 65 taps
 
 
@@ -190,6 +197,9 @@ SIGNATURES = {
     "cs_segment_clean": (_I, [_P, _P, _I, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _I, C.POINTER(CSSegmentParams),
                               C.POINTER(CSCleanParams), _P, _I, _P]),
     "cs_segment_clean_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "cs_segment_hysteresis": (_I, [_P, _P, _I, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _I, C.POINTER(CSSegmentParams),
+                                   C.POINTER(CSLocalParams), C.POINTER(CSHysteresisParams), _P, _I, _P]),
+    "cs_segment_hysteresis_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "cs_segment_smooth": (_I, [_P, _P, _I, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _I, C.POINTER(CSSmoothParams), _P, _I]),
     "cs_segment_smooth_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "cs_fit_create": (_I, [_I, C.POINTER(_P)]),

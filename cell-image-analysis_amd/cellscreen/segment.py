@@ -43,6 +43,19 @@ rises towards the extraction's limit (batch * max_label <= 2^22).  min_area (bel
 denoise=True and a local_delta of a few noise sigmas make fewer of them.  The mask feeds the same hole filling, labelling and
 split; with background_radius the local rule runs on the corrected plane.
 
+Hysteresis threshold, in the place of the plain cut or of the local rule (cs_segment_hysteresis; tests/hysteresis_reference.py
+restates it), off by default.  One number per pixel leaves a choice between two evils: set low, noise passes as speckle, and
+min_area, which goes by size, takes a small real object with it; set high, the speckle is gone and so is every cell's dim rim,
+and the regions the extraction measures are smaller than the cells.  Two numbers end it: a pixel is foreground if it passes the
+weak rule and is connected, through pixels that pass it too, to a pixel that passes the strong rule, which is
+skimage.filters.apply_hysteresis_threshold decided in integers.  The strong rule is the one the segmenter has anyway.  The weak
+one has the same form with a lower number: weak_threshold as an int is in counts, low = min(weak_threshold, t); as a float
+strictly between 0 and 1 it is a fraction of the strong threshold, low = (t * q) >> 16 with q = int(f * 65536 + 0.5), the form
+for Otsu, whose t is not known in advance; with threshold="local" weak_delta stands in local_delta's place (same window, floor
+and tie rule).  Components are taken under the segmenter's connectivity; speckle has no strong pixel and goes whatever its
+size, a cell keeps its whole weak extent.  The hole filling, the cleanup, the labels and the split see the resulting 0 / 1
+plane; the thresholds reported stay the strong rule's.  The low number is never chosen automatically.
+
 Mask cleanup, between the hole filling and the labels (cs_segment_clean; tests/clean_reference.py restates it), off by default:
 open_radius=r (1..15) opens the mask, r erosions then r dilations by the 3 x 3 square (open_connectivity=2, the default) or
 cross (1), which is scipy.ndimage.binary_opening(mask, generate_binary_structure(2, k), iterations=r) bit for bit: speckle and
@@ -67,6 +80,8 @@ correction, the threshold, the cleanup, the labels and the split see the smoothe
     seg = ThresholdSegmenter(threshold="local", local_radius=25, local_delta=60)      # bright and dim cells in one field
     seg = ThresholdSegmenter(threshold="local", local_radius=25, local_delta=40, min_area=50)         # ... without the speckle
     seg = ThresholdSegmenter(smooth_sigma=2)                           # faint cells in noise: Gaussian first
+    seg = ThresholdSegmenter(threshold="local", local_radius=25, local_delta=200, weak_delta=40)      # no speckle, whole cells
+    seg = ThresholdSegmenter(weak_threshold=0.2)                       # Otsu's threshold for the cores, a fifth of it for the rims
 
     screening = ProductionMutantScreening(model_dir, cell_extractor=threshold_cell_extractor())
 """
@@ -217,6 +232,50 @@ def clean_params(open_radius=None, open_connectivity: int = 2, min_area=None) ->
     return p
 
 
+def hysteresis_params(threshold="otsu", weak_threshold=None, weak_delta=None, local_delta: int = 0) -> Optional[L.CSHysteresisParams]:
+    """cs_hysteresis_params from the Python arguments, None with neither option (no hysteresis); anything out of range or in
+    the wrong combination raises before a handle exists.  weak_threshold belongs to the global rules: an int in 0..65535 is
+    absolute (with a fixed threshold not above it), a float strictly between 0 and 1 a fraction of the strong threshold, kept as
+    q = int(f * 65536 + 0.5) in 1..65535.  weak_delta belongs to threshold="local": an int in -65535..65535, not above
+    local_delta."""
+    local = isinstance(threshold, str) and threshold == "local"
+    if weak_threshold is None and weak_delta is None:
+        return None
+    if weak_threshold is not None and weak_delta is not None:
+        raise ValueError("weak_threshold and weak_delta exclude each other: one weak rule")
+    p = L.CSHysteresisParams()
+    if weak_delta is not None:
+        if isinstance(weak_delta, (bool, np.bool_)) or not isinstance(weak_delta, (int, np.integer)):
+            raise TypeError(f"weak_delta must be None or an integer, got {type(weak_delta).__name__}")
+        if not local:
+            raise ValueError("weak_delta belongs to threshold='local'; the global rules take weak_threshold")
+        if not -65535 <= int(weak_delta) <= 65535:
+            raise ValueError(f"weak_delta {weak_delta} outside -65535..65535")
+        if int(weak_delta) > int(local_delta):
+            raise ValueError(f"weak_delta {weak_delta} above local_delta {local_delta}: the weak rule is the lower one")
+        p.mode, p.weak = L.WEAK_LOCAL, int(weak_delta)
+        return p
+    if isinstance(weak_threshold, (bool, np.bool_)) or not isinstance(weak_threshold, (int, float, np.integer, np.floating)):
+        raise TypeError(f"weak_threshold must be None, an integer (counts) or a float (fraction), got {type(weak_threshold).__name__}")
+    if local:
+        raise ValueError("weak_threshold belongs to the global rules; threshold='local' takes weak_delta")
+    if isinstance(weak_threshold, (int, np.integer)):
+        if not 0 <= int(weak_threshold) <= 65535:
+            raise ValueError(f"weak_threshold {weak_threshold} outside 0..65535")
+        if not isinstance(threshold, str) and int(weak_threshold) > int(threshold):
+            raise ValueError(f"weak_threshold {weak_threshold} above threshold {threshold}: the weak rule is the lower one")
+        p.mode, p.weak = L.WEAK_ABSOLUTE, int(weak_threshold)
+        return p
+    f = float(weak_threshold)
+    if not 0.0 < f < 1.0:                                                       # NaN fails both
+        raise ValueError(f"weak_threshold {weak_threshold}: a fraction lies strictly between 0 and 1")
+    q = int(f * 65536 + 0.5)
+    if not 1 <= q <= 65535:
+        raise ValueError(f"weak_threshold {weak_threshold} rounds to {q} / 65536, outside 1..65535")
+    p.mode, p.weak = L.WEAK_FRACTION, q
+    return p
+
+
 SMOOTH_SIGMA_MIN, SMOOTH_SIGMA_MAX = 0.25, 15.875         # radius int(4 sigma + 0.5) = 1..64
 
 
@@ -301,16 +360,26 @@ class ThresholdSegmenter:
     mask makes one more round trip.
     smooth_sigma (None or 0.25..15.875): the Gaussian smoothing of the module text, before everything else; denoise then runs
     the median before the Gaussian and needs no background_radius.  With numpy input the smoothed plane makes one more round
-    trip."""
+    trip.
+    weak_threshold (None, an int in 0..65535: counts, or a float strictly between 0 and 1: a fraction of the strong threshold)
+    and, with threshold="local", weak_delta (None or an int in -65535..65535, not above local_delta): the hysteresis threshold
+    of the module text, in the place of the plain cut or of the local rule; the threshold (or local_delta) stays the strong
+    rule and is what `thresholds` reports.  The hole filling and every later stage see its 0 / 1 plane.  With numpy input that
+    plane makes one more round trip through the host, as the other stages' planes do."""
 
     def __init__(self, device_id: int = 0, threshold="otsu", connectivity: int = 1, fill_holes: bool = True,
                  extractor: Optional[CellExtractor] = None, split_touching: bool = False, split_h: int = 3,
                  background_radius: Optional[int] = None, denoise: bool = False, local_radius: Optional[int] = None,
                  local_delta: int = 0, local_floor: int = -1, open_radius: Optional[int] = None, open_connectivity: int = 2,
                  min_area: Optional[int] = None, smooth_sigma: Optional[float] = None, split_by: str = "distance",
-                 split_depth: int = SPLIT_DEPTH, split_contrast: int = SPLIT_CONTRAST):
+                 split_depth: int = SPLIT_DEPTH, split_contrast: int = SPLIT_CONTRAST, weak_threshold=None,
+                 weak_delta: Optional[int] = None):
         self._params, self._local, self._background = _threshold_mode(threshold, connectivity, fill_holes, local_radius, local_delta,
                                                                       local_floor, background_radius, denoise, smooth_sigma)
+        self._hysteresis = hysteresis_params(threshold, weak_threshold, weak_delta, local_delta)
+        # what takes the hysteresis stage's 0 / 1 plane: the fixed threshold 0, and the hole filling as requested
+        self._after_hysteresis = segment_params(0, connectivity, fill_holes)
+        self.weak_threshold, self.weak_delta = weak_threshold, (None if weak_delta is None else int(weak_delta))
         self._smooth = smooth_params(smooth_sigma, denoise)
         self.smooth_sigma = None if smooth_sigma is None else float(smooth_sigma)
         self._split = split_params(split_touching, split_h)
@@ -496,9 +565,10 @@ class ThresholdSegmenter:
             self._local_timing()                                    # reads the times, which waits for the plane: torch may use it
         return mask
 
-    def _clean_mask(self, images, B, H, W, Cn, channel, ptype, on_dev, thresholds=None):
-        """The cleaned 0 / 1 plane [B,H,W] uint8 where the images are; a device plane is complete in the handle's stream order
-        only.  thresholds: an int32 [B] array for the thresholds of the mask, which costs a device plane its one wait."""
+    def _hysteresis_mask(self, images, B, H, W, Cn, channel, ptype, on_dev, thresholds=None):
+        """The 0 / 1 plane [B,H,W] uint8 of the hysteresis threshold where the images are; a device plane is complete in the
+        handle's stream order only.  thresholds: an int32 [B] array for the strong thresholds, which costs a device plane its
+        one wait unless the rule is local (-1, no reading)."""
         if on_dev:
             import torch
             mask = torch.empty((B, H, W), dtype=torch.uint8, device=images.device)
@@ -506,7 +576,55 @@ class ThresholdSegmenter:
         else:
             mask = np.empty((B, H, W), np.uint8)
         kind = L.CS_MEM_DEVICE if on_dev else L.CS_MEM_HOST
-        L.check(self._lib.cs_segment_clean(self._handle, L._ptr(images), ptype, Cn, channel, B, H, W, kind, C.byref(self._params),
+        L.check(self._lib.cs_segment_hysteresis(self._handle, L._ptr(images), ptype, Cn, channel, B, H, W, kind, C.byref(self._params),
+                                                None if self._local is None else C.byref(self._local), C.byref(self._hysteresis),
+                                                L._ptr(mask), kind, None if thresholds is None else thresholds.ctypes.data))
+        return mask
+
+    def _hysteresis_timing(self):
+        a, b = C.c_double(), C.c_double()
+        L.check(self._lib.cs_segment_hysteresis_last_timing(self._handle, C.byref(a), C.byref(b)))
+        return {"hysteresis_level_ms": a.value, "hysteresis_link_ms": b.value}
+
+    def _thresholded(self, images, B, H, W, Cn, channel, ptype, on_dev, thresholds=None):
+        """The 0 / 1 plane of whichever stage stands in the plain cut's place (hysteresis, else the local rule), or None."""
+        if self._hysteresis is not None:
+            return self._hysteresis_mask(images, B, H, W, Cn, channel, ptype, on_dev, thresholds)
+        if self._local is not None:
+            return self._local_mask(images, B, H, W, Cn, channel, ptype, on_dev)
+        return None
+
+    def hysteresis_mask_batch(self, images, channel: Optional[int] = None):
+        """The mask of the hysteresis threshold, before the hole filling: [B,H,W] uint8, 1 = foreground, numpy for numpy input,
+        a CUDA tensor for tensor input (complete when this returns).  Needs weak_threshold or weak_delta; with smooth_sigma and
+        background_radius it is the mask of what they make."""
+        B, H, W, Cn, channel, ptype, on_dev = self._check(images, channel)
+        if self._hysteresis is None:
+            raise ValueError("hysteresis_mask_batch needs weak_threshold or weak_delta: this segmenter has one rule")
+        if self._smooth is not None:
+            images = self._smoothed(images, B, H, W, Cn, channel, ptype, on_dev)
+            Cn, channel = 1, 0
+        if self._background is not None:
+            images = self._correct(images, B, H, W, Cn, channel, ptype, on_dev)
+            Cn, channel = 1, 0
+        mask = self._hysteresis_mask(images, B, H, W, Cn, channel, ptype, on_dev)
+        if on_dev:
+            self._hysteresis_timing()                               # reads the times, which waits for the plane: torch may use it
+        return mask
+
+    def _clean_mask(self, images, B, H, W, Cn, channel, ptype, on_dev, thresholds=None, params=None):
+        """The cleaned 0 / 1 plane [B,H,W] uint8 where the images are; a device plane is complete in the handle's stream order
+        only.  thresholds: an int32 [B] array for the thresholds of the mask, which costs a device plane its one wait.
+        params: what cuts the plane, the segmenter's own unless a stage before has made it 0 / 1."""
+        if on_dev:
+            import torch
+            mask = torch.empty((B, H, W), dtype=torch.uint8, device=images.device)
+            L.order_after_torch(self._lib.cs_preproc_wait_stream, self._handle, images, mask)
+        else:
+            mask = np.empty((B, H, W), np.uint8)
+        kind = L.CS_MEM_DEVICE if on_dev else L.CS_MEM_HOST
+        L.check(self._lib.cs_segment_clean(self._handle, L._ptr(images), ptype, Cn, channel, B, H, W, kind,
+                                           C.byref(self._params if params is None else params),
                                            C.byref(self._clean), L._ptr(mask), kind,
                                            None if thresholds is None else thresholds.ctypes.data))
         return mask
@@ -529,10 +647,13 @@ class ThresholdSegmenter:
         if self._background is not None:
             images = self._correct(images, B, H, W, Cn, channel, ptype, on_dev)
             Cn, channel = 1, 0
-        if self._local is not None:
-            images = self._local_mask(images, B, H, W, Cn, channel, ptype, on_dev)
-            Cn, channel, ptype = 1, 0, PIX_U8
-        mask = self._clean_mask(images, B, H, W, Cn, channel, ptype, on_dev)
+        params = None
+        plane = self._thresholded(images, B, H, W, Cn, channel, ptype, on_dev)
+        if plane is not None:
+            images, Cn, channel, ptype = plane, 1, 0, PIX_U8
+            if self._hysteresis is not None:
+                params = self._after_hysteresis
+        mask = self._clean_mask(images, B, H, W, Cn, channel, ptype, on_dev, params=params)
         if on_dev:
             self._clean_timing()                                    # reads the times, which waits for the plane: torch may use it
         return mask
@@ -558,21 +679,33 @@ class ThresholdSegmenter:
             Cn, channel = 1, 0
         # what split_by="intensity" takes its heights from: the plane the threshold stage sees, never a 0 / 1 plane
         guide, guide_cn, guide_channel, guide_ptype = images, Cn, channel, ptype
-        if self._local is not None:
+        params, reported = self._params, None
+        otsu = self._params.threshold_mode == L.THRESH_OTSU
+        if self._hysteresis is not None:
+            # the 0 / 1 plane in the channel's place, cut at the fixed threshold 0; the thresholds are the strong rule's, read
+            # here (Otsu's are computed here; a fixed one and local mode's -1 need no reading)
+            reported = np.zeros(B, np.int32)
+            images = self._hysteresis_mask(images, B, H, W, Cn, channel, ptype, on_dev, reported if otsu else None)
+            if not otsu:
+                reported[:] = self._params.threshold
+            Cn, channel, ptype, params = 1, 0, PIX_U8, self._after_hysteresis
+        elif self._local is not None:
             # the 0 / 1 plane in the channel's place, cut at the fixed threshold 0: hole filling, labels and the split as they are
             images = self._local_mask(images, B, H, W, Cn, channel, ptype, on_dev)
             Cn, channel, ptype = 1, 0, PIX_U8
         n_labels = np.zeros(B, np.int32)
         thresholds = np.zeros(B, np.int32)
-        params, reported = self._params, None
         if self._clean is not None:
             # the cleaned 0 / 1 plane in the channel's place, cut at the fixed threshold 0 and not filled again; the thresholds
-            # are the cleanup's (Otsu's are computed there; a fixed one and local mode's -1 need no reading)
-            reported = np.zeros(B, np.int32)
-            otsu = self._params.threshold_mode == L.THRESH_OTSU
-            images = self._clean_mask(images, B, H, W, Cn, channel, ptype, on_dev, reported if otsu else None)
-            if not otsu:
-                reported[:] = self._params.threshold
+            # are the cleanup's (Otsu's are computed there; a fixed one and local mode's -1 need no reading) unless the
+            # hysteresis stage has reported them already
+            if reported is None:
+                reported = np.zeros(B, np.int32)
+                images = self._clean_mask(images, B, H, W, Cn, channel, ptype, on_dev, reported if otsu else None)
+                if not otsu:
+                    reported[:] = self._params.threshold
+            else:
+                images = self._clean_mask(images, B, H, W, Cn, channel, ptype, on_dev, params=params)
             Cn, channel, ptype, params = 1, 0, PIX_U8, self._after_clean
         if on_dev:
             import torch
@@ -619,11 +752,15 @@ class ThresholdSegmenter:
         local_median_ms and local_ms (the sums and the comparison) of the last mask; with open_radius or min_area also open_ms
         and min_area_ms of the last cleanup (0 for a step that is off), and threshold_ms is then the labelling call's cut of the
         cleaned plane; with smooth_sigma also smooth_ms (the two passes) of the last smoothing, and smooth_median_ms when the
-        median ran there."""
+        median ran there; with weak_threshold or weak_delta also hysteresis_level_ms (thresholds or sums, and the level plane)
+        and hysteresis_link_ms (weak components, flags, the kept plane) of the last hysteresis stage, which then stands in the
+        local rule's place: local_ms is not reported."""
         extra = self._smooth_timing() if self._smooth is not None else {}
         if self._background is not None:
             extra.update(self._background_timing())
-        if self._local is not None:
+        if self._hysteresis is not None:
+            extra.update(self._hysteresis_timing())
+        elif self._local is not None:
             extra.update(self._local_timing())
         if self._clean is not None:
             extra.update(self._clean_timing())
@@ -655,7 +792,7 @@ def threshold_cell_extractor(device_id: int = 0, out_hw=(OUT_SIDE, OUT_SIDE), th
                              local_delta: int = 0, local_floor: int = -1, open_radius: Optional[int] = None,
                              open_connectivity: int = 2, mask_min_area: Optional[int] = None,
                              smooth_sigma: Optional[float] = None, split_by: str = "distance", split_depth: int = SPLIT_DEPTH,
-                             split_contrast: int = SPLIT_CONTRAST, **qc):
+                             split_contrast: int = SPLIT_CONTRAST, weak_threshold=None, weak_delta: Optional[int] = None, **qc):
     """The `cell_extractor(image_path) -> (cells, stats)` that ProductionMutantScreening and create_training_dataset accept,
     with the built-in segmenter in StarDist's place: the file is read (extract.read_image / split_channels), uploaded once,
     segmented and extracted on one handle, and the labels never leave the device.  Not StarDist: see the module text.
@@ -666,13 +803,15 @@ def threshold_cell_extractor(device_id: int = 0, out_hw=(OUT_SIDE, OUT_SIDE), th
     open_radius and open_connectivity as for ThresholdSegmenter, and mask_min_area for its min_area: the mask cleanup before
     the labels.  The name differs here because min_area is, and stays, the extraction's own area rule among **qc.
     smooth_sigma as for ThresholdSegmenter: the segmentation channel is smoothed first, the extraction reads the raw one.
-    split_by, split_depth and split_contrast as for ThresholdSegmenter; split_by="intensity" wants smooth_sigma."""
+    split_by, split_depth and split_contrast as for ThresholdSegmenter; split_by="intensity" wants smooth_sigma.
+    weak_threshold and weak_delta as for ThresholdSegmenter: the hysteresis threshold in the plain cut's place."""
     out_hw = check_out_hw(out_hw)
     _threshold_mode(threshold, connectivity, fill_holes, local_radius, local_delta, local_floor, background_radius, denoise,
                     smooth_sigma)
     split_params(split_touching, split_h)
     split_intensity_params(split_touching, split_by, split_h, split_depth, split_contrast)
     clean_params(open_radius, open_connectivity, mask_min_area)
+    hysteresis_params(threshold, weak_threshold, weak_delta, local_delta)
     qc_params(**qc)
     st = {}
 
@@ -690,7 +829,8 @@ def threshold_cell_extractor(device_id: int = 0, out_hw=(OUT_SIDE, OUT_SIDE), th
                                          denoise=denoise, local_radius=local_radius, local_delta=local_delta,
                                          local_floor=local_floor, open_radius=open_radius, open_connectivity=open_connectivity,
                                          min_area=mask_min_area, smooth_sigma=smooth_sigma, split_by=split_by,
-                                         split_depth=split_depth, split_contrast=split_contrast)
+                                         split_depth=split_depth, split_contrast=split_contrast, weak_threshold=weak_threshold,
+                                         weak_delta=weak_delta)
         host = np.ascontiguousarray(img)[None]
         dev = torch.from_numpy(host.view(np.int16) if host.dtype == np.uint16 else host).to(torch.device("cuda", device_id))
         labels, _, _ = st["s"].segment_batch(dev, channel=seg_ch)

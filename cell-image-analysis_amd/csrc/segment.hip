@@ -30,6 +30,8 @@
 //   cl_*         cs_segment_clean only: the optional cleanup of the mask BEFORE the labelling (binary opening on a bit-packed
 //                tile in LDS, minimum area by pixel counts per union-find root); see "mask cleanup" further down.  Its plane
 //                then stands in the channel's place, cut at the fixed threshold 0.
+//   hy_*         cs_segment_hysteresis only: the hysteresis threshold in the plain cut's (or the local rule's) place, a level
+//                plane (0 / weak / strong), its weak components, and a flag per root; see "hysteresis threshold" further down.
 //   sm_*         cs_segment_smooth only: the optional Gaussian smoothing of the channel BEFORE all of the above, the background
 //                correction included (separable, 16-bit fixed-point weights, one rounding); see "Gaussian smoothing".
 // The final parents are a function of the mask alone (the minimum index of a component), so the labels do not depend on
@@ -1111,11 +1113,22 @@ __global__ __launch_bounds__(SG_THREADS) void lt_rows(const PIX* __restrict__ in
     for (int pos = tp; pos < seg; pos += 64) dst[pos] = s[pos + 2 * r] - (pos ? s[pos - 1] : 0u);
 }
 
-// grid (ceil(W / LT_COL_W), ceil(H / (LT_COL_TILES * TR)), B).  x: the pixels, addressed as lt_rows' in; out: [B][H][W] 0 / 1.
-template <typename PIX>
+// what lt_cols writes for one pixel: 0 / 1 of the one rule, or with LEVELS the level under two deltas (n_weak <= n_delta): 0, 1 where
+// only the weak rule holds, 2 where the strong one does.  Both compare the one margin n * v - S; the floor is common to both.
+template <bool LEVELS>
+__device__ inline unsigned char lt_cut(long long n, int v, long long S, long long n_delta, long long n_weak, int floor)
+{
+    if (!LEVELS) return (n * v - S - n_delta > 0 && v > floor) ? 1 : 0;
+    const long long m = n * v - S;
+    return v > floor ? (m - n_delta > 0 ? 2 : (m - n_weak > 0 ? 1 : 0)) : 0;
+}
+
+// grid (ceil(W / LT_COL_W), ceil(H / (LT_COL_TILES * TR)), B).  x: the pixels, addressed as lt_rows' in; out: [B][H][W] 0 / 1,
+// with LEVELS (cs_segment_hysteresis) 0 / 1 / 2.
+template <typename PIX, bool LEVELS>
 __global__ __launch_bounds__(SG_THREADS) void lt_cols(const unsigned int* __restrict__ sums, const PIX* __restrict__ x, size_t x_img,
-                                                      int x_pix, int H, int W, int r, int TR, long long n, long long n_delta, int floor,
-                                                      unsigned char* __restrict__ out)
+                                                      int x_pix, int H, int W, int r, int TR, long long n, long long n_delta,
+                                                      long long n_weak, int floor, unsigned char* __restrict__ out)
 {
     const int col = blockIdx.x * LT_COL_W + (threadIdx.x & 63);
     const int y0 = (blockIdx.y * LT_COL_TILES + (threadIdx.x >> 6)) * TR, y1 = min(y0 + TR, H);
@@ -1138,13 +1151,13 @@ __global__ __launch_bounds__(SG_THREADS) void lt_cols(const unsigned int* __rest
         }
 #pragma unroll
         for (int u = 0; u < LT_COL_U; ++u) {
-            oc[(size_t)(y + u) * W] = (n * v[u] - S - n_delta > 0 && v[u] > floor) ? 1 : 0;
+            oc[(size_t)(y + u) * W] = lt_cut<LEVELS>(n, v[u], S, n_delta, n_weak, floor);
             S += (long long)in[u] - (long long)gone[u];
         }
     }
     for (; y < y1; ++y) {
         const int v = xc[(size_t)y * W * x_pix];
-        oc[(size_t)y * W] = (n * v - S - n_delta > 0 && v > floor) ? 1 : 0;
+        oc[(size_t)y * W] = lt_cut<LEVELS>(n, v, S, n_delta, n_weak, floor);
         S += (long long)sc[(size_t)lt_fold(y + r + 1, H) * W] - (long long)sc[(size_t)lt_fold(y - r, H) * W];
     }
 }
@@ -1410,6 +1423,68 @@ __global__ __launch_bounds__(SG_THREADS) void cl_drop(int HW, const int* __restr
     }
 }
 
+// ---- hysteresis threshold (cs_segment_hysteresis) -----------------------------------------------------------------------------
+// Two rules of one form, the weak one with the lower number, so that strong pixels are weak pixels too.  The result keeps the
+// pixels of those components of the weak mask (under the segmenter's connectivity) that hold at least one strong pixel:
+// skimage.filters.apply_hysteresis_threshold with integer rules (tests/hysteresis_reference.py restates it).
+//   hy_levels   global rule: level = 2 where x > thr[b], 1 where x > low_b only, else 0; low_b = min(weak, thr[b]) in counts or
+//               (thr[b] * q) >> 16 as a fraction, derived from the image's own threshold on the device.
+//   lt_cols<PIX, true>   local rule: the level under local_delta and the weak delta from the one margin (lt_rows as it is).
+//   label_mask  components of "level != 0": sg_tile takes any non-zero byte for foreground.
+//   hy_mark     flag[root] = 1 for every pixel of level 2, in a zeroed int plane with one slot per pixel of each image (the
+//               area step's counts plane).  Every writer stores the same constant: plain stores, no atomics, and the outcome
+//               does not depend on their order.  A wave without a strong pixel (most of a field) skips the parent loads.
+//   hy_keep     out = 1 where the pixel's root is flagged.
+// Roots are indices inside their own image and the flags are addressed image by image, so nothing crosses between the images
+// of a batch.  Comparisons and stores of constants only: the plane is a function of its own image alone.
+// grid (nchunks, B)
+template <typename PIX>
+__global__ __launch_bounds__(SG_THREADS) void hy_levels(const PIX* __restrict__ image, int C, int ch, int HW, const int* __restrict__ thr,
+                                                        int fraction, int weak, unsigned char* __restrict__ level)
+{
+    const int b = blockIdx.y, th = thr[b];
+    const int low = fraction ? (int)(((unsigned long long)(unsigned int)max(th, 0) * (unsigned int)weak) >> 16) : min(weak, th);
+    const PIX* img = image + (size_t)b * HW * C + ch;
+    unsigned char* m = level + (size_t)b * HW;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = blockIdx.x * SG_CHUNK + k * SG_THREADS + threadIdx.x;
+        if (i >= HW) continue;
+        const int v = (int)img[(size_t)i * C];
+        m[i] = v > th ? 2 : (v > low ? 1 : 0);
+    }
+}
+
+// grid (nchunks, B); flag: [B][HW], zero before; P after sg_flatten: every pixel of level > 0 holds its root
+__global__ __launch_bounds__(SG_THREADS) void hy_mark(int HW, const unsigned char* __restrict__ level, const int* __restrict__ P,
+                                                      int* __restrict__ flag)
+{
+    const size_t base = (size_t)blockIdx.y * HW;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = blockIdx.x * SG_CHUNK + k * SG_THREADS + threadIdx.x;
+        const bool strong = i < HW && level[base + i] == 2;
+        if (__ballot(strong) == 0ull) continue;         // the whole wave decides alike
+        if (!strong) continue;
+        const int root = P[base + i];
+        if (root >= 0) flag[base + root] = 1;
+    }
+}
+
+// grid (nchunks, B)
+__global__ __launch_bounds__(SG_THREADS) void hy_keep(int HW, const int* __restrict__ P, const int* __restrict__ flag,
+                                                      unsigned char* __restrict__ out)
+{
+    const size_t base = (size_t)blockIdx.y * HW;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = blockIdx.x * SG_CHUNK + k * SG_THREADS + threadIdx.x;
+        if (i >= HW) continue;
+        const int root = P[base + i];
+        out[base + i] = root >= 0 && flag[base + root] != 0 ? 1 : 0;
+    }
+}
+
 // ---- host state ---------------------------------------------------------------------------------------------------------------
 struct SegmentState {
     DevBuf img, lab, mask, parent, slab, hist, thr, chunks, counts;
@@ -1419,11 +1494,15 @@ struct SegmentState {
     DevBuf lt_in, lt_med, lt_sum, lt_out;               // cs_segment_local only: upload, median, row sums, host staging
     DevBuf cl_out;                                      // cs_segment_clean only: host staging
     DevBuf sm_in, sm_med, sm_t, sm_out;                 // cs_segment_smooth only: upload, median, row pass, host staging
+    DevBuf hy_out;                                      // cs_segment_hysteresis only: host staging
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     hipEvent_t bev[3] = {nullptr, nullptr, nullptr};
     hipEvent_t lev[3] = {nullptr, nullptr, nullptr};
     hipEvent_t cev[4] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t sev[3] = {nullptr, nullptr, nullptr};
+    hipEvent_t hev[3] = {nullptr, nullptr, nullptr};
+    bool hy_pending = false;                            // hev of a call that left its plane on the device: not read yet
+    double hy_level_ms = 0.0, hy_link_ms = 0.0;
     bool sm_pending = false;                            // sev of a call that left its plane on the device: not read yet
     bool sm_median = false;                             // that call ran the median
     double sm_median_ms = 0.0, sm_smooth_ms = 0.0;
@@ -1451,6 +1530,8 @@ struct SegmentState {
         for (hipEvent_t e : cev)
             if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : sev)
+            if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : hev)
             if (e) (void)hipEventDestroy(e);
     }
 };
@@ -1531,10 +1612,12 @@ struct SegmentCall {
     size_t npx;
     int* d_lab;
     dim3 pgrid;
+    const void* d_img;
 };
 
-static int segment_mask(cs_preproc* p, const void* image, int pixel_type, int32_t channels, int32_t channel, int32_t batch, int32_t height,
-                        int32_t width, int in_kind, const cs_segment_params& sp, int32_t* labels, int labels_kind, SegmentCall& c)
+// the state, the uploads and the common workspace
+static int segment_begin(cs_preproc* p, const void* image, int pixel_type, int32_t channels, int32_t batch, int32_t height, int32_t width,
+                         int in_kind, int32_t* labels, int labels_kind, SegmentCall& c)
 {
     HIPCHK(hipSetDevice(p->device));
     if (!p->seg) p->seg = new SegmentState();
@@ -1561,18 +1644,42 @@ static int segment_mask(cs_preproc* p, const void* image, int pixel_type, int32_
     if ((rc = S.mask.ensure(npx)) || (rc = S.parent.ensure(npx * sizeof(int))) || (rc = S.thr.ensure(batch * sizeof(int))) ||
         (rc = S.chunks.ensure((size_t)batch * nchunks * sizeof(int))) || (rc = S.counts.ensure(batch * sizeof(int))))
         return rc;
+    c = SegmentCall{(int)batch, H, W, HW, nchunks, npx, d_lab, dim3((unsigned)nchunks, (unsigned)batch), d_img};
+    return CS_OK;
+}
 
-    HIPCHK(hipEventRecord(S.ev[0], st));
+// thr[b]: the fixed threshold, or Otsu's of image b
+static int segment_thresholds(SegmentState& S, const SegmentCall& c, int pixel_type, int C, int channel, const cs_segment_params& sp,
+                              hipStream_t st)
+{
+    int rc;
     if (sp.threshold_mode == CS_THRESH_FIXED) {
-        hipLaunchKernelGGL(sg_fixed, dim3((unsigned)((batch + SG_THREADS - 1) / SG_THREADS)), dim3(SG_THREADS), 0, st, S.thr.as<int>(), (int)batch,
-                           (int)sp.threshold);
+        hipLaunchKernelGGL(sg_fixed, dim3((unsigned)((c.batch + SG_THREADS - 1) / SG_THREADS)), dim3(SG_THREADS), 0, st, S.thr.as<int>(),
+                           c.batch, (int)sp.threshold);
         HIPCHK(hipGetLastError());
     } else if (pixel_type == CS_PIX_U8) {
-        if ((rc = otsu_thresholds<unsigned char, 256>((const unsigned char*)d_img, C, channel, batch, HW, S, st))) return rc;
+        if ((rc = otsu_thresholds<unsigned char, 256>((const unsigned char*)c.d_img, C, channel, c.batch, c.HW, S, st))) return rc;
     } else {
-        if ((rc = otsu_thresholds<unsigned short, 65536>((const unsigned short*)d_img, C, channel, batch, HW, S, st))) return rc;
+        if ((rc = otsu_thresholds<unsigned short, 65536>((const unsigned short*)c.d_img, C, channel, c.batch, c.HW, S, st))) return rc;
     }
-    const dim3 pgrid((unsigned)nchunks, (unsigned)batch);
+    return CS_OK;
+}
+
+static int segment_mask(cs_preproc* p, const void* image, int pixel_type, int32_t channels, int32_t channel, int32_t batch, int32_t height,
+                        int32_t width, int in_kind, const cs_segment_params& sp, int32_t* labels, int labels_kind, SegmentCall& c)
+{
+    int rc;
+    if ((rc = segment_begin(p, image, pixel_type, channels, batch, height, width, in_kind, labels, labels_kind, c))) return rc;
+    SegmentState& S = *p->seg;
+    hipStream_t st = p->stream;
+    const int H = c.H, W = c.W, HW = c.HW, C = channels, nchunks = c.nchunks;
+    const size_t npx = c.npx;
+    const void* d_img = c.d_img;
+    int* d_lab = c.d_lab;
+    const dim3 pgrid = c.pgrid;
+
+    HIPCHK(hipEventRecord(S.ev[0], st));
+    if ((rc = segment_thresholds(S, c, pixel_type, C, channel, sp, st))) return rc;
     if (pixel_type == CS_PIX_U8)
         hipLaunchKernelGGL(sg_mask<unsigned char>, pgrid, dim3(SG_THREADS), 0, st, (const unsigned char*)d_img, C, (int)channel, HW,
                            S.thr.as<int>(), S.mask.as<unsigned char>());
@@ -1591,7 +1698,6 @@ static int segment_mask(cs_preproc* p, const void* image, int pixel_type, int32_
         hipLaunchKernelGGL(sg_fill, pgrid, dim3(SG_THREADS), 0, st, HW, S.parent.as<int>(), d_lab, S.mask.as<unsigned char>());
         HIPCHK(hipGetLastError());
     }
-    c = SegmentCall{(int)batch, H, W, HW, nchunks, npx, d_lab, pgrid};
     return CS_OK;
 }
 
@@ -1658,10 +1764,11 @@ static int background_times(SegmentState& S)
     return CS_OK;
 }
 
-// median (optional), row sums, column sums + compare on the stream; d_out is a [B][H][W] uint8 plane on the device
+// median (optional), row sums, column sums + compare on the stream; d_out is a [B][H][W] uint8 plane on the device: 0 / 1, or
+// with weak_delta (cs_segment_hysteresis) the levels 0 / 1 / 2 under that delta and lp.delta
 template <typename PIX>
 static int local_launch(SegmentState& S, const PIX* d_img, int C, int ch, int batch, int H, int W, const cs_local_params& lp,
-                        unsigned char* d_out, hipStream_t st)
+                        unsigned char* d_out, hipStream_t st, const int32_t* weak_delta = nullptr)
 {
     const int HW = H * W, r = lp.radius, TR = bg_col_rows(r);
     int rc;
@@ -1685,10 +1792,23 @@ static int local_launch(SegmentState& S, const PIX* d_img, int C, int ch, int ba
     const dim3 cgrid((unsigned)((W + LT_COL_W - 1) / LT_COL_W), (unsigned)((H + LT_COL_TILES * TR - 1) / (LT_COL_TILES * TR)), (unsigned)batch);
     const long long n = (long long)(2 * r + 1) * (2 * r + 1);
     hipLaunchKernelGGL(lt_rows<PIX>, rgrid, dim3(SG_THREADS), 0, st, x, x_img, x_pix, H, W, r, S.lt_sum.as<unsigned int>());
-    hipLaunchKernelGGL(lt_cols<PIX>, cgrid, dim3(SG_THREADS), 0, st, (const unsigned int*)S.lt_sum.as<unsigned int>(), x, x_img, x_pix, H, W, r,
-                       TR, n, n * lp.delta, (int)lp.floor, d_out);
+    if (weak_delta)
+        hipLaunchKernelGGL((lt_cols<PIX, true>), cgrid, dim3(SG_THREADS), 0, st, (const unsigned int*)S.lt_sum.as<unsigned int>(), x, x_img,
+                           x_pix, H, W, r, TR, n, n * lp.delta, n * *weak_delta, (int)lp.floor, d_out);
+    else
+        hipLaunchKernelGGL((lt_cols<PIX, false>), cgrid, dim3(SG_THREADS), 0, st, (const unsigned int*)S.lt_sum.as<unsigned int>(), x, x_img,
+                           x_pix, H, W, r, TR, n, n * lp.delta, 0ll, (int)lp.floor, d_out);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(S.lev[2], st));
+    return CS_OK;
+}
+
+static int local_check(const cs_local_params& lp)
+{
+    if (lp.radius < 1 || lp.radius > LT_MAX_R) return fail(CS_ERR_INVALID, "local radius %d outside 1..%d", (int)lp.radius, LT_MAX_R);
+    if (lp.delta < -65535 || lp.delta > 65535) return fail(CS_ERR_INVALID, "local delta %d outside -65535..65535", (int)lp.delta);
+    if (lp.floor < -1 || lp.floor > 65535) return fail(CS_ERR_INVALID, "local floor %d outside -1..65535", (int)lp.floor);
+    if (lp.median != 0 && lp.median != 1) return fail(CS_ERR_INVALID, "median %d: 0 or 1", (int)lp.median);
     return CS_OK;
 }
 
@@ -1781,6 +1901,18 @@ static int clean_times(SegmentState& S)
     S.cl_open_ms = S.cl_opened ? ms : 0.0;              // without a step its two records are back to back
     HIPCHK(hipEventElapsedTime(&ms, S.cev[2], S.cev[3]));
     S.cl_area_ms = S.cl_dropped ? ms : 0.0;
+    return CS_OK;
+}
+
+static int hysteresis_times(SegmentState& S)
+{
+    float ms = 0.f;
+    HIPCHK(hipEventSynchronize(S.hev[2]));
+    S.hy_pending = false;
+    HIPCHK(hipEventElapsedTime(&ms, S.hev[0], S.hev[1]));
+    S.hy_level_ms = ms;
+    HIPCHK(hipEventElapsedTime(&ms, S.hev[1], S.hev[2]));
+    S.hy_link_ms = ms;
     return CS_OK;
 }
 
@@ -2137,10 +2269,7 @@ int cs_segment_local(cs_preproc* p, const void* image, int pixel_type, int32_t c
         return fail(CS_ERR_INVALID, "channel %d of %d: need 0 <= channel < channels", (int)channel, (int)channels);
     if (batch < 1 || height < 1 || width < 1) return fail(CS_ERR_INVALID, "batch %d, height %d, width %d: all must be >= 1", (int)batch,
                                                           (int)height, (int)width);
-    if (params->radius < 1 || params->radius > LT_MAX_R) return fail(CS_ERR_INVALID, "local radius %d outside 1..%d", (int)params->radius, LT_MAX_R);
-    if (params->delta < -65535 || params->delta > 65535) return fail(CS_ERR_INVALID, "local delta %d outside -65535..65535", (int)params->delta);
-    if (params->floor < -1 || params->floor > 65535) return fail(CS_ERR_INVALID, "local floor %d outside -1..65535", (int)params->floor);
-    if (params->median != 0 && params->median != 1) return fail(CS_ERR_INVALID, "median %d: 0 or 1", (int)params->median);
+    if (const int bad = local_check(*params)) return bad;
     if (height > kSegMaxSide || width > kSegMaxSide)
         return fail(CS_ERR_UNSUPPORTED, "image %dx%d: sides above %d are not supported", (int)height, (int)width, kSegMaxSide);
     if (batch > kSegMaxBatch) return fail(CS_ERR_UNSUPPORTED, "batch %d: at most %d images per call", (int)batch, kSegMaxBatch);
@@ -2275,6 +2404,106 @@ int cs_segment_clean_last_timing(const cs_preproc* p, double* mask_ms, double* o
     if (mask_ms) *mask_ms = S ? S->cl_mask_ms : 0.0;
     if (open_ms) *open_ms = S ? S->cl_open_ms : 0.0;
     if (area_ms) *area_ms = S ? S->cl_area_ms : 0.0;
+    return CS_OK;
+}
+
+int cs_segment_hysteresis(cs_preproc* p, const void* image, int pixel_type, int32_t channels, int32_t channel, int32_t batch,
+                          int32_t height, int32_t width, int in_kind, const cs_segment_params* params, const cs_local_params* local,
+                          const cs_hysteresis_params* hysteresis, uint8_t* out, int out_kind, int32_t* thresholds)
+{
+    if (!hysteresis || !out) return fail(CS_ERR_INVALID, "NULL argument");
+    cs_segment_params sp;
+    // segment_check's rules with the plane in the labels' place: it looks at no more of them than NULL and the kind
+    int rc = segment_check(image, pixel_type, channels, channel, batch, height, width, in_kind, params, (const int32_t*)out, out_kind,
+                           (const int32_t*)out, sp);
+    if (rc) return rc;
+    const int mode = hysteresis->mode, weak = hysteresis->weak;
+    if (mode != CS_WEAK_ABSOLUTE && mode != CS_WEAK_FRACTION && mode != CS_WEAK_LOCAL)
+        return fail(CS_ERR_INVALID, "hysteresis mode %d: CS_WEAK_ABSOLUTE, CS_WEAK_FRACTION or CS_WEAK_LOCAL", mode);
+    if (hysteresis->reserved[0] != 0 || hysteresis->reserved[1] != 0) return fail(CS_ERR_INVALID, "cs_hysteresis_params.reserved must be 0");
+    if (mode == CS_WEAK_LOCAL) {
+        if (!local) return fail(CS_ERR_INVALID, "CS_WEAK_LOCAL needs cs_local_params");
+        if ((rc = local_check(*local))) return rc;
+        if (weak < -65535 || weak > 65535) return fail(CS_ERR_INVALID, "weak delta %d outside -65535..65535", weak);
+        if (weak > local->delta) return fail(CS_ERR_INVALID, "weak delta %d above the local delta %d", weak, (int)local->delta);
+    } else {
+        if (local) return fail(CS_ERR_INVALID, "cs_local_params belong to CS_WEAK_LOCAL: pass NULL");
+        if (mode == CS_WEAK_ABSOLUTE) {
+            if (weak < 0 || weak > 65535) return fail(CS_ERR_INVALID, "weak threshold %d outside 0..65535", weak);
+            if (sp.threshold_mode == CS_THRESH_FIXED && weak > sp.threshold)
+                return fail(CS_ERR_INVALID, "weak threshold %d above the threshold %d", weak, (int)sp.threshold);
+        } else if (weak < 1 || weak > 65535)
+            return fail(CS_ERR_INVALID, "weak fraction %d / 65536 outside 1..65535", weak);
+    }
+    if (!p) {
+        rc = require_gfx950(0);
+        return rc ? rc : fail(CS_ERR_INVALID, "handle is NULL");
+    }
+    // the workspace of a call whose labels go to the host: its 4 bytes per pixel hold the flags
+    SegmentCall c;
+    if ((rc = segment_begin(p, image, pixel_type, channels, batch, height, width, in_kind, nullptr, CS_MEM_HOST, c))) return rc;
+    SegmentState& S = *p->seg;
+    for (hipEvent_t& e : S.hev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    for (hipEvent_t& e : S.lev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    hipStream_t st = p->stream;
+    unsigned char* d_out = out;
+    if (out_kind == CS_MEM_HOST) {
+        if ((rc = S.hy_out.ensure(c.npx))) return rc;
+        d_out = S.hy_out.as<unsigned char>();
+    }
+    S.hy_pending = false;
+    unsigned char* level = S.mask.as<unsigned char>();
+    HIPCHK(hipEventRecord(S.hev[0], st));
+    if (mode == CS_WEAK_LOCAL) {
+        S.lt_pending = false;                           // local_launch records over the events of an earlier cs_segment_local
+        if (pixel_type == CS_PIX_U8)
+            rc = local_launch<unsigned char>(S, (const unsigned char*)c.d_img, channels, channel, batch, c.H, c.W, *local, level, st, &weak);
+        else
+            rc = local_launch<unsigned short>(S, (const unsigned short*)c.d_img, channels, channel, batch, c.H, c.W, *local, level, st, &weak);
+        if (rc) return rc;
+    } else {
+        if ((rc = segment_thresholds(S, c, pixel_type, channels, channel, sp, st))) return rc;
+        if (pixel_type == CS_PIX_U8)
+            hipLaunchKernelGGL(hy_levels<unsigned char>, c.pgrid, dim3(SG_THREADS), 0, st, (const unsigned char*)c.d_img, (int)channels,
+                               (int)channel, c.HW, (const int*)S.thr.as<int>(), (int)(mode == CS_WEAK_FRACTION), weak, level);
+        else
+            hipLaunchKernelGGL(hy_levels<unsigned short>, c.pgrid, dim3(SG_THREADS), 0, st, (const unsigned short*)c.d_img, (int)channels,
+                               (int)channel, c.HW, (const int*)S.thr.as<int>(), (int)(mode == CS_WEAK_FRACTION), weak, level);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(S.hev[1], st));
+    HIPCHK(hipMemsetAsync(c.d_lab, 0, c.npx * sizeof(int), st));
+    HIPCHK(label_mask(level, batch, c.H, c.W, 0, sp.connectivity == 2, S.parent.as<int>(), nullptr, c.nchunks, st));
+    hipLaunchKernelGGL(hy_mark, c.pgrid, dim3(SG_THREADS), 0, st, c.HW, (const unsigned char*)level, (const int*)S.parent.as<int>(), c.d_lab);
+    hipLaunchKernelGGL(hy_keep, c.pgrid, dim3(SG_THREADS), 0, st, c.HW, (const int*)S.parent.as<int>(), (const int*)c.d_lab, d_out);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(S.hev[2], st));
+    const bool read_thr = thresholds && mode != CS_WEAK_LOCAL;
+    if (thresholds && mode == CS_WEAK_LOCAL)
+        for (int b = 0; b < batch; ++b) thresholds[b] = -1;                 // no single number
+    if (out_kind == CS_MEM_DEVICE && in_kind == CS_MEM_DEVICE && !read_thr) {
+        S.hy_pending = true;                            // no host synchronisation: the times are read when they are asked for
+        return CS_OK;
+    }
+    if (read_thr) HIPCHK(hipMemcpyAsync(thresholds, S.thr.p, batch * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (out_kind == CS_MEM_HOST) HIPCHK(hipMemcpyAsync(out, d_out, c.npx, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));                     // the one host synchronisation: host buffers are free / filled
+    return hysteresis_times(S);
+}
+
+int cs_segment_hysteresis_last_timing(const cs_preproc* p, double* level_ms, double* link_ms)
+{
+    if (!p) return fail(CS_ERR_INVALID, "handle is NULL");
+    SegmentState* S = p->seg;
+    if (S && S->hy_pending) {
+        HIPCHK(hipSetDevice(p->device));
+        const int rc = hysteresis_times(*S);
+        if (rc) return rc;
+    }
+    if (level_ms) *level_ms = S ? S->hy_level_ms : 0.0;
+    if (link_ms) *link_ms = S ? S->hy_link_ms : 0.0;
     return CS_OK;
 }
 

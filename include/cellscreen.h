@@ -29,7 +29,8 @@
  *   cs_segment_threshold / cs_segment_split / cs_segment_split_intensity
  *        the library's own classical segmenter (no reference counterpart, and no StarDist): Otsu or
  *        fixed threshold, optional hole filling, connected-component labels for the extraction above
- *        (cs_segment_smooth, cs_segment_background, cs_segment_local, cs_segment_clean: optional stages before the labels)
+ *        (cs_segment_smooth, cs_segment_background, cs_segment_local, cs_segment_hysteresis, cs_segment_clean: optional stages
+ *        before the labels)
  *   cs_fit_scaler / cs_fit_pca_moments / cs_fit_pca_subspace / cs_fit_project / cs_fit_ocsvm
  *        RobustScaler / PCA / OneClassSVM fits of create_anomaly_detector
  *                                                 CAE_improved_modeltrain.py:408-427
@@ -600,6 +601,52 @@ int cs_segment_clean(cs_preproc *p, const void *image, int pixel_type, int32_t c
 /* Device time of the last cs_segment_clean: threshold + mask + hole filling, the opening (0 without it), and the labelling,
  * counting and dropping of the area step (0 without it).  Waits for that call's plane if it was left on the device. */
 int cs_segment_clean_last_timing(const cs_preproc *p, double *mask_ms, double *open_ms, double *area_ms);
+
+/* Hysteresis threshold, in the place of the plain cut (or of cs_segment_local): two rules of one form instead of one.  A pixel is
+ * foreground if it passes the weak rule and is connected, through pixels that pass it too, to a pixel that passes the strong
+ * rule: skimage.filters.apply_hysteresis_threshold, decided in integers.  Speckle has no strong pixel and goes whatever its
+ * size; a cell keeps its whole weak extent.  Each image on its own:
+ *   strong    the rule there is without this stage.  Global: x > t_b, t_b Otsu's threshold of image b or the fixed one.
+ *             CS_WEAK_LOCAL: n * x - S - n * local->delta > 0 and x > local->floor, as cs_segment_local.
+ *   weak      CS_WEAK_ABSOLUTE: x > low_b, low_b = min(weak, t_b), weak in counts (0..65535; with CS_THRESH_FIXED not above the
+ *             threshold).  CS_WEAK_FRACTION: low_b = (t_b * weak) >> 16, weak = q in 1..65535, a fraction q / 65536 of the strong
+ *             threshold: the form for CS_THRESH_OTSU, where t_b is not known in advance.  CS_WEAK_LOCAL: the strong rule with the
+ *             delta `weak` (-65535..65535, not above local->delta) in local->delta's place; window, reflected edges, floor and
+ *             tie rule (an exact tie is background) are the same.  So every strong pixel is a weak pixel.
+ *   result    the pixels of those components of the weak mask, under params->connectivity, that hold at least one strong pixel.
+ *             With low_b = t_b (or weak = local->delta) it is the plain mask.
+ * image, pixel_type, channels, channel, batch, height, width, in_kind, params: as cs_segment_threshold; with CS_WEAK_LOCAL
+ *      params->threshold_mode and params->threshold are not read.  params->fill_holes is checked and NOT applied: the plane is
+ *      taken before the hole filling, which the labelling call after it does (see out).
+ * local: the local rule's parameters with CS_WEAK_LOCAL (its median runs once, here), NULL otherwise.
+ * out: [batch][height][width] uint8, 0 / 1, out_kind.  Left on the device it is cs_segment_threshold's, cs_segment_split's or
+ *      cs_segment_clean's `image` with pixel_type CS_PIX_U8, channels = 1, channel = 0, CS_THRESH_FIXED and threshold = 0, on
+ *      the same handle (the same stream: no ordering needed); hole filling, cleanup, labels and the split follow unchanged.
+ * thresholds: out, host [batch], or NULL: the strong rule's threshold per image; -1 with CS_WEAK_LOCAL (no single number).
+ * Workspace on the device: cs_segment_threshold's with labels that go to the host (9 bytes per pixel, and the histogram tables
+ * for CS_THRESH_OTSU; the 4 bytes of the labels hold one flag per root), with CS_WEAK_LOCAL cs_segment_local's sums and median
+ * plane, 1 byte per pixel more for an `out` on the host, and the image itself when it comes from the host.
+ * Host synchronisations: none when image and out are both on the device and no threshold has to be read (thresholds NULL, or
+ * CS_WEAK_LOCAL); the plane is then complete in stream order and the times are read when cs_segment_hysteresis_last_timing asks
+ * for them, which waits for the plane.  Else one.
+ * Bad arguments (NULL hysteresis among them, an unknown mode, weak out of its mode's range or above the strong number, reserved
+ * not 0, local missing with CS_WEAK_LOCAL or given without it): CS_ERR_INVALID before any device work; sides above 4096, batches
+ * above 65535: CS_ERR_UNSUPPORTED; without a gfx950 device (p == NULL): CS_ERR_NO_DEVICE. */
+enum { CS_WEAK_ABSOLUTE = 0, CS_WEAK_FRACTION = 1, CS_WEAK_LOCAL = 2 };
+typedef struct cs_hysteresis_params {
+    int32_t mode;                     /* CS_WEAK_ABSOLUTE, CS_WEAK_FRACTION or CS_WEAK_LOCAL */
+    int32_t weak;                     /* counts, q (fraction q / 65536), or the weak delta */
+    int32_t reserved[2];              /* 0 */
+} cs_hysteresis_params;
+int cs_segment_hysteresis(cs_preproc *p, const void *image, int pixel_type, int32_t channels, int32_t channel,
+                          int32_t batch, int32_t height, int32_t width, int in_kind,
+                          const cs_segment_params *params, const cs_local_params *local /* NULL unless CS_WEAK_LOCAL */,
+                          const cs_hysteresis_params *hysteresis /* not NULL */,
+                          uint8_t *out, int out_kind, int32_t *thresholds /* may be NULL */);
+/* Device time of the last cs_segment_hysteresis: everything up to the level plane (thresholds or median and sums, and the
+ * comparison), then the weak components, the flags and the kept plane.  Waits for that call's plane if it was left on the
+ * device. */
+int cs_segment_hysteresis_last_timing(const cs_preproc *p, double *level_ms, double *link_ms);
 
 /* Gaussian smoothing of the segmentation channel, before everything else: for noisy fields, where the threshold shatters a
  * faint cell into fragments that no cleanup of the mask can put together again.  Integers only, each image on its own:

@@ -40,6 +40,14 @@ min_area_ms per image, and the ratios of the cleaned figures to the uncleaned on
 bound and no opening, the extracted cells are compared too.  Then open_ms alone at the radii 1, 3, 7 and 15 with both
 structures, which shows what the radius costs.  No time is a pass condition.
 
+--hysteresis [--weak-delta W] [--strong-delta D] measures the hysteresis threshold (cs_segment_hysteresis,
+ThresholdSegmenter(threshold="local", local_delta=D, weak_delta=W); 40 and 200 by default) on --clean's speckled scene and
+writes profiles/segment_hysteresis_bench.json.  One image's plane and labels are compared with the host restatement
+(tests/hysteresis_reference.py) first; then, in the same run, three segmenters of radius 25: the local rule at delta W alone,
+the same with min_area=50, and weak W / strong D: images/s of segment_batch and of segment + extract, the label counts and the
+stage times of each, the two new stage times per image, and the ratios of the third to the other two.  The first two are
+--clean --delta 40's configurations (profiles/segment_clean_delta40_bench.json).  No time is a pass condition.
+
 --smooth SIGMA [--denoise] measures the Gaussian smoothing (cs_segment_smooth, ThresholdSegmenter(smooth_sigma=SIGMA)) and writes
 profiles/segment_smooth_bench.json.  The scene is faint cells in noise: every image is 16 fields of
 tests/test_smooth_cpu.py's faint_cell_scene (512 x 512, 40 cells of peak 250 over noise of sigma 100) side by side, cut by
@@ -60,7 +68,8 @@ the regions found, the stage times and the host synchronisations per call.  No t
 Usage: python tools/bench_segment.py [--images 32] [--side 2048] [--cells 1000] [--reps 10] [--warmup 2] [--host-images 4]
                                      [--split [--split-cells 3000] [--split-h 3]] [--background R [--denoise]]
                                      [--local R [--delta D] [--denoise]] [--clean [--open R] [--min-area A] [--delta D]] [--smooth SIGMA [--denoise]]
-                                     [--split-intensity [--split-depth 16] [--split-contrast 0]]"""
+                                     [--split-intensity [--split-depth 16] [--split-contrast 0]]
+                                     [--hysteresis [--weak-delta 40] [--strong-delta 200]]"""
 import argparse
 import json
 import os
@@ -464,6 +473,90 @@ def clean_leg(a):
     print(line)
 
 
+def hysteresis_leg(a):
+    import torch
+    import hysteresis_reference as HR
+    import segment_reference as R
+    from build import source_hash
+    from cellscreen import extract as X
+    from cellscreen import segment as S
+    from test_local_cpu import dim_cell_scene
+
+    fill = not a.no_fill_holes
+    dev = torch.device("cuda", 0)
+    med = lambda v: float(np.median(v))
+    tiles = a.side // 512
+    if tiles < 1 or a.side % 512:
+        raise SystemExit("--hysteresis needs --side a multiple of 512: the scene is made of 512 x 512 fields")
+    fields = [dim_cell_scene(seed)[0] for seed in range(tiles * tiles)]
+    base = np.block([[fields[i * tiles + j] for j in range(tiles)] for i in range(tiles)])
+    variants = [base, base[::-1], base[:, ::-1], base[::-1, ::-1]]          # four distinct images from one painting
+    imgs = np.ascontiguousarray(np.stack([variants[b % 4] for b in range(a.images)]))
+    ti = torch.from_numpy(imgs.view(np.int16)).to(dev)
+    torch.cuda.synchronize()
+    radius, weak, strong, min_area = 25, a.weak_delta, a.strong_delta, 50
+    common = dict(threshold="local", connectivity=a.connectivity, fill_holes=fill, local_radius=radius)
+    ext = X.CellExtractor(0)
+    configs = (("weak_alone", S.ThresholdSegmenter(0, extractor=ext, local_delta=weak, **common)),
+               ("weak_min_area", S.ThresholdSegmenter(0, extractor=ext, local_delta=weak, min_area=min_area, **common)),
+               ("hysteresis", S.ThresholdSegmenter(0, extractor=ext, local_delta=strong, weak_delta=weak, **common)))
+
+    def timed(fn, seg):
+        walls, stages = [], []
+        for k in range(a.warmup + a.reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = fn()
+            torch.cuda.synchronize()
+            if k >= a.warmup:
+                walls.append(time.perf_counter() - t0)
+                stages.append(seg.last_timing())
+        return out, walls, stages
+
+    # outputs first: one image's plane and labels against the host restatement
+    hyst = configs[2][1]
+    one = ti[:1].contiguous()
+    plane = hyst.hysteresis_mask_batch(one)
+    labels, n, _ = hyst.segment_batch(one)
+    want = HR.hysteresis(HR.levels_local(imgs[0], radius, strong, weak), a.connectivity)
+    hl, hn = R.label_mask(R.ndimage.binary_fill_holes(want > 0) if fill else want > 0, a.connectivity)
+    assert np.array_equal(plane[0].cpu().numpy(), want), "plane differs from the restatement"
+    assert hn == int(n[0]) and np.array_equal(labels[0].cpu().numpy(), hl), "labels differ from the restatement"
+
+    spread = lambda stages, k: [round(med([t[k] for t in stages]), 4), round(min(t[k] for t in stages), 4),
+                                round(max(t[k] for t in stages), 4)]
+    wall3 = lambda walls: [round(med(walls) * 1e3, 3), round(min(walls) * 1e3, 3), round(max(walls) * 1e3, 3)]
+    res = {"tool": "bench_segment --hysteresis", "source_hash": source_hash(), "images": a.images, "side": a.side,
+           "connectivity": a.connectivity, "fill_holes": fill, "local_radius": radius, "weak_delta": weak, "strong_delta": strong,
+           "min_area": min_area, "cells_painted_per_image": 40 * tiles * tiles, "reps": a.reps, "warmup": a.warmup,
+           "outputs_equal": True}
+    walls_of, chain_of = {}, {}
+    for name, seg in configs:
+        (_, n_lab, _), walls, stages = timed(lambda: seg.segment_batch(ti), seg)
+        r, chain, _ = timed(lambda: ext.extract_batch(ti, seg.segment_batch(ti)[0]), seg)
+        walls_of[name], chain_of[name] = med(walls), med(chain)
+        res[name] = {"labels_per_image": round(float(n_lab.mean()), 1), "regions_measured": len(r.regions),
+                     "cells_extracted": int(r.cells.shape[0]), "segment_images_per_s": round(a.images / med(walls), 2),
+                     "segment_wall_ms": wall3(walls), "segment_extract_images_per_s": round(a.images / med(chain), 2),
+                     "segment_extract_wall_ms": wall3(chain),
+                     **{k: spread(stages, k) for k in sorted(stages[0])}}
+    st = res["hysteresis"]
+    res["hysteresis_level_ms_per_image"] = round(st["hysteresis_level_ms"][0] / a.images, 5)
+    res["hysteresis_link_ms_per_image"] = round(st["hysteresis_link_ms"][0] / a.images, 5)
+    res["min_area_ms_per_image"] = round(res["weak_min_area"]["min_area_ms"][0] / a.images, 5)
+    for other in ("weak_alone", "weak_min_area"):
+        res[f"hysteresis_over_{other}_segment_time"] = round(walls_of["hysteresis"] / walls_of[other], 3)
+        res[f"hysteresis_over_{other}_segment_extract_time"] = round(chain_of["hysteresis"] / chain_of[other], 3)
+    ext.close()
+    line = json.dumps(res)
+    out = a.out if a.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "segment_hysteresis_bench.json")
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            f.write(line + "\n")
+    print(line)
+
+
 def smooth_leg(a):
     import torch
     import segment_reference as R
@@ -586,7 +679,16 @@ def main():
     ap.add_argument("--min-area", type=int, default=None, metavar="A", help="with --clean: min_area (50 when --open is not given either)")
     ap.add_argument("--smooth", type=float, default=None, metavar="SIGMA",
                     help="measure the Gaussian smoothing on a field of faint cells in noise (profiles/segment_smooth_bench.json)")
+    ap.add_argument("--hysteresis", action="store_true",
+                    help="measure the hysteresis threshold on --clean's speckled scene (profiles/segment_hysteresis_bench.json)")
+    ap.add_argument("--weak-delta", type=int, default=40, metavar="W", help="with --hysteresis: the weak delta")
+    ap.add_argument("--strong-delta", type=int, default=200, metavar="D", help="with --hysteresis: the strong delta")
     a = ap.parse_args()
+    if a.hysteresis:
+        if (a.split or a.split_intensity or a.background is not None or a.local is not None or a.clean or a.delta
+                or a.smooth is not None or a.denoise or a.open is not None or a.min_area is not None):
+            ap.error("--hysteresis is measured on its own")
+        return hysteresis_leg(a)
     if a.split_intensity:
         if a.split or a.background is not None or a.local is not None or a.clean or a.delta or a.smooth is not None or a.denoise:
             ap.error("--split-intensity is measured on its own")
