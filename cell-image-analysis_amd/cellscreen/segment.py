@@ -465,198 +465,150 @@ class ThresholdSegmenter:
                 raise ValueError("images must be C-contiguous")
         return B, H, W, Cn, int(channel), ptype, on_dev
 
-    def _smoothed(self, images, B, H, W, Cn, channel, ptype, on_dev):
-        """The smoothed plane [B,H,W] where the images are; a device plane is complete in the handle's stream order only."""
+    def _plane(self, src, dtype, fn, *params, after=()):
+        """The source with the plane that `fn`, a cs_segment_* entry point that makes one, makes of it in the channel's place:
+        [B,H,W] of `dtype` (None: the images' own), allocated where the images are; a device plane is complete in the handle's
+        stream order only.  params: what the entry point takes between the image and the plane, after: what follows the plane."""
+        images, B, H, W, Cn, channel, ptype, on_dev = src
         if on_dev:
             import torch
-            plane = torch.empty((B, H, W), dtype=images.dtype, device=images.device)
+            plane = torch.empty((B, H, W), dtype=images.dtype if dtype is None else torch.uint8, device=images.device)
             L.order_after_torch(self._lib.cs_preproc_wait_stream, self._handle, images, plane)
         else:
-            plane = np.empty((B, H, W), images.dtype)
+            plane = np.empty((B, H, W), images.dtype if dtype is None else dtype)
         kind = L.CS_MEM_DEVICE if on_dev else L.CS_MEM_HOST
-        L.check(self._lib.cs_segment_smooth(self._handle, L._ptr(images), ptype, Cn, channel, B, H, W, kind, C.byref(self._smooth),
-                                            L._ptr(plane), kind))
-        return plane
+        L.check(fn(self._handle, L._ptr(images), ptype, Cn, channel, B, H, W, kind, *params, L._ptr(plane), kind, *after))
+        return plane, B, H, W, 1, 0, (ptype if dtype is None else PIX_U8), on_dev
+
+    def _front(self, src, upto, report=False):
+        """The front of the pipeline on a checked source (images, B, H, W, Cn, channel, ptype, on_dev), up to and including the
+        stage `upto`: "smooth", "background", "local" (the local rule, whatever else is set), "threshold" (the stage in the plain
+        cut's place: hysteresis, else the local rule) or "clean"; a stage that is off is passed over, and each stage takes the
+        plane of the one before in the channel's place.  Returns (src, params, reported, guide): the current plane as a source,
+        the cs_segment_params that cut it, with report the int32 [B] thresholds of the strong rule where a stage here had to
+        read them (else None), and the source the thresholding stage saw."""
+        last = ("smooth", "background", "local", "threshold", "clean").index(upto)
+        lib, B = self._lib, src[1]
+        if self._smooth is not None:
+            src = self._plane(src, None, lib.cs_segment_smooth, C.byref(self._smooth))
+        if last >= 1 and self._background is not None:
+            # the library's final synchronisation comes after everything that reads the plane
+            src = self._plane(src, None, lib.cs_segment_background, C.byref(self._background))
+        # what split_by="intensity" takes its heights from: the plane the threshold stage sees, never a 0 / 1 plane
+        guide = src
+        params, reported = self._params, None
+        otsu = self._params.threshold_mode == L.THRESH_OTSU
+
+        def strong():
+            """Where a stage writes the strong thresholds: Otsu's are computed there, which costs a device plane its one wait; a
+            fixed one and local mode's -1 need no reading."""
+            reported = np.zeros(B, np.int32)
+            if otsu:
+                return reported, reported.ctypes.data
+            reported[:] = self._params.threshold
+            return reported, None
+
+        if last >= 2 and self._hysteresis is not None and upto != "local":
+            # the 0 / 1 plane in the channel's place, cut at the fixed threshold 0
+            reported, thr = strong() if report else (None, None)
+            src = self._plane(src, np.uint8, lib.cs_segment_hysteresis, C.byref(self._params),
+                              None if self._local is None else C.byref(self._local), C.byref(self._hysteresis), after=(thr,))
+            params = self._after_hysteresis
+        elif last >= 2 and self._local is not None:
+            # the 0 / 1 plane in the channel's place, cut at the fixed threshold 0: hole filling, labels and the split as they are
+            src = self._plane(src, np.uint8, lib.cs_segment_local, C.byref(self._local))
+        if last >= 4 and self._clean is not None:
+            # the cleaned 0 / 1 plane in the channel's place, cut at the fixed threshold 0 and not filled again; the thresholds
+            # are the cleanup's unless the hysteresis stage has reported them already
+            thr = None
+            if report and reported is None:
+                reported, thr = strong()
+            src = self._plane(src, np.uint8, lib.cs_segment_clean, C.byref(params), C.byref(self._clean), after=(thr,))
+            params = self._after_clean
+        return src, params, reported, guide
+
+    def _times(self, fn, n):
+        """The n device milliseconds that a cs_segment_*_last_timing reports; for a plane left on the device it waits for it."""
+        v = [C.c_double() for _ in range(n)]
+        L.check(fn(self._handle, *(C.byref(x) for x in v)))
+        return tuple(x.value for x in v)
 
     def _smooth_timing(self):
-        a, b = C.c_double(), C.c_double()
-        L.check(self._lib.cs_segment_smooth_last_timing(self._handle, C.byref(a), C.byref(b)))
-        t = {"smooth_ms": b.value}
+        a, b = self._times(self._lib.cs_segment_smooth_last_timing, 2)
+        t = {"smooth_ms": b}
         if self._smooth.median:
-            t["smooth_median_ms"] = a.value
+            t["smooth_median_ms"] = a
         return t
 
     def smooth_batch(self, images, channel: Optional[int] = None):
         """The smoothed plane of `channel` that every later stage starts from: [B,H,W] of the images' dtype, numpy for numpy
         input, a CUDA tensor for tensor input (complete when this returns).  Needs smooth_sigma."""
-        B, H, W, Cn, channel, ptype, on_dev = self._check(images, channel)
+        src = (images, *self._check(images, channel))
         if self._smooth is None:
             raise ValueError("smooth_batch needs smooth_sigma: this segmenter smooths nothing")
-        plane = self._smoothed(images, B, H, W, Cn, channel, ptype, on_dev)
-        if on_dev:
+        src = self._front(src, "smooth")[0]
+        if src[-1]:
             self._smooth_timing()                                   # reads the times, which waits for the plane: torch may use it
-        return plane
-
-    def _correct(self, images, B, H, W, Cn, channel, ptype, on_dev):
-        """The corrected plane [B,H,W] where the images are; a device plane is complete in the handle's stream order only."""
-        if on_dev:
-            import torch
-            plane = torch.empty((B, H, W), dtype=images.dtype, device=images.device)
-            L.order_after_torch(self._lib.cs_preproc_wait_stream, self._handle, images, plane)
-        else:
-            plane = np.empty((B, H, W), images.dtype)
-        kind = L.CS_MEM_DEVICE if on_dev else L.CS_MEM_HOST
-        L.check(self._lib.cs_segment_background(self._handle, L._ptr(images), ptype, Cn, channel, B, H, W, kind,
-                                                C.byref(self._background), L._ptr(plane), kind))
-        return plane
+        return src[0]
 
     def _background_timing(self):
-        a, b = C.c_double(), C.c_double()
-        L.check(self._lib.cs_segment_background_last_timing(self._handle, C.byref(a), C.byref(b)))
-        return {"median_ms": a.value, "background_ms": b.value}
+        return dict(zip(("median_ms", "background_ms"), self._times(self._lib.cs_segment_background_last_timing, 2)))
 
     def correct_batch(self, images, channel: Optional[int] = None):
         """The background-corrected plane of `channel` that segment_batch thresholds: [B,H,W] of the images' dtype, numpy for
         numpy input, a CUDA tensor for tensor input (complete when this returns).  Needs background_radius."""
-        B, H, W, Cn, channel, ptype, on_dev = self._check(images, channel)
+        src = (images, *self._check(images, channel))
         if self._background is None:
             raise ValueError("correct_batch needs background_radius: this segmenter corrects nothing")
-        if self._smooth is not None:
-            images = self._smoothed(images, B, H, W, Cn, channel, ptype, on_dev)
-            Cn, channel = 1, 0
-        plane = self._correct(images, B, H, W, Cn, channel, ptype, on_dev)
-        if on_dev:
+        src = self._front(src, "background")[0]
+        if src[-1]:
             self._background_timing()                               # reads the times, which waits for the plane: torch may use it
-        return plane
-
-    def _local_mask(self, images, B, H, W, Cn, channel, ptype, on_dev):
-        """The 0 / 1 plane [B,H,W] uint8 where the images are; a device plane is complete in the handle's stream order only."""
-        if on_dev:
-            import torch
-            mask = torch.empty((B, H, W), dtype=torch.uint8, device=images.device)
-            L.order_after_torch(self._lib.cs_preproc_wait_stream, self._handle, images, mask)
-        else:
-            mask = np.empty((B, H, W), np.uint8)
-        kind = L.CS_MEM_DEVICE if on_dev else L.CS_MEM_HOST
-        L.check(self._lib.cs_segment_local(self._handle, L._ptr(images), ptype, Cn, channel, B, H, W, kind, C.byref(self._local),
-                                           L._ptr(mask), kind))
-        return mask
+        return src[0]
 
     def _local_timing(self):
-        a, b = C.c_double(), C.c_double()
-        L.check(self._lib.cs_segment_local_last_timing(self._handle, C.byref(a), C.byref(b)))
-        return {"local_median_ms": a.value, "local_ms": b.value}
+        return dict(zip(("local_median_ms", "local_ms"), self._times(self._lib.cs_segment_local_last_timing, 2)))
 
     def local_mask_batch(self, images, channel: Optional[int] = None):
         """The mask of the local mean threshold that segment_batch fills and labels: [B,H,W] uint8, 1 = foreground, numpy for
         numpy input, a CUDA tensor for tensor input (complete when this returns).  Needs threshold="local"; with
         background_radius it is the mask of the corrected plane."""
-        B, H, W, Cn, channel, ptype, on_dev = self._check(images, channel)
+        src = (images, *self._check(images, channel))
         if self._local is None:
             raise ValueError("local_mask_batch needs threshold='local'")
-        if self._smooth is not None:
-            images = self._smoothed(images, B, H, W, Cn, channel, ptype, on_dev)
-            Cn, channel = 1, 0
-        if self._background is not None:
-            images = self._correct(images, B, H, W, Cn, channel, ptype, on_dev)
-            Cn, channel = 1, 0
-        mask = self._local_mask(images, B, H, W, Cn, channel, ptype, on_dev)
-        if on_dev:
+        src = self._front(src, "local")[0]
+        if src[-1]:
             self._local_timing()                                    # reads the times, which waits for the plane: torch may use it
-        return mask
-
-    def _hysteresis_mask(self, images, B, H, W, Cn, channel, ptype, on_dev, thresholds=None):
-        """The 0 / 1 plane [B,H,W] uint8 of the hysteresis threshold where the images are; a device plane is complete in the
-        handle's stream order only.  thresholds: an int32 [B] array for the strong thresholds, which costs a device plane its
-        one wait unless the rule is local (-1, no reading)."""
-        if on_dev:
-            import torch
-            mask = torch.empty((B, H, W), dtype=torch.uint8, device=images.device)
-            L.order_after_torch(self._lib.cs_preproc_wait_stream, self._handle, images, mask)
-        else:
-            mask = np.empty((B, H, W), np.uint8)
-        kind = L.CS_MEM_DEVICE if on_dev else L.CS_MEM_HOST
-        L.check(self._lib.cs_segment_hysteresis(self._handle, L._ptr(images), ptype, Cn, channel, B, H, W, kind, C.byref(self._params),
-                                                None if self._local is None else C.byref(self._local), C.byref(self._hysteresis),
-                                                L._ptr(mask), kind, None if thresholds is None else thresholds.ctypes.data))
-        return mask
+        return src[0]
 
     def _hysteresis_timing(self):
-        a, b = C.c_double(), C.c_double()
-        L.check(self._lib.cs_segment_hysteresis_last_timing(self._handle, C.byref(a), C.byref(b)))
-        return {"hysteresis_level_ms": a.value, "hysteresis_link_ms": b.value}
-
-    def _thresholded(self, images, B, H, W, Cn, channel, ptype, on_dev, thresholds=None):
-        """The 0 / 1 plane of whichever stage stands in the plain cut's place (hysteresis, else the local rule), or None."""
-        if self._hysteresis is not None:
-            return self._hysteresis_mask(images, B, H, W, Cn, channel, ptype, on_dev, thresholds)
-        if self._local is not None:
-            return self._local_mask(images, B, H, W, Cn, channel, ptype, on_dev)
-        return None
+        return dict(zip(("hysteresis_level_ms", "hysteresis_link_ms"), self._times(self._lib.cs_segment_hysteresis_last_timing, 2)))
 
     def hysteresis_mask_batch(self, images, channel: Optional[int] = None):
         """The mask of the hysteresis threshold, before the hole filling: [B,H,W] uint8, 1 = foreground, numpy for numpy input,
         a CUDA tensor for tensor input (complete when this returns).  Needs weak_threshold or weak_delta; with smooth_sigma and
         background_radius it is the mask of what they make."""
-        B, H, W, Cn, channel, ptype, on_dev = self._check(images, channel)
+        src = (images, *self._check(images, channel))
         if self._hysteresis is None:
             raise ValueError("hysteresis_mask_batch needs weak_threshold or weak_delta: this segmenter has one rule")
-        if self._smooth is not None:
-            images = self._smoothed(images, B, H, W, Cn, channel, ptype, on_dev)
-            Cn, channel = 1, 0
-        if self._background is not None:
-            images = self._correct(images, B, H, W, Cn, channel, ptype, on_dev)
-            Cn, channel = 1, 0
-        mask = self._hysteresis_mask(images, B, H, W, Cn, channel, ptype, on_dev)
-        if on_dev:
+        src = self._front(src, "threshold")[0]
+        if src[-1]:
             self._hysteresis_timing()                               # reads the times, which waits for the plane: torch may use it
-        return mask
-
-    def _clean_mask(self, images, B, H, W, Cn, channel, ptype, on_dev, thresholds=None, params=None):
-        """The cleaned 0 / 1 plane [B,H,W] uint8 where the images are; a device plane is complete in the handle's stream order
-        only.  thresholds: an int32 [B] array for the thresholds of the mask, which costs a device plane its one wait.
-        params: what cuts the plane, the segmenter's own unless a stage before has made it 0 / 1."""
-        if on_dev:
-            import torch
-            mask = torch.empty((B, H, W), dtype=torch.uint8, device=images.device)
-            L.order_after_torch(self._lib.cs_preproc_wait_stream, self._handle, images, mask)
-        else:
-            mask = np.empty((B, H, W), np.uint8)
-        kind = L.CS_MEM_DEVICE if on_dev else L.CS_MEM_HOST
-        L.check(self._lib.cs_segment_clean(self._handle, L._ptr(images), ptype, Cn, channel, B, H, W, kind,
-                                           C.byref(self._params if params is None else params),
-                                           C.byref(self._clean), L._ptr(mask), kind,
-                                           None if thresholds is None else thresholds.ctypes.data))
-        return mask
+        return src[0]
 
     def _clean_timing(self):
-        v = [C.c_double() for _ in range(3)]
-        L.check(self._lib.cs_segment_clean_last_timing(self._handle, *(C.byref(x) for x in v)))
-        return {"open_ms": v[1].value, "min_area_ms": v[2].value}
+        return dict(zip(("open_ms", "min_area_ms"), self._times(self._lib.cs_segment_clean_last_timing, 3)[1:]))
 
     def clean_mask_batch(self, images, channel: Optional[int] = None):
         """The cleaned mask that segment_batch labels: [B,H,W] uint8, 1 = foreground, numpy for numpy input, a CUDA tensor for
         tensor input (complete when this returns).  Needs open_radius or min_area; with background_radius and threshold="local"
         it is the cleaned mask of what they make."""
-        B, H, W, Cn, channel, ptype, on_dev = self._check(images, channel)
+        src = (images, *self._check(images, channel))
         if self._clean is None:
             raise ValueError("clean_mask_batch needs open_radius or min_area: this segmenter cleans nothing")
-        if self._smooth is not None:
-            images = self._smoothed(images, B, H, W, Cn, channel, ptype, on_dev)
-            Cn, channel = 1, 0
-        if self._background is not None:
-            images = self._correct(images, B, H, W, Cn, channel, ptype, on_dev)
-            Cn, channel = 1, 0
-        params = None
-        plane = self._thresholded(images, B, H, W, Cn, channel, ptype, on_dev)
-        if plane is not None:
-            images, Cn, channel, ptype = plane, 1, 0, PIX_U8
-            if self._hysteresis is not None:
-                params = self._after_hysteresis
-        mask = self._clean_mask(images, B, H, W, Cn, channel, ptype, on_dev, params=params)
-        if on_dev:
+        src = self._front(src, "clean")[0]
+        if src[-1]:
             self._clean_timing()                                    # reads the times, which waits for the plane: torch may use it
-        return mask
+        return src[0]
 
     def segment_batch(self, images, channel: Optional[int] = None, return_distance: bool = False):
         """images: [B,H,W] or [B,H,W,C] uint8 / uint16, numpy or CUDA tensors of the segmenter's device; the channel that is
@@ -665,48 +617,13 @@ class ThresholdSegmenter:
         component's first pixel), numpy for numpy input and a CUDA tensor for tensor input; n_labels and thresholds int32
         numpy [B].  return_distance (split_touching only): a fourth result, uint8 [B,H,W] where the labels are: the distance
         to the background in half pixels, capped at 255; with split_by="intensity" the heights Hq the split used instead."""
-        B, H, W, Cn, channel, ptype, on_dev = self._check(images, channel)
+        src = (images, *self._check(images, channel))
         if return_distance and self._split is None:
             raise ValueError("return_distance needs split_touching=True: the plain segmenter computes no distances")
-        if self._smooth is not None:
-            # every later stage takes the smoothed plane in the channel's place
-            images = self._smoothed(images, B, H, W, Cn, channel, ptype, on_dev)
-            Cn, channel = 1, 0
-        if self._background is not None:
-            # threshold, label and split the corrected plane in the channel's place; the library's final synchronisation
-            # comes after everything that reads the plane
-            images = self._correct(images, B, H, W, Cn, channel, ptype, on_dev)
-            Cn, channel = 1, 0
-        # what split_by="intensity" takes its heights from: the plane the threshold stage sees, never a 0 / 1 plane
-        guide, guide_cn, guide_channel, guide_ptype = images, Cn, channel, ptype
-        params, reported = self._params, None
-        otsu = self._params.threshold_mode == L.THRESH_OTSU
-        if self._hysteresis is not None:
-            # the 0 / 1 plane in the channel's place, cut at the fixed threshold 0; the thresholds are the strong rule's, read
-            # here (Otsu's are computed here; a fixed one and local mode's -1 need no reading)
-            reported = np.zeros(B, np.int32)
-            images = self._hysteresis_mask(images, B, H, W, Cn, channel, ptype, on_dev, reported if otsu else None)
-            if not otsu:
-                reported[:] = self._params.threshold
-            Cn, channel, ptype, params = 1, 0, PIX_U8, self._after_hysteresis
-        elif self._local is not None:
-            # the 0 / 1 plane in the channel's place, cut at the fixed threshold 0: hole filling, labels and the split as they are
-            images = self._local_mask(images, B, H, W, Cn, channel, ptype, on_dev)
-            Cn, channel, ptype = 1, 0, PIX_U8
+        # every stage takes the plane of the one before in the channel's place; threshold, label and split what they leave
+        (images, B, H, W, Cn, channel, ptype, on_dev), params, reported, guide = self._front(src, "clean", report=True)
         n_labels = np.zeros(B, np.int32)
         thresholds = np.zeros(B, np.int32)
-        if self._clean is not None:
-            # the cleaned 0 / 1 plane in the channel's place, cut at the fixed threshold 0 and not filled again; the thresholds
-            # are the cleanup's (Otsu's are computed there; a fixed one and local mode's -1 need no reading) unless the
-            # hysteresis stage has reported them already
-            if reported is None:
-                reported = np.zeros(B, np.int32)
-                images = self._clean_mask(images, B, H, W, Cn, channel, ptype, on_dev, reported if otsu else None)
-                if not otsu:
-                    reported[:] = self._params.threshold
-            else:
-                images = self._clean_mask(images, B, H, W, Cn, channel, ptype, on_dev, params=params)
-            Cn, channel, ptype, params = 1, 0, PIX_U8, self._after_clean
         if on_dev:
             import torch
             labels = torch.empty((B, H, W), dtype=torch.int32, device=images.device)
@@ -732,8 +649,8 @@ class ThresholdSegmenter:
                 dist = np.empty((B, H, W), np.uint8)
         if self._split_intensity is not None:
             L.check(self._lib.cs_segment_split_intensity(self._handle, L._ptr(images), ptype, Cn, channel, B, H, W, kind,
-                                                         C.byref(params), C.byref(self._split_intensity), L._ptr(guide), guide_ptype,
-                                                         guide_cn, guide_channel, L._ptr(labels), kind, n_labels.ctypes.data,
+                                                         C.byref(params), C.byref(self._split_intensity), L._ptr(guide[0]), guide[6],
+                                                         guide[4], guide[5], L._ptr(labels), kind, n_labels.ctypes.data,
                                                          thresholds.ctypes.data, L._ptr(dist)))
         else:
             L.check(self._lib.cs_segment_split(self._handle, L._ptr(images), ptype, Cn, channel, B, H, W, kind, C.byref(params),
@@ -765,15 +682,12 @@ class ThresholdSegmenter:
         if self._clean is not None:
             extra.update(self._clean_timing())
         if self._split is None:
-            a, b = C.c_double(), C.c_double()
-            L.check(self._lib.cs_segment_last_timing(self._handle, C.byref(a), C.byref(b)))
-            return dict({"threshold_ms": a.value, "label_ms": b.value}, **extra)
-        v = [C.c_double() for _ in range(4)]
+            return dict(zip(("threshold_ms", "label_ms"), self._times(self._lib.cs_segment_last_timing, 2)), **extra)
         if self._split_intensity is not None:
-            L.check(self._lib.cs_segment_split_intensity_last_timing(self._handle, *(C.byref(x) for x in v)))
-            return dict(zip(("threshold_ms", "height_ms", "seed_ms", "flood_ms"), (x.value for x in v)), **extra)
-        L.check(self._lib.cs_segment_split_last_timing(self._handle, *(C.byref(x) for x in v)))
-        return dict(zip(("threshold_ms", "distance_ms", "seed_ms", "flood_ms"), (x.value for x in v)), **extra)
+            return dict(zip(("threshold_ms", "height_ms", "seed_ms", "flood_ms"),
+                            self._times(self._lib.cs_segment_split_intensity_last_timing, 4)), **extra)
+        return dict(zip(("threshold_ms", "distance_ms", "seed_ms", "flood_ms"), self._times(self._lib.cs_segment_split_last_timing, 4)),
+                    **extra)
 
 
     def last_host_syncs(self) -> int:

@@ -1486,57 +1486,72 @@ __global__ __launch_bounds__(SG_THREADS) void hy_keep(int HW, const int* __restr
 }
 
 // ---- host state ---------------------------------------------------------------------------------------------------------------
-struct SegmentState {
-    DevBuf img, lab, mask, parent, slab, hist, thr, chunks, counts;
-    DevBuf dq, rec, key, ttop, ctrl;                    // cs_segment_split and cs_segment_split_intensity only
-    DevBuf si_guide;                                    // cs_segment_split_intensity only: a guide uploaded from the host
-    DevBuf bg_in, bg_med, bg_a, bg_b, bg_out;           // cs_segment_background only: upload, median, two planes, host staging
-    DevBuf lt_in, lt_med, lt_sum, lt_out;               // cs_segment_local only: upload, median, row sums, host staging
-    DevBuf cl_out;                                      // cs_segment_clean only: host staging
-    DevBuf sm_in, sm_med, sm_t, sm_out;                 // cs_segment_smooth only: upload, median, row pass, host staging
-    DevBuf hy_out;                                      // cs_segment_hysteresis only: host staging
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t bev[3] = {nullptr, nullptr, nullptr};
-    hipEvent_t lev[3] = {nullptr, nullptr, nullptr};
-    hipEvent_t cev[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t sev[3] = {nullptr, nullptr, nullptr};
-    hipEvent_t hev[3] = {nullptr, nullptr, nullptr};
-    bool hy_pending = false;                            // hev of a call that left its plane on the device: not read yet
-    double hy_level_ms = 0.0, hy_link_ms = 0.0;
-    bool sm_pending = false;                            // sev of a call that left its plane on the device: not read yet
-    bool sm_median = false;                             // that call ran the median
-    double sm_median_ms = 0.0, sm_smooth_ms = 0.0;
-    bool cl_pending = false;                            // cev of a call that left its plane on the device: not read yet
-    bool cl_opened = false, cl_dropped = false;         // the steps that call ran
-    double cl_mask_ms = 0.0, cl_open_ms = 0.0, cl_area_ms = 0.0;
-    bool lt_pending = false;                            // lev of a call that left its plane on the device: not read yet
-    bool lt_median = false;                             // that call ran the median
-    double lt_median_ms = 0.0, lt_sum_ms = 0.0;
-    bool bg_pending = false;                            // bev of a call that left its plane on the device: not read yet
-    bool bg_median = false;                             // that call ran the median
-    double bg_median_ms = 0.0, bg_tophat_ms = 0.0;
-    double threshold_ms = 0.0, label_ms = 0.0;
-    double sp_threshold_ms = 0.0, sp_distance_ms = 0.0, sp_seed_ms = 0.0, sp_flood_ms = 0.0;
-    double si_threshold_ms = 0.0, si_height_ms = 0.0, si_seed_ms = 0.0, si_flood_ms = 0.0;
-    int sp_recon_reads = 0, sp_flood_reads = 0;         // control-word reads (one host synchronisation each) of the last split of either kind
-    ~SegmentState()
+// The device times of one family of entry points: up to five events on the handle's stream, created on first use, and the
+// spans between neighbours in milliseconds.  A new call records over the events of an earlier one whichever entry point it
+// came through (cs_segment_hysteresis runs the local rule's launch), so the first record drops what was not read yet.
+struct StageClock {
+    static constexpr int kEvents = 5;
+    hipEvent_t ev[kEvents] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    bool ran[kEvents - 1] = {false, false, false, false};   // span k, ev[k] .. ev[k + 1]: its step ran in the call that recorded it
+    int last = 0;                                       // the last event of that call
+    bool pending = false;                               // the events of a call that left its plane on the device: not read yet
+    double ms[kEvents - 1] = {0.0, 0.0, 0.0, 0.0};
+    StageClock() = default;
+    StageClock(const StageClock&) = delete;
+    StageClock& operator=(const StageClock&) = delete;
+    ~StageClock()
     {
         for (hipEvent_t e : ev)
             if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : bev)
-            if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : lev)
-            if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : cev)
-            if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : sev)
-            if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : hev)
-            if (e) (void)hipEventDestroy(e);
+    }
+    // event k on the stream; step_ran: whether the step of the span that ends here ran
+    int record(int k, hipStream_t st, bool step_ran = true)
+    {
+        if (!ev[k]) HIPCHK(hipEventCreate(&ev[k]));
+        HIPCHK(hipEventRecord(ev[k], st));
+        if (k == 0) pending = false;
+        else ran[k - 1] = step_ran;
+        last = k;
+        return CS_OK;
+    }
+    // waits for the last event and takes the spans
+    int finish()
+    {
+        HIPCHK(hipEventSynchronize(ev[last]));
+        pending = false;
+        for (int k = 0; k < last; ++k) {
+            float t = 0.f;
+            HIPCHK(hipEventElapsedTime(&t, ev[k], ev[k + 1]));
+            ms[k] = ran[k] ? t : 0.0;                   // without its step a span's two records are back to back
+        }
+        return CS_OK;
     }
 };
 
+struct SegmentState {
+    DevBuf img, lab, mask, parent, slab, hist, thr, chunks, counts;     // img: the upload of a host image, whichever entry point
+    DevBuf med, stage;                                  // the 3 x 3 median's plane; a plane on its way to a host buffer
+    DevBuf dq, rec, key, ttop, ctrl;                    // cs_segment_split and cs_segment_split_intensity only
+    DevBuf si_guide;                                    // cs_segment_split_intensity only: a guide uploaded from the host
+    DevBuf bg_a, bg_b;                                  // cs_segment_background only: two planes
+    DevBuf lt_sum;                                      // cs_segment_local only: row sums
+    DevBuf sm_t;                                        // cs_segment_smooth only: row pass
+    // img, med and stage serve every stage: each use is ordered on the handle's one stream, a call that uploads or stages
+    // synchronises before it returns, a median plane is consumed inside the call that made it, and DevBuf::ensure frees with
+    // hipFree, which waits for the device.
+    StageClock clk_thr, clk_sp, clk_si, clk_bg, clk_lt, clk_cl, clk_sm, clk_hy;
+    int sp_recon_reads = 0, sp_flood_reads = 0;         // control-word reads (one host synchronisation each) of the last split of either kind
+};
+
 void segment_state_free(SegmentState* s) { delete s; }
+
+// f(PIX()) with the pixel type of the call; f is a generic lambda
+template <typename F>
+static auto by_pixel(int pixel_type, F&& f)
+{
+    if (pixel_type == CS_PIX_U8) return f((unsigned char)0);
+    return f((unsigned short)0);
+}
 
 // tile union-find, border merge, path compression (with the root counts when chunk_cnt is given); with `val` only neighbours
 // of equal val are joined
@@ -1576,22 +1591,33 @@ static int otsu_thresholds(const PIX* img, int C, int ch, int batch, int HW, Seg
     return CS_OK;
 }
 
-// The argument rules that cs_segment_threshold and cs_segment_split share; sp receives the parameters in force.
-static int segment_check(const void* image, int pixel_type, int32_t channels, int32_t channel, int32_t batch, int32_t height, int32_t width,
-                         int in_kind, const cs_segment_params* params, const int32_t* labels, int labels_kind, const int32_t* n_labels,
-                         cs_segment_params& sp)
+// The argument rules of the image and of where the result goes that every entry point shares, up to the sizes; out_name is what
+// the entry point calls the kind of its output.  image_limits has the rest: some entry points have rules of their own between.
+static int image_check(const void* image, const void* out, int pixel_type, int32_t channels, int32_t channel, int32_t batch, int32_t height,
+                       int32_t width, int in_kind, int out_kind, const char* out_name)
 {
-    if (!image || !labels || !n_labels) return fail(CS_ERR_INVALID, "NULL argument");
+    if (!image || !out) return fail(CS_ERR_INVALID, "NULL argument");
     if (pixel_type != CS_PIX_U8 && pixel_type != CS_PIX_U16) return fail(CS_ERR_INVALID, "pixel_type must be CS_PIX_U8 or CS_PIX_U16");
-    if ((in_kind != CS_MEM_HOST && in_kind != CS_MEM_DEVICE) || (labels_kind != CS_MEM_HOST && labels_kind != CS_MEM_DEVICE))
-        return fail(CS_ERR_INVALID, "in_kind / labels_kind must be CS_MEM_HOST or CS_MEM_DEVICE");
+    if ((in_kind != CS_MEM_HOST && in_kind != CS_MEM_DEVICE) || (out_kind != CS_MEM_HOST && out_kind != CS_MEM_DEVICE))
+        return fail(CS_ERR_INVALID, "in_kind / %s must be CS_MEM_HOST or CS_MEM_DEVICE", out_name);
     if (channels < 1 || channel < 0 || channel >= channels)
         return fail(CS_ERR_INVALID, "channel %d of %d: need 0 <= channel < channels", (int)channel, (int)channels);
     if (batch < 1 || height < 1 || width < 1) return fail(CS_ERR_INVALID, "batch %d, height %d, width %d: all must be >= 1", (int)batch,
                                                           (int)height, (int)width);
+    return CS_OK;
+}
+
+static int image_limits(int32_t batch, int32_t height, int32_t width)
+{
     if (height > kSegMaxSide || width > kSegMaxSide)
         return fail(CS_ERR_UNSUPPORTED, "image %dx%d: sides above %d are not supported", (int)height, (int)width, kSegMaxSide);
     if (batch > kSegMaxBatch) return fail(CS_ERR_UNSUPPORTED, "batch %d: at most %d images per call", (int)batch, kSegMaxBatch);
+    return CS_OK;
+}
+
+// The rules of cs_segment_params; sp receives the parameters in force.
+static int segment_check(const cs_segment_params* params, cs_segment_params& sp)
+{
     sp = cs_segment_params{CS_THRESH_OTSU, 0, 1, 0};
     if (params) {
         sp = *params;
@@ -1605,8 +1631,94 @@ static int segment_check(const void* image, int pixel_type, int32_t channels, in
     return CS_OK;
 }
 
-// What both entry points do up to the mask: the state, the uploads, the common workspace, the thresholds, the mask (between
-// ev[0] and ev[1]) and the hole filling.  d_img / d_lab are where the image and the labels are on the device.
+// after the argument rules: without a handle the device's absence is reported before the handle's
+static int handle_check(const cs_preproc* p)
+{
+    if (p) return CS_OK;
+    const int rc = require_gfx950(0);
+    return rc ? rc : fail(CS_ERR_INVALID, "handle is NULL");
+}
+
+static int state_begin(cs_preproc* p)
+{
+    HIPCHK(hipSetDevice(p->device));
+    if (!p->seg) p->seg = new SegmentState();
+    return CS_OK;
+}
+
+// d_img: where the image is on the device, the upload buffer for a host image
+static int upload_image(SegmentState& S, const void* image, size_t bytes, int in_kind, hipStream_t st, const void*& d_img)
+{
+    d_img = image;
+    if (in_kind == CS_MEM_HOST) {
+        if (const int rc = S.img.ensure(bytes)) return rc;
+        HIPCHK(hipMemcpyAsync(S.img.p, image, bytes, hipMemcpyHostToDevice, st));
+        d_img = S.img.p;
+    }
+    return CS_OK;
+}
+
+// A call that produces a plane (background, local, clean, smooth, hysteresis): where its image and its plane are.
+struct PlaneCall {
+    SegmentState* S;
+    hipStream_t st;
+    bool on_device;                                     // image and plane are both the caller's device memory
+    const void* d_img;                                  // the image on the device (null: segment_begin uploads it later)
+    void* host;                                         // the caller's host plane, or null
+    void* d_out;                                        // the plane on the device: the caller's pointer, or the staging plane
+    size_t out_bytes;
+};
+
+// the state, the upload (image_bytes 0: none here) and the device destination of the plane
+static int plane_begin(cs_preproc* p, const void* image, size_t image_bytes, int in_kind, void* out, size_t out_bytes, int out_kind,
+                       PlaneCall& c)
+{
+    int rc;
+    if ((rc = state_begin(p))) return rc;
+    SegmentState& S = *p->seg;
+    c = PlaneCall{&S, p->stream, in_kind == CS_MEM_DEVICE && out_kind == CS_MEM_DEVICE, nullptr, nullptr, out, out_bytes};
+    if (image_bytes && (rc = upload_image(S, image, image_bytes, in_kind, c.st, c.d_img))) return rc;
+    if (out_kind == CS_MEM_HOST) {
+        if ((rc = S.stage.ensure(out_bytes))) return rc;
+        c.host = out;
+        c.d_out = S.stage.p;
+    }
+    return CS_OK;
+}
+
+// The end of such a call, its launches and the clock's last record on the stream.  thresholds: where S.thr goes, or null.
+static int plane_end(const PlaneCall& c, StageClock& clk, int32_t* thresholds, int batch)
+{
+    if (c.on_device && !thresholds) {
+        clk.pending = true;                             // no host synchronisation: the times are read when they are asked for
+        return CS_OK;
+    }
+    if (thresholds) HIPCHK(hipMemcpyAsync(thresholds, c.S->thr.p, batch * sizeof(int), hipMemcpyDeviceToHost, c.st));
+    if (c.host) HIPCHK(hipMemcpyAsync(c.host, c.d_out, c.out_bytes, hipMemcpyDeviceToHost, c.st));
+    HIPCHK(hipStreamSynchronize(c.st));                   // the one host synchronisation: the caller's host buffers are free / filled
+    return clk.finish();
+}
+
+// What every cs_segment_*_last_timing does: the spans of the family's last call, read now if that call left them on the
+// device; a handle that has not segmented yet reports zeros.
+static int clock_read(const cs_preproc* p, StageClock SegmentState::*which, std::initializer_list<double*> out)
+{
+    if (!p) return fail(CS_ERR_INVALID, "handle is NULL");
+    StageClock* clk = p->seg ? &(p->seg->*which) : nullptr;
+    if (clk && clk->pending) {
+        HIPCHK(hipSetDevice(p->device));
+        if (const int rc = clk->finish()) return rc;
+    }
+    int k = 0;
+    for (double* o : out) {
+        if (o) *o = clk ? clk->ms[k] : 0.0;
+        ++k;
+    }
+    return CS_OK;
+}
+
+// What the labelling entry points do up to the mask: the state, the uploads, the common workspace, the thresholds, the mask
+// (between the clock's events 0 and 1) and the hole filling.  d_img / d_lab are where the image and the labels are on the device.
 struct SegmentCall {
     int batch, H, W, HW, nchunks;
     size_t npx;
@@ -1619,23 +1731,14 @@ struct SegmentCall {
 static int segment_begin(cs_preproc* p, const void* image, int pixel_type, int32_t channels, int32_t batch, int32_t height, int32_t width,
                          int in_kind, int32_t* labels, int labels_kind, SegmentCall& c)
 {
-    HIPCHK(hipSetDevice(p->device));
-    if (!p->seg) p->seg = new SegmentState();
+    int rc;
+    if ((rc = state_begin(p))) return rc;
     SegmentState& S = *p->seg;
-    for (hipEvent_t& e : S.ev)
-        if (!e) HIPCHK(hipEventCreate(&e));
-    hipStream_t st = p->stream;
-    const int H = height, W = width, HW = H * W, C = channels;
-    const size_t esz = pixel_type == CS_PIX_U8 ? 1 : 2;
+    const int H = height, W = width, HW = H * W;
     const size_t npx = (size_t)batch * HW;
     const int nchunks = (HW + SG_CHUNK - 1) / SG_CHUNK;
-    int rc;
-    const void* d_img = image;
-    if (in_kind == CS_MEM_HOST) {
-        if ((rc = S.img.ensure(npx * C * esz))) return rc;
-        HIPCHK(hipMemcpyAsync(S.img.p, image, npx * C * esz, hipMemcpyHostToDevice, st));
-        d_img = S.img.p;
-    }
+    const void* d_img;
+    if ((rc = upload_image(S, image, npx * channels * (pixel_type == CS_PIX_U8 ? 1 : 2), in_kind, p->stream, d_img))) return rc;
     int* d_lab = labels;
     if (labels_kind == CS_MEM_HOST) {
         if ((rc = S.lab.ensure(npx * sizeof(int)))) return rc;
@@ -1652,21 +1755,22 @@ static int segment_begin(cs_preproc* p, const void* image, int pixel_type, int32
 static int segment_thresholds(SegmentState& S, const SegmentCall& c, int pixel_type, int C, int channel, const cs_segment_params& sp,
                               hipStream_t st)
 {
-    int rc;
     if (sp.threshold_mode == CS_THRESH_FIXED) {
         hipLaunchKernelGGL(sg_fixed, dim3((unsigned)((c.batch + SG_THREADS - 1) / SG_THREADS)), dim3(SG_THREADS), 0, st, S.thr.as<int>(),
                            c.batch, (int)sp.threshold);
         HIPCHK(hipGetLastError());
-    } else if (pixel_type == CS_PIX_U8) {
-        if ((rc = otsu_thresholds<unsigned char, 256>((const unsigned char*)c.d_img, C, channel, c.batch, c.HW, S, st))) return rc;
-    } else {
-        if ((rc = otsu_thresholds<unsigned short, 65536>((const unsigned short*)c.d_img, C, channel, c.batch, c.HW, S, st))) return rc;
+        return CS_OK;
     }
-    return CS_OK;
+    return by_pixel(pixel_type, [&](auto pix) {
+        using PIX = decltype(pix);
+        return otsu_thresholds<PIX, (sizeof(PIX) == 1 ? 256 : 65536)>((const PIX*)c.d_img, C, channel, c.batch, c.HW, S, st);
+    });
 }
 
+// clk: the clock whose events 0 and 1 frame the thresholds and the mask (the state may not exist before this call), or null
 static int segment_mask(cs_preproc* p, const void* image, int pixel_type, int32_t channels, int32_t channel, int32_t batch, int32_t height,
-                        int32_t width, int in_kind, const cs_segment_params& sp, int32_t* labels, int labels_kind, SegmentCall& c)
+                        int32_t width, int in_kind, const cs_segment_params& sp, int32_t* labels, int labels_kind, SegmentCall& c,
+                        StageClock SegmentState::*which)
 {
     int rc;
     if ((rc = segment_begin(p, image, pixel_type, channels, batch, height, width, in_kind, labels, labels_kind, c))) return rc;
@@ -1674,20 +1778,19 @@ static int segment_mask(cs_preproc* p, const void* image, int pixel_type, int32_
     hipStream_t st = p->stream;
     const int H = c.H, W = c.W, HW = c.HW, C = channels, nchunks = c.nchunks;
     const size_t npx = c.npx;
-    const void* d_img = c.d_img;
     int* d_lab = c.d_lab;
     const dim3 pgrid = c.pgrid;
+    StageClock* clk = which ? &(S.*which) : nullptr;
 
-    HIPCHK(hipEventRecord(S.ev[0], st));
+    if (clk && (rc = clk->record(0, st))) return rc;
     if ((rc = segment_thresholds(S, c, pixel_type, C, channel, sp, st))) return rc;
-    if (pixel_type == CS_PIX_U8)
-        hipLaunchKernelGGL(sg_mask<unsigned char>, pgrid, dim3(SG_THREADS), 0, st, (const unsigned char*)d_img, C, (int)channel, HW,
-                           S.thr.as<int>(), S.mask.as<unsigned char>());
-    else
-        hipLaunchKernelGGL(sg_mask<unsigned short>, pgrid, dim3(SG_THREADS), 0, st, (const unsigned short*)d_img, C, (int)channel, HW,
-                           S.thr.as<int>(), S.mask.as<unsigned char>());
+    by_pixel(pixel_type, [&](auto pix) {
+        using PIX = decltype(pix);
+        hipLaunchKernelGGL(sg_mask<PIX>, pgrid, dim3(SG_THREADS), 0, st, (const PIX*)c.d_img, C, (int)channel, HW, S.thr.as<int>(),
+                           S.mask.as<unsigned char>());
+    });
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(S.ev[1], st));
+    if (clk && (rc = clk->record(1, st))) return rc;
 
     if (sp.fill_holes) {
         // background components, 4-connected; the label buffer holds the "touches the image border" flags meanwhile
@@ -1711,6 +1814,33 @@ static hipError_t number_regions(SegmentState& S, const SegmentCall& c, hipStrea
     return hipGetLastError();
 }
 
+// The channel as a stage's passes read it: pointer, image stride and pixel stride in elements.
+template <typename PIX>
+struct ChannelView {
+    const PIX* p;
+    size_t img;
+    int pix;
+};
+
+// The optional 3 x 3 median of a stage, between its clock's events 0 and 1: x views the median's plane, else the channel in place.
+template <typename PIX>
+static int median_step(SegmentState& S, StageClock& clk, const PIX* d_img, int C, int ch, int batch, int H, int W, bool median,
+                       hipStream_t st, ChannelView<PIX>& x)
+{
+    const int HW = H * W;
+    int rc;
+    x = ChannelView<PIX>{d_img + ch, (size_t)HW * C, C};
+    if ((rc = clk.record(0, st))) return rc;
+    if (median) {
+        if ((rc = S.med.ensure((size_t)batch * HW * sizeof(PIX)))) return rc;
+        hipLaunchKernelGGL(bg_median<PIX>, dim3((unsigned)((HW + SG_CHUNK - 1) / SG_CHUNK), (unsigned)batch), dim3(SG_THREADS), 0, st, d_img, C,
+                           ch, H, W, S.med.as<PIX>());
+        HIPCHK(hipGetLastError());
+        x = ChannelView<PIX>{S.med.as<PIX>(), (size_t)HW, 1};
+    }
+    return clk.record(1, st, median);
+}
+
 // median (optional) and the four passes of the top-hat on the stream; d_out is a [B][H][W] plane on the device
 template <typename PIX>
 static int background_launch(SegmentState& S, const PIX* d_img, int C, int ch, int batch, int H, int W, int r, bool median, PIX* d_out,
@@ -1720,48 +1850,22 @@ static int background_launch(SegmentState& S, const PIX* d_img, int C, int ch, i
     const size_t plane = (size_t)batch * HW * sizeof(PIX);
     int rc;
     if ((rc = S.bg_a.ensure(plane)) || (rc = S.bg_b.ensure(plane))) return rc;
-    const PIX* x = d_img + ch;                          // what the opening is subtracted from
-    size_t x_img = (size_t)HW * C;
-    int x_pix = C;
-    HIPCHK(hipEventRecord(S.bev[0], st));
-    S.bg_median = median;
-    if (median) {
-        if ((rc = S.bg_med.ensure(plane))) return rc;
-        hipLaunchKernelGGL(bg_median<PIX>, dim3((unsigned)((HW + SG_CHUNK - 1) / SG_CHUNK), (unsigned)batch), dim3(SG_THREADS), 0, st, d_img, C,
-                           ch, H, W, S.bg_med.as<PIX>());
-        HIPCHK(hipGetLastError());
-        x = S.bg_med.as<PIX>();
-        x_img = (size_t)HW;
-        x_pix = 1;
-    }
-    HIPCHK(hipEventRecord(S.bev[1], st));
+    ChannelView<PIX> x;                                 // what the opening is subtracted from
+    if ((rc = median_step(S, S.clk_bg, d_img, C, ch, batch, H, W, median, st, x))) return rc;
     PIX *A = S.bg_a.as<PIX>(), *B = S.bg_b.as<PIX>();
     const dim3 rgrid((unsigned)((W + BG_ROW_SEG - 1) / BG_ROW_SEG), (unsigned)((H + BG_ROW_LINES - 1) / BG_ROW_LINES), (unsigned)batch);
     const dim3 cgrid((unsigned)((W + BG_COL_W - 1) / BG_COL_W), (unsigned)((H + TR - 1) / TR), (unsigned)batch);
     const size_t lds = (size_t)(std::min(TR, H) + 2 * r) * BG_COL_W * sizeof(unsigned short);
     HIPCHK(hipFuncSetAttribute((const void*)bg_cols<PIX, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     HIPCHK(hipFuncSetAttribute((const void*)bg_cols<PIX, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((bg_rows<PIX, false, false>), rgrid, dim3(SG_THREADS), 0, st, x, x_img, x_pix, H, W, r, levels, (const PIX*)nullptr,
+    hipLaunchKernelGGL((bg_rows<PIX, false, false>), rgrid, dim3(SG_THREADS), 0, st, x.p, x.img, x.pix, H, W, r, levels, (const PIX*)nullptr,
                        (size_t)0, 0, A);
     hipLaunchKernelGGL((bg_cols<PIX, false>), cgrid, dim3(BG_COL_THREADS), lds, st, (const PIX*)A, H, W, r, levels, TR, B);
     hipLaunchKernelGGL((bg_cols<PIX, true>), cgrid, dim3(BG_COL_THREADS), lds, st, (const PIX*)B, H, W, r, levels, TR, A);
-    hipLaunchKernelGGL((bg_rows<PIX, true, true>), rgrid, dim3(SG_THREADS), 0, st, (const PIX*)A, (size_t)HW, 1, H, W, r, levels, x, x_img,
-                       x_pix, d_out);
+    hipLaunchKernelGGL((bg_rows<PIX, true, true>), rgrid, dim3(SG_THREADS), 0, st, (const PIX*)A, (size_t)HW, 1, H, W, r, levels, x.p, x.img,
+                       x.pix, d_out);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(S.bev[2], st));
-    return CS_OK;
-}
-
-static int background_times(SegmentState& S)
-{
-    float ms = 0.f;
-    HIPCHK(hipEventSynchronize(S.bev[2]));
-    S.bg_pending = false;
-    HIPCHK(hipEventElapsedTime(&ms, S.bev[0], S.bev[1]));
-    S.bg_median_ms = S.bg_median ? ms : 0.0;            // without it the two records are back to back
-    HIPCHK(hipEventElapsedTime(&ms, S.bev[1], S.bev[2]));
-    S.bg_tophat_ms = ms;
-    return CS_OK;
+    return S.clk_bg.record(2, st);
 }
 
 // median (optional), row sums, column sums + compare on the stream; d_out is a [B][H][W] uint8 plane on the device: 0 / 1, or
@@ -1773,34 +1877,20 @@ static int local_launch(SegmentState& S, const PIX* d_img, int C, int ch, int ba
     const int HW = H * W, r = lp.radius, TR = bg_col_rows(r);
     int rc;
     if ((rc = S.lt_sum.ensure((size_t)batch * HW * sizeof(unsigned int)))) return rc;
-    const PIX* x = d_img + ch;                          // both sides of the comparison read this
-    size_t x_img = (size_t)HW * C;
-    int x_pix = C;
-    HIPCHK(hipEventRecord(S.lev[0], st));
-    S.lt_median = lp.median != 0;
-    if (lp.median) {
-        if ((rc = S.lt_med.ensure((size_t)batch * HW * sizeof(PIX)))) return rc;
-        hipLaunchKernelGGL(bg_median<PIX>, dim3((unsigned)((HW + SG_CHUNK - 1) / SG_CHUNK), (unsigned)batch), dim3(SG_THREADS), 0, st, d_img, C,
-                           ch, H, W, S.lt_med.as<PIX>());
-        HIPCHK(hipGetLastError());
-        x = S.lt_med.as<PIX>();
-        x_img = (size_t)HW;
-        x_pix = 1;
-    }
-    HIPCHK(hipEventRecord(S.lev[1], st));
+    ChannelView<PIX> x;                                 // both sides of the comparison read this
+    if ((rc = median_step(S, S.clk_lt, d_img, C, ch, batch, H, W, lp.median != 0, st, x))) return rc;
     const dim3 rgrid((unsigned)((W + LT_ROW_SEG - 1) / LT_ROW_SEG), (unsigned)((H + LT_ROW_LINES - 1) / LT_ROW_LINES), (unsigned)batch);
     const dim3 cgrid((unsigned)((W + LT_COL_W - 1) / LT_COL_W), (unsigned)((H + LT_COL_TILES * TR - 1) / (LT_COL_TILES * TR)), (unsigned)batch);
     const long long n = (long long)(2 * r + 1) * (2 * r + 1);
-    hipLaunchKernelGGL(lt_rows<PIX>, rgrid, dim3(SG_THREADS), 0, st, x, x_img, x_pix, H, W, r, S.lt_sum.as<unsigned int>());
+    hipLaunchKernelGGL(lt_rows<PIX>, rgrid, dim3(SG_THREADS), 0, st, x.p, x.img, x.pix, H, W, r, S.lt_sum.as<unsigned int>());
     if (weak_delta)
-        hipLaunchKernelGGL((lt_cols<PIX, true>), cgrid, dim3(SG_THREADS), 0, st, (const unsigned int*)S.lt_sum.as<unsigned int>(), x, x_img,
-                           x_pix, H, W, r, TR, n, n * lp.delta, n * *weak_delta, (int)lp.floor, d_out);
+        hipLaunchKernelGGL((lt_cols<PIX, true>), cgrid, dim3(SG_THREADS), 0, st, (const unsigned int*)S.lt_sum.as<unsigned int>(), x.p, x.img,
+                           x.pix, H, W, r, TR, n, n * lp.delta, n * *weak_delta, (int)lp.floor, d_out);
     else
-        hipLaunchKernelGGL((lt_cols<PIX, false>), cgrid, dim3(SG_THREADS), 0, st, (const unsigned int*)S.lt_sum.as<unsigned int>(), x, x_img,
-                           x_pix, H, W, r, TR, n, n * lp.delta, 0ll, (int)lp.floor, d_out);
+        hipLaunchKernelGGL((lt_cols<PIX, false>), cgrid, dim3(SG_THREADS), 0, st, (const unsigned int*)S.lt_sum.as<unsigned int>(), x.p, x.img,
+                           x.pix, H, W, r, TR, n, n * lp.delta, 0ll, (int)lp.floor, d_out);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(S.lev[2], st));
-    return CS_OK;
+    return S.clk_lt.record(2, st);
 }
 
 static int local_check(const cs_local_params& lp)
@@ -1812,18 +1902,6 @@ static int local_check(const cs_local_params& lp)
     return CS_OK;
 }
 
-static int local_times(SegmentState& S)
-{
-    float ms = 0.f;
-    HIPCHK(hipEventSynchronize(S.lev[2]));
-    S.lt_pending = false;
-    HIPCHK(hipEventElapsedTime(&ms, S.lev[0], S.lev[1]));
-    S.lt_median_ms = S.lt_median ? ms : 0.0;            // without it the two records are back to back
-    HIPCHK(hipEventElapsedTime(&ms, S.lev[1], S.lev[2]));
-    S.lt_sum_ms = ms;
-    return CS_OK;
-}
-
 // median (optional), row pass, column pass on the stream; d_out is a [B][H][W] plane on the device
 template <typename PIX>
 static int smooth_launch(SegmentState& S, const PIX* d_img, int C, int ch, int batch, int H, int W, const SmWeights& wt, bool median,
@@ -1832,42 +1910,16 @@ static int smooth_launch(SegmentState& S, const PIX* d_img, int C, int ch, int b
     const int HW = H * W, r = wt.r;
     int rc;
     if ((rc = S.sm_t.ensure((size_t)batch * HW * sizeof(unsigned int)))) return rc;
-    const PIX* x = d_img + ch;
-    size_t x_img = (size_t)HW * C;
-    int x_pix = C;
-    HIPCHK(hipEventRecord(S.sev[0], st));
-    S.sm_median = median;
-    if (median) {
-        if ((rc = S.sm_med.ensure((size_t)batch * HW * sizeof(PIX)))) return rc;
-        hipLaunchKernelGGL(bg_median<PIX>, dim3((unsigned)((HW + SG_CHUNK - 1) / SG_CHUNK), (unsigned)batch), dim3(SG_THREADS), 0, st, d_img, C,
-                           ch, H, W, S.sm_med.as<PIX>());
-        HIPCHK(hipGetLastError());
-        x = S.sm_med.as<PIX>();
-        x_img = (size_t)HW;
-        x_pix = 1;
-    }
-    HIPCHK(hipEventRecord(S.sev[1], st));
+    ChannelView<PIX> x;
+    if ((rc = median_step(S, S.clk_sm, d_img, C, ch, batch, H, W, median, st, x))) return rc;
     const dim3 rgrid((unsigned)((W + SM_ROW_SEG - 1) / SM_ROW_SEG), (unsigned)((H + SM_ROW_LINES - 1) / SM_ROW_LINES), (unsigned)batch);
     const dim3 cgrid((unsigned)((W + SM_COL_W - 1) / SM_COL_W), (unsigned)((H + SM_COL_TR - 1) / SM_COL_TR), (unsigned)batch);
     const size_t lds = (size_t)(std::min(SM_COL_TR, H) + 2 * r + SM_COL_E) * SM_COL_W * sizeof(unsigned int);
     HIPCHK(hipFuncSetAttribute((const void*)sm_cols<PIX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(sm_rows<PIX>, rgrid, dim3(SG_THREADS), 0, st, x, x_img, x_pix, H, W, wt, S.sm_t.as<unsigned int>());
+    hipLaunchKernelGGL(sm_rows<PIX>, rgrid, dim3(SG_THREADS), 0, st, x.p, x.img, x.pix, H, W, wt, S.sm_t.as<unsigned int>());
     hipLaunchKernelGGL(sm_cols<PIX>, cgrid, dim3(SG_THREADS), lds, st, (const unsigned int*)S.sm_t.as<unsigned int>(), H, W, wt, d_out);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(S.sev[2], st));
-    return CS_OK;
-}
-
-static int smooth_times(SegmentState& S)
-{
-    float ms = 0.f;
-    HIPCHK(hipEventSynchronize(S.sev[2]));
-    S.sm_pending = false;
-    HIPCHK(hipEventElapsedTime(&ms, S.sev[0], S.sev[1]));
-    S.sm_median_ms = S.sm_median ? ms : 0.0;            // without it the two records are back to back
-    HIPCHK(hipEventElapsedTime(&ms, S.sev[1], S.sev[2]));
-    S.sm_smooth_ms = ms;
-    return CS_OK;
+    return S.clk_sm.record(2, st);
 }
 
 // the table rules of cs_smooth_params; wt receives the table in force
@@ -1890,32 +1942,6 @@ static int smooth_check(const cs_smooth_params& sp, SmWeights& wt)
     return CS_OK;
 }
 
-static int clean_times(SegmentState& S)
-{
-    float ms = 0.f;
-    HIPCHK(hipEventSynchronize(S.cev[3]));
-    S.cl_pending = false;
-    HIPCHK(hipEventElapsedTime(&ms, S.cev[0], S.cev[1]));
-    S.cl_mask_ms = ms;
-    HIPCHK(hipEventElapsedTime(&ms, S.cev[1], S.cev[2]));
-    S.cl_open_ms = S.cl_opened ? ms : 0.0;              // without a step its two records are back to back
-    HIPCHK(hipEventElapsedTime(&ms, S.cev[2], S.cev[3]));
-    S.cl_area_ms = S.cl_dropped ? ms : 0.0;
-    return CS_OK;
-}
-
-static int hysteresis_times(SegmentState& S)
-{
-    float ms = 0.f;
-    HIPCHK(hipEventSynchronize(S.hev[2]));
-    S.hy_pending = false;
-    HIPCHK(hipEventElapsedTime(&ms, S.hev[0], S.hev[1]));
-    S.hy_level_ms = ms;
-    HIPCHK(hipEventElapsedTime(&ms, S.hev[1], S.hev[2]));
-    S.hy_link_ms = ms;
-    return CS_OK;
-}
-
 // The workspace of the two splits beyond segment_mask's: heights, reconstruction, keys, tile tops, control words.
 struct SplitCall {
     dim3 tgrid;
@@ -1934,10 +1960,10 @@ static int split_workspace(SegmentState& S, const SegmentCall& c, SplitCall& w)
 }
 
 // What cs_segment_split and cs_segment_split_intensity share once the height plane (S.dq), the marker (S.rec) and the batch's
-// largest height (ctrl[CT_VMAX]) are on the stream: ev[2], the reconstruction, the seeds, the flood, the numbering, the copies
-// out and the one final synchronisation.  times_ms: the four spans between ev[0] .. ev[4].  dist: the optional copy of S.dq.
+// largest height (ctrl[CT_VMAX]) are on the stream: the clock's event 2, the reconstruction, the seeds, the flood, the numbering,
+// the copies out, the one final synchronisation and the clock's four spans.  dist: the optional copy of S.dq.
 static int split_watershed(SegmentState& S, const SegmentCall& c, const SplitCall& w, int conn8, hipStream_t st, int32_t* labels,
-                           int labels_kind, int32_t* n_labels, int32_t* thresholds, uint8_t* dist, double* times_ms)
+                           int labels_kind, int32_t* n_labels, int32_t* thresholds, uint8_t* dist, StageClock& clk)
 {
     const int H = c.H, W = c.W, HW = c.HW;
     const dim3 tgrid = w.tgrid;
@@ -1946,7 +1972,8 @@ static int split_watershed(SegmentState& S, const SegmentCall& c, const SplitCal
     unsigned long long* key = S.key.as<unsigned long long>();
     int *ctrl = S.ctrl.as<int>(), *parent = S.parent.as<int>();
     const dim3 one(1);
-    HIPCHK(hipEventRecord(S.ev[2], st));
+    int rc;
+    if ((rc = clk.record(2, st))) return rc;
 
     // h-maxima: reconstruction in rounds, read back once per group of rounds; the bound of HW rounds never binds in practice
     hipLaunchKernelGGL(sp_start, one, one, 0, st, ctrl, 0);
@@ -1970,7 +1997,7 @@ static int split_watershed(SegmentState& S, const SegmentCall& c, const SplitCal
     hipLaunchKernelGGL(sg_rank<true>, c.pgrid, dim3(SG_THREADS), 0, st, HW, parent, S.chunks.as<int>(), c.nchunks, c.d_lab, (const int*)drop);
     hipLaunchKernelGGL(sp_seedkey, c.pgrid, dim3(SG_THREADS), 0, st, HW, parent, c.d_lab, key);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(S.ev[3], st));
+    if ((rc = clk.record(3, st))) return rc;
 
     // flood, level by level from the batch's largest Dq; then each region's first pixel and the numbering
     HIPCHK(hipMemsetAsync(S.ttop.p, 0xff, ntiles, st));
@@ -1989,18 +2016,13 @@ static int split_watershed(SegmentState& S, const SegmentCall& c, const SplitCal
     hipLaunchKernelGGL(sp_parent, c.pgrid, dim3(SG_THREADS), 0, st, HW, key, c.d_lab, parent, S.chunks.as<int>(), c.nchunks);
     HIPCHK(hipGetLastError());
     HIPCHK(number_regions(S, c, st));
-    HIPCHK(hipEventRecord(S.ev[4], st));
+    if ((rc = clk.record(4, st))) return rc;
     HIPCHK(hipMemcpyAsync(n_labels, S.counts.p, c.batch * sizeof(int), hipMemcpyDeviceToHost, st));
     if (thresholds) HIPCHK(hipMemcpyAsync(thresholds, S.thr.p, c.batch * sizeof(int), hipMemcpyDeviceToHost, st));
     if (labels_kind == CS_MEM_HOST) HIPCHK(hipMemcpyAsync(labels, c.d_lab, c.npx * sizeof(int), hipMemcpyDeviceToHost, st));
     if (dist) HIPCHK(hipMemcpyAsync(dist, dq, c.npx, labels_kind == CS_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
     HIPCHK(hipStreamSynchronize(st));
-    for (int k = 0; k < 4; ++k) {
-        float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, S.ev[k], S.ev[k + 1]));
-        times_ms[k] = ms;
-    }
-    return CS_OK;
+    return clk.finish();
 }
 
 // component ranges and heights of the mask in S.mask under the guide, on the stream: S.dq, S.rec and ctrl[CT_VMAX] as sp_rows
@@ -2025,56 +2047,50 @@ int cs_segment_threshold(cs_preproc* p, const void* image, int pixel_type, int32
                          int32_t width, int in_kind, const cs_segment_params* params, int32_t* labels, int labels_kind, int32_t* n_labels,
                          int32_t* thresholds)
 {
+    if (!n_labels) return fail(CS_ERR_INVALID, "NULL argument");
     cs_segment_params sp;
-    int rc = segment_check(image, pixel_type, channels, channel, batch, height, width, in_kind, params, labels, labels_kind, n_labels, sp);
-    if (rc) return rc;
-    if (!p) {
-        rc = require_gfx950(0);
-        return rc ? rc : fail(CS_ERR_INVALID, "handle is NULL");
-    }
+    int rc;
+    if ((rc = image_check(image, labels, pixel_type, channels, channel, batch, height, width, in_kind, labels_kind, "labels_kind")) ||
+        (rc = image_limits(batch, height, width)) || (rc = segment_check(params, sp)) || (rc = handle_check(p)))
+        return rc;
     SegmentCall c;
-    if ((rc = segment_mask(p, image, pixel_type, channels, channel, batch, height, width, in_kind, sp, labels, labels_kind, c))) return rc;
+    if ((rc = segment_mask(p, image, pixel_type, channels, channel, batch, height, width, in_kind, sp, labels, labels_kind, c,
+                           &SegmentState::clk_thr)))
+        return rc;
     SegmentState& S = *p->seg;
     hipStream_t st = p->stream;
     HIPCHK(label_mask(S.mask.as<unsigned char>(), batch, c.H, c.W, 0, sp.connectivity == 2, S.parent.as<int>(), S.chunks.as<int>(), c.nchunks, st));
     HIPCHK(number_regions(S, c, st));
-    HIPCHK(hipEventRecord(S.ev[2], st));
+    if ((rc = S.clk_thr.record(2, st))) return rc;
     HIPCHK(hipMemcpyAsync(n_labels, S.counts.p, batch * sizeof(int), hipMemcpyDeviceToHost, st));
     if (thresholds) HIPCHK(hipMemcpyAsync(thresholds, S.thr.p, batch * sizeof(int), hipMemcpyDeviceToHost, st));
     if (labels_kind == CS_MEM_HOST) HIPCHK(hipMemcpyAsync(labels, c.d_lab, c.npx * sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));                     // the one host synchronisation: the counts
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, S.ev[0], S.ev[1]));
-    S.threshold_ms = ms;
-    HIPCHK(hipEventElapsedTime(&ms, S.ev[1], S.ev[2]));
-    S.label_ms = ms;
-    return CS_OK;
+    return S.clk_thr.finish();
 }
 
 int cs_segment_last_timing(const cs_preproc* p, double* threshold_ms, double* label_ms)
 {
-    if (!p) return fail(CS_ERR_INVALID, "handle is NULL");
-    const SegmentState* S = p->seg;
-    if (threshold_ms) *threshold_ms = S ? S->threshold_ms : 0.0;
-    if (label_ms) *label_ms = S ? S->label_ms : 0.0;
-    return CS_OK;
+    return clock_read(p, &SegmentState::clk_thr, {threshold_ms, label_ms});
 }
 
 int cs_segment_split(cs_preproc* p, const void* image, int pixel_type, int32_t channels, int32_t channel, int32_t batch, int32_t height,
                      int32_t width, int in_kind, const cs_segment_params* params, const cs_split_params* split, int32_t* labels,
                      int labels_kind, int32_t* n_labels, int32_t* thresholds, uint8_t* dist)
 {
+    if (!n_labels) return fail(CS_ERR_INVALID, "NULL argument");
     cs_segment_params sp;
-    int rc = segment_check(image, pixel_type, channels, channel, batch, height, width, in_kind, params, labels, labels_kind, n_labels, sp);
-    if (rc) return rc;
+    int rc;
+    if ((rc = image_check(image, labels, pixel_type, channels, channel, batch, height, width, in_kind, labels_kind, "labels_kind")) ||
+        (rc = image_limits(batch, height, width)) || (rc = segment_check(params, sp)))
+        return rc;
     const int h = split ? (int)split->h : 3;
     if (h < 1 || h > 255) return fail(CS_ERR_INVALID, "split h %d outside 1..255 (half pixels)", h);
-    if (!p) {
-        rc = require_gfx950(0);
-        return rc ? rc : fail(CS_ERR_INVALID, "handle is NULL");
-    }
+    if ((rc = handle_check(p))) return rc;
     SegmentCall c;
-    if ((rc = segment_mask(p, image, pixel_type, channels, channel, batch, height, width, in_kind, sp, labels, labels_kind, c))) return rc;
+    if ((rc = segment_mask(p, image, pixel_type, channels, channel, batch, height, width, in_kind, sp, labels, labels_kind, c,
+                           &SegmentState::clk_sp)))
+        return rc;
     SegmentState& S = *p->seg;
     hipStream_t st = p->stream;
     const int H = c.H, W = c.W;
@@ -2088,24 +2104,12 @@ int cs_segment_split(cs_preproc* p, const void* image, int pixel_type, int32_t c
     hipLaunchKernelGGL(sp_rows, dim3((unsigned)((W + SP_ROW - 1) / SP_ROW), (unsigned)H, (unsigned)batch), dim3(SG_THREADS), 0, st,
                        S.key.as<const unsigned char>(), H, W, h, S.dq.as<unsigned char>(), S.rec.as<unsigned char>(), S.ctrl.as<int>());
     HIPCHK(hipGetLastError());
-    double t[4];
-    if ((rc = split_watershed(S, c, w, sp.connectivity == 2, st, labels, labels_kind, n_labels, thresholds, dist, t))) return rc;
-    S.sp_threshold_ms = t[0];
-    S.sp_distance_ms = t[1];
-    S.sp_seed_ms = t[2];
-    S.sp_flood_ms = t[3];
-    return CS_OK;
+    return split_watershed(S, c, w, sp.connectivity == 2, st, labels, labels_kind, n_labels, thresholds, dist, S.clk_sp);
 }
 
 int cs_segment_split_last_timing(const cs_preproc* p, double* threshold_ms, double* distance_ms, double* seed_ms, double* flood_ms)
 {
-    if (!p) return fail(CS_ERR_INVALID, "handle is NULL");
-    const SegmentState* S = p->seg;
-    if (threshold_ms) *threshold_ms = S ? S->sp_threshold_ms : 0.0;
-    if (distance_ms) *distance_ms = S ? S->sp_distance_ms : 0.0;
-    if (seed_ms) *seed_ms = S ? S->sp_seed_ms : 0.0;
-    if (flood_ms) *flood_ms = S ? S->sp_flood_ms : 0.0;
-    return CS_OK;
+    return clock_read(p, &SegmentState::clk_sp, {threshold_ms, distance_ms, seed_ms, flood_ms});
 }
 
 int cs_segment_split_intensity(cs_preproc* p, const void* image, int pixel_type, int32_t channels, int32_t channel, int32_t batch,
@@ -2114,9 +2118,12 @@ int cs_segment_split_intensity(cs_preproc* p, const void* image, int pixel_type,
                                int32_t guide_channel, int32_t* labels, int labels_kind, int32_t* n_labels, int32_t* thresholds,
                                uint8_t* height)
 {
+    if (!n_labels) return fail(CS_ERR_INVALID, "NULL argument");
     cs_segment_params sp;
-    int rc = segment_check(image, pixel_type, channels, channel, batch, height_px, width, in_kind, params, labels, labels_kind, n_labels, sp);
-    if (rc) return rc;
+    int rc;
+    if ((rc = image_check(image, labels, pixel_type, channels, channel, batch, height_px, width, in_kind, labels_kind, "labels_kind")) ||
+        (rc = image_limits(batch, height_px, width)) || (rc = segment_check(params, sp)))
+        return rc;
     if (!split || !guide) return fail(CS_ERR_INVALID, "NULL argument");
     if (split->depth < 1 || split->depth > 254) return fail(CS_ERR_INVALID, "split depth %d outside 1..254 (levels)", (int)split->depth);
     if (split->min_contrast < 0 || split->min_contrast > 65535)
@@ -2126,12 +2133,11 @@ int cs_segment_split_intensity(cs_preproc* p, const void* image, int pixel_type,
         return fail(CS_ERR_INVALID, "guide_pixel_type must be CS_PIX_U8 or CS_PIX_U16");
     if (guide_channels < 1 || guide_channel < 0 || guide_channel >= guide_channels)
         return fail(CS_ERR_INVALID, "guide channel %d of %d: need 0 <= channel < channels", (int)guide_channel, (int)guide_channels);
-    if (!p) {
-        rc = require_gfx950(0);
-        return rc ? rc : fail(CS_ERR_INVALID, "handle is NULL");
-    }
+    if ((rc = handle_check(p))) return rc;
     SegmentCall c;
-    if ((rc = segment_mask(p, image, pixel_type, channels, channel, batch, height_px, width, in_kind, sp, labels, labels_kind, c))) return rc;
+    if ((rc = segment_mask(p, image, pixel_type, channels, channel, batch, height_px, width, in_kind, sp, labels, labels_kind, c,
+                           &SegmentState::clk_si)))
+        return rc;
     SegmentState& S = *p->seg;
     hipStream_t st = p->stream;
     SplitCall w;
@@ -2152,30 +2158,16 @@ int cs_segment_split_intensity(cs_preproc* p, const void* image, int pixel_type,
     HIPCHK(hipMemsetAsync(S.key.p, 0x7f, c.npx * sizeof(int), st));
     HIPCHK(hipMemsetAsync(S.key.as<int>() + c.npx, 0, c.npx * sizeof(int), st));
     HIPCHK(label_mask(S.mask.as<unsigned char>(), batch, c.H, c.W, 0, conn8, S.parent.as<int>(), nullptr, c.nchunks, st));
-    if (guide_pixel_type == CS_PIX_U8)
-        HIPCHK(heights_launch(S, c, (const unsigned char*)d_guide, (int)guide_channels, (int)guide_channel, (int)split->depth,
-                              (int)split->min_contrast, st));
-    else
-        HIPCHK(heights_launch(S, c, (const unsigned short*)d_guide, (int)guide_channels, (int)guide_channel, (int)split->depth,
-                              (int)split->min_contrast, st));
-    double t[4];
-    if ((rc = split_watershed(S, c, w, conn8, st, labels, labels_kind, n_labels, thresholds, height, t))) return rc;
-    S.si_threshold_ms = t[0];
-    S.si_height_ms = t[1];
-    S.si_seed_ms = t[2];
-    S.si_flood_ms = t[3];
-    return CS_OK;
+    HIPCHK(by_pixel(guide_pixel_type, [&](auto pix) {
+        using PIX = decltype(pix);
+        return heights_launch(S, c, (const PIX*)d_guide, (int)guide_channels, (int)guide_channel, (int)split->depth, (int)split->min_contrast, st);
+    }));
+    return split_watershed(S, c, w, conn8, st, labels, labels_kind, n_labels, thresholds, height, S.clk_si);
 }
 
 int cs_segment_split_intensity_last_timing(const cs_preproc* p, double* threshold_ms, double* height_ms, double* seed_ms, double* flood_ms)
 {
-    if (!p) return fail(CS_ERR_INVALID, "handle is NULL");
-    const SegmentState* S = p->seg;
-    if (threshold_ms) *threshold_ms = S ? S->si_threshold_ms : 0.0;
-    if (height_ms) *height_ms = S ? S->si_height_ms : 0.0;
-    if (seed_ms) *seed_ms = S ? S->si_seed_ms : 0.0;
-    if (flood_ms) *flood_ms = S ? S->si_flood_ms : 0.0;
-    return CS_OK;
+    return clock_read(p, &SegmentState::clk_si, {threshold_ms, height_ms, seed_ms, flood_ms});
 }
 
 int cs_segment_split_last_syncs(const cs_preproc* p, int32_t* reconstruction, int32_t* flood)
@@ -2190,182 +2182,80 @@ int cs_segment_split_last_syncs(const cs_preproc* p, int32_t* reconstruction, in
 int cs_segment_background(cs_preproc* p, const void* image, int pixel_type, int32_t channels, int32_t channel, int32_t batch, int32_t height,
                           int32_t width, int in_kind, const cs_background_params* params, void* out, int out_kind)
 {
-    if (!image || !params || !out) return fail(CS_ERR_INVALID, "NULL argument");
-    if (pixel_type != CS_PIX_U8 && pixel_type != CS_PIX_U16) return fail(CS_ERR_INVALID, "pixel_type must be CS_PIX_U8 or CS_PIX_U16");
-    if ((in_kind != CS_MEM_HOST && in_kind != CS_MEM_DEVICE) || (out_kind != CS_MEM_HOST && out_kind != CS_MEM_DEVICE))
-        return fail(CS_ERR_INVALID, "in_kind / out_kind must be CS_MEM_HOST or CS_MEM_DEVICE");
-    if (channels < 1 || channel < 0 || channel >= channels)
-        return fail(CS_ERR_INVALID, "channel %d of %d: need 0 <= channel < channels", (int)channel, (int)channels);
-    if (batch < 1 || height < 1 || width < 1) return fail(CS_ERR_INVALID, "batch %d, height %d, width %d: all must be >= 1", (int)batch,
-                                                          (int)height, (int)width);
+    if (!params) return fail(CS_ERR_INVALID, "NULL argument");
+    int rc;
+    if ((rc = image_check(image, out, pixel_type, channels, channel, batch, height, width, in_kind, out_kind, "out_kind"))) return rc;
     if (params->radius < 1 || params->radius > BG_MAX_R) return fail(CS_ERR_INVALID, "background radius %d outside 1..%d", (int)params->radius, BG_MAX_R);
     if (params->median != 0 && params->median != 1) return fail(CS_ERR_INVALID, "median %d: 0 or 1", (int)params->median);
-    if (height > kSegMaxSide || width > kSegMaxSide)
-        return fail(CS_ERR_UNSUPPORTED, "image %dx%d: sides above %d are not supported", (int)height, (int)width, kSegMaxSide);
-    if (batch > kSegMaxBatch) return fail(CS_ERR_UNSUPPORTED, "batch %d: at most %d images per call", (int)batch, kSegMaxBatch);
-    if (!p) {
-        const int rc = require_gfx950(0);
-        return rc ? rc : fail(CS_ERR_INVALID, "handle is NULL");
-    }
-    HIPCHK(hipSetDevice(p->device));
-    if (!p->seg) p->seg = new SegmentState();
-    SegmentState& S = *p->seg;
-    for (hipEvent_t& e : S.bev)
-        if (!e) HIPCHK(hipEventCreate(&e));
-    hipStream_t st = p->stream;
-    const size_t esz = pixel_type == CS_PIX_U8 ? 1 : 2;
-    const size_t npx = (size_t)batch * height * width;
-    int rc;
-    const void* d_img = image;
-    if (in_kind == CS_MEM_HOST) {
-        if ((rc = S.bg_in.ensure(npx * channels * esz))) return rc;
-        HIPCHK(hipMemcpyAsync(S.bg_in.p, image, npx * channels * esz, hipMemcpyHostToDevice, st));
-        d_img = S.bg_in.p;
-    }
-    void* d_out = out;
-    if (out_kind == CS_MEM_HOST) {
-        if ((rc = S.bg_out.ensure(npx * esz))) return rc;
-        d_out = S.bg_out.p;
-    }
-    S.bg_pending = false;
-    if (pixel_type == CS_PIX_U8)
-        rc = background_launch<unsigned char>(S, (const unsigned char*)d_img, channels, channel, batch, height, width, params->radius,
-                                              params->median != 0, (unsigned char*)d_out, st);
-    else
-        rc = background_launch<unsigned short>(S, (const unsigned short*)d_img, channels, channel, batch, height, width, params->radius,
-                                               params->median != 0, (unsigned short*)d_out, st);
-    if (rc) return rc;
-    if (out_kind == CS_MEM_DEVICE && in_kind == CS_MEM_DEVICE) {
-        S.bg_pending = true;                            // no host synchronisation: the times are read when they are asked for
-        return CS_OK;
-    }
-    if (out_kind == CS_MEM_HOST) HIPCHK(hipMemcpyAsync(out, d_out, npx * esz, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));                     // the one host synchronisation: the caller's host buffers are free / filled
-    return background_times(S);
+    if ((rc = image_limits(batch, height, width)) || (rc = handle_check(p))) return rc;
+    const size_t esz = pixel_type == CS_PIX_U8 ? 1 : 2, npx = (size_t)batch * height * width;
+    PlaneCall c;
+    if ((rc = plane_begin(p, image, npx * channels * esz, in_kind, out, npx * esz, out_kind, c))) return rc;
+    rc = by_pixel(pixel_type, [&](auto pix) {
+        using PIX = decltype(pix);
+        return background_launch(*c.S, (const PIX*)c.d_img, channels, channel, batch, height, width, params->radius, params->median != 0,
+                                 (PIX*)c.d_out, c.st);
+    });
+    return rc ? rc : plane_end(c, c.S->clk_bg, nullptr, batch);
 }
 
 int cs_segment_background_last_timing(const cs_preproc* p, double* median_ms, double* tophat_ms)
 {
-    if (!p) return fail(CS_ERR_INVALID, "handle is NULL");
-    SegmentState* S = p->seg;
-    if (S && S->bg_pending) {
-        HIPCHK(hipSetDevice(p->device));
-        const int rc = background_times(*S);
-        if (rc) return rc;
-    }
-    if (median_ms) *median_ms = S ? S->bg_median_ms : 0.0;
-    if (tophat_ms) *tophat_ms = S ? S->bg_tophat_ms : 0.0;
-    return CS_OK;
+    return clock_read(p, &SegmentState::clk_bg, {median_ms, tophat_ms});
 }
 
 int cs_segment_local(cs_preproc* p, const void* image, int pixel_type, int32_t channels, int32_t channel, int32_t batch, int32_t height,
                      int32_t width, int in_kind, const cs_local_params* params, uint8_t* out, int out_kind)
 {
-    if (!image || !params || !out) return fail(CS_ERR_INVALID, "NULL argument");
-    if (pixel_type != CS_PIX_U8 && pixel_type != CS_PIX_U16) return fail(CS_ERR_INVALID, "pixel_type must be CS_PIX_U8 or CS_PIX_U16");
-    if ((in_kind != CS_MEM_HOST && in_kind != CS_MEM_DEVICE) || (out_kind != CS_MEM_HOST && out_kind != CS_MEM_DEVICE))
-        return fail(CS_ERR_INVALID, "in_kind / out_kind must be CS_MEM_HOST or CS_MEM_DEVICE");
-    if (channels < 1 || channel < 0 || channel >= channels)
-        return fail(CS_ERR_INVALID, "channel %d of %d: need 0 <= channel < channels", (int)channel, (int)channels);
-    if (batch < 1 || height < 1 || width < 1) return fail(CS_ERR_INVALID, "batch %d, height %d, width %d: all must be >= 1", (int)batch,
-                                                          (int)height, (int)width);
-    if (const int bad = local_check(*params)) return bad;
-    if (height > kSegMaxSide || width > kSegMaxSide)
-        return fail(CS_ERR_UNSUPPORTED, "image %dx%d: sides above %d are not supported", (int)height, (int)width, kSegMaxSide);
-    if (batch > kSegMaxBatch) return fail(CS_ERR_UNSUPPORTED, "batch %d: at most %d images per call", (int)batch, kSegMaxBatch);
-    if (!p) {
-        const int rc = require_gfx950(0);
-        return rc ? rc : fail(CS_ERR_INVALID, "handle is NULL");
-    }
-    HIPCHK(hipSetDevice(p->device));
-    if (!p->seg) p->seg = new SegmentState();
-    SegmentState& S = *p->seg;
-    for (hipEvent_t& e : S.lev)
-        if (!e) HIPCHK(hipEventCreate(&e));
-    hipStream_t st = p->stream;
-    const size_t esz = pixel_type == CS_PIX_U8 ? 1 : 2;
-    const size_t npx = (size_t)batch * height * width;
+    if (!params) return fail(CS_ERR_INVALID, "NULL argument");
     int rc;
-    const void* d_img = image;
-    if (in_kind == CS_MEM_HOST) {
-        if ((rc = S.lt_in.ensure(npx * channels * esz))) return rc;
-        HIPCHK(hipMemcpyAsync(S.lt_in.p, image, npx * channels * esz, hipMemcpyHostToDevice, st));
-        d_img = S.lt_in.p;
-    }
-    unsigned char* d_out = out;
-    if (out_kind == CS_MEM_HOST) {
-        if ((rc = S.lt_out.ensure(npx))) return rc;
-        d_out = S.lt_out.as<unsigned char>();
-    }
-    S.lt_pending = false;
-    if (pixel_type == CS_PIX_U8)
-        rc = local_launch<unsigned char>(S, (const unsigned char*)d_img, channels, channel, batch, height, width, *params, d_out, st);
-    else
-        rc = local_launch<unsigned short>(S, (const unsigned short*)d_img, channels, channel, batch, height, width, *params, d_out, st);
-    if (rc) return rc;
-    if (out_kind == CS_MEM_DEVICE && in_kind == CS_MEM_DEVICE) {
-        S.lt_pending = true;                            // no host synchronisation: the times are read when they are asked for
-        return CS_OK;
-    }
-    if (out_kind == CS_MEM_HOST) HIPCHK(hipMemcpyAsync(out, d_out, npx, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));                     // the one host synchronisation: the caller's host buffers are free / filled
-    return local_times(S);
+    if ((rc = image_check(image, out, pixel_type, channels, channel, batch, height, width, in_kind, out_kind, "out_kind")) ||
+        (rc = local_check(*params)) || (rc = image_limits(batch, height, width)) || (rc = handle_check(p)))
+        return rc;
+    const size_t esz = pixel_type == CS_PIX_U8 ? 1 : 2, npx = (size_t)batch * height * width;
+    PlaneCall c;
+    if ((rc = plane_begin(p, image, npx * channels * esz, in_kind, out, npx, out_kind, c))) return rc;
+    rc = by_pixel(pixel_type, [&](auto pix) {
+        using PIX = decltype(pix);
+        return local_launch(*c.S, (const PIX*)c.d_img, channels, channel, batch, height, width, *params, (unsigned char*)c.d_out, c.st);
+    });
+    return rc ? rc : plane_end(c, c.S->clk_lt, nullptr, batch);
 }
 
 int cs_segment_local_last_timing(const cs_preproc* p, double* median_ms, double* sum_ms)
 {
-    if (!p) return fail(CS_ERR_INVALID, "handle is NULL");
-    SegmentState* S = p->seg;
-    if (S && S->lt_pending) {
-        HIPCHK(hipSetDevice(p->device));
-        const int rc = local_times(*S);
-        if (rc) return rc;
-    }
-    if (median_ms) *median_ms = S ? S->lt_median_ms : 0.0;
-    if (sum_ms) *sum_ms = S ? S->lt_sum_ms : 0.0;
-    return CS_OK;
+    return clock_read(p, &SegmentState::clk_lt, {median_ms, sum_ms});
 }
 
 int cs_segment_clean(cs_preproc* p, const void* image, int pixel_type, int32_t channels, int32_t channel, int32_t batch, int32_t height,
                      int32_t width, int in_kind, const cs_segment_params* params, const cs_clean_params* clean, uint8_t* out, int out_kind,
                      int32_t* thresholds)
 {
-    if (!clean || !out) return fail(CS_ERR_INVALID, "NULL argument");
+    if (!clean) return fail(CS_ERR_INVALID, "NULL argument");
     cs_segment_params sp;
-    // segment_check's rules with the plane in the labels' place: it looks at no more of them than NULL and the kind
-    int rc = segment_check(image, pixel_type, channels, channel, batch, height, width, in_kind, params, (const int32_t*)out, out_kind,
-                           (const int32_t*)out, sp);
-    if (rc) return rc;
+    int rc;
+    if ((rc = image_check(image, out, pixel_type, channels, channel, batch, height, width, in_kind, out_kind, "labels_kind")) ||
+        (rc = image_limits(batch, height, width)) || (rc = segment_check(params, sp)))
+        return rc;
     const int r = clean->open_radius, k = clean->open_connectivity, a = clean->min_area;
     if (r < 0 || r > CL_MAX_R) return fail(CS_ERR_INVALID, "open_radius %d outside 0..%d (0: no opening)", r, CL_MAX_R);
     if (k != 1 && k != 2) return fail(CS_ERR_INVALID, "open_connectivity %d: 1 (cross) or 2 (square)", k);
     if (a < 0 || a > CL_MAX_AREA) return fail(CS_ERR_INVALID, "min_area %d outside 0..%d (0: no area step)", a, CL_MAX_AREA);
     if (r == 0 && a == 0) return fail(CS_ERR_INVALID, "open_radius and min_area are both 0: nothing to clean");
-    if (!p) {
-        rc = require_gfx950(0);
-        return rc ? rc : fail(CS_ERR_INVALID, "handle is NULL");
-    }
-    HIPCHK(hipSetDevice(p->device));
-    if (!p->seg) p->seg = new SegmentState();
-    SegmentState& S = *p->seg;
-    for (hipEvent_t& e : S.cev)
-        if (!e) HIPCHK(hipEventCreate(&e));
-    hipStream_t st = p->stream;
-    const size_t npx = (size_t)batch * height * width;
-    unsigned char* d_out = out;
-    if (out_kind == CS_MEM_HOST) {
-        if ((rc = S.cl_out.ensure(npx))) return rc;
-        d_out = S.cl_out.as<unsigned char>();
-    }
-    S.cl_pending = false;
-    S.cl_opened = r > 0;
-    S.cl_dropped = a > 0;
-    HIPCHK(hipEventRecord(S.cev[0], st));
+    if ((rc = handle_check(p))) return rc;
+    // segment_mask uploads a host image, after the clock's first event: the upload counts as the mask's time
+    PlaneCall pc;
+    if ((rc = plane_begin(p, nullptr, 0, in_kind, out, (size_t)batch * height * width, out_kind, pc))) return rc;
+    SegmentState& S = *pc.S;
+    hipStream_t st = pc.st;
+    unsigned char* d_out = (unsigned char*)pc.d_out;
+    if ((rc = S.clk_cl.record(0, st))) return rc;
     // the mask as the segmenter makes it; its workspace for labels that go to the host (4 bytes per pixel) holds the hole
     // filling's flags and then the pixel counts
     SegmentCall c;
-    if ((rc = segment_mask(p, image, pixel_type, channels, channel, batch, height, width, in_kind, sp, nullptr, CS_MEM_HOST, c))) return rc;
-    HIPCHK(hipEventRecord(S.cev[1], st));
+    if ((rc = segment_mask(p, image, pixel_type, channels, channel, batch, height, width, in_kind, sp, nullptr, CS_MEM_HOST, c, nullptr)))
+        return rc;
+    if ((rc = S.clk_cl.record(1, st))) return rc;
     const unsigned char* cur = S.mask.as<unsigned char>();
     if (r > 0) {
         const dim3 ogrid((unsigned)((c.W + CL_TW - 1) / CL_TW), (unsigned)((c.H + CL_TH - 1) / CL_TH), (unsigned)batch);
@@ -2373,7 +2263,7 @@ int cs_segment_clean(cs_preproc* p, const void* image, int pixel_type, int32_t c
         HIPCHK(hipGetLastError());
         cur = d_out;
     }
-    HIPCHK(hipEventRecord(S.cev[2], st));
+    if ((rc = S.clk_cl.record(2, st, r > 0))) return rc;
     if (a > 0) {
         HIPCHK(hipMemsetAsync(c.d_lab, 0, c.npx * sizeof(int), st));
         HIPCHK(label_mask(cur, batch, c.H, c.W, 0, sp.connectivity == 2, S.parent.as<int>(), nullptr, c.nchunks, st));
@@ -2381,42 +2271,25 @@ int cs_segment_clean(cs_preproc* p, const void* image, int pixel_type, int32_t c
         hipLaunchKernelGGL(cl_drop, c.pgrid, dim3(SG_THREADS), 0, st, c.HW, (const int*)S.parent.as<int>(), (const int*)c.d_lab, a, d_out);
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipEventRecord(S.cev[3], st));
-    if (out_kind == CS_MEM_DEVICE && in_kind == CS_MEM_DEVICE && !thresholds) {
-        S.cl_pending = true;                            // no host synchronisation: the times are read when they are asked for
-        return CS_OK;
-    }
-    if (thresholds) HIPCHK(hipMemcpyAsync(thresholds, S.thr.p, batch * sizeof(int), hipMemcpyDeviceToHost, st));
-    if (out_kind == CS_MEM_HOST) HIPCHK(hipMemcpyAsync(out, d_out, npx, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));                     // the one host synchronisation: host buffers are free / filled
-    return clean_times(S);
+    if ((rc = S.clk_cl.record(3, st, a > 0))) return rc;
+    return plane_end(pc, S.clk_cl, thresholds, batch);
 }
 
 int cs_segment_clean_last_timing(const cs_preproc* p, double* mask_ms, double* open_ms, double* area_ms)
 {
-    if (!p) return fail(CS_ERR_INVALID, "handle is NULL");
-    SegmentState* S = p->seg;
-    if (S && S->cl_pending) {
-        HIPCHK(hipSetDevice(p->device));
-        const int rc = clean_times(*S);
-        if (rc) return rc;
-    }
-    if (mask_ms) *mask_ms = S ? S->cl_mask_ms : 0.0;
-    if (open_ms) *open_ms = S ? S->cl_open_ms : 0.0;
-    if (area_ms) *area_ms = S ? S->cl_area_ms : 0.0;
-    return CS_OK;
+    return clock_read(p, &SegmentState::clk_cl, {mask_ms, open_ms, area_ms});
 }
 
 int cs_segment_hysteresis(cs_preproc* p, const void* image, int pixel_type, int32_t channels, int32_t channel, int32_t batch,
                           int32_t height, int32_t width, int in_kind, const cs_segment_params* params, const cs_local_params* local,
                           const cs_hysteresis_params* hysteresis, uint8_t* out, int out_kind, int32_t* thresholds)
 {
-    if (!hysteresis || !out) return fail(CS_ERR_INVALID, "NULL argument");
+    if (!hysteresis) return fail(CS_ERR_INVALID, "NULL argument");
     cs_segment_params sp;
-    // segment_check's rules with the plane in the labels' place: it looks at no more of them than NULL and the kind
-    int rc = segment_check(image, pixel_type, channels, channel, batch, height, width, in_kind, params, (const int32_t*)out, out_kind,
-                           (const int32_t*)out, sp);
-    if (rc) return rc;
+    int rc;
+    if ((rc = image_check(image, out, pixel_type, channels, channel, batch, height, width, in_kind, out_kind, "labels_kind")) ||
+        (rc = image_limits(batch, height, width)) || (rc = segment_check(params, sp)))
+        return rc;
     const int mode = hysteresis->mode, weak = hysteresis->weak;
     if (mode != CS_WEAK_ABSOLUTE && mode != CS_WEAK_FRACTION && mode != CS_WEAK_LOCAL)
         return fail(CS_ERR_INVALID, "hysteresis mode %d: CS_WEAK_ABSOLUTE, CS_WEAK_FRACTION or CS_WEAK_LOCAL", mode);
@@ -2435,145 +2308,68 @@ int cs_segment_hysteresis(cs_preproc* p, const void* image, int pixel_type, int3
         } else if (weak < 1 || weak > 65535)
             return fail(CS_ERR_INVALID, "weak fraction %d / 65536 outside 1..65535", weak);
     }
-    if (!p) {
-        rc = require_gfx950(0);
-        return rc ? rc : fail(CS_ERR_INVALID, "handle is NULL");
-    }
-    // the workspace of a call whose labels go to the host: its 4 bytes per pixel hold the flags
+    if ((rc = handle_check(p))) return rc;
+    // the workspace of a call whose labels go to the host: its 4 bytes per pixel hold the flags; segment_begin uploads a host image
     SegmentCall c;
     if ((rc = segment_begin(p, image, pixel_type, channels, batch, height, width, in_kind, nullptr, CS_MEM_HOST, c))) return rc;
-    SegmentState& S = *p->seg;
-    for (hipEvent_t& e : S.hev)
-        if (!e) HIPCHK(hipEventCreate(&e));
-    for (hipEvent_t& e : S.lev)
-        if (!e) HIPCHK(hipEventCreate(&e));
-    hipStream_t st = p->stream;
-    unsigned char* d_out = out;
-    if (out_kind == CS_MEM_HOST) {
-        if ((rc = S.hy_out.ensure(c.npx))) return rc;
-        d_out = S.hy_out.as<unsigned char>();
-    }
-    S.hy_pending = false;
-    unsigned char* level = S.mask.as<unsigned char>();
-    HIPCHK(hipEventRecord(S.hev[0], st));
+    PlaneCall pc;
+    if ((rc = plane_begin(p, nullptr, 0, in_kind, out, c.npx, out_kind, pc))) return rc;
+    SegmentState& S = *pc.S;
+    hipStream_t st = pc.st;
+    unsigned char *level = S.mask.as<unsigned char>(), *d_out = (unsigned char*)pc.d_out;
+    if ((rc = S.clk_hy.record(0, st))) return rc;
     if (mode == CS_WEAK_LOCAL) {
-        S.lt_pending = false;                           // local_launch records over the events of an earlier cs_segment_local
-        if (pixel_type == CS_PIX_U8)
-            rc = local_launch<unsigned char>(S, (const unsigned char*)c.d_img, channels, channel, batch, c.H, c.W, *local, level, st, &weak);
-        else
-            rc = local_launch<unsigned short>(S, (const unsigned short*)c.d_img, channels, channel, batch, c.H, c.W, *local, level, st, &weak);
+        rc = by_pixel(pixel_type, [&](auto pix) {
+            using PIX = decltype(pix);
+            return local_launch(S, (const PIX*)c.d_img, channels, channel, batch, c.H, c.W, *local, level, st, &weak);
+        });
         if (rc) return rc;
     } else {
         if ((rc = segment_thresholds(S, c, pixel_type, channels, channel, sp, st))) return rc;
-        if (pixel_type == CS_PIX_U8)
-            hipLaunchKernelGGL(hy_levels<unsigned char>, c.pgrid, dim3(SG_THREADS), 0, st, (const unsigned char*)c.d_img, (int)channels,
-                               (int)channel, c.HW, (const int*)S.thr.as<int>(), (int)(mode == CS_WEAK_FRACTION), weak, level);
-        else
-            hipLaunchKernelGGL(hy_levels<unsigned short>, c.pgrid, dim3(SG_THREADS), 0, st, (const unsigned short*)c.d_img, (int)channels,
-                               (int)channel, c.HW, (const int*)S.thr.as<int>(), (int)(mode == CS_WEAK_FRACTION), weak, level);
+        by_pixel(pixel_type, [&](auto pix) {
+            using PIX = decltype(pix);
+            hipLaunchKernelGGL(hy_levels<PIX>, c.pgrid, dim3(SG_THREADS), 0, st, (const PIX*)c.d_img, (int)channels, (int)channel, c.HW,
+                               (const int*)S.thr.as<int>(), (int)(mode == CS_WEAK_FRACTION), weak, level);
+        });
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipEventRecord(S.hev[1], st));
+    if ((rc = S.clk_hy.record(1, st))) return rc;
     HIPCHK(hipMemsetAsync(c.d_lab, 0, c.npx * sizeof(int), st));
     HIPCHK(label_mask(level, batch, c.H, c.W, 0, sp.connectivity == 2, S.parent.as<int>(), nullptr, c.nchunks, st));
     hipLaunchKernelGGL(hy_mark, c.pgrid, dim3(SG_THREADS), 0, st, c.HW, (const unsigned char*)level, (const int*)S.parent.as<int>(), c.d_lab);
     hipLaunchKernelGGL(hy_keep, c.pgrid, dim3(SG_THREADS), 0, st, c.HW, (const int*)S.parent.as<int>(), (const int*)c.d_lab, d_out);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(S.hev[2], st));
-    const bool read_thr = thresholds && mode != CS_WEAK_LOCAL;
+    if ((rc = S.clk_hy.record(2, st))) return rc;
     if (thresholds && mode == CS_WEAK_LOCAL)
         for (int b = 0; b < batch; ++b) thresholds[b] = -1;                 // no single number
-    if (out_kind == CS_MEM_DEVICE && in_kind == CS_MEM_DEVICE && !read_thr) {
-        S.hy_pending = true;                            // no host synchronisation: the times are read when they are asked for
-        return CS_OK;
-    }
-    if (read_thr) HIPCHK(hipMemcpyAsync(thresholds, S.thr.p, batch * sizeof(int), hipMemcpyDeviceToHost, st));
-    if (out_kind == CS_MEM_HOST) HIPCHK(hipMemcpyAsync(out, d_out, c.npx, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));                     // the one host synchronisation: host buffers are free / filled
-    return hysteresis_times(S);
+    return plane_end(pc, S.clk_hy, mode == CS_WEAK_LOCAL ? nullptr : thresholds, batch);
 }
 
 int cs_segment_hysteresis_last_timing(const cs_preproc* p, double* level_ms, double* link_ms)
 {
-    if (!p) return fail(CS_ERR_INVALID, "handle is NULL");
-    SegmentState* S = p->seg;
-    if (S && S->hy_pending) {
-        HIPCHK(hipSetDevice(p->device));
-        const int rc = hysteresis_times(*S);
-        if (rc) return rc;
-    }
-    if (level_ms) *level_ms = S ? S->hy_level_ms : 0.0;
-    if (link_ms) *link_ms = S ? S->hy_link_ms : 0.0;
-    return CS_OK;
+    return clock_read(p, &SegmentState::clk_hy, {level_ms, link_ms});
 }
 
 int cs_segment_smooth(cs_preproc* p, const void* image, int pixel_type, int32_t channels, int32_t channel, int32_t batch, int32_t height,
                       int32_t width, int in_kind, const cs_smooth_params* params, void* plane, int plane_kind)
 {
-    if (!image || !params || !plane) return fail(CS_ERR_INVALID, "NULL argument");
-    if (pixel_type != CS_PIX_U8 && pixel_type != CS_PIX_U16) return fail(CS_ERR_INVALID, "pixel_type must be CS_PIX_U8 or CS_PIX_U16");
-    if ((in_kind != CS_MEM_HOST && in_kind != CS_MEM_DEVICE) || (plane_kind != CS_MEM_HOST && plane_kind != CS_MEM_DEVICE))
-        return fail(CS_ERR_INVALID, "in_kind / plane_kind must be CS_MEM_HOST or CS_MEM_DEVICE");
-    if (channels < 1 || channel < 0 || channel >= channels)
-        return fail(CS_ERR_INVALID, "channel %d of %d: need 0 <= channel < channels", (int)channel, (int)channels);
-    if (batch < 1 || height < 1 || width < 1) return fail(CS_ERR_INVALID, "batch %d, height %d, width %d: all must be >= 1", (int)batch,
-                                                          (int)height, (int)width);
+    if (!params) return fail(CS_ERR_INVALID, "NULL argument");
     SmWeights wt;
-    int rc = smooth_check(*params, wt);
-    if (rc) return rc;
-    if (height > kSegMaxSide || width > kSegMaxSide)
-        return fail(CS_ERR_UNSUPPORTED, "image %dx%d: sides above %d are not supported", (int)height, (int)width, kSegMaxSide);
-    if (batch > kSegMaxBatch) return fail(CS_ERR_UNSUPPORTED, "batch %d: at most %d images per call", (int)batch, kSegMaxBatch);
-    if (!p) {
-        rc = require_gfx950(0);
-        return rc ? rc : fail(CS_ERR_INVALID, "handle is NULL");
-    }
-    HIPCHK(hipSetDevice(p->device));
-    if (!p->seg) p->seg = new SegmentState();
-    SegmentState& S = *p->seg;
-    for (hipEvent_t& e : S.sev)
-        if (!e) HIPCHK(hipEventCreate(&e));
-    hipStream_t st = p->stream;
-    const size_t esz = pixel_type == CS_PIX_U8 ? 1 : 2;
-    const size_t npx = (size_t)batch * height * width;
-    const void* d_img = image;
-    if (in_kind == CS_MEM_HOST) {
-        if ((rc = S.sm_in.ensure(npx * channels * esz))) return rc;
-        HIPCHK(hipMemcpyAsync(S.sm_in.p, image, npx * channels * esz, hipMemcpyHostToDevice, st));
-        d_img = S.sm_in.p;
-    }
-    void* d_out = plane;
-    if (plane_kind == CS_MEM_HOST) {
-        if ((rc = S.sm_out.ensure(npx * esz))) return rc;
-        d_out = S.sm_out.p;
-    }
-    S.sm_pending = false;
-    if (pixel_type == CS_PIX_U8)
-        rc = smooth_launch<unsigned char>(S, (const unsigned char*)d_img, channels, channel, batch, height, width, wt, params->median != 0,
-                                          (unsigned char*)d_out, st);
-    else
-        rc = smooth_launch<unsigned short>(S, (const unsigned short*)d_img, channels, channel, batch, height, width, wt, params->median != 0,
-                                           (unsigned short*)d_out, st);
-    if (rc) return rc;
-    if (plane_kind == CS_MEM_DEVICE && in_kind == CS_MEM_DEVICE) {
-        S.sm_pending = true;                            // no host synchronisation: the times are read when they are asked for
-        return CS_OK;
-    }
-    if (plane_kind == CS_MEM_HOST) HIPCHK(hipMemcpyAsync(plane, d_out, npx * esz, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));                     // the one host synchronisation: the caller's host buffers are free / filled
-    return smooth_times(S);
+    int rc;
+    if ((rc = image_check(image, plane, pixel_type, channels, channel, batch, height, width, in_kind, plane_kind, "plane_kind")) ||
+        (rc = smooth_check(*params, wt)) || (rc = image_limits(batch, height, width)) || (rc = handle_check(p)))
+        return rc;
+    const size_t esz = pixel_type == CS_PIX_U8 ? 1 : 2, npx = (size_t)batch * height * width;
+    PlaneCall c;
+    if ((rc = plane_begin(p, image, npx * channels * esz, in_kind, plane, npx * esz, plane_kind, c))) return rc;
+    rc = by_pixel(pixel_type, [&](auto pix) {
+        using PIX = decltype(pix);
+        return smooth_launch(*c.S, (const PIX*)c.d_img, channels, channel, batch, height, width, wt, params->median != 0, (PIX*)c.d_out, c.st);
+    });
+    return rc ? rc : plane_end(c, c.S->clk_sm, nullptr, batch);
 }
 
 int cs_segment_smooth_last_timing(const cs_preproc* p, double* median_ms, double* smooth_ms)
 {
-    if (!p) return fail(CS_ERR_INVALID, "handle is NULL");
-    SegmentState* S = p->seg;
-    if (S && S->sm_pending) {
-        HIPCHK(hipSetDevice(p->device));
-        const int rc = smooth_times(*S);
-        if (rc) return rc;
-    }
-    if (median_ms) *median_ms = S ? S->sm_median_ms : 0.0;
-    if (smooth_ms) *smooth_ms = S ? S->sm_smooth_ms : 0.0;
-    return CS_OK;
+    return clock_read(p, &SegmentState::clk_sm, {median_ms, smooth_ms});
 }

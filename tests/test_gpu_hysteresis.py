@@ -377,6 +377,79 @@ def test_stage_off_is_the_segmenter_as_it_was(segs, scenes):
     assert np.array_equal(same[0], lab90[0]) and np.array_equal(same[1], lab90[1]) and np.array_equal(same[2], lab90[2])
 
 
+# ---- one handle through every stage --------------------------------------------------------------------------------------------
+# Three configurations on one handle, so that its upload buffer, median plane and host-staging plane are shared between every
+# stage, called in turn on inputs that grow, shrink and change element size, channel count and batch: each buffer is reused too
+# small, then too large.  The sizes are the smallest that cross a 64 x 16 tile border both ways with widths no multiple of 64.
+WALK_SHAPES = [(np.uint16, (2, 48, 80, 3)), (np.uint8, (3, 72, 200)), (np.uint16, (2, 48, 80, 3))]
+WALK_CONFIGS = [dict(smooth_sigma=1, denoise=True, background_radius=5),
+                dict(threshold="local", local_radius=4, local_delta=3, weak_delta=0, min_area=4, open_radius=1),
+                dict(split_touching=True, split_by="intensity", smooth_sigma=1)]
+WALK_OFF = [("median_ms",), (), ()]                     # the steps that are off: the median ran in the smoothing, not in the correction
+
+
+def walk_input(dtype, shape, seed):
+    """A few Gaussian blobs (two of them overlapping) on noise, in every channel, from a seed."""
+    rng = np.random.default_rng(seed)
+    top = int(np.iinfo(dtype).max)
+    B, H, W = shape[:3]
+    yy, xx = np.mgrid[0:H, 0:W]
+    out = np.empty(shape, dtype)
+    for idx in np.ndindex(B, *shape[3:]):
+        f = top * 0.1 + rng.normal(0.0, top * 0.01, (H, W))
+        centres = [(int(rng.integers(8, H - 8)), int(rng.integers(8, W - 8))) for _ in range(5)]
+        centres.append((centres[0][0], centres[0][1] + 6))
+        for cy, cx in centres:
+            f += top * 0.5 * np.exp(-((yy - cy) ** 2 + (xx - cx) ** 2) / (2 * 2.5 ** 2))
+        out[(idx[0], Ellipsis) + idx[1:]] = np.clip(f, 0, top).astype(dtype)
+    return out
+
+
+def walk_expected(imgs):
+    """[(labels, n_labels, thresholds)] of WALK_CONFIGS from the host restatements, composed as the tests above compose them;
+    the third with the heights as a fourth."""
+    chan = imgs if imgs.ndim == 3 else imgs[..., 2]
+    a, b = [], []
+    for raw in chan:
+        raw = np.ascontiguousarray(raw)
+        a.append(R.segment(BR.correct(MR.smooth_sigma(raw, 1.0, True), 5, False), "otsu", 1, True))
+        filled = R.ndimage.binary_fill_holes(HR.hysteresis(HR.levels_local(raw, 4, 3, 0), 1) > 0)
+        b.append(R.label_mask(CR.clean(filled, 1, 2, 4, 1) > 0, 1) + (-1,))
+    stacked = [(np.stack([o[0] for o in out]), np.array([o[1] for o in out], np.int32), np.array([o[2] for o in out], np.int32))
+               for out in (a, b)]
+    return stacked + [IR.segment_batch(imgs, smooth_sigma=1)[:4]]
+
+
+@pytest.fixture(scope="module")
+def walk():
+    inputs = [walk_input(dtype, shape, 11 + k) for k, (dtype, shape) in enumerate(WALK_SHAPES[:2])]
+    expected = [walk_expected(x) for x in inputs]
+    for per_input in expected:
+        for want in per_input:
+            assert (want[1] >= 2).all()                                           # no case is vacuous
+    for x in inputs:
+        x.setflags(write=False)
+    return inputs + inputs[:1], expected + expected[:1]
+
+
+@pytest.mark.parametrize("on_device", [False, True], ids=["numpy", "tensor"])
+def test_one_handle_through_every_stage_growing_and_shrinking(segs, walk, on_device):
+    inputs, expected = walk
+    for imgs, per_input in zip(inputs, expected):
+        x = as_tensor(imgs.copy()) if on_device else imgs
+        for kw, off, want in zip(WALK_CONFIGS, WALK_OFF, per_input):
+            s = segs(**kw)
+            got = s.segment_batch(x, return_distance=len(want) == 4)
+            if on_device:
+                got = tuple(g.cpu().numpy() if hasattr(g, "is_cuda") else g for g in got)
+            assert len(got) == len(want)
+            for g, w in zip(got, want):
+                assert np.array_equal(g, w), (kw, imgs.shape)
+            if on_device:
+                t = s.last_timing()
+                assert all(t[key] == 0.0 for key in off) and t == s.last_timing(), (kw, t)
+
+
 # ---- the C ABI with a device ------------------------------------------------------------------------------------------------------
 def test_error_codes_with_a_handle():
     lib = L.load_library()

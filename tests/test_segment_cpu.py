@@ -1,12 +1,15 @@
 """CPU tests of the built-in segmenter (cellscreen/segment.py, csrc/segment.hip): the restatement of
 tests/segment_reference.py against tests/golden/golden_segment.npz (scikit-image 0.18.3 + SciPy 1.7.1), the numbering rule of
-the labels, and the wrapper's and the C ABI's refusals before any device work."""
+the labels, and the wrapper's and the C ABI's refusals before any device work; for all eight cs_segment_* entry points, the
+recorded status and text of every refusal (tests/golden/segment_arg_errors.json)."""
 import ctypes as C
+import json
 import os
 
 import numpy as np
 import pytest
 
+import segment_arg_cases as AC
 import segment_reference as R
 from cellscreen import _lib as L
 from cellscreen import segment as S
@@ -155,3 +158,18 @@ def test_c_abi_refuses_and_reports_no_device():
         with pytest.raises(L.CellScreenError) as ei:
             S.ThresholdSegmenter(0).segment_batch(imgs)
         assert ei.value.status == -4
+
+
+def test_every_entry_point_refuses_with_the_recorded_status_and_text():
+    """tools/make_golden_segment_arg_errors.py: one or two argument rules broken per call, a NULL handle; which rule answers,
+    with which status and in which words, is the ABI's and stays."""
+    with open(os.path.join(os.path.dirname(GOLDEN), "segment_arg_errors.json")) as f:
+        recorded = json.load(f)
+    cases = AC.cases()
+    assert sorted(recorded) == sorted(AC.ENTRIES) and len(AC.ENTRIES) == 8
+    assert [(e, name) for e, name, _ in cases] == [(e, row[0]) for e, rows in recorded.items() for row in rows]
+    want = {(e, row[0]): (row[1], row[2]) for e, rows in recorded.items() for row in rows}
+    assert len(want) == len(cases) >= 600 and {s for s, _ in want.values()} == {-1, -6}
+    lib = L.load_library()
+    for entry, name, over in cases:
+        assert AC.call(lib, entry, over) == want[entry, name], (entry, name)
