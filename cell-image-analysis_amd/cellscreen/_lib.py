@@ -131,6 +131,11 @@ class CSHysteresisParams(C.Structure):
 WEAK_ABSOLUTE, WEAK_FRACTION, WEAK_LOCAL = 0, 1, 2      # cs_hysteresis_params.mode
 
 
+class CSNoiseParams(C.Structure):
+    _fields_ = [("tile", C.c_int32), ("k8", C.c_int32), ("weak_k8", C.c_int32), ("floor8", C.c_int32), ("connectivity", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
+
+
 SMOOTH_MAX_RADIUS = 64                  # cs_smooth_params.weights holds 65 taps
 
 
@@ -200,6 +205,8 @@ SIGNATURES = {
     "cs_segment_hysteresis": (_I, [_P, _P, _I, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _I, C.POINTER(CSSegmentParams),
                                    C.POINTER(CSLocalParams), C.POINTER(CSHysteresisParams), _P, _I, _P]),
     "cs_segment_hysteresis_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "cs_segment_noise": (_I, [_P, _P, _I, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _I, C.POINTER(CSNoiseParams), _P, _I, _P]),
+    "cs_segment_noise_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "cs_segment_smooth": (_I, [_P, _P, _I, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _I, C.POINTER(CSSmoothParams), _P, _I]),
     "cs_segment_smooth_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "cs_fit_create": (_I, [_I, C.POINTER(_P)]),

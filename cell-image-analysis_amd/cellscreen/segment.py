@@ -56,6 +56,17 @@ and tie rule).  Components are taken under the segmenter's connectivity; speckle
 size, a cell keeps its whole weak extent.  The hole filling, the cleanup, the labels and the split see the resulting 0 / 1
 plane; the thresholds reported stay the strong rule's.  The low number is never chosen automatically.
 
+Noise-adaptive threshold, threshold="noise", in the place of all of the above rules (cs_segment_noise; tests/noise_reference.py
+restates it).  Every other rule takes its numbers in counts, which do not travel between exposures, cameras, bit depths or even
+the fields of one plate; the one unit that does is the image's own background noise.  The background level and the noise are
+estimated on a mesh of noise_tile x noise_tile tiles with robust statistics (the median, and 1.4826 times the median absolute
+deviation, not below noise_floor counts), each map is median-filtered over 3 x 3 tiles (a tile that a cell fills is rejected)
+and interpolated bilinearly to every pixel, and foreground is  x > background + noise_k * sigma, decided in 64-bit integers
+with noise_k in 1/256 (an exact tie is background), as SExtractor and photutils' Background2D cut.  It follows a sloping
+background without the top-hat, and weak_k (not above noise_k) is the weak rule of the hysteresis threshold above: noise_k=6,
+weak_k=3 keeps whole cells and no speckle.  The tile must stay well above a cell's width; a slope inside a tile inflates the
+sigma, and a field so crowded that most tiles are mostly cell biases both maps upward.  The thresholds reported are -1.
+
 Mask cleanup, between the hole filling and the labels (cs_segment_clean; tests/clean_reference.py restates it), off by default:
 open_radius=r (1..15) opens the mask, r erosions then r dilations by the 3 x 3 square (open_connectivity=2, the default) or
 cross (1), which is scipy.ndimage.binary_opening(mask, generate_binary_structure(2, k), iterations=r) bit for bit: speckle and
@@ -82,6 +93,8 @@ correction, the threshold, the cleanup, the labels and the split see the smoothe
     seg = ThresholdSegmenter(smooth_sigma=2)                           # faint cells in noise: Gaussian first
     seg = ThresholdSegmenter(threshold="local", local_radius=25, local_delta=200, weak_delta=40)      # no speckle, whole cells
     seg = ThresholdSegmenter(weak_threshold=0.2)                       # Otsu's threshold for the cores, a fifth of it for the rims
+    seg = ThresholdSegmenter(threshold="noise")                        # 5 sigmas above the local background, no number in counts
+    seg = ThresholdSegmenter(threshold="noise", noise_k=6, weak_k=3)   # ... cores at 6 sigmas, rims down to 3, no speckle
 
     screening = ProductionMutantScreening(model_dir, cell_extractor=threshold_cell_extractor())
 """
@@ -276,6 +289,61 @@ def hysteresis_params(threshold="otsu", weak_threshold=None, weak_delta=None, lo
     return p
 
 
+NOISE_K, NOISE_TILE, NOISE_FLOOR = 5.0, 64, 1.0           # the defaults of threshold="noise"
+NOISE_TILES = (16, 32, 64, 128, 256)
+NOISE_K8_MAX, NOISE_FLOOR_MAX = 16383, 4095
+
+
+def noise_params(noise_k=NOISE_K, noise_tile: int = NOISE_TILE, noise_floor=NOISE_FLOOR, weak_k=None,
+                 connectivity: int = 1) -> L.CSNoiseParams:
+    """cs_noise_params from the Python arguments of threshold="noise"; anything out of range raises before a handle exists.
+    noise_k and weak_k are kept in 1/256, k8 = int(k * 256 + 0.5) in 1..16383 with weak_k8 not above k8; noise_floor (counts,
+    0..4095) as floor8 = int(f * 256 + 0.5); noise_tile is a power of two in 16..256."""
+    def number(name, v):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise TypeError(f"{name} must be a number, got {type(v).__name__}")
+        if math.isnan(float(v)) or math.isinf(float(v)):
+            raise ValueError(f"{name} {v} is not a finite number")
+        return float(v)
+
+    k = number("noise_k", noise_k)
+    f = number("noise_floor", noise_floor)
+    if isinstance(noise_tile, (bool, np.bool_)) or not isinstance(noise_tile, (int, np.integer)):
+        raise TypeError(f"noise_tile must be an integer, got {type(noise_tile).__name__}")
+    if int(noise_tile) not in NOISE_TILES:
+        raise ValueError(f"noise_tile {noise_tile}: a power of two in 16..256")
+    k8 = int(k * 256 + 0.5) if 0.0 < k < 1e6 else 0
+    if not 1 <= k8 <= NOISE_K8_MAX:
+        raise ValueError(f"noise_k {noise_k} is {k8} / 256, outside 1..{NOISE_K8_MAX} / 256")
+    if not 0.0 <= f <= NOISE_FLOOR_MAX:
+        raise ValueError(f"noise_floor {noise_floor} outside 0..{NOISE_FLOOR_MAX}")
+    weak8 = -1
+    if weak_k is not None:
+        w = number("weak_k", weak_k)
+        weak8 = int(w * 256 + 0.5) if 0.0 < w < 1e6 else 0
+        if not 1 <= weak8 <= k8:
+            raise ValueError(f"weak_k {weak_k} is {weak8} / 256, outside 1..{k8} / 256 (noise_k): the weak rule is the lower one")
+    if isinstance(connectivity, bool) or connectivity not in (1, 2):
+        raise ValueError(f"connectivity must be 1 (4 neighbours) or 2 (8 neighbours), got {connectivity!r}")
+    p = L.CSNoiseParams()
+    p.tile, p.k8, p.weak_k8, p.floor8, p.connectivity = int(noise_tile), k8, weak8, int(f * 256 + 0.5), int(connectivity)
+    return p
+
+
+def _noise_mode(threshold, connectivity=1, noise_k=NOISE_K, noise_tile=NOISE_TILE, noise_floor=NOISE_FLOOR, weak_k=None,
+                weak_threshold=None, weak_delta=None) -> Optional[L.CSNoiseParams]:
+    """cs_noise_params of a segmenter's arguments, None without threshold="noise".  noise_k, noise_tile, noise_floor and weak_k
+    belong to "noise" alone; with it the weak rule is weak_k, and weak_threshold and weak_delta are refused."""
+    if not (isinstance(threshold, str) and threshold == "noise"):
+        noise_params(noise_k, noise_tile, noise_floor, weak_k)                  # a bad value is a mistake either way
+        if float(noise_k) != NOISE_K or int(noise_tile) != NOISE_TILE or float(noise_floor) != NOISE_FLOOR or weak_k is not None:
+            raise ValueError("noise_k, noise_tile, noise_floor and weak_k belong to threshold='noise'")
+        return None
+    if weak_threshold is not None or weak_delta is not None:
+        raise ValueError("weak_threshold and weak_delta belong to the other rules; threshold='noise' takes weak_k")
+    return noise_params(noise_k, noise_tile, noise_floor, weak_k, connectivity)
+
+
 SMOOTH_SIGMA_MIN, SMOOTH_SIGMA_MAX = 0.25, 15.875         # radius int(4 sigma + 0.5) = 1..64
 
 
@@ -327,6 +395,11 @@ def _threshold_mode(threshold, connectivity, fill_holes, local_radius, local_del
     rule."""
     if smooth_params(smooth_sigma, denoise) is not None:
         denoise = False
+    if isinstance(threshold, str) and threshold == "noise":
+        # cs_segment_noise makes a 0 / 1 plane, as the local rule: the fixed threshold 0 for what follows
+        if local_radius is not None or local_delta != 0 or local_floor != -1:
+            raise ValueError("local_radius, local_delta and local_floor belong to threshold='local'")
+        return segment_params(0, connectivity, fill_holes), None, background_params(background_radius, denoise)
     if isinstance(threshold, str) and threshold == "local":
         if not isinstance(denoise, (bool, np.bool_)):
             raise TypeError(f"denoise must be a bool, got {type(denoise).__name__}")
@@ -365,7 +438,12 @@ class ThresholdSegmenter:
     and, with threshold="local", weak_delta (None or an int in -65535..65535, not above local_delta): the hysteresis threshold
     of the module text, in the place of the plain cut or of the local rule; the threshold (or local_delta) stays the strong
     rule and is what `thresholds` reports.  The hole filling and every later stage see its 0 / 1 plane.  With numpy input that
-    plane makes one more round trip through the host, as the other stages' planes do."""
+    plane makes one more round trip through the host, as the other stages' planes do.
+    threshold="noise": the noise-adaptive threshold of the module text in the place of all these rules, with noise_k (sigmas
+    above the local background, kept in 1/256, default 5), noise_tile (the mesh tile's side, a power of two in 16..256, default
+    64), noise_floor (the least sigma in counts, 0..4095, default 1) and weak_k (None, or the weak rule's k, not above noise_k);
+    these four belong to "noise" alone, and local_*, weak_threshold and weak_delta are refused with it.  The thresholds it
+    reports are -1.  With numpy input its plane makes one more round trip through the host."""
 
     def __init__(self, device_id: int = 0, threshold="otsu", connectivity: int = 1, fill_holes: bool = True,
                  extractor: Optional[CellExtractor] = None, split_touching: bool = False, split_h: int = 3,
@@ -373,10 +451,14 @@ class ThresholdSegmenter:
                  local_delta: int = 0, local_floor: int = -1, open_radius: Optional[int] = None, open_connectivity: int = 2,
                  min_area: Optional[int] = None, smooth_sigma: Optional[float] = None, split_by: str = "distance",
                  split_depth: int = SPLIT_DEPTH, split_contrast: int = SPLIT_CONTRAST, weak_threshold=None,
-                 weak_delta: Optional[int] = None):
+                 weak_delta: Optional[int] = None, noise_k: float = NOISE_K, noise_tile: int = NOISE_TILE,
+                 noise_floor: float = NOISE_FLOOR, weak_k: Optional[float] = None):
         self._params, self._local, self._background = _threshold_mode(threshold, connectivity, fill_holes, local_radius, local_delta,
                                                                       local_floor, background_radius, denoise, smooth_sigma)
-        self._hysteresis = hysteresis_params(threshold, weak_threshold, weak_delta, local_delta)
+        self._noise = _noise_mode(threshold, connectivity, noise_k, noise_tile, noise_floor, weak_k, weak_threshold, weak_delta)
+        self.noise_k, self.noise_tile, self.noise_floor = float(noise_k), int(noise_tile), float(noise_floor)
+        self.weak_k = None if weak_k is None else float(weak_k)
+        self._hysteresis = None if self._noise is not None else hysteresis_params(threshold, weak_threshold, weak_delta, local_delta)
         # what takes the hysteresis stage's 0 / 1 plane: the fixed threshold 0, and the hole filling as requested
         self._after_hysteresis = segment_params(0, connectivity, fill_holes)
         self.weak_threshold, self.weak_delta = weak_threshold, (None if weak_delta is None else int(weak_delta))
@@ -483,7 +565,7 @@ class ThresholdSegmenter:
     def _front(self, src, upto, report=False):
         """The front of the pipeline on a checked source (images, B, H, W, Cn, channel, ptype, on_dev), up to and including the
         stage `upto`: "smooth", "background", "local" (the local rule, whatever else is set), "threshold" (the stage in the plain
-        cut's place: hysteresis, else the local rule) or "clean"; a stage that is off is passed over, and each stage takes the
+        cut's place: the noise rule, else hysteresis, else the local rule) or "clean"; a stage that is off is passed over, and each stage takes the
         plane of the one before in the channel's place.  Returns (src, params, reported, guide): the current plane as a source,
         the cs_segment_params that cut it, with report the int32 [B] thresholds of the strong rule where a stage here had to
         read them (else None), and the source the thresholding stage saw."""
@@ -508,7 +590,10 @@ class ThresholdSegmenter:
             reported[:] = self._params.threshold
             return reported, None
 
-        if last >= 2 and self._hysteresis is not None and upto != "local":
+        if last >= 2 and self._noise is not None:
+            # the 0 / 1 plane in the channel's place, cut at the fixed threshold 0
+            src = self._plane(src, np.uint8, lib.cs_segment_noise, C.byref(self._noise), after=(None,))
+        elif last >= 2 and self._hysteresis is not None and upto != "local":
             # the 0 / 1 plane in the channel's place, cut at the fixed threshold 0
             reported, thr = strong() if report else (None, None)
             src = self._plane(src, np.uint8, lib.cs_segment_hysteresis, C.byref(self._params),
@@ -595,6 +680,33 @@ class ThresholdSegmenter:
             self._hysteresis_timing()                               # reads the times, which waits for the plane: torch may use it
         return src[0]
 
+    def _noise_timing(self):
+        return dict(zip(("noise_mesh_ms", "noise_cut_ms", "noise_link_ms"), self._times(self._lib.cs_segment_noise_last_timing, 3)))
+
+    def noise_mask_batch(self, images, channel: Optional[int] = None):
+        """The mask of the noise-adaptive threshold, before the hole filling: [B,H,W] uint8, 1 = foreground, numpy for numpy
+        input, a CUDA tensor for tensor input (complete when this returns).  Needs threshold="noise"; with smooth_sigma and
+        background_radius it is the mask of what they make."""
+        src = (images, *self._check(images, channel))
+        if self._noise is None:
+            raise ValueError("noise_mask_batch needs threshold='noise'")
+        src = self._front(src, "threshold")[0]
+        if src[-1]:
+            self._noise_timing()                                    # reads the times, which waits for the plane: torch may use it
+        return src[0]
+
+    def noise_mesh_batch(self, images, channel: Optional[int] = None):
+        """The mesh of the noise-adaptive threshold after its 3 x 3 filter: int32 numpy [B, 2, my, mx], the background B8 then
+        the noise S8, both in 1/256 counts, my = max(1, H // noise_tile) tiles down and mx across.  Needs threshold="noise"."""
+        src = (images, *self._check(images, channel))
+        if self._noise is None:
+            raise ValueError("noise_mesh_batch needs threshold='noise'")
+        src = self._front(src, "background")[0]
+        B, H, W = src[1:4]
+        mesh = np.zeros((B, 2, max(1, H // self.noise_tile), max(1, W // self.noise_tile)), np.int32)
+        self._plane(src, np.uint8, self._lib.cs_segment_noise, C.byref(self._noise), after=(mesh.ctypes.data,))
+        return mesh
+
     def _clean_timing(self):
         return dict(zip(("open_ms", "min_area_ms"), self._times(self._lib.cs_segment_clean_last_timing, 3)[1:]))
 
@@ -637,7 +749,7 @@ class ThresholdSegmenter:
                                                    thresholds.ctypes.data))
             if reported is not None:
                 thresholds = reported
-            if self._local is not None:
+            if self._local is not None or self._noise is not None:
                 thresholds[:] = -1                                  # no single number
             return labels, n_labels, thresholds
         dist = None
@@ -658,7 +770,7 @@ class ThresholdSegmenter:
                                                thresholds.ctypes.data, L._ptr(dist)))
         if reported is not None:
             thresholds = reported
-        if self._local is not None:
+        if self._local is not None or self._noise is not None:
             thresholds[:] = -1
         return (labels, n_labels, thresholds, dist) if return_distance else (labels, n_labels, thresholds)
 
@@ -671,11 +783,15 @@ class ThresholdSegmenter:
         cleaned plane; with smooth_sigma also smooth_ms (the two passes) of the last smoothing, and smooth_median_ms when the
         median ran there; with weak_threshold or weak_delta also hysteresis_level_ms (thresholds or sums, and the level plane)
         and hysteresis_link_ms (weak components, flags, the kept plane) of the last hysteresis stage, which then stands in the
-        local rule's place: local_ms is not reported."""
+        local rule's place: local_ms is not reported; with threshold="noise" noise_mesh_ms (tile statistics and the mesh filter),
+        noise_cut_ms (the cut or the level plane) and noise_link_ms (with weak_k: weak components, flags, the kept plane; else 0)
+        of the last noise stage."""
         extra = self._smooth_timing() if self._smooth is not None else {}
         if self._background is not None:
             extra.update(self._background_timing())
-        if self._hysteresis is not None:
+        if self._noise is not None:
+            extra.update(self._noise_timing())
+        elif self._hysteresis is not None:
             extra.update(self._hysteresis_timing())
         elif self._local is not None:
             extra.update(self._local_timing())
@@ -706,7 +822,9 @@ def threshold_cell_extractor(device_id: int = 0, out_hw=(OUT_SIDE, OUT_SIDE), th
                              local_delta: int = 0, local_floor: int = -1, open_radius: Optional[int] = None,
                              open_connectivity: int = 2, mask_min_area: Optional[int] = None,
                              smooth_sigma: Optional[float] = None, split_by: str = "distance", split_depth: int = SPLIT_DEPTH,
-                             split_contrast: int = SPLIT_CONTRAST, weak_threshold=None, weak_delta: Optional[int] = None, **qc):
+                             split_contrast: int = SPLIT_CONTRAST, weak_threshold=None, weak_delta: Optional[int] = None,
+                             noise_k: float = NOISE_K, noise_tile: int = NOISE_TILE, noise_floor: float = NOISE_FLOOR,
+                             weak_k: Optional[float] = None, **qc):
     """The `cell_extractor(image_path) -> (cells, stats)` that ProductionMutantScreening and create_training_dataset accept,
     with the built-in segmenter in StarDist's place: the file is read (extract.read_image / split_channels), uploaded once,
     segmented and extracted on one handle, and the labels never leave the device.  Not StarDist: see the module text.
@@ -718,14 +836,16 @@ def threshold_cell_extractor(device_id: int = 0, out_hw=(OUT_SIDE, OUT_SIDE), th
     the labels.  The name differs here because min_area is, and stays, the extraction's own area rule among **qc.
     smooth_sigma as for ThresholdSegmenter: the segmentation channel is smoothed first, the extraction reads the raw one.
     split_by, split_depth and split_contrast as for ThresholdSegmenter; split_by="intensity" wants smooth_sigma.
-    weak_threshold and weak_delta as for ThresholdSegmenter: the hysteresis threshold in the plain cut's place."""
+    weak_threshold and weak_delta as for ThresholdSegmenter: the hysteresis threshold in the plain cut's place.
+    threshold="noise" with noise_k, noise_tile, noise_floor and weak_k as for ThresholdSegmenter: the noise-adaptive threshold."""
     out_hw = check_out_hw(out_hw)
     _threshold_mode(threshold, connectivity, fill_holes, local_radius, local_delta, local_floor, background_radius, denoise,
                     smooth_sigma)
     split_params(split_touching, split_h)
     split_intensity_params(split_touching, split_by, split_h, split_depth, split_contrast)
     clean_params(open_radius, open_connectivity, mask_min_area)
-    hysteresis_params(threshold, weak_threshold, weak_delta, local_delta)
+    if _noise_mode(threshold, connectivity, noise_k, noise_tile, noise_floor, weak_k, weak_threshold, weak_delta) is None:
+        hysteresis_params(threshold, weak_threshold, weak_delta, local_delta)
     qc_params(**qc)
     st = {}
 
@@ -744,7 +864,8 @@ def threshold_cell_extractor(device_id: int = 0, out_hw=(OUT_SIDE, OUT_SIDE), th
                                          local_floor=local_floor, open_radius=open_radius, open_connectivity=open_connectivity,
                                          min_area=mask_min_area, smooth_sigma=smooth_sigma, split_by=split_by,
                                          split_depth=split_depth, split_contrast=split_contrast, weak_threshold=weak_threshold,
-                                         weak_delta=weak_delta)
+                                         weak_delta=weak_delta, noise_k=noise_k, noise_tile=noise_tile, noise_floor=noise_floor,
+                                         weak_k=weak_k)
         host = np.ascontiguousarray(img)[None]
         dev = torch.from_numpy(host.view(np.int16) if host.dtype == np.uint16 else host).to(torch.device("cuda", device_id))
         labels, _, _ = st["s"].segment_batch(dev, channel=seg_ch)

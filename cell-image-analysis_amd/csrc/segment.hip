@@ -32,6 +32,8 @@
 //                then stands in the channel's place, cut at the fixed threshold 0.
 //   hy_*         cs_segment_hysteresis only: the hysteresis threshold in the plain cut's (or the local rule's) place, a level
 //                plane (0 / weak / strong), its weak components, and a flag per root; see "hysteresis threshold" further down.
+//   ns_*         cs_segment_noise only: the noise-adaptive threshold in the plain cut's place, background + k * noise from robust
+//                statistics on a mesh of tiles; see "noise-adaptive threshold" further down.
 //   sm_*         cs_segment_smooth only: the optional Gaussian smoothing of the channel BEFORE all of the above, the background
 //                correction included (separable, 16-bit fixed-point weights, one rounding); see "Gaussian smoothing".
 // The final parents are a function of the mask alone (the minimum index of a component), so the labels do not depend on
@@ -1485,6 +1487,181 @@ __global__ __launch_bounds__(SG_THREADS) void hy_keep(int HW, const int* __restr
     }
 }
 
+// ---- noise-adaptive threshold (cs_segment_noise) ------------------------------------------------------------------------------
+// The cut is background + k * noise, both estimated from the image on a mesh of tiles (tests/noise_reference.py
+// restates it).  Along an axis of n pixels there are m = max(1, n >> shift) tiles of side T = 1 << shift; the last one runs to
+// n and is at most 2T - 1 wide.
+//   ns_stats    one workgroup per tile and image: an exact selection of the lower median (rank (N - 1) / 2) and then of the same
+//               rank among |x - med|, each by radix: a 256-bin LDS histogram of the high byte (hist_add's wave aggregation),
+//               a scan to the bucket that holds the rank, then the low byte among that bucket's values (uint8: the one pass).
+//               A tile of at most 4096 pixels (every regular tile up to T = 64) is read once and stays in 16 registers; the
+//               others (up to 511 x 511) are read again in each pass, row by row.  Counts are integers: the atomics' order
+//               cannot change them.  Writes B8 = 256 med and S8 = max((dev * 97164) >> 8, floor8).
+//   ns_filter   the median of the 3 x 3 mesh neighbourhood (mesh replicated at its edges) of both maps, one thread per node.
+//   ns_cut      per pixel the two nodes and weights of each axis (bilinear between tile centres at doubled coordinates
+//               C2_i = start_i + end_i - 1, constant outside the outer centres), N_B, N_S and D in 64-bit integers, and
+//               256 (256 v D - N_B) > k8 N_S; with a weak rule the 0 / 1 / 2 level plane of the hysteresis stage, whose
+//               label_mask, hy_mark and hy_keep then run as they are.
+// The mesh is addressed image by image; nothing crosses between the images of a batch.  No floating point anywhere.
+static constexpr int NS_REG = 16;                       // pixels a thread of ns_stats keeps in registers
+static constexpr int NS_MAD_Q16 = 97164;                // 1.4826 * 65536
+
+// The bucket of a 256-bin histogram that holds `rank`, and the rank inside it: sel[0], sel[1].  All 256 threads call it; the
+// bins are complete before and may be cleared after.
+__device__ inline void ns_find(const unsigned int* bins, int rank, int* sel, unsigned int* wsum)
+{
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const unsigned int c = bins[t];
+    unsigned int incl = c;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const unsigned int o = __shfl_up(incl, d);
+        if (lane >= d) incl += o;
+    }
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    for (int q = 0; q < wave; ++q) incl += wsum[q];
+    const unsigned int excl = incl - c;
+    if (excl <= (unsigned int)rank && (unsigned int)rank < incl) { sel[0] = t; sel[1] = rank - (int)excl; }
+    __syncthreads();
+}
+
+// grid (mx, my, B); mesh: [B][2][my][mx], B8 then S8
+template <typename PIX>
+__global__ __launch_bounds__(SG_THREADS) void ns_stats(const PIX* __restrict__ image, int C, int ch, int H, int W, int shift, int floor8,
+                                                       int* __restrict__ mesh)
+{
+    __shared__ unsigned int bins[256];
+    __shared__ unsigned int wsum[SG_WAVES];
+    __shared__ int sel[2];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int mx = gridDim.x, my = gridDim.y, b = blockIdx.z;
+    const int x0 = blockIdx.x << shift, y0 = blockIdx.y << shift;
+    const int tw = ((int)blockIdx.x == mx - 1 ? W : x0 + (1 << shift)) - x0, th = ((int)blockIdx.y == my - 1 ? H : y0 + (1 << shift)) - y0;
+    const int N = tw * th, rank = (N - 1) >> 1;
+    const PIX* img = image + ((size_t)b * H * W + (size_t)y0 * W + x0) * C + ch;
+    const bool in_regs = N <= NS_REG * SG_THREADS;      // the whole workgroup decides alike
+    int reg[NS_REG];
+    if (in_regs) {
+#pragma unroll
+        for (int k = 0; k < NS_REG; ++k) {
+            const int i = k * SG_THREADS + t;
+            reg[k] = i < N ? (int)img[((size_t)(i / tw) * W + i % tw) * C] : 0;
+        }
+    }
+    // f(value, valid) on every pixel of the tile, called by whole waves
+    auto each = [&](auto&& f) {
+        if (in_regs) {
+#pragma unroll
+            for (int k = 0; k < NS_REG; ++k) {
+                if (k * SG_THREADS >= N) break;
+                f(reg[k], k * SG_THREADS + t < N);
+            }
+        } else {
+            for (int y = wave; y < th; y += SG_WAVES)
+                for (int xb = 0; xb < tw; xb += 64) {
+                    const bool in = xb + lane < tw;
+                    f(in ? (int)img[((size_t)y * W + xb + lane) * C] : 0, in);
+                }
+        }
+    };
+    // the value of `rank` among |x - centre| (centre < 0: among x itself)
+    auto select = [&](int centre) {
+        auto key = [&](int v) { return centre < 0 ? v : abs(v - centre); };
+        int hi = 0, r = rank;
+        if (sizeof(PIX) > 1) {
+            bins[t] = 0u;
+            __syncthreads();
+            each([&](int v, bool ok) { hist_add(bins, key(v) >> 8, ok); });
+            __syncthreads();
+            ns_find(bins, r, sel, wsum);
+            hi = sel[0]; r = sel[1];
+            __syncthreads();                            // sel is read before the next ns_find writes it
+        }
+        bins[t] = 0u;
+        __syncthreads();
+        each([&](int v, bool ok) {
+            const int q = key(v);
+            hist_add(bins, q & 255, ok && (q >> 8) == hi);
+        });
+        __syncthreads();
+        ns_find(bins, r, sel, wsum);
+        const int lo = sel[0];
+        __syncthreads();
+        return (hi << 8) | lo;
+    };
+    const int med = select(-1);
+    const int dev = select(med);
+    if (t == 0) {
+        const size_t node = ((size_t)b * 2 * my + blockIdx.y) * mx + blockIdx.x;
+        mesh[node] = 256 * med;
+        mesh[node + (size_t)my * mx] = max((int)(((long long)dev * NS_MAD_Q16) >> 8), floor8);
+    }
+}
+
+// grid (ceil(my * mx / 256), 2, B): raw and out are [B][2][my][mx]
+__global__ __launch_bounds__(SG_THREADS) void ns_filter(const int* __restrict__ raw, int my, int mx, int* __restrict__ out)
+{
+    const int n = blockIdx.x * SG_THREADS + threadIdx.x;
+    if (n >= my * mx) return;
+    const int j = n / mx, i = n % mx;
+    const size_t base = ((size_t)blockIdx.z * 2 + blockIdx.y) * my * mx;
+    int v[9];
+#pragma unroll
+    for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+        for (int dx = -1; dx <= 1; ++dx)
+            v[(dy + 1) * 3 + dx + 1] = raw[base + (size_t)min(max(j + dy, 0), my - 1) * mx + min(max(i + dx, 0), mx - 1)];
+    // the fifth of nine: Paeth's network of 19 exchanges
+#define NS_SORT2(a, b) { const int lo_ = min(v[a], v[b]), hi_ = max(v[a], v[b]); v[a] = lo_; v[b] = hi_; }
+    NS_SORT2(1, 2) NS_SORT2(4, 5) NS_SORT2(7, 8) NS_SORT2(0, 1) NS_SORT2(3, 4) NS_SORT2(6, 7) NS_SORT2(1, 2) NS_SORT2(4, 5)
+    NS_SORT2(7, 8) NS_SORT2(0, 3) NS_SORT2(5, 8) NS_SORT2(4, 7) NS_SORT2(3, 6) NS_SORT2(1, 4) NS_SORT2(2, 5) NS_SORT2(4, 7)
+    NS_SORT2(4, 2) NS_SORT2(6, 4) NS_SORT2(4, 2)
+#undef NS_SORT2
+    out[base + n] = v[4];
+}
+
+// One axis of the interpolation at pixel p: the first of the two nodes, the second's offset (0 with a single node), w0, w1.
+struct NsAxis {
+    int i0, step, w0, w1;
+};
+__device__ inline NsAxis ns_axis(int p, int n, int m, int shift)
+{
+    if (m == 1) return NsAxis{0, 0, 1, 0};
+    const int T = 1 << shift;
+    const int i0 = min(max((2 * p - T + 1) >> (shift + 1), 0), m - 2);      // arithmetic shift: -1 left of the first centre
+    const int c0 = 2 * i0 * T + T - 1;
+    const int c1 = i0 + 1 == m - 1 ? (m - 1) * T + n - 1 : c0 + 2 * T;       // the last tile runs to n
+    const int D = c1 - c0, w1 = min(max(2 * p - c0, 0), D);
+    return NsAxis{i0, 1, D - w1, w1};
+}
+
+// grid (nchunks, B); mesh: the filtered [B][2][my][mx]; weak8 < 0: a 0 / 1 plane, else levels 0 / 1 / 2
+template <typename PIX>
+__global__ __launch_bounds__(SG_THREADS) void ns_cut(const PIX* __restrict__ image, int C, int ch, int H, int W, int shift, int my, int mx,
+                                                     const int* __restrict__ mesh, int k8, int weak8, unsigned char* __restrict__ out)
+{
+    const int b = blockIdx.y, HW = H * W;
+    const PIX* img = image + (size_t)b * HW * C + ch;
+    const int* mB = mesh + (size_t)b * 2 * my * mx;
+    const int* mS = mB + (size_t)my * mx;
+    unsigned char* o = out + (size_t)b * HW;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = blockIdx.x * SG_CHUNK + k * SG_THREADS + threadIdx.x;
+        if (i >= HW) continue;
+        const NsAxis ay = ns_axis(i / W, H, my, shift), ax = ns_axis(i % W, W, mx, shift);
+        const int n00 = ay.i0 * mx + ax.i0, n01 = n00 + ax.step, n10 = n00 + ay.step * mx, n11 = n10 + ax.step;
+        const long long w00 = ay.w0 * ax.w0, w01 = ay.w0 * ax.w1, w10 = ay.w1 * ax.w0, w11 = ay.w1 * ax.w1;     // each below 2^20
+        const long long NB = w00 * mB[n00] + w01 * mB[n01] + w10 * mB[n10] + w11 * mB[n11];
+        const long long NS = w00 * mS[n00] + w01 * mS[n01] + w10 * mS[n10] + w11 * mS[n11];
+        const long long D = (long long)(ay.w0 + ay.w1) * (ax.w0 + ax.w1);
+        const long long lhs = 256 * (256 * (long long)img[(size_t)i * C] * D - NB);
+        const int strong = lhs > k8 * NS ? 1 : 0;
+        o[i] = (unsigned char)(weak8 < 0 ? strong : strong + (lhs > weak8 * NS ? 1 : 0));
+    }
+}
+
 // ---- host state ---------------------------------------------------------------------------------------------------------------
 // The device times of one family of entry points: up to five events on the handle's stream, created on first use, and the
 // spans between neighbours in milliseconds.  A new call records over the events of an earlier one whichever entry point it
@@ -1536,10 +1713,11 @@ struct SegmentState {
     DevBuf bg_a, bg_b;                                  // cs_segment_background only: two planes
     DevBuf lt_sum;                                      // cs_segment_local only: row sums
     DevBuf sm_t;                                        // cs_segment_smooth only: row pass
+    DevBuf ns_mesh;                                     // cs_segment_noise only: the mesh before and after its filter
     // img, med and stage serve every stage: each use is ordered on the handle's one stream, a call that uploads or stages
     // synchronises before it returns, a median plane is consumed inside the call that made it, and DevBuf::ensure frees with
     // hipFree, which waits for the device.
-    StageClock clk_thr, clk_sp, clk_si, clk_bg, clk_lt, clk_cl, clk_sm, clk_hy;
+    StageClock clk_thr, clk_sp, clk_si, clk_bg, clk_lt, clk_cl, clk_sm, clk_hy, clk_ns;
     int sp_recon_reads = 0, sp_flood_reads = 0;         // control-word reads (one host synchronisation each) of the last split of either kind
 };
 
@@ -2372,4 +2550,82 @@ int cs_segment_smooth(cs_preproc* p, const void* image, int pixel_type, int32_t 
 int cs_segment_smooth_last_timing(const cs_preproc* p, double* median_ms, double* smooth_ms)
 {
     return clock_read(p, &SegmentState::clk_sm, {median_ms, smooth_ms});
+}
+
+int cs_segment_noise(cs_preproc* p, const void* image, int pixel_type, int32_t channels, int32_t channel, int32_t batch, int32_t height,
+                     int32_t width, int in_kind, const cs_noise_params* noise, uint8_t* out, int out_kind, int32_t* mesh)
+{
+    if (!noise) return fail(CS_ERR_INVALID, "NULL argument");
+    int rc;
+    if ((rc = image_check(image, out, pixel_type, channels, channel, batch, height, width, in_kind, out_kind, "out_kind"))) return rc;
+    const int T = noise->tile, k8 = noise->k8, weak8 = noise->weak_k8, floor8 = noise->floor8;
+    if (T < 16 || T > 256 || (T & (T - 1)) != 0) return fail(CS_ERR_INVALID, "noise tile %d: a power of two in 16..256", T);
+    if (k8 < 1 || k8 > 16383) return fail(CS_ERR_INVALID, "noise k8 %d outside 1..16383", k8);
+    if (weak8 != -1 && (weak8 < 1 || weak8 > k8)) return fail(CS_ERR_INVALID, "weak k8 %d: -1 (no weak rule) or 1..k8 = %d", weak8, k8);
+    if (floor8 < 0 || floor8 > 4095 * 256) return fail(CS_ERR_INVALID, "noise floor8 %d outside 0..%d", floor8, 4095 * 256);
+    if (weak8 != -1 && noise->connectivity != 1 && noise->connectivity != 2)
+        return fail(CS_ERR_INVALID, "connectivity %d: 1 or 2", (int)noise->connectivity);
+    if (noise->reserved[0] != 0 || noise->reserved[1] != 0 || noise->reserved[2] != 0)
+        return fail(CS_ERR_INVALID, "cs_noise_params.reserved must be 0");
+    if ((rc = image_limits(batch, height, width)) || (rc = handle_check(p))) return rc;
+    const bool link = weak8 != -1;
+    const size_t esz = pixel_type == CS_PIX_U8 ? 1 : 2, npx = (size_t)batch * height * width;
+    // with a weak rule the workspace of a labelling call whose labels go to the host: its 4 bytes per pixel hold the flags
+    SegmentCall c;
+    PlaneCall pc;
+    if (link) {
+        if ((rc = segment_begin(p, image, pixel_type, channels, batch, height, width, in_kind, nullptr, CS_MEM_HOST, c)) ||
+            (rc = plane_begin(p, nullptr, 0, in_kind, out, npx, out_kind, pc)))
+            return rc;
+        pc.d_img = c.d_img;
+    } else if ((rc = plane_begin(p, image, npx * channels * esz, in_kind, out, npx, out_kind, pc)))
+        return rc;
+    SegmentState& S = *pc.S;
+    hipStream_t st = pc.st;
+    const int H = height, W = width;
+    int shift = 4;
+    while ((1 << shift) < T) ++shift;
+    const int my = std::max(1, H >> shift), mx = std::max(1, W >> shift);
+    const size_t nodes = (size_t)batch * 2 * my * mx;
+    if ((rc = S.ns_mesh.ensure(2 * nodes * sizeof(int)))) return rc;
+    int *raw = S.ns_mesh.as<int>(), *filt = raw + nodes;
+    unsigned char* level = link ? S.mask.as<unsigned char>() : (unsigned char*)pc.d_out;
+    const dim3 pgrid((unsigned)((H * W + SG_CHUNK - 1) / SG_CHUNK), (unsigned)batch);
+    if ((rc = S.clk_ns.record(0, st))) return rc;
+    by_pixel(pixel_type, [&](auto pix) {
+        using PIX = decltype(pix);
+        hipLaunchKernelGGL(ns_stats<PIX>, dim3((unsigned)mx, (unsigned)my, (unsigned)batch), dim3(SG_THREADS), 0, st, (const PIX*)pc.d_img,
+                           (int)channels, (int)channel, H, W, shift, floor8, raw);
+    });
+    hipLaunchKernelGGL(ns_filter, dim3((unsigned)((my * mx + SG_THREADS - 1) / SG_THREADS), 2u, (unsigned)batch), dim3(SG_THREADS), 0, st,
+                       (const int*)raw, my, mx, filt);
+    HIPCHK(hipGetLastError());
+    if ((rc = S.clk_ns.record(1, st))) return rc;
+    by_pixel(pixel_type, [&](auto pix) {
+        using PIX = decltype(pix);
+        hipLaunchKernelGGL(ns_cut<PIX>, pgrid, dim3(SG_THREADS), 0, st, (const PIX*)pc.d_img, (int)channels, (int)channel, H, W, shift, my, mx,
+                           (const int*)filt, k8, weak8, level);
+    });
+    HIPCHK(hipGetLastError());
+    if ((rc = S.clk_ns.record(2, st))) return rc;
+    if (link) {
+        HIPCHK(hipMemsetAsync(c.d_lab, 0, c.npx * sizeof(int), st));
+        HIPCHK(label_mask(level, batch, H, W, 0, noise->connectivity == 2, S.parent.as<int>(), nullptr, c.nchunks, st));
+        hipLaunchKernelGGL(hy_mark, c.pgrid, dim3(SG_THREADS), 0, st, c.HW, (const unsigned char*)level, (const int*)S.parent.as<int>(), c.d_lab);
+        hipLaunchKernelGGL(hy_keep, c.pgrid, dim3(SG_THREADS), 0, st, c.HW, (const int*)S.parent.as<int>(), (const int*)c.d_lab,
+                           (unsigned char*)pc.d_out);
+        HIPCHK(hipGetLastError());
+    }
+    if ((rc = S.clk_ns.record(3, st, link))) return rc;
+    if (mesh) HIPCHK(hipMemcpyAsync(mesh, filt, nodes * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (mesh && pc.on_device) {
+        HIPCHK(hipStreamSynchronize(st));                 // the one host synchronisation: the mesh is filled
+        return S.clk_ns.finish();
+    }
+    return plane_end(pc, S.clk_ns, nullptr, batch);
+}
+
+int cs_segment_noise_last_timing(const cs_preproc* p, double* mesh_ms, double* cut_ms, double* link_ms)
+{
+    return clock_read(p, &SegmentState::clk_ns, {mesh_ms, cut_ms, link_ms});
 }

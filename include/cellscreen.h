@@ -29,8 +29,8 @@
  *   cs_segment_threshold / cs_segment_split / cs_segment_split_intensity
  *        the library's own classical segmenter (no reference counterpart, and no StarDist): Otsu or
  *        fixed threshold, optional hole filling, connected-component labels for the extraction above
- *        (cs_segment_smooth, cs_segment_background, cs_segment_local, cs_segment_hysteresis, cs_segment_clean: optional stages
- *        before the labels)
+ *        (cs_segment_smooth, cs_segment_background, cs_segment_local, cs_segment_hysteresis, cs_segment_noise,
+ *        cs_segment_clean: optional stages before the labels)
  *   cs_fit_scaler / cs_fit_pca_moments / cs_fit_pca_subspace / cs_fit_project / cs_fit_ocsvm
  *        RobustScaler / PCA / OneClassSVM fits of create_anomaly_detector
  *                                                 CAE_improved_modeltrain.py:408-427
@@ -647,6 +647,59 @@ int cs_segment_hysteresis(cs_preproc *p, const void *image, int pixel_type, int3
  * comparison), then the weak components, the flags and the kept plane.  Waits for that call's plane if it was left on the
  * device. */
 int cs_segment_hysteresis_last_timing(const cs_preproc *p, double *level_ms, double *link_ms);
+
+/* Noise-adaptive threshold, in the place of the plain cut, of cs_segment_local or of cs_segment_hysteresis: foreground is
+ * "k sigmas above the local background", both estimated from the image itself on a coarse mesh of tiles, as SExtractor and
+ * photutils' Background2D cut.  One dimensionless number serves every exposure, camera and bit depth, a sloping background needs
+ * no top-hat, and a second k gives the hysteresis pair.  Integers only, no tolerance anywhere, each image on its own; x is the
+ * channel:
+ *   mesh      tile side T = tile.  Along an axis of n pixels there are m = max(1, n / T) tiles; tile i covers [i T, (i + 1) T),
+ *             the last one runs to n (at most 2T - 1 wide).  An image smaller than T is one tile.
+ *   tile      over the tile's N pixels: med = the value of rank (N - 1) / 2 in sorted order (the lower median), dev = the value
+ *             of the same rank among |x - med|; B8 = 256 med, S8 = max((dev * 97164) >> 8, floor8): 97164 = 1.4826 * 65536, so
+ *             S8 is the Gaussian-equivalent sigma in 1/256 counts; floor8 guards flat or clipped backgrounds, where dev = 0.
+ *   filter    B8 and S8 are each replaced by the median (fifth of nine) of their 3 x 3 mesh neighbourhood, the mesh replicated
+ *             at its edges: a tile that a cell fills is rejected.
+ *   maps      bilinear between tile centres, constant outside the outer centres, without a division: along an axis node i sits
+ *             at the doubled coordinate C2_i = start_i + end_i - 1 (end exclusive); for pixel p take i with C2_i <= 2p < C2_(i+1),
+ *             clamped to the first or last pair of nodes; D = C2_(i+1) - C2_i, w1 = clamp(2p - C2_i, 0, D), w0 = D - w1; an axis
+ *             with a single node has D = 1, w0 = 1.  N_B(y, x) = sum over the four nodes of wy * wx * B8, N_S the same sum of S8,
+ *             D = Dy * Dx.
+ *   rule      a pixel v is foreground iff 256 * (256 * v * D - N_B) > k8 * N_S (64-bit: D < 2^20, N_S < 2^45, k8 < 2^14); an
+ *             exact tie is background, as in cs_segment_local.
+ *   weak      weak_k8 != -1: the same inequality with weak_k8 (1..k8) is the weak rule, and the result keeps the components of
+ *             the weak mask, under `connectivity`, that hold a strong pixel, as cs_segment_hysteresis does with its two rules.
+ * image, pixel_type, channels, channel, batch, height, width, in_kind: as cs_segment_threshold; the channel is read in place.
+ *      The outputs of cs_segment_smooth and cs_segment_background are valid images (channels = 1, channel = 0).
+ * out: [batch][height][width] uint8, 0 / 1, out_kind.  Left on the device it is cs_segment_threshold's, cs_segment_split's or
+ *      cs_segment_clean's `image` with pixel_type CS_PIX_U8, channels = 1, channel = 0, CS_THRESH_FIXED and threshold = 0, on
+ *      the same handle (the same stream: no ordering needed); hole filling, cleanup, labels and the split follow unchanged.
+ * mesh: out, host [batch][2][my][mx] int32, or NULL: the mesh after the filter, B8 then S8 (my, mx: the tiles along height, width).
+ * Workspace on the device: the mesh, two int32 per tile before the filter and two after; with a weak rule cs_segment_threshold's
+ * with labels that go to the host (9 bytes per pixel; the 4 bytes of the labels hold one flag per root); 1 byte per pixel more
+ * for an `out` on the host, and the image itself when it comes from the host.
+ * Host synchronisations: none when image and out are both on the device and mesh is NULL (the plane is complete in stream
+ * order; the times are read when cs_segment_noise_last_timing asks for them, which waits for the plane), else one.
+ * Bad arguments (NULL noise among them, tile not a power of two in 16..256, k8 outside 1..16383, weak_k8 neither -1 nor in
+ * 1..k8, floor8 outside 0..4095 * 256, with a weak rule connectivity not 1 or 2, reserved not 0): CS_ERR_INVALID before any
+ * device work; sides above 4096, batches above 65535: CS_ERR_UNSUPPORTED; without a gfx950 device (p == NULL):
+ * CS_ERR_NO_DEVICE. */
+typedef struct cs_noise_params {
+    int32_t tile;                     /* 16, 32, 64, 128 or 256: the side of a mesh tile */
+    int32_t k8;                       /* 1..16383: k in 1/256, int(k * 256 + 0.5) */
+    int32_t weak_k8;                  /* -1: no weak rule, else 1..k8 */
+    int32_t floor8;                   /* 0..4095 * 256: the least sigma in 1/256 counts */
+    int32_t connectivity;             /* 1 or 2; read with a weak rule */
+    int32_t reserved[3];              /* 0 */
+} cs_noise_params;
+int cs_segment_noise(cs_preproc *p, const void *image, int pixel_type, int32_t channels, int32_t channel,
+                     int32_t batch, int32_t height, int32_t width, int in_kind,
+                     const cs_noise_params *noise /* not NULL */, uint8_t *out, int out_kind,
+                     int32_t *mesh /* may be NULL */);
+/* Device time of the last cs_segment_noise: the tile statistics and the mesh filter, the cut (or the level plane), and with a
+ * weak rule the weak components, the flags and the kept plane (0 without it).  Waits for that call's plane if it was left on
+ * the device. */
+int cs_segment_noise_last_timing(const cs_preproc *p, double *mesh_ms, double *cut_ms, double *link_ms);
 
 /* Gaussian smoothing of the segmentation channel, before everything else: for noisy fields, where the threshold shatters a
  * faint cell into fragments that no cleanup of the mask can put together again.  Integers only, each image on its own:

@@ -65,11 +65,17 @@ heights are compared with the host restatement first (and the distance split's l
 the same run, split_by="distance" (--split's mode) and split_by="intensity": images/s of segment_batch and of segment + extract,
 the regions found, the stage times and the host synchronisations per call.  No time is a pass condition.
 
+--noise [--noise-k K] [--tile T] measures the noise-adaptive threshold (cs_segment_noise, ThresholdSegmenter(threshold="noise",
+noise_k=K, noise_tile=T); 5 and 64 by default) in its place and writes profiles/segment_noise_bench.json.  On the scene --local
+uses, one image's mesh, mask and labels are compared with the host restatement (tests/noise_reference.py) first; then, in the
+same run, three segmenters: the noise rule, the local rule of radius 25 (the figure to set it beside), and the top-hat of radius
+51 with Otsu, with the stage times of each in milliseconds per image.  No time is a pass condition.
+
 Usage: python tools/bench_segment.py [--images 32] [--side 2048] [--cells 1000] [--reps 10] [--warmup 2] [--host-images 4]
                                      [--split [--split-cells 3000] [--split-h 3]] [--background R [--denoise]]
                                      [--local R [--delta D] [--denoise]] [--clean [--open R] [--min-area A] [--delta D]] [--smooth SIGMA [--denoise]]
                                      [--split-intensity [--split-depth 16] [--split-contrast 0]]
-                                     [--hysteresis [--weak-delta 40] [--strong-delta 200]]"""
+                                     [--hysteresis [--weak-delta 40] [--strong-delta 200]] [--noise [--noise-k 5] [--tile 64]]"""
 import argparse
 import json
 import os
@@ -365,6 +371,75 @@ def local_leg(a):
     res["local_over_otsu_wall_time"] = round(med(walls) / med(plain_walls), 3)
     line = json.dumps(res)
     out = a.out if a.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "segment_local_bench.json")
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            f.write(line + "\n")
+    print(line)
+
+
+NOISE_LOCAL_RADIUS = 25                                 # the local rule that --noise is set beside
+
+
+def noise_leg(a):
+    import torch
+    import noise_reference as NR
+    from build import source_hash
+    from cellscreen import segment as S
+    from cellscreen import synth
+
+    fill = not a.no_fill_holes
+    dev = torch.device("cuda", 0)
+    med = lambda v: float(np.median(v))
+    imgs, _ = synth.label_images(2024, a.images, hw=(a.side, a.side), n_cells=a.cells)
+    ti = torch.from_numpy(imgs.view(np.int16)).to(dev)
+    torch.cuda.synchronize()
+
+    def timed(seg):
+        walls, stages = [], []
+        for k in range(a.warmup + a.reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = seg.segment_batch(ti)
+            torch.cuda.synchronize()
+            if k >= a.warmup:
+                walls.append(time.perf_counter() - t0)
+                stages.append(seg.last_timing())
+        return out, walls, stages
+
+    def row(out, walls, stages):
+        per_image = {k: round(med([t[k] for t in stages]) / a.images, 5) for k in stages[0]}
+        return dict(components=int(out[1].sum()), images_per_s=round(a.images / med(walls), 2),
+                    wall_ms_per_image=[round(f(walls) * 1e3 / a.images, 4) for f in (med, min, max)], stage_ms_per_image=per_image)
+
+    res = {"tool": "bench_segment --noise", "source_hash": source_hash(), "images": a.images, "side": a.side,
+           "connectivity": a.connectivity, "fill_holes": fill, "noise_k": a.noise_k, "noise_tile": a.tile, "reps": a.reps,
+           "warmup": a.warmup}
+    seg = S.ThresholdSegmenter(0, "noise", a.connectivity, fill, noise_k=a.noise_k, noise_tile=a.tile)
+    # outputs first: one image's mesh, mask and labels against the host restatement
+    one = ti[:1].contiguous()
+    chan = np.ascontiguousarray(imgs[0, ..., 2])
+    k8 = NR.k8_of(a.noise_k)
+    assert np.array_equal(seg.noise_mesh_batch(one)[0], NR.mesh(chan, a.tile, 256)), "mesh differs from the restatement"
+    assert np.array_equal(seg.noise_mask_batch(one)[0].cpu().numpy(), NR.noise_mask(chan, a.tile, k8)), "mask differs from the restatement"
+    labels, n, thr = seg.segment_batch(one)
+    hl, hn, _ = NR.segment(chan, a.tile, k8, None, 256, a.connectivity, fill)
+    assert hn == int(n[0]) and int(thr[0]) == -1 and np.array_equal(labels[0].cpu().numpy(), hl), "labels differ from the restatement"
+    res["noise"] = dict(row(*timed(seg)), outputs_equal=True)
+    seg.close()
+    local = S.ThresholdSegmenter(0, "local", a.connectivity, fill, local_radius=NOISE_LOCAL_RADIUS)
+    res["local"] = dict(row(*timed(local)), radius=NOISE_LOCAL_RADIUS)
+    local.close()
+    tophat = S.ThresholdSegmenter(0, "otsu", a.connectivity, fill, background_radius=TOPHAT_RADIUS)
+    res["background"] = dict(row(*timed(tophat)), radius=TOPHAT_RADIUS)
+    tophat.close()
+    stage = lambda r, keys: sum(r["stage_ms_per_image"][k] for k in keys)
+    noise_ms, local_ms = stage(res["noise"], ("noise_mesh_ms", "noise_cut_ms", "noise_link_ms")), stage(res["local"], ("local_median_ms", "local_ms"))
+    res["noise_stage_ms_per_image"], res["local_stage_ms_per_image"] = round(noise_ms, 5), round(local_ms, 5)
+    res["noise_over_local_stage_time"] = round(noise_ms / local_ms, 3)
+    res["noise_over_local_wall_time"] = round(res["noise"]["wall_ms_per_image"][0] / res["local"]["wall_ms_per_image"][0], 3)
+    line = json.dumps(res)
+    out = a.out if a.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "segment_noise_bench.json")
     if out:
         os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
         with open(out, "w") as f:
@@ -683,7 +758,18 @@ def main():
                     help="measure the hysteresis threshold on --clean's speckled scene (profiles/segment_hysteresis_bench.json)")
     ap.add_argument("--weak-delta", type=int, default=40, metavar="W", help="with --hysteresis: the weak delta")
     ap.add_argument("--strong-delta", type=int, default=200, metavar="D", help="with --hysteresis: the strong delta")
+    ap.add_argument("--noise", action="store_true",
+                    help="measure the noise-adaptive threshold beside the local rule and the top-hat (profiles/segment_noise_bench.json)")
+    ap.add_argument("--noise-k", type=float, default=5.0, metavar="K", help="with --noise: sigmas above the local background")
+    ap.add_argument("--tile", type=int, default=64, metavar="T", help="with --noise: the mesh tile's side")
     a = ap.parse_args()
+    if a.noise:
+        if (a.split or a.split_intensity or a.background is not None or a.local is not None or a.clean or a.delta or a.hysteresis
+                or a.smooth is not None or a.denoise or a.open is not None or a.min_area is not None):
+            ap.error("--noise is measured on its own")
+        return noise_leg(a)
+    if a.noise_k != 5.0 or a.tile != 64:
+        ap.error("--noise-k and --tile need --noise")
     if a.hysteresis:
         if (a.split or a.split_intensity or a.background is not None or a.local is not None or a.clean or a.delta
                 or a.smooth is not None or a.denoise or a.open is not None or a.min_area is not None):
