@@ -136,6 +136,10 @@ class CSNoiseParams(C.Structure):
                 ("reserved", C.c_int32 * 3)]
 
 
+class CSMatchParams(C.Structure):
+    _fields_ = [("table_log2", C.c_int32), ("reserved", C.c_int32)]
+
+
 SMOOTH_MAX_RADIUS = 64                  # cs_smooth_params.weights holds 65 taps
 
 
@@ -209,6 +213,9 @@ SIGNATURES = {
     "cs_segment_noise_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "cs_segment_smooth": (_I, [_P, _P, _I, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _I, C.POINTER(CSSmoothParams), _P, _I]),
     "cs_segment_smooth_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "cs_label_match": (_I, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _I, C.c_int32, C.c_int32, C.POINTER(CSMatchParams), _P, _P, _I, _P]),
+    "cs_label_match_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "cs_label_match_last_table": (_I, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "cs_fit_create": (_I, [_I, C.POINTER(_P)]),
     "cs_fit_free": (None, [_P]),
     "cs_fit_wait_stream": (_I, [_P, _P]),

@@ -95,6 +95,7 @@ correction, the threshold, the cleanup, the labels and the split see the smoothe
     seg = ThresholdSegmenter(weak_threshold=0.2)                       # Otsu's threshold for the cores, a fifth of it for the rims
     seg = ThresholdSegmenter(threshold="noise")                        # 5 sigmas above the local background, no number in counts
     seg = ThresholdSegmenter(threshold="noise", noise_k=6, weak_k=3)   # ... cores at 6 sigmas, rims down to 3, no speckle
+    stats, labels, n_labels = seg.score_batch(images, truth)           # how good any of these is against true labels: score.py
 
     screening = ProductionMutantScreening(model_dir, cell_extractor=threshold_cell_extractor())
 """
@@ -110,6 +111,7 @@ from . import _lib as L
 from .extract import (IMAGE_NO_CELLS, IMAGE_OK, MAX_SIDE, CellExtractor, _is_tensor, qc_params, read_image, region_stats,
                       split_channels)
 from .preprocess import OUT_SIDE, PIX_U8, PIX_U16, Preprocessor, check_out_hw
+from .score import THRESHOLDS as SCORE_THRESHOLDS, LabelMatcher, check_thresholds
 
 MAX_BATCH = 65535
 
@@ -483,6 +485,8 @@ class ThresholdSegmenter:
         self.device_id = device_id
         self._ext = extractor
         self._pre: Optional[Preprocessor] = None        # own handle: created by the first call, after its argument checks
+        self._matcher = LabelMatcher(device_id, extractor=self)     # score_batch: cs_label_match on this segmenter's handle
+        self._scored = False                            # the last call was a score_batch: last_timing reports the match
 
     @property
     def _handle(self):
@@ -732,6 +736,7 @@ class ThresholdSegmenter:
         src = (images, *self._check(images, channel))
         if return_distance and self._split is None:
             raise ValueError("return_distance needs split_touching=True: the plain segmenter computes no distances")
+        self._scored = False
         # every stage takes the plane of the one before in the channel's place; threshold, label and split what they leave
         (images, B, H, W, Cn, channel, ptype, on_dev), params, reported, guide = self._front(src, "clean", report=True)
         n_labels = np.zeros(B, np.int32)
@@ -774,6 +779,21 @@ class ThresholdSegmenter:
             thresholds[:] = -1
         return (labels, n_labels, thresholds, dist) if return_distance else (labels, n_labels, thresholds)
 
+    def score_batch(self, images, truth, channel: Optional[int] = None, thresholds=SCORE_THRESHOLDS, max_truth: Optional[int] = None):
+        """segment_batch, then the labels scored where they are against `truth` (int32 [B,H,W], numpy or a CUDA tensor, 0 =
+        background) on the same handle: cellscreen/score.py.  Returns (stats, labels, n_labels): LabelMatch.stats(thresholds) of
+        the batch, and segment_batch's labels and counts.  max_truth: the largest label `truth` may hold (None: its maximum).
+        The thresholds, `truth` and the images are checked before the device is touched."""
+        check_thresholds(thresholds)
+        B, H, W = self._check(images, channel)[:3]
+        self._matcher._check_one("truth", truth)
+        if tuple(truth.shape) != (B, H, W):
+            raise ValueError(f"truth {tuple(truth.shape)} and images {tuple(images.shape)} differ in batch or height x width")
+        labels, n_labels, _ = self.segment_batch(images, channel)
+        m = self._matcher.match_batch(labels, truth, max_pred=max(1, int(n_labels.max())), max_truth=max_truth)
+        self._scored = True
+        return m.stats(thresholds), labels, n_labels
+
     def last_timing(self):
         """Device milliseconds of the last call's stages; with split_touching the stages of cs_segment_split (with
         split_by="intensity" those of cs_segment_split_intensity: height_ms where the other has distance_ms); with
@@ -785,7 +805,8 @@ class ThresholdSegmenter:
         and hysteresis_link_ms (weak components, flags, the kept plane) of the last hysteresis stage, which then stands in the
         local rule's place: local_ms is not reported; with threshold="noise" noise_mesh_ms (tile statistics and the mesh filter),
         noise_cut_ms (the cut or the level plane) and noise_link_ms (with weak_k: weak components, flags, the kept plane; else 0)
-        of the last noise stage."""
+        of the last noise stage; after score_batch also match_count_ms (clearing and cs_label_match's one pass over the two label
+        planes) and match_reduce_ms (its reduction into the tables)."""
         extra = self._smooth_timing() if self._smooth is not None else {}
         if self._background is not None:
             extra.update(self._background_timing())
@@ -797,6 +818,8 @@ class ThresholdSegmenter:
             extra.update(self._local_timing())
         if self._clean is not None:
             extra.update(self._clean_timing())
+        if self._scored:
+            extra.update(self._matcher.last_timing())
         if self._split is None:
             return dict(zip(("threshold_ms", "label_ms"), self._times(self._lib.cs_segment_last_timing, 2)), **extra)
         if self._split_intensity is not None:

@@ -86,6 +86,8 @@ struct ExtractState;                            // extract.hip: the state betwee
 void extract_state_free(ExtractState* s);
 struct SegmentState;                            // segment.hip: the buffers of cs_segment_threshold
 void segment_state_free(SegmentState* s);
+struct MatchState;                              // match.hip: the buffers of cs_label_match
+void match_state_free(MatchState* s);
 
 int upload(DevBuf& d, const void* src, size_t bytes);
 int check_arch(const cs_cae_weights* w, int expect_convs, const char* what);
@@ -93,7 +95,8 @@ int require_gfx950(int device_id);
 
 }  // namespace cs
 
-// The preprocess handle (include/cellscreen.h); its extraction entry points live in extract.hip, its segmenter in segment.hip.
+// The preprocess handle (include/cellscreen.h); its extraction entry points live in extract.hip, its segmenter in segment.hip,
+// its label scoring in match.hip.
 struct cs_preproc {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -110,10 +113,12 @@ struct cs_preproc {
     int64_t last_pixels = 0;
     cs::ExtractState* ext = nullptr;    // created by the first cs_extract_measure
     cs::SegmentState* seg = nullptr;    // created by the first cs_segment_* call
+    cs::MatchState* match = nullptr;    // created by the first cs_label_match
     ~cs_preproc()
     {
         cs::extract_state_free(ext);
         cs::segment_state_free(seg);
+        cs::match_state_free(match);
         if (hdesc) (void)hipHostFree(hdesc);
     }
 };

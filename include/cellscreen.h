@@ -31,6 +31,9 @@
  *        fixed threshold, optional hole filling, connected-component labels for the extraction above
  *        (cs_segment_smooth, cs_segment_background, cs_segment_local, cs_segment_hysteresis, cs_segment_noise,
  *        cs_segment_clean: optional stages before the labels)
+ *   cs_label_match
+ *        scores a label image against ground truth: object matching by intersection over union, the
+ *        rule of StarDist's `matching` made unique (no reference counterpart)
  *   cs_fit_scaler / cs_fit_pca_moments / cs_fit_pca_subspace / cs_fit_project / cs_fit_ocsvm
  *        RobustScaler / PCA / OneClassSVM fits of create_anomaly_detector
  *                                                 CAE_improved_modeltrain.py:408-427
@@ -737,6 +740,43 @@ int cs_segment_smooth(cs_preproc *p, const void *image, int pixel_type, int32_t 
 /* Device time of the last cs_segment_smooth: the median (0 without it) and the two passes.  Waits for that call's plane if it
  * was left on the device. */
 int cs_segment_smooth_last_timing(const cs_preproc *p, double *median_ms, double *smooth_ms);
+
+/* ---- scoring label images against ground truth ------------------------------------------------ */
+/* Object matching by intersection over union between two label images per field, `pred` and `truth` (0 = background, every
+ * value > 0 that occurs is one object, connected or not).  The device makes the tables below; TP / FP / FN, precision, recall,
+ * F1 and panoptic quality at any IoU threshold in [0.5, 1] follow from them on the host in integers (cellscreen/score.py,
+ * DESIGN 3s).  With A the pixel count of an object and I(p, t) that of an intersection, per image:
+ *   area     A of the object
+ *   partner  the object of the other image with the largest I; ties go to the smaller label; 0 when it meets none
+ *   overlap  I with the partner
+ *   n_major  the number of objects of the other image that lie mostly inside this one: 2 * I > A_other
+ * A pair (p, t) matches at tq / 65536 when p and t are each other's partner, 2 * I > U and I * 65536 >= tq * U, where
+ * U = A_p + A_t - I: the strict 2 * I > U makes the candidate of an object unique, so no assignment problem is solved.
+ * pred, truth: [batch][height][width] int32, both in_kind.  Left on the device by cs_segment_* on this handle they are read in
+ *         stream order, as cs_extract_measure reads them.  height, width 1..4096, batch 1..65535 (above: CS_ERR_UNSUPPORTED).
+ * max_pred, max_truth: 1..2^20, batch * max at most 2^22 for each (above: CS_ERR_UNSUPPORTED).  A label that is negative or
+ *         above its max is CS_ERR_INVALID, detected on the device and reported by this call; the tables are then undefined and
+ *         the handle stays usable.
+ * pred_table, truth_table: out, [batch][max][4] int32 {area, partner, overlap, n_major}, row l - 1 for label l, both
+ *         table_kind; the row of a label that does not occur is all zeros.
+ * n_pairs: out, host [batch], or NULL: the number of distinct pairs (p > 0, t > 0) with I > 0.
+ * The pair counts live in an open-addressing table on the device, 12 bytes per slot.  params NULL or table_log2 0: its first
+ * capacity is the power of two >= 2 * batch * (max_pred + max_truth), at least 2^16; else 2^table_log2, 10..26.  A table that
+ * proves too small is doubled and the call runs again (cs_label_match_last_table counts the doublings); beyond 2^26 slots:
+ * CS_ERR_NOMEM.  Every result is a sum, a maximum or a count of integers: bit-identical run to run, and independent of the
+ * capacity and of the other images of the batch.  One host synchronisation per attempt.  Other bad arguments: CS_ERR_INVALID
+ * before any device work; without a gfx950 device (p == NULL): CS_ERR_NO_DEVICE. */
+typedef struct cs_match_params {
+    int32_t table_log2;               /* 0: automatic; else 10..26: the first capacity */
+    int32_t reserved;                 /* must be 0 */
+} cs_match_params;
+int cs_label_match(cs_preproc *p, const int32_t *pred, const int32_t *truth, int32_t batch, int32_t height, int32_t width,
+                   int in_kind, int32_t max_pred, int32_t max_truth, const cs_match_params *params, int32_t *pred_table,
+                   int32_t *truth_table, int table_kind, int64_t *n_pairs);
+/* Device time of the last cs_label_match (its last attempt): clearing and the counting pass, and the reduction into the tables. */
+int cs_label_match_last_timing(const cs_preproc *p, double *count_ms, double *reduce_ms);
+/* The capacity (as log2) the last cs_label_match ended with, and how many times it doubled the table. */
+int cs_label_match_last_table(const cs_preproc *p, int32_t *table_log2, int32_t *grows);
 
 /* ---- detector fitting (create_anomaly_detector, CAE_improved_modeltrain.py:394-446) -------- */
 /* The fit of what cs_screen's tail evaluates, for the training set's encoder features

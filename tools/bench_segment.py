@@ -71,11 +71,17 @@ uses, one image's mesh, mask and labels are compared with the host restatement (
 same run, three segmenters: the noise rule, the local rule of radius 25 (the figure to set it beside), and the top-hat of radius
 51 with Otsu, with the stage times of each in milliseconds per image.  No time is a pass condition.
 
+--score measures the label scoring (cs_label_match, cellscreen/score.py) and writes profiles/segment_score_bench.json.  On the
+scene --local uses (whose painted labels are the truth), one image's tables are compared with the host restatement
+(tests/match_reference.py) first; then, in the same run: images/s of segment_batch, of LabelMatcher.match_batch on its labels
+(with the two device stage times per image and the pair table's capacity), of score_batch (segment + match + the statistics),
+and of the numpy restatement on --host-images images.  No time is a pass condition.
+
 Usage: python tools/bench_segment.py [--images 32] [--side 2048] [--cells 1000] [--reps 10] [--warmup 2] [--host-images 4]
                                      [--split [--split-cells 3000] [--split-h 3]] [--background R [--denoise]]
                                      [--local R [--delta D] [--denoise]] [--clean [--open R] [--min-area A] [--delta D]] [--smooth SIGMA [--denoise]]
                                      [--split-intensity [--split-depth 16] [--split-contrast 0]]
-                                     [--hysteresis [--weak-delta 40] [--strong-delta 200]] [--noise [--noise-k 5] [--tile 64]]"""
+                                     [--hysteresis [--weak-delta 40] [--strong-delta 200]] [--noise [--noise-k 5] [--tile 64]] [--score]"""
 import argparse
 import json
 import os
@@ -725,6 +731,80 @@ DEFAULT_OUT = os.path.join(ROOT, "profiles", "segment_bench.json")
 TOPHAT_RADIUS = 51                                      # the top-hat that --local is set beside: --background 51's figure
 
 
+def score_leg(a):
+    import torch
+    import match_reference as MR
+    from build import source_hash
+    from cellscreen import score as SC
+    from cellscreen import segment as S
+    from cellscreen import synth
+
+    fill = not a.no_fill_holes
+    dev = torch.device("cuda", 0)
+    med = lambda v: float(np.median(v))
+    imgs, labs = synth.label_images(2024, a.images, hw=(a.side, a.side), n_cells=a.cells)
+    ti = torch.from_numpy(imgs.view(np.int16)).to(dev)
+    tl = torch.from_numpy(labs).to(dev)
+    max_truth = int(labs.max())
+    torch.cuda.synchronize()
+    seg = S.ThresholdSegmenter(0, "otsu", a.connectivity, fill)
+    matcher = SC.LabelMatcher(0, extractor=seg)
+
+    def timed(fn, timing=None):
+        walls, stages = [], []
+        for k in range(a.warmup + a.reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = fn()
+            torch.cuda.synchronize()
+            if k >= a.warmup:
+                walls.append(time.perf_counter() - t0)
+                stages.append(timing() if timing else {})
+        return out, walls, stages
+
+    wall3 = lambda walls: [round(f(walls) * 1e3 / a.images, 4) for f in (med, min, max)]
+    per_image = lambda stages: {k: round(med([t[k] for t in stages]) / a.images, 5) for k in stages[0]}
+    (labels, n_labels, _), seg_walls, seg_stages = timed(lambda: seg.segment_batch(ti), seg.last_timing)
+    max_pred = max(1, int(n_labels.max()))
+    # outputs first: one image's tables against the host restatement
+    one = matcher.match_batch(labels[:1].contiguous(), tl[:1].contiguous(), max_pred=max_pred, max_truth=max_truth)
+    hp, ht, hn = MR.tables(labels[0].cpu().numpy(), labs[0], max_pred, max_truth)
+    assert np.array_equal(one.pred, hp) and np.array_equal(one.truth, ht) and np.array_equal(one.n_pairs, hn), "tables differ from the restatement"
+    m, match_walls, match_stages = timed(lambda: matcher.match_batch(labels, tl, max_pred=max_pred, max_truth=max_truth), matcher.last_timing)
+    log2, grows = matcher.last_table()
+    (stats, _, _), score_walls, _ = timed(lambda: seg.score_batch(ti, tl, max_truth=max_truth))
+    nh = max(1, min(a.host_images, a.images))
+    host_labels = labels[:nh].cpu().numpy()
+    host_walls = []
+    for _ in range(2):
+        t0 = time.perf_counter()
+        MR.tables(host_labels, labs[:nh], max_pred, max_truth)
+        host_walls.append(time.perf_counter() - t0)
+    seg.close()
+    tot = stats["total"]
+    res = {"tool": "bench_segment --score", "source_hash": source_hash(), "images": a.images, "side": a.side, "cells": a.cells,
+           "connectivity": a.connectivity, "fill_holes": fill, "reps": a.reps, "warmup": a.warmup, "outputs_equal": True,
+           "max_pred": max_pred, "max_truth": max_truth, "pairs": int(m.n_pairs.sum()), "table_log2": log2, "grows": grows,
+           "segment": {"images_per_s": round(a.images / med(seg_walls), 2), "wall_ms_per_image": wall3(seg_walls),
+                       "stage_ms_per_image": per_image(seg_stages)},
+           "match": {"images_per_s": round(a.images / med(match_walls), 2), "wall_ms_per_image": wall3(match_walls),
+                     "stage_ms_per_image": per_image(match_stages)},
+           "score_batch": {"images_per_s": round(a.images / med(score_walls), 2), "wall_ms_per_image": wall3(score_walls)},
+           "host_images": nh, "host_restatement_ms_per_image": round(med(host_walls) * 1e3 / nh, 2),
+           "host_note": "tests/match_reference.py: numpy.unique on the pair codes per image, one process, labels already on the host",
+           "n_pred": tot["n_pred"], "n_true": tot["n_true"], "merged": tot["merged"], "split": tot["split"],
+           "by_threshold": [{k: (round(v, 4) if isinstance(v, float) else v) for k, v in r.items()} for r in tot["by_threshold"]]}
+    res["match_over_segment_wall_time"] = round(med(match_walls) / med(seg_walls), 3)
+    res["host_over_device_match_time"] = round(med(host_walls) / nh / (med(match_walls) / a.images), 1)
+    line = json.dumps(res)
+    out = a.out if a.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "segment_score_bench.json")
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            f.write(line + "\n")
+    print(line)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=32)
@@ -762,7 +842,13 @@ def main():
                     help="measure the noise-adaptive threshold beside the local rule and the top-hat (profiles/segment_noise_bench.json)")
     ap.add_argument("--noise-k", type=float, default=5.0, metavar="K", help="with --noise: sigmas above the local background")
     ap.add_argument("--tile", type=int, default=64, metavar="T", help="with --noise: the mesh tile's side")
+    ap.add_argument("--score", action="store_true", help="measure the label scoring beside the segmentation (profiles/segment_score_bench.json)")
     a = ap.parse_args()
+    if a.score:
+        if (a.noise or a.split or a.split_intensity or a.background is not None or a.local is not None or a.clean or a.delta or a.hysteresis
+                or a.smooth is not None or a.denoise or a.open is not None or a.min_area is not None):
+            ap.error("--score is measured on its own")
+        return score_leg(a)
     if a.noise:
         if (a.split or a.split_intensity or a.background is not None or a.local is not None or a.clean or a.delta or a.hysteresis
                 or a.smooth is not None or a.denoise or a.open is not None or a.min_area is not None):
