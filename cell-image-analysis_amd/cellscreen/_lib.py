@@ -140,6 +140,10 @@ class CSMatchParams(C.Structure):
     _fields_ = [("table_log2", C.c_int32), ("reserved", C.c_int32)]
 
 
+class CSExpandParams(C.Structure):
+    _fields_ = [("max_d2", C.c_int32), ("reserved", C.c_int32)]
+
+
 SMOOTH_MAX_RADIUS = 64                  # cs_smooth_params.weights holds 65 taps
 
 
@@ -216,6 +220,8 @@ SIGNATURES = {
     "cs_label_match": (_I, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _I, C.c_int32, C.c_int32, C.POINTER(CSMatchParams), _P, _P, _I, _P]),
     "cs_label_match_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "cs_label_match_last_table": (_I, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "cs_label_expand": (_I, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _I, C.POINTER(CSExpandParams), _P, _P, _I]),
+    "cs_label_expand_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "cs_fit_create": (_I, [_I, C.POINTER(_P)]),
     "cs_fit_free": (None, [_P]),
     "cs_fit_wait_stream": (_I, [_P, _P]),

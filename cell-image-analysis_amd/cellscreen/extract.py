@@ -290,14 +290,23 @@ def split_channels(image: np.ndarray):
     raise ValueError(f"image of shape {image.shape}: a 2-D image or [H,W,>=3] channels expected")
 
 
-def label_cell_extractor(segment: Callable[[np.ndarray], np.ndarray], device_id: int = 0, out_hw=(OUT_SIDE, OUT_SIDE), **qc):
+def label_cell_extractor(segment: Callable[[np.ndarray], np.ndarray], device_id: int = 0, out_hw=(OUT_SIDE, OUT_SIDE),
+                         expand_distance=None, **qc):
     """The `cell_extractor(image_path) -> (cells, stats)` that ProductionMutantScreening accepts, from a segmenter
     `segment(seg_channel) -> labels`.  The seg channel is handed over untouched (csbdeep's normalize belongs to the
     segmenter), e.g. label_cell_extractor(lambda seg: model.predict_instances(normalize(seg))[0]).  Errors raise; the
     screening driver's try turns them into the reference's "Error processing" line and ([], []).
     out_hw: the size of the cells, 64 x 64 as the reference's resize by default; for a model built with
-    input_shape=(H, W, 1) pass out_hw=(H, W)."""
+    input_shape=(H, W, 1) pass out_hw=(H, W).
+    expand_distance (None, or a number of pixels in 1..127): for a segmenter of nuclei, such as StarDist's 2D_versatile_fluo,
+    whose labels cover the stain and not the cell.  The labels are uploaded, grown by that distance on the extractor's handle
+    (cellscreen/expand.py: every label spreads outwards and stops halfway to its neighbours, ids unchanged) and extracted
+    without coming back to the host; integer labels are cast to int32, and ids that do not fit raise.  The QC numbers among
+    **qc stay the caller's: a grown nucleus is judged by the same min_area and max_area unless they are changed to fit it."""
     out_hw = check_out_hw(out_hw)
+    if expand_distance is not None:
+        from .expand import expand_params                # expand.py imports this module
+        expand_params(expand_distance)
     ext = {}
 
     def cell_extractor(image_path: str):
@@ -308,7 +317,10 @@ def label_cell_extractor(segment: Callable[[np.ndarray], np.ndarray], device_id:
             raise ValueError(f"segmenter returned labels of shape {labels.shape} for an image of {img.shape[:2]}")
         if "x" not in ext:
             ext["x"] = CellExtractor(device_id, out_hw, **qc)
-        r = ext["x"].extract_batch(np.ascontiguousarray(img)[None], np.ascontiguousarray(labels)[None], channel=ch)
+        if expand_distance is None:
+            r = ext["x"].extract_batch(np.ascontiguousarray(img)[None], np.ascontiguousarray(labels)[None], channel=ch)
+        else:
+            r = _extract_grown(ext, img, labels, ch, expand_distance)
         st = int(r.status[0])
         if st != IMAGE_OK:
             raise ValueError("a passing region has a bounding-box side below 8 px (equalize_adapthist raises)" if st == IMAGE_NO_CELLS
@@ -316,3 +328,27 @@ def label_cell_extractor(segment: Callable[[np.ndarray], np.ndarray], device_id:
         return list(r.cells), region_stats(r.regions)
 
     return cell_extractor
+
+
+def _extract_grown(ext: dict, img: np.ndarray, labels: np.ndarray, ch: int, expand_distance) -> Extraction:
+    """label_cell_extractor with expand_distance: image and labels go up once, the labels are grown in place on the
+    extractor's handle and extracted where they are; only the cells come back.  ext: the closure's state, the CellExtractor
+    "x" and the expander "e"."""
+    import torch
+
+    from .expand import LabelExpander
+    if img.dtype not in (np.uint8, np.uint16):
+        raise TypeError(f"image dtype {img.dtype}: uint8 or uint16 expected")
+    if not np.issubdtype(labels.dtype, np.integer):
+        raise TypeError(f"label dtype {labels.dtype}: an integer label image expected")
+    if labels.size and (int(labels.min()) < -(1 << 31) or int(labels.max()) >= 1 << 31):
+        raise ValueError(f"label ids {int(labels.min())}..{int(labels.max())} do not fit int32")
+    if "e" not in ext:
+        ext["e"] = LabelExpander(ext["x"].device_id, extractor=ext["x"])
+    dev = torch.device("cuda", ext["x"].device_id)
+    host = np.ascontiguousarray(img)[None]
+    d_img = torch.from_numpy(host.view(np.int16) if host.dtype == np.uint16 else host).to(dev)
+    d_lab = torch.from_numpy(np.ascontiguousarray(labels, np.int32)[None]).to(dev)
+    ext["e"].expand_batch(d_lab, expand_distance, out=d_lab)
+    r = ext["x"].extract_batch(d_img, d_lab, channel=ch)
+    return r._replace(cells=r.cells.cpu().numpy())

@@ -96,6 +96,7 @@ correction, the threshold, the cleanup, the labels and the split see the smoothe
     seg = ThresholdSegmenter(threshold="noise")                        # 5 sigmas above the local background, no number in counts
     seg = ThresholdSegmenter(threshold="noise", noise_k=6, weak_k=3)   # ... cores at 6 sigmas, rims down to 3, no speckle
     stats, labels, n_labels = seg.score_batch(images, truth)           # how good any of these is against true labels: score.py
+    seg = ThresholdSegmenter(expand_distance=6)                        # a nuclear stain segmented, the labels grown 6 px: expand.py
 
     screening = ProductionMutantScreening(model_dir, cell_extractor=threshold_cell_extractor())
 """
@@ -111,6 +112,7 @@ from . import _lib as L
 from .extract import (IMAGE_NO_CELLS, IMAGE_OK, MAX_SIDE, CellExtractor, _is_tensor, qc_params, read_image, region_stats,
                       split_channels)
 from .preprocess import OUT_SIDE, PIX_U8, PIX_U16, Preprocessor, check_out_hw
+from .expand import LabelExpander, expand_params
 from .score import THRESHOLDS as SCORE_THRESHOLDS, LabelMatcher, check_thresholds
 
 MAX_BATCH = 65535
@@ -445,7 +447,12 @@ class ThresholdSegmenter:
     above the local background, kept in 1/256, default 5), noise_tile (the mesh tile's side, a power of two in 16..256, default
     64), noise_floor (the least sigma in counts, 0..4095, default 1) and weak_k (None, or the weak rule's k, not above noise_k);
     these four belong to "noise" alone, and local_*, weak_threshold and weak_delta are refused with it.  The thresholds it
-    reports are -1.  With numpy input its plane makes one more round trip through the host."""
+    reports are -1.  With numpy input its plane makes one more round trip through the host.
+    expand_distance (None, or a number of pixels in 1..127): the labels, after the split where there is one, are grown in place
+    by that distance on the same handle (cs_label_expand, cellscreen/expand.py): every region spreads outwards and stops halfway
+    to its neighbours, as skimage.segmentation.expand_labels does.  For a channel that stains a part of the cell, the nucleus
+    say, while the other channel is measured over the whole cell.  n_labels, thresholds and return_distance are what they are
+    without it; score_batch scores the grown labels.  With numpy input the labels make one more round trip through the host."""
 
     def __init__(self, device_id: int = 0, threshold="otsu", connectivity: int = 1, fill_holes: bool = True,
                  extractor: Optional[CellExtractor] = None, split_touching: bool = False, split_h: int = 3,
@@ -454,7 +461,9 @@ class ThresholdSegmenter:
                  min_area: Optional[int] = None, smooth_sigma: Optional[float] = None, split_by: str = "distance",
                  split_depth: int = SPLIT_DEPTH, split_contrast: int = SPLIT_CONTRAST, weak_threshold=None,
                  weak_delta: Optional[int] = None, noise_k: float = NOISE_K, noise_tile: int = NOISE_TILE,
-                 noise_floor: float = NOISE_FLOOR, weak_k: Optional[float] = None):
+                 noise_floor: float = NOISE_FLOOR, weak_k: Optional[float] = None, expand_distance=None):
+        self._expand = None if expand_distance is None else expand_params(expand_distance)
+        self.expand_distance = expand_distance
         self._params, self._local, self._background = _threshold_mode(threshold, connectivity, fill_holes, local_radius, local_delta,
                                                                       local_floor, background_radius, denoise, smooth_sigma)
         self._noise = _noise_mode(threshold, connectivity, noise_k, noise_tile, noise_floor, weak_k, weak_threshold, weak_delta)
@@ -487,6 +496,7 @@ class ThresholdSegmenter:
         self._pre: Optional[Preprocessor] = None        # own handle: created by the first call, after its argument checks
         self._matcher = LabelMatcher(device_id, extractor=self)     # score_batch: cs_label_match on this segmenter's handle
         self._scored = False                            # the last call was a score_batch: last_timing reports the match
+        self._expander = LabelExpander(device_id, extractor=self)   # expand_distance: cs_label_expand on this segmenter's handle
 
     @property
     def _handle(self):
@@ -756,6 +766,7 @@ class ThresholdSegmenter:
                 thresholds = reported
             if self._local is not None or self._noise is not None:
                 thresholds[:] = -1                                  # no single number
+            self._grow(labels)
             return labels, n_labels, thresholds
         dist = None
         if return_distance:
@@ -777,7 +788,13 @@ class ThresholdSegmenter:
             thresholds = reported
         if self._local is not None or self._noise is not None:
             thresholds[:] = -1
+        self._grow(labels)
         return (labels, n_labels, thresholds, dist) if return_distance else (labels, n_labels, thresholds)
+
+    def _grow(self, labels):
+        """expand_distance: the labels of segment_batch grown where they are."""
+        if self._expand is not None:
+            self._expander.expand_batch(labels, self.expand_distance, out=labels)
 
     def score_batch(self, images, truth, channel: Optional[int] = None, thresholds=SCORE_THRESHOLDS, max_truth: Optional[int] = None):
         """segment_batch, then the labels scored where they are against `truth` (int32 [B,H,W], numpy or a CUDA tensor, 0 =
@@ -806,7 +823,8 @@ class ThresholdSegmenter:
         local rule's place: local_ms is not reported; with threshold="noise" noise_mesh_ms (tile statistics and the mesh filter),
         noise_cut_ms (the cut or the level plane) and noise_link_ms (with weak_k: weak components, flags, the kept plane; else 0)
         of the last noise stage; after score_batch also match_count_ms (clearing and cs_label_match's one pass over the two label
-        planes) and match_reduce_ms (its reduction into the tables)."""
+        planes) and match_reduce_ms (its reduction into the tables); with expand_distance also expand_columns_ms and expand_rows_ms,
+        the two passes of the last cs_label_expand."""
         extra = self._smooth_timing() if self._smooth is not None else {}
         if self._background is not None:
             extra.update(self._background_timing())
@@ -820,6 +838,8 @@ class ThresholdSegmenter:
             extra.update(self._clean_timing())
         if self._scored:
             extra.update(self._matcher.last_timing())
+        if self._expand is not None:
+            extra.update(self._expander.last_timing())
         if self._split is None:
             return dict(zip(("threshold_ms", "label_ms"), self._times(self._lib.cs_segment_last_timing, 2)), **extra)
         if self._split_intensity is not None:
@@ -847,7 +867,7 @@ def threshold_cell_extractor(device_id: int = 0, out_hw=(OUT_SIDE, OUT_SIDE), th
                              smooth_sigma: Optional[float] = None, split_by: str = "distance", split_depth: int = SPLIT_DEPTH,
                              split_contrast: int = SPLIT_CONTRAST, weak_threshold=None, weak_delta: Optional[int] = None,
                              noise_k: float = NOISE_K, noise_tile: int = NOISE_TILE, noise_floor: float = NOISE_FLOOR,
-                             weak_k: Optional[float] = None, **qc):
+                             weak_k: Optional[float] = None, expand_distance=None, **qc):
     """The `cell_extractor(image_path) -> (cells, stats)` that ProductionMutantScreening and create_training_dataset accept,
     with the built-in segmenter in StarDist's place: the file is read (extract.read_image / split_channels), uploaded once,
     segmented and extracted on one handle, and the labels never leave the device.  Not StarDist: see the module text.
@@ -860,8 +880,13 @@ def threshold_cell_extractor(device_id: int = 0, out_hw=(OUT_SIDE, OUT_SIDE), th
     smooth_sigma as for ThresholdSegmenter: the segmentation channel is smoothed first, the extraction reads the raw one.
     split_by, split_depth and split_contrast as for ThresholdSegmenter; split_by="intensity" wants smooth_sigma.
     weak_threshold and weak_delta as for ThresholdSegmenter: the hysteresis threshold in the plain cut's place.
-    threshold="noise" with noise_k, noise_tile, noise_floor and weak_k as for ThresholdSegmenter: the noise-adaptive threshold."""
+    threshold="noise" with noise_k, noise_tile, noise_floor and weak_k as for ThresholdSegmenter: the noise-adaptive threshold.
+    expand_distance as for ThresholdSegmenter: the labels are grown by that many pixels before the extraction, for a
+    segmentation channel that stains the nucleus alone.  The QC numbers among **qc stay the caller's: a grown region is judged
+    by the same min_area and max_area (and border, eccentricity and intensity rules) unless they are changed to fit it."""
     out_hw = check_out_hw(out_hw)
+    if expand_distance is not None:
+        expand_params(expand_distance)
     _threshold_mode(threshold, connectivity, fill_holes, local_radius, local_delta, local_floor, background_radius, denoise,
                     smooth_sigma)
     split_params(split_touching, split_h)
@@ -888,7 +913,7 @@ def threshold_cell_extractor(device_id: int = 0, out_hw=(OUT_SIDE, OUT_SIDE), th
                                          min_area=mask_min_area, smooth_sigma=smooth_sigma, split_by=split_by,
                                          split_depth=split_depth, split_contrast=split_contrast, weak_threshold=weak_threshold,
                                          weak_delta=weak_delta, noise_k=noise_k, noise_tile=noise_tile, noise_floor=noise_floor,
-                                         weak_k=weak_k)
+                                         weak_k=weak_k, expand_distance=expand_distance)
         host = np.ascontiguousarray(img)[None]
         dev = torch.from_numpy(host.view(np.int16) if host.dtype == np.uint16 else host).to(torch.device("cuda", device_id))
         labels, _, _ = st["s"].segment_batch(dev, channel=seg_ch)

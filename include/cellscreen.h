@@ -34,6 +34,10 @@
  *   cs_label_match
  *        scores a label image against ground truth: object matching by intersection over union, the
  *        rule of StarDist's `matching` made unique (no reference counterpart)
+ *   cs_label_expand
+ *        grows the objects of a label image outwards by a fixed distance, halfway to their neighbours at
+ *        most: skimage.segmentation.expand_labels between a nuclear segmentation and the extraction
+ *        (no reference counterpart)
  *   cs_fit_scaler / cs_fit_pca_moments / cs_fit_pca_subspace / cs_fit_project / cs_fit_ocsvm
  *        RobustScaler / PCA / OneClassSVM fits of create_anomaly_detector
  *                                                 CAE_improved_modeltrain.py:408-427
@@ -777,6 +781,31 @@ int cs_label_match(cs_preproc *p, const int32_t *pred, const int32_t *truth, int
 int cs_label_match_last_timing(const cs_preproc *p, double *count_ms, double *reduce_ms);
 /* The capacity (as log2) the last cs_label_match ended with, and how many times it doubled the table. */
 int cs_label_match_last_table(const cs_preproc *p, int32_t *table_log2, int32_t *grows);
+
+/* ---- growing labels by a distance ---------------------------------------------------------------- */
+/* Every object of a label image grows outwards by sqrt(max_d2) pixels, and where two objects would meet each stops halfway
+ * (tests/expand_reference.py restates the rule).  All integers, a function of the labels alone: with D2 the squared
+ * Euclidean distance from a background pixel to the nearest pixel with a label > 0 of the same image (outside the image there
+ * is nothing), a pixel with D2 <= max_d2 takes the label of that nearest pixel, the smallest label where several pixels of
+ * different labels lie at that D2; labelled pixels keep their label, every other pixel stays 0, and no id is renumbered.  Off
+ * the ties that is skimage.segmentation.expand_labels(labels, distance) with max_d2 the largest integer whose square root is
+ * <= distance; the library's choice among equidistant pixels follows its scan order, this one the labels alone.
+ * labels: [batch][height][width] int32, in_kind.  Left on the device by cs_segment_* on this handle they are read in stream
+ *         order, as cs_extract_measure reads them.  height, width 1..4096, batch 1..65535 (above: CS_ERR_UNSUPPORTED).  A
+ *         negative label is CS_ERR_INVALID, detected on the device and reported by this call; the outputs are then undefined
+ *         and the handle stays usable.
+ * params: not NULL; max_d2 1..16129 (distances up to 127 px), reserved 0.
+ * out:    [batch][height][width] int32, out_kind; may be `labels` itself.
+ * d2:     NULL, or [batch][height][width] uint16 where `out` is: 0 on labelled pixels, D2 where it is <= max_d2, 65535 elsewhere.
+ * No atomics and no floating point: bit-identical run to run, and nothing crosses between the images of a batch.  Scratch
+ * (5 bytes per pixel, and a host image's upload) comes from the buffers the handle's segmenter stages share.  One host
+ * synchronisation per call.  Other bad arguments: CS_ERR_INVALID before any device work; without a gfx950 device (p == NULL):
+ * CS_ERR_NO_DEVICE. */
+typedef struct cs_expand_params { int32_t max_d2; /* 1..16129 */ int32_t reserved; /* 0 */ } cs_expand_params;
+int cs_label_expand(cs_preproc *p, const int32_t *labels, int32_t batch, int32_t height, int32_t width, int in_kind,
+                    const cs_expand_params *params, int32_t *out, uint16_t *d2 /* or NULL */, int out_kind);
+/* Device time of the last cs_label_expand: the column pass (with the clearing of the status word) and the row pass. */
+int cs_label_expand_last_timing(const cs_preproc *p, double *columns_ms, double *rows_ms);
 
 /* ---- detector fitting (create_anomaly_detector, CAE_improved_modeltrain.py:394-446) -------- */
 /* The fit of what cs_screen's tail evaluates, for the training set's encoder features
