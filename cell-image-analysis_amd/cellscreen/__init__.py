@@ -3,6 +3,8 @@ libcellscreen.so (hand-written gfx950 HIP).  Importing this package loads no nat
 Engine / ProductionMutantScreening do, and fail loudly when the library or a GPU is missing."""
 from . import spec  # noqa: F401
 from .expand import LabelExpander, expand_params  # noqa: F401
+from .intensity import IntensityMeasurer, ObjectTable  # noqa: F401
 from .spec import CAEWeights, DetectorParams, OCSVMParams  # noqa: F401
 
-__all__ = ["spec", "CAEWeights", "DetectorParams", "OCSVMParams", "LabelExpander", "expand_params"]
+__all__ = ["spec", "CAEWeights", "DetectorParams", "OCSVMParams", "LabelExpander", "expand_params", "IntensityMeasurer",
+           "ObjectTable"]

@@ -84,7 +84,7 @@ hipError_t launch_preprocess(const void* pix, int pixel_type, const CropDesc* de
                              uint16_t* clahe, float* out, int out_h, int out_w, hipStream_t stream);
 struct ExtractState;                            // extract.hip: the state between cs_extract_measure and cs_extract_fill
 void extract_state_free(ExtractState* s);
-struct SegmentState;                            // segment_internal.hpp: the buffers of cs_segment_* and cs_label_expand
+struct SegmentState;                            // segment_internal.hpp: the buffers of cs_segment_*, cs_label_expand, cs_label_intensity
 void segment_state_free(SegmentState* s);
 struct MatchState;                              // match.hip: the buffers of cs_label_match
 void match_state_free(MatchState* s);
@@ -96,7 +96,7 @@ int require_gfx950(int device_id);
 }  // namespace cs
 
 // The preprocess handle (include/cellscreen.h); its extraction entry points live in extract.hip, its segmenter in segment.hip,
-// its label scoring in match.hip, its label expansion in expand.hip.
+// its label scoring in match.hip, its label expansion in expand.hip, its intensity measurement in intensity.hip.
 struct cs_preproc {
     int device = 0;
     hipStream_t stream = nullptr;

@@ -1,4 +1,4 @@
-// segment_internal.hpp -- the segmenter's host layer as its translation units share it (segment.hip, expand.hip): the state
+// segment_internal.hpp -- the segmenter's host layer as its translation units share it (segment.hip, expand.hip, intensity.hip): the state
 // behind cs_preproc::seg with its shared buffers, the one clock, and the argument checks every entry point on that state makes.
 #pragma once
 #include "api_internal.hpp"
@@ -65,7 +65,9 @@ struct SegmentState {
     // hipFree, which waits for the device.
     // cs_label_expand (expand.hip) has no buffer of its own: column distances in mask, column labels in parent, a host image's
     // labels in lab, a host d2 plane in stage, its status word in ctrl.
-    StageClock clk_thr, clk_sp, clk_si, clk_bg, clk_lt, clk_cl, clk_sm, clk_hy, clk_ns, clk_ex;
+    // cs_label_intensity (intensity.hip) has none either: a host image in img, its labels in lab, its exclude plane in parent,
+    // the two tables on their way to the host in stage, its status word in ctrl.
+    StageClock clk_thr, clk_sp, clk_si, clk_bg, clk_lt, clk_cl, clk_sm, clk_hy, clk_ns, clk_ex, clk_in;
     int sp_recon_reads = 0, sp_flood_reads = 0;         // control-word reads (one host synchronisation each) of the last split of either kind
 };
 

@@ -38,6 +38,11 @@
  *        grows the objects of a label image outwards by a fixed distance, halfway to their neighbours at
  *        most: skimage.segmentation.expand_labels between a nuclear segmentation and the extraction
  *        (no reference counterpart)
+ *   cs_label_intensity
+ *        measures every object of a label image in every channel: area, centroid, integrated / mean / std /
+ *        min / max intensity and the intensity-weighted centroid, as exact integer sums
+ *        (skimage.measure.regionprops with an intensity image, scipy.ndimage's labelled statistics,
+ *        CellProfiler's MeasureObjectIntensity; no reference counterpart)
  *   cs_fit_scaler / cs_fit_pca_moments / cs_fit_pca_subspace / cs_fit_project / cs_fit_ocsvm
  *        RobustScaler / PCA / OneClassSVM fits of create_anomaly_detector
  *                                                 CAE_improved_modeltrain.py:408-427
@@ -806,6 +811,37 @@ int cs_label_expand(cs_preproc *p, const int32_t *labels, int32_t batch, int32_t
                     const cs_expand_params *params, int32_t *out, uint16_t *d2 /* or NULL */, int out_kind);
 /* Device time of the last cs_label_expand: the column pass (with the clearing of the status word) and the row pass. */
 int cs_label_expand_last_timing(const cs_preproc *p, double *columns_ms, double *rows_ms);
+
+/* ---- per-object intensities ------------------------------------------------------------------------- */
+/* What every object of a label image measures in every channel of an image, as exact integer sums (DESIGN 3u;
+ * tests/intensity_reference.py restates the rule).  An object is the set of pixels of one image with one label > 0, connected
+ * or not, less the pixels where `exclude` is non-zero; r and c are the row and the column of a pixel in its image, v its value
+ * in a channel.  scipy.ndimage.sum / mean / standard_deviation / minimum / maximum / center_of_mass over the labels, and
+ * skimage.measure.regionprops' intensity properties, follow from the sums (cellscreen/intensity.py).
+ * image:  [batch][height][width][channels] uint8 / uint16 (pixel_type), channels 1..4, every channel is measured; more than 4:
+ *         CS_ERR_UNSUPPORTED (the caller splits the stack).
+ * labels: [batch][height][width] int32, 0 = background.  Left on the device by cs_segment_* or cs_label_expand on this handle
+ *         they are read in stream order.  A label that is negative or above max_label is CS_ERR_INVALID, detected on the device
+ *         and reported by this call (whatever `exclude` holds there); it is never used as an index, the tables are then
+ *         undefined and the handle stays usable.
+ * exclude: NULL, or [batch][height][width] int32: a pixel whose value is non-zero, whatever the value, belongs to no object.
+ *         With the nuclei as `exclude` under the grown cells as `labels` the objects are the rings of cytoplasm.
+ * image, labels and exclude are all in_kind.  height, width 1..4096, batch 1..65535 (above: CS_ERR_UNSUPPORTED).
+ * max_label: 1..2^20, an upper bound of the labels; it sizes the tables, row b * max_label + label - 1 for label `label` of
+ *         image b.  Above 2^20, or batch * max_label * channels above 2^22: CS_ERR_UNSUPPORTED.
+ * geom:   out, [batch][max_label][3] int64: area, sum r, sum c.
+ * stats:  out, [batch][max_label][channels][6] int64: sum v, sum v^2, sum v * r, sum v * c, min v, max v.  Both out_kind.
+ *         An object that does not occur, or that `exclude` covers whole, has all-zero rows, its minimum included.
+ * No floating point: every result is a sum, a minimum or a maximum of integers, bit-identical run to run and independent of the
+ * other images of the batch.  Uploads of host inputs and host tables on their way back go through the buffers the handle's
+ * segmenter stages share.  One host synchronisation per call.  Other bad arguments: CS_ERR_INVALID before any device work;
+ * without a gfx950 device (p == NULL): CS_ERR_NO_DEVICE. */
+int cs_label_intensity(cs_preproc *p, const void *image, int pixel_type, int32_t channels,
+                       const int32_t *labels, const int32_t *exclude /* or NULL */,
+                       int32_t batch, int32_t height, int32_t width, int in_kind, int32_t max_label,
+                       int64_t *geom, int64_t *stats, int out_kind);
+/* Device time of the last cs_label_intensity: clearing the tables and the status word, and the pass with its closing step. */
+int cs_label_intensity_last_timing(const cs_preproc *p, double *clear_ms, double *pass_ms);
 
 /* ---- detector fitting (create_anomaly_detector, CAE_improved_modeltrain.py:394-446) -------- */
 /* The fit of what cs_screen's tail evaluates, for the training set's encoder features
