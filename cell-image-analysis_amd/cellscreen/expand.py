@@ -17,15 +17,12 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Optional
 
 import numpy as np
 
 from . import _lib as L
-from .extract import MAX_SIDE, _is_tensor
-from .preprocess import Preprocessor
+from ._labels import MAX_BATCH, MAX_SIDE, LabelTool, _is_tensor, check_label_plane, check_stack_shape  # noqa: F401
 
-MAX_BATCH = 65535
 MAX_DISTANCE = 127
 D2_FAR = 65535                          # the d2 of a pixel that no label reaches
 
@@ -52,66 +49,19 @@ def expand_params(distance) -> L.CSExpandParams:
     return p
 
 
-class LabelExpander:
+class LabelExpander(LabelTool):
     """cs_label_expand on one preprocess handle (one GPU, one stream).  extractor: a CellExtractor (or a ThresholdSegmenter)
     whose handle and stream to share, so that labels a segmenter left on the device are read in stream order and the grown
     labels feed extract_batch without leaving the device."""
-
-    def __init__(self, device_id: int = 0, extractor=None):
-        if extractor is not None and extractor.device_id != device_id:
-            raise ValueError(f"extractor is on device {extractor.device_id}, the expander on {device_id}")
-        self._lib = L.load_library()
-        self.device_id = device_id
-        self._ext = extractor
-        self._pre: Optional[Preprocessor] = None        # own handle: created by the first call, after its argument checks
-
-    @property
-    def _handle(self):
-        if self._ext is not None:
-            return self._ext._handle
-        if self._pre is None:
-            self._pre = Preprocessor(self.device_id)
-        return self._pre._h
-
-    def close(self):
-        """Frees the expander's own handle (a shared one stays its owner's); a later call makes a new one."""
-        if self._pre is not None:
-            self._pre.close()
-            self._pre = None
+    _noun = "the expander"
 
     # ---- argument checks: everything is refused before the device is touched ---------------------------------------
-    def _check_one(self, name, a):
-        if _is_tensor(a):
-            import torch
-            if a.dtype != torch.int32:
-                raise TypeError(f"{name} tensor dtype {a.dtype}: int32 expected")
-            if not a.is_cuda:
-                raise ValueError(f"{name} is a CPU tensor; pass numpy arrays or CUDA tensors")
-            if a.device.index != self.device_id:
-                raise ValueError(f"{name} is on {a.device}, the expander on cuda:{self.device_id}")
-            if not a.is_contiguous():
-                raise ValueError(f"{name} is not contiguous")
-        elif isinstance(a, np.ndarray):
-            if a.dtype != np.int32:
-                raise TypeError(f"{name} dtype {a.dtype}: int32 expected")
-            if not a.flags.c_contiguous:
-                raise ValueError(f"{name} must be C-contiguous")
-        else:
-            raise TypeError(f"unsupported input type {type(a)} for {name}")
-        if a.ndim != 3:
-            raise ValueError(f"{name} must be [B,H,W], got shape {tuple(a.shape)}")
-
     def _check(self, labels, out):
-        self._check_one("labels", labels)
+        check_label_plane("labels", labels, self.device_id, self._noun)
         B, H, W = (int(x) for x in labels.shape)
-        if B < 1 or H < 1 or W < 1:
-            raise ValueError(f"empty batch or image: shape {tuple(labels.shape)}")
-        if H > MAX_SIDE or W > MAX_SIDE:
-            raise ValueError(f"image sides above {MAX_SIDE} are not supported, got {H}x{W}")
-        if B > MAX_BATCH:
-            raise ValueError(f"at most {MAX_BATCH} images per call, got {B}")
+        check_stack_shape(B, H, W, labels.shape)
         if out is not None:
-            self._check_one("out", out)
+            check_label_plane("out", out, self.device_id, self._noun)
             if _is_tensor(out) != _is_tensor(labels):
                 raise TypeError("labels and out must both be numpy arrays or both be CUDA tensors")
             if tuple(out.shape) != (B, H, W):

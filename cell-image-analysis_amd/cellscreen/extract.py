@@ -24,13 +24,12 @@ from typing import Callable, List, NamedTuple, Optional
 import numpy as np
 
 from . import _lib as L
+from ._labels import MAX_LABEL, MAX_SIDE, _is_tensor  # noqa: F401
 from .preprocess import CLIP_LIMIT, MAX_RATIO, OUT_SIDE, PIX_U8, PIX_U16, Preprocessor, check_out_hw
 
 QC_BORDER, QC_AREA, QC_ECCENTRICITY, QC_INTENSITY = 1, 2, 4, 8          # cs_region.failed bits
 IMAGE_OK, IMAGE_NO_CELLS, IMAGE_UNSUPPORTED = 0, 1, 2                   # per-image status
-MAX_LABEL = 1 << 20                                                     # per image (csrc/extract.hip)
 MAX_SLOTS = 1 << 22                                                     # batch * max_label
-MAX_SIDE = 4096
 
 # the reference's thresholds (improved_detection.py:69-91) and clip limit (:98)
 REFERENCE_QC = dict(border=10, min_area=200, max_area=8000, max_eccentricity=0.95, min_mean=0.5, min_std=0.1,
@@ -64,10 +63,6 @@ def region_stats(regions: np.ndarray) -> List[dict]:
         out.append({"area": int(r["area"]), "eccentricity": float(r["eccentricity"]), "solidity": float(r["solidity"]),
                     "mean_intensity": float(r["mean_intensity"]), "std_intensity": float(r["std_intensity"])})
     return out
-
-
-def _is_tensor(a) -> bool:
-    return not isinstance(a, np.ndarray) and hasattr(a, "data_ptr")
 
 
 class CellExtractor:

@@ -21,15 +21,13 @@ from __future__ import annotations
 import ctypes as C
 import math
 from dataclasses import dataclass
-from typing import Optional
 
 import numpy as np
 
 from . import _lib as L
-from .extract import MAX_LABEL, MAX_SIDE, _is_tensor
-from .preprocess import PIX_U8, PIX_U16, Preprocessor
+from ._labels import MAX_BATCH, MAX_LABEL, MAX_SIDE, LabelTool, _is_tensor, check_stack_shape  # noqa: F401
+from .preprocess import PIX_U8, PIX_U16
 
-MAX_BATCH = 65535
 MAX_CHANNELS = 4
 MAX_CELLS = 1 << 22                     # batch * max_label * channels
 
@@ -81,34 +79,14 @@ def object_table(geom: np.ndarray, stats: np.ndarray) -> ObjectTable:
                        geom=g, stats=s)
 
 
-class IntensityMeasurer:
+class IntensityMeasurer(LabelTool):
     """cs_label_intensity on one preprocess handle (one GPU, one stream).  extractor: a CellExtractor (or a ThresholdSegmenter)
     whose handle and stream to share, so that labels a segmenter or a LabelExpander on that handle left on the device are read
     in stream order."""
+    _noun = "the measurer"
 
-    def __init__(self, device_id: int = 0, extractor=None):
-        if extractor is not None and extractor.device_id != device_id:
-            raise ValueError(f"extractor is on device {extractor.device_id}, the measurer on {device_id}")
-        self._lib = L.load_library()
-        self.device_id = device_id
-        self._ext = extractor
-        self._pre: Optional[Preprocessor] = None        # own handle: created by the first call, after its argument checks
-
-    @property
-    def _handle(self):
-        if self._ext is not None:
-            return self._ext._handle
-        if self._pre is None:
-            self._pre = Preprocessor(self.device_id)
-        return self._pre._h
-
-    def close(self):
-        """Frees the measurer's own handle (a shared one stays its owner's); a later call makes a new one."""
-        if self._pre is not None:
-            self._pre.close()
-            self._pre = None
-
-    # ---- argument checks: everything is refused before the device is touched ---------------------------------------
+    # ---- argument checks: everything is refused before the device is touched.  The planes are checked together, kind and shape
+    # before dtype and device, so check_label_plane, which finishes one plane before the next, would answer in another order ----
     def _check(self, image, labels, exclude, max_label):
         planes = [("image", image), ("labels", labels)] + ([("exclude", exclude)] if exclude is not None else [])
         for name, a in planes:
@@ -126,12 +104,7 @@ class IntensityMeasurer:
                 raise ValueError(f"image {tuple(image.shape)} and {name} {tuple(a.shape)} differ in batch or height x width")
         B, H, W = (int(x) for x in labels.shape)
         nc = int(image.shape[3]) if image.ndim == 4 else 1
-        if B < 1 or H < 1 or W < 1 or nc < 1:
-            raise ValueError(f"empty batch or image: shape {tuple(image.shape)}")
-        if H > MAX_SIDE or W > MAX_SIDE:
-            raise ValueError(f"image sides above {MAX_SIDE} are not supported, got {H}x{W}")
-        if B > MAX_BATCH:
-            raise ValueError(f"at most {MAX_BATCH} images per call, got {B}")
+        check_stack_shape(B, H, W, image.shape, nc)
         if nc > MAX_CHANNELS:
             raise ValueError(f"{nc} channels: at most {MAX_CHANNELS} are measured per call, split the stack")
         if on_dev:

@@ -18,16 +18,13 @@ This measures agreement of objects, not boundary accuracy: there is no Hausdorff
 from __future__ import annotations
 
 import ctypes as C
-from typing import NamedTuple, Optional
+from typing import NamedTuple
 
 import numpy as np
 
 from . import _lib as L
-from .extract import MAX_SIDE, _is_tensor
-from .preprocess import Preprocessor
+from ._labels import MAX_BATCH, MAX_LABEL, MAX_SIDE, LabelTool, _is_tensor, check_label_plane, check_stack_shape  # noqa: F401
 
-MAX_BATCH = 65535
-MAX_LABEL = 1 << 20                     # per image
 MAX_ROWS = 1 << 22                      # batch * max label, for each side
 TABLE_LOG2 = (10, 26)
 THRESHOLDS = (0.5, 0.55, 0.6, 0.65, 0.7, 0.75, 0.8, 0.85, 0.9)
@@ -136,68 +133,24 @@ def _check_max(name, v, B):
     return int(v)
 
 
-class LabelMatcher:
+class LabelMatcher(LabelTool):
     """cs_label_match on one preprocess handle (one GPU, one stream).  extractor: a CellExtractor (or a ThresholdSegmenter)
     whose handle and stream to share, so that labels a segmenter left on the device are read in stream order; table_log2: the
     first capacity of the pair table (None: automatic)."""
+    _noun = "the matcher"
 
     def __init__(self, device_id: int = 0, extractor=None, table_log2=None):
         self._params = match_params(table_log2)
-        if extractor is not None and extractor.device_id != device_id:
-            raise ValueError(f"extractor is on device {extractor.device_id}, the matcher on {device_id}")
-        self._lib = L.load_library()
-        self.device_id = device_id
-        self._ext = extractor
-        self._pre: Optional[Preprocessor] = None        # own handle: created by the first call, after its argument checks
-
-    @property
-    def _handle(self):
-        if self._ext is not None:
-            return self._ext._handle
-        if self._pre is None:
-            self._pre = Preprocessor(self.device_id)
-        return self._pre._h
-
-    def close(self):
-        """Frees the matcher's own handle (a shared one stays its owner's); a later call makes a new one."""
-        if self._pre is not None:
-            self._pre.close()
-            self._pre = None
+        super().__init__(device_id, extractor)
 
     # ---- argument checks: everything is refused before the device is touched ---------------------------------------
-    def _check_one(self, name, a):
-        if _is_tensor(a):
-            import torch
-            if a.dtype != torch.int32:
-                raise TypeError(f"{name} tensor dtype {a.dtype}: int32 expected")
-            if not a.is_cuda:
-                raise ValueError(f"{name} is a CPU tensor; pass numpy arrays or CUDA tensors")
-            if a.device.index != self.device_id:
-                raise ValueError(f"{name} is on {a.device}, the matcher on cuda:{self.device_id}")
-            if not a.is_contiguous():
-                raise ValueError(f"{name} is not contiguous")
-        elif isinstance(a, np.ndarray):
-            if a.dtype != np.int32:
-                raise TypeError(f"{name} dtype {a.dtype}: int32 expected")
-            if not a.flags.c_contiguous:
-                raise ValueError(f"{name} must be C-contiguous")
-        else:
-            raise TypeError(f"unsupported input type {type(a)} for {name}")
-        if a.ndim != 3:
-            raise ValueError(f"{name} must be [B,H,W], got shape {tuple(a.shape)}")
-
     def _check(self, pred, truth, max_pred, max_truth):
-        self._check_one("pred", pred)
-        self._check_one("truth", truth)
+        check_label_plane("pred", pred, self.device_id, self._noun)
+        check_label_plane("truth", truth, self.device_id, self._noun)
         if tuple(pred.shape) != tuple(truth.shape):
             raise ValueError(f"pred {tuple(pred.shape)} and truth {tuple(truth.shape)} differ in shape")
         B, H, W = (int(x) for x in pred.shape)
-        if B < 1 or H < 1 or W < 1:
-            raise ValueError(f"empty batch or image: shape {tuple(pred.shape)}")
-        if H > MAX_SIDE or W > MAX_SIDE:
-            raise ValueError(f"image sides above {MAX_SIDE} are not supported, got {H}x{W}")
-        if B > MAX_BATCH:
-            raise ValueError(f"at most {MAX_BATCH} images per call, got {B}")
+        check_stack_shape(B, H, W, pred.shape)
         if max_pred is not None:
             max_pred = _check_max("max_pred", max_pred, B)
         if max_truth is not None:

@@ -109,13 +109,11 @@ from typing import Optional
 import numpy as np
 
 from . import _lib as L
-from .extract import (IMAGE_NO_CELLS, IMAGE_OK, MAX_SIDE, CellExtractor, _is_tensor, qc_params, read_image, region_stats,
-                      split_channels)
+from ._labels import MAX_BATCH, MAX_SIDE, _is_tensor, check_label_plane, check_stack_shape  # noqa: F401
+from .extract import IMAGE_NO_CELLS, IMAGE_OK, CellExtractor, qc_params, read_image, region_stats, split_channels
 from .preprocess import OUT_SIDE, PIX_U8, PIX_U16, Preprocessor, check_out_hw
 from .expand import LabelExpander, expand_params
 from .score import THRESHOLDS as SCORE_THRESHOLDS, LabelMatcher, check_thresholds
-
-MAX_BATCH = 65535
 
 
 def segment_params(threshold="otsu", connectivity: int = 1, fill_holes: bool = True) -> L.CSSegmentParams:
@@ -521,12 +519,7 @@ class ThresholdSegmenter:
             raise ValueError(f"images must be [B,H,W] or [B,H,W,C], got shape {tuple(images.shape)}")
         B, H, W = (int(x) for x in images.shape[:3])
         Cn = int(images.shape[3]) if images.ndim == 4 else 1
-        if B < 1 or H < 1 or W < 1 or Cn < 1:
-            raise ValueError(f"empty batch or image: shape {tuple(images.shape)}")
-        if H > MAX_SIDE or W > MAX_SIDE:
-            raise ValueError(f"image sides above {MAX_SIDE} are not supported, got {H}x{W}")
-        if B > MAX_BATCH:
-            raise ValueError(f"at most {MAX_BATCH} images per call, got {B}")
+        check_stack_shape(B, H, W, images.shape, Cn)
         if channel is None:
             if Cn == 1:
                 channel = 0
@@ -803,7 +796,7 @@ class ThresholdSegmenter:
         The thresholds, `truth` and the images are checked before the device is touched."""
         check_thresholds(thresholds)
         B, H, W = self._check(images, channel)[:3]
-        self._matcher._check_one("truth", truth)
+        check_label_plane("truth", truth, self.device_id, self._matcher._noun)
         if tuple(truth.shape) != (B, H, W):
             raise ValueError(f"truth {tuple(truth.shape)} and images {tuple(images.shape)} differ in batch or height x width")
         labels, n_labels, _ = self.segment_batch(images, channel)

@@ -1,4 +1,5 @@
-// api_internal.hpp -- helpers shared by the C-ABI translation units (api.hip, train_api.hip).
+// api_internal.hpp -- helpers shared by the C-ABI translation units (api.hip, train_api.hip, preprocess.hip, fit.hip and, through
+// stage_host.hpp, the entry points on the preprocess handle): the error record, HIPCHK, DevBuf, and the handle itself.
 #pragma once
 #include "../../include/cellscreen.h"
 #include "common.hpp"
@@ -84,9 +85,9 @@ hipError_t launch_preprocess(const void* pix, int pixel_type, const CropDesc* de
                              uint16_t* clahe, float* out, int out_h, int out_w, hipStream_t stream);
 struct ExtractState;                            // extract.hip: the state between cs_extract_measure and cs_extract_fill
 void extract_state_free(ExtractState* s);
-struct SegmentState;                            // segment_internal.hpp: the buffers of cs_segment_*, cs_label_expand, cs_label_intensity
+struct SegmentState;                            // segment_internal.hpp: the buffers and clocks of cs_segment_*, cs_label_expand, cs_label_intensity
 void segment_state_free(SegmentState* s);
-struct MatchState;                              // match.hip: the buffers of cs_label_match
+struct MatchState;                              // match.hip: the buffers, the pair table and the clock of cs_label_match
 void match_state_free(MatchState* s);
 
 int upload(DevBuf& d, const void* src, size_t bytes);
@@ -96,7 +97,10 @@ int require_gfx950(int device_id);
 }  // namespace cs
 
 // The preprocess handle (include/cellscreen.h); its extraction entry points live in extract.hip, its segmenter in segment.hip,
-// its label scoring in match.hip, its label expansion in expand.hip, its intensity measurement in intensity.hip.
+// its label scoring in match.hip, its label expansion in expand.hip, its intensity measurement in intensity.hip.  All five take
+// their argument rules, the handle check and their clocks from stage_host.hpp; each keeps a state of its own below (expand and
+// intensity share the segmenter's), since what must survive between calls differs: extract's uploads from measure to fill,
+// match's pair table.
 struct cs_preproc {
     int device = 0;
     hipStream_t stream = nullptr;

@@ -145,14 +145,12 @@ int cs_label_expand(cs_preproc* p, const int32_t* labels, int32_t batch, int32_t
                     const cs_expand_params* params, int32_t* out, uint16_t* d2, int out_kind)
 {
     if (!labels || !out || !params) return fail(CS_ERR_INVALID, "NULL argument");
-    if ((in_kind != CS_MEM_HOST && in_kind != CS_MEM_DEVICE) || (out_kind != CS_MEM_HOST && out_kind != CS_MEM_DEVICE))
-        return fail(CS_ERR_INVALID, "in_kind / out_kind must be CS_MEM_HOST or CS_MEM_DEVICE");
-    if (batch < 1 || height < 1 || width < 1) return fail(CS_ERR_INVALID, "batch %d, height %d, width %d: all must be >= 1", (int)batch,
-                                                          (int)height, (int)width);
+    if (!mem_kind(in_kind) || !mem_kind(out_kind)) return fail(CS_ERR_INVALID, "in_kind / out_kind must be CS_MEM_HOST or CS_MEM_DEVICE");
+    int rc;
+    if ((rc = stack_dims(batch, height, width))) return rc;
     if (params->max_d2 < 1 || params->max_d2 > kExMaxD2)
         return fail(CS_ERR_INVALID, "max_d2 %d outside 1..%d (distances up to %d px)", (int)params->max_d2, kExMaxD2, EX_HALO);
     if (params->reserved != 0) return fail(CS_ERR_INVALID, "cs_expand_params.reserved must be 0");
-    int rc;
     if ((rc = image_limits(batch, height, width)) || (rc = handle_check(p)) || (rc = state_begin(p))) return rc;
     SegmentState& S = *p->seg;
     hipStream_t st = p->stream;

@@ -6,10 +6,9 @@
 //         mean / std rule on the bbox rectangle, then equalize_adapthist + resize (preprocess.hip)
 //
 // Four kernels per batch, then the preprocess kernel itself:
-//   ex_label_pass   ONE read of the int32 label images.  A lane owns 4 columns x 16 rows and keeps the bbox of the
-//                   label it is in; label rows are long runs of one value, so it flushes (four integer atomics) only
-//                   when the label changes.  At the end the 64 lanes of a wave merge their open labels by wave
-//                   reduction, one set of atomics per distinct label.
+//   ex_label_pass   ONE read of the int32 label images, on the tile of label_tile.hpp.  A lane keeps the bbox of the
+//                   label it is in and flushes (four integer atomics) only when the label changes.  At the end the 64
+//                   lanes of a wave merge their open labels (merge_open_runs), one set of atomics per distinct label.
 //   ex_region_pass  one workgroup per (image, label) slot over the region's bbox window: exact int64 moment sums
 //                   (area, first and second moments), exact intensity sums of the analysis channel over the whole
 //                   rectangle, each row's extreme pixels (LDS), the convex hull of the pixel-edge midpoints as two
@@ -20,22 +19,17 @@
 //                   analysis channel into the ragged layout preprocess.hip reads.
 // Integers throughout up to the final quotients; no float atomics, so every output is bit-identical run to run and
 // independent of which other images share the batch (a slot's work reads nothing but its own image).
-#include "api_internal.hpp"
-
-#include <hip/hip_runtime.h>
+#include "label_tile.hpp"
+#include "stage_host.hpp"
 
 #include <algorithm>
 #include <climits>
 
 namespace cs {
 
-static constexpr int EX_THREADS = 256;
+static constexpr int EX_THREADS = LT_THREADS;           // of the region pass, the sweeps and the gather too
 static constexpr int EX_WAVES = EX_THREADS / 64;
-static constexpr int LP_ROWS = 16;                      // rows per wave in the label pass
-static constexpr int LP_COLS = 4 * 64;                  // columns per wave (4 per lane)
-static constexpr int kMaxLabel = 1 << 20;               // per image
 static constexpr int64_t kMaxSlots = 1 << 22;           // batch * max_label
-static constexpr int kMaxSide = 4096;                   // image height / width (LDS of the region pass: ~20 B per row)
 static constexpr int SCAN_THREADS = 1024;
 
 struct ExQc {
@@ -58,25 +52,6 @@ struct SlotIdx {
 struct GatherDesc {
     int image, minr, minc, pad;
 };
-
-__device__ inline int ex_wave_min(int v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = min(v, __shfl_xor(v, m));
-    return v;
-}
-__device__ inline int ex_wave_max(int v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = max(v, __shfl_xor(v, m));
-    return v;
-}
-__device__ inline long long ex_wave_sum(long long v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
 
 __device__ inline long long floor_div(long long a, long long d) { return a >= 0 ? a / d : -((-a + d - 1) / d); }   // d > 0
 __device__ inline long long ceil_div(long long a, long long d) { return -floor_div(-a, d); }
@@ -130,30 +105,22 @@ __device__ inline void bbox_flush(int4* bbox, int64_t slot, int r0, int c0, int 
 __global__ __launch_bounds__(EX_THREADS) void ex_label_pass(const int* __restrict__ labels, int H, int W, int max_label,
                                                             int4* __restrict__ bbox, ExCounts* __restrict__ counts)
 {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int b = blockIdx.z;
-    const int c_base = blockIdx.x * LP_COLS + 4 * lane;
-    const int r_base = (blockIdx.y * EX_WAVES + wave) * LP_ROWS;
-    const int* lab = labels + (size_t)b * H * W;
-    const int64_t slot0 = (int64_t)b * max_label - 1;
+    const LabelTile tile = label_tile();
+    const int r_base = tile.r_base, c_base = tile.c_base;
+    const int* lab = labels + (size_t)tile.b * H * W;
+    const int64_t slot0 = (int64_t)tile.b * max_label - 1;
     const bool vec = (W & 3) == 0 && ((uintptr_t)labels & 15) == 0 && c_base + 3 < W;
 
-    int v[LP_ROWS][4];
+    int v[LT_ROWS][4];
 #pragma unroll
-    for (int i = 0; i < LP_ROWS; ++i) {
+    for (int i = 0; i < LT_ROWS; ++i) {
         const int r = r_base + i;
-        if (r < H && vec) {
-            const int4 q = *(const int4*)(lab + (size_t)r * W + c_base);
-            v[i][0] = q.x; v[i][1] = q.y; v[i][2] = q.z; v[i][3] = q.w;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) v[i][k] = (r < H && c_base + k < W) ? lab[(size_t)r * W + c_base + k] : 0;
-        }
+        label_load4(lab + (size_t)r * W + c_base, r < H ? W - c_base : 0, vec && r < H, v[i]);
     }
     unsigned int err = 0u;
     int L = 0, r0 = 0, c0 = 0, r1 = 0, c1 = 0;
 #pragma unroll
-    for (int i = 0; i < LP_ROWS; ++i) {
+    for (int i = 0; i < LT_ROWS; ++i) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int x = v[i][k];
@@ -170,17 +137,11 @@ __global__ __launch_bounds__(EX_THREADS) void ex_label_pass(const int* __restric
     }
     if (err) atomicOr(&counts->err, err);
     // the open label of every lane: one set of atomics per distinct label of the wave
-    for (;;) {
-        const unsigned long long m = __ballot(L != 0);
-        if (m == 0ull) break;
-        const int leader = __ffsll((long long)m) - 1;
-        const int Lw = __shfl(L, leader);
-        const bool mine = L == Lw;
-        const int a = ex_wave_min(mine ? r0 : INT_MAX), bmin = ex_wave_min(mine ? c0 : INT_MAX);
-        const int cmax = ex_wave_max(mine ? r1 : -1), dmax = ex_wave_max(mine ? c1 : -1);
-        if (lane == leader) bbox_flush(bbox, slot0 + Lw, a, bmin, cmax, dmax);
-        if (mine) L = 0;
-    }
+    merge_open_runs(L != 0, L, tile.lane, [&](int Lw, bool mine, bool leader) {
+        const int a = wave_min(mine ? r0 : INT_MAX), bmin = wave_min(mine ? c0 : INT_MAX);
+        const int cmax = wave_max(mine ? r1 : -1), dmax = wave_max(mine ? c1 : -1);
+        if (leader) bbox_flush(bbox, slot0 + Lw, a, bmin, cmax, dmax);
+    });
 }
 
 // ---- per-region pass -------------------------------------------------------------------------------------------------------
@@ -279,14 +240,14 @@ __global__ __launch_bounds__(EX_THREADS) void ex_region_pass(const int* __restri
                 jmin = min(jmin, j); jmax = max(jmax, j);
             }
         }
-        jmin = ex_wave_min(jmin);
-        jmax = ex_wave_max(jmax);
+        jmin = wave_min(jmin);
+        jmax = wave_max(jmax);
         if (lane == 0) { rowL[i] = (short)jmin; rowR[i] = (short)jmax; }
     }
     long long v[8] = {n, si, sj, sii, sjj, sij, (long long)sx, (long long)sxx};
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-        v[k] = ex_wave_sum(v[k]);
+        v[k] = wave_sum(v[k]);
         if (lane == 0) red[wave][k] = v[k];
     }
     __syncthreads();                                    // rowL / rowR and the partial sums are complete
@@ -308,7 +269,7 @@ __global__ __launch_bounds__(EX_THREADS) void ex_region_pass(const int* __restri
         const long long a = max(jl, 0ll), e = min(jr, (long long)w - 1);
         if (e >= a) cnt += e - a + 1;
     }
-    cnt = ex_wave_sum(cnt);
+    cnt = wave_sum(cnt);
     if (lane == 0) red[wave][8] = cnt;
     __syncthreads();
     if (tid != 0) return;
@@ -427,9 +388,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void ex_scan(cs_region* __restrict__ 
         idx[s] = q;
     }
     // largest preprocess LDS over the cells
-    long long m = lds;
-#pragma unroll
-    for (int k = 32; k >= 1; k >>= 1) m = max(m, (long long)__shfl_xor(m, k));
+    long long m = wave_max(lds);
     if ((t & 63) == 0) lmax[t >> 6] = m;
     __syncthreads();
     if (t == 0) {
@@ -479,7 +438,7 @@ struct ExtractState {
     DevBuf lab, img;                                    // uploads of host inputs
     DevBuf bbox, rec, idx, flags, status, counts;
     DevBuf regions, cell_image, desc, gat, cpix, clahe, cells;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    StageClock clk;                                     // spans: label, region, between the two calls (no step), cells
     bool measured = false;
     const void* d_img = nullptr;
     int ptype = 0, C = 1, ch = 0, batch = 0, H = 0, W = 0, max_label = 0;
@@ -487,12 +446,6 @@ struct ExtractState {
     int64_t nslots = 0;
     double clip_limit = 0.02;
     ExCounts host{};
-    double label_ms = 0.0, region_ms = 0.0, cells_ms = 0.0;
-    ~ExtractState()
-    {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
 };
 
 void extract_state_free(ExtractState* s) { delete s; }
@@ -510,17 +463,14 @@ int cs_extract_measure(cs_preproc* p, const void* image, int pixel_type, int32_t
     if (n_cells) *n_cells = 0;
     if (!image || !labels || !n_regions || !n_cells) return fail(CS_ERR_INVALID, "NULL argument");
     if (pixel_type != CS_PIX_U8 && pixel_type != CS_PIX_U16) return fail(CS_ERR_INVALID, "pixel_type must be CS_PIX_U8 or CS_PIX_U16");
-    if (in_kind != CS_MEM_HOST && in_kind != CS_MEM_DEVICE) return fail(CS_ERR_INVALID, "in_kind must be CS_MEM_HOST or CS_MEM_DEVICE");
+    if (!mem_kind(in_kind)) return fail(CS_ERR_INVALID, "in_kind must be CS_MEM_HOST or CS_MEM_DEVICE");
     if (channels < 1 || channel < 0 || channel >= channels)
         return fail(CS_ERR_INVALID, "channel %d of %d: need 0 <= channel < channels", (int)channel, (int)channels);
-    if (batch < 1 || height < 1 || width < 1) return fail(CS_ERR_INVALID, "batch %d, height %d, width %d: all must be >= 1", (int)batch,
-                                                          (int)height, (int)width);
-    if (height > kMaxSide || width > kMaxSide)
-        return fail(CS_ERR_UNSUPPORTED, "image %dx%d: sides above %d are not supported", (int)height, (int)width, kMaxSide);
+    int rc;
+    if ((rc = stack_dims(batch, height, width)) || (rc = side_limits(height, width))) return rc;   // the region pass keeps ~20 B of LDS per row
     if (max_label < 0) return fail(CS_ERR_INVALID, "max_label is negative");
-    if (max_label > kMaxLabel || (int64_t)batch * max_label > kMaxSlots)
-        return fail(CS_ERR_UNSUPPORTED, "max_label %d x batch %d: per-label tables are capped at %d labels per image and %lld per batch; "
-                    "relabel sparse ids in order first", (int)max_label, (int)batch, kMaxLabel, (long long)kMaxSlots);
+    if ((rc = label_cap("max_label", max_label, batch, 0, kMaxSlots, "per-label tables", "per batch; relabel sparse ids in order first")))
+        return rc;
     cs_qc_params q{10, 200, 8000, 0, 0.95, 0.5, 0.1, 0.02};
     if (qc) {
         q = *qc;
@@ -529,24 +479,18 @@ int cs_extract_measure(cs_preproc* p, const void* image, int pixel_type, int32_t
             !(q.min_std == q.min_std))
             return fail(CS_ERR_INVALID, "cs_qc_params holds a NaN");
     }
-    if (!p) {
-        const int rc = require_gfx950(0);
-        return rc ? rc : fail(CS_ERR_INVALID, "handle is NULL");
-    }
+    if ((rc = handle_check(p))) return rc;
     HIPCHK(hipSetDevice(p->device));
     if (!p->ext) p->ext = new ExtractState();
     ExtractState& S = *p->ext;
     S.measured = false;
     p->extract_pending = false;
     const int out_h = p->out_h, out_w = p->out_w;
-    for (hipEvent_t& e : S.ev)
-        if (!e) HIPCHK(hipEventCreate(&e));
 
     const size_t esz = pixel_type == CS_PIX_U8 ? 1 : 2;
     const size_t npx = (size_t)batch * height * width;
     const int* d_lab;
     const void* d_img;
-    int rc;
     if (in_kind == CS_MEM_DEVICE) {
         d_lab = labels;
         d_img = image;
@@ -568,13 +512,11 @@ int cs_extract_measure(cs_preproc* p, const void* image, int pixel_type, int32_t
     hipLaunchKernelGGL(ex_init, dim3(init_blocks), dim3(EX_THREADS), 0, p->stream, S.bbox.as<int4>(), nslots, S.flags.as<unsigned int>(),
                        (int)batch, S.counts.as<ExCounts>());
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(S.ev[0], p->stream));
-    const dim3 lgrid((unsigned)((width + LP_COLS - 1) / LP_COLS), (unsigned)((height + EX_WAVES * LP_ROWS - 1) / (EX_WAVES * LP_ROWS)),
-                     (unsigned)batch);
-    hipLaunchKernelGGL(ex_label_pass, lgrid, dim3(EX_THREADS), 0, p->stream, d_lab, (int)height, (int)width, (int)max_label,
+    if ((rc = S.clk.record(0, p->stream))) return rc;
+    hipLaunchKernelGGL(ex_label_pass, label_tile_grid(batch, height, width), dim3(EX_THREADS), 0, p->stream, d_lab, (int)height, (int)width, (int)max_label,
                        S.bbox.as<int4>(), S.counts.as<ExCounts>());
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(S.ev[1], p->stream));
+    if ((rc = S.clk.record(1, p->stream))) return rc;
     if (nslots > 0) {
         const size_t lds = (((size_t)4 * height + 15) & ~(size_t)15) + (size_t)2 * (2 * height + 2) * sizeof(int);
         if (pixel_type == CS_PIX_U8) {
@@ -593,15 +535,11 @@ int cs_extract_measure(cs_preproc* p, const void* image, int pixel_type, int32_t
     hipLaunchKernelGGL(ex_scan, dim3(1), dim3(SCAN_THREADS), 0, p->stream, S.rec.as<cs_region>(), nslots, (int)std::max(max_label, 1),
                        S.flags.as<unsigned int>(), (int)batch, S.status.as<int>(), S.idx.as<SlotIdx>(), S.counts.as<ExCounts>());
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(S.ev[2], p->stream));
+    if ((rc = S.clk.record(2, p->stream))) return rc;
     HIPCHK(hipMemcpyAsync(&S.host, S.counts.p, sizeof(ExCounts), hipMemcpyDeviceToHost, p->stream));
     HIPCHK(hipStreamSynchronize(p->stream));              // host synchronisation 1 of 2: the counts
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, S.ev[0], S.ev[1]));
-    S.label_ms = ms;
-    HIPCHK(hipEventElapsedTime(&ms, S.ev[1], S.ev[2]));
-    S.region_ms = ms;
-    S.cells_ms = 0.0;
+    if ((rc = S.clk.finish())) return rc;
+    S.clk.ms[3] = 0.0;                                    // the cells of an earlier fill are not this measure's
     if (S.host.err & 1u) return fail(CS_ERR_INVALID, "negative label in the label images");
     if (S.host.err & 2u) return fail(CS_ERR_INVALID, "a label exceeds max_label = %d", (int)max_label);
     S.d_img = d_img;
@@ -619,19 +557,15 @@ int cs_extract_measure(cs_preproc* p, const void* image, int pixel_type, int32_t
 int cs_extract_fill(cs_preproc* p, cs_region* regions, int32_t* image_status, int table_kind, float* cells, int32_t* cell_image,
                     int cells_kind)
 {
-    if ((table_kind != CS_MEM_HOST && table_kind != CS_MEM_DEVICE) || (cells_kind != CS_MEM_HOST && cells_kind != CS_MEM_DEVICE))
-        return fail(CS_ERR_INVALID, "table_kind / cells_kind must be CS_MEM_HOST or CS_MEM_DEVICE");
-    if (!p) {
-        const int rc = require_gfx950(0);
-        return rc ? rc : fail(CS_ERR_INVALID, "handle is NULL");
-    }
+    if (!mem_kind(table_kind) || !mem_kind(cells_kind)) return fail(CS_ERR_INVALID, "table_kind / cells_kind must be CS_MEM_HOST or CS_MEM_DEVICE");
+    int rc;
+    if ((rc = handle_check(p))) return rc;
     if (!p->ext || !p->ext->measured) return fail(CS_ERR_INVALID, "cs_extract_fill without a successful cs_extract_measure on this handle");
     HIPCHK(hipSetDevice(p->device));
     ExtractState& S = *p->ext;
     const int64_t nreg = S.host.n_regions, ncell = S.host.n_cells;
     const bool tdev = table_kind == CS_MEM_DEVICE, dev = cells_kind == CS_MEM_DEVICE;
     const size_t cell = (size_t)S.out_h * S.out_w;       // floats of one cell, as measured
-    int rc;
     cs_region* d_reg = nullptr;
     if (regions && nreg > 0) {
         if (tdev) d_reg = regions;
@@ -667,7 +601,7 @@ int cs_extract_fill(cs_preproc* p, cs_region* regions, int32_t* image_status, in
                            d_reg, S.desc.as<CropDesc>(), S.gat.as<GatherDesc>(), d_cimg);
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipEventRecord(S.ev[3], p->stream));
+    if ((rc = S.clk.record(3, p->stream, false))) return rc;      // since the measure's last event: no step of this clock
     if (d_cells) {
         if (S.ptype == CS_PIX_U8)
             hipLaunchKernelGGL(ex_gather<unsigned char>, dim3((unsigned)ncell), dim3(EX_THREADS), 0, p->stream, (const unsigned char*)S.d_img,
@@ -679,7 +613,7 @@ int cs_extract_fill(cs_preproc* p, cs_region* regions, int32_t* image_status, in
         HIPCHK(launch_preprocess(S.cpix.p, S.ptype, S.desc.as<CropDesc>(), ncell, S.clip_limit, (size_t)S.host.lds, S.clahe.as<uint16_t>(),
                                  d_cells, S.out_h, S.out_w, p->stream));
     }
-    HIPCHK(hipEventRecord(S.ev[4], p->stream));
+    if ((rc = S.clk.record(4, p->stream))) return rc;
     if (image_status) {
         if (tdev) HIPCHK(hipMemcpyAsync(image_status, S.status.p, S.batch * sizeof(int), hipMemcpyDeviceToDevice, p->stream));
         else HIPCHK(hipMemcpyAsync(image_status, S.status.p, S.batch * sizeof(int), hipMemcpyDeviceToHost, p->stream));
@@ -690,19 +624,12 @@ int cs_extract_fill(cs_preproc* p, cs_region* regions, int32_t* image_status, in
         if (d_cells) HIPCHK(hipMemcpyAsync(cells, d_cells, (size_t)ncell * cell * sizeof(float), hipMemcpyDeviceToHost, p->stream));
     }
     HIPCHK(hipStreamSynchronize(p->stream));              // host synchronisation 2 of 2: the table and the cells
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, S.ev[3], S.ev[4]));
-    S.cells_ms = ms;
+    if ((rc = S.clk.finish())) return rc;
     p->extract_pending = false;                           // the handle's output size may change again
     return CS_OK;
 }
 
 int cs_extract_last_timing(const cs_preproc* p, double* label_ms, double* region_ms, double* cells_ms)
 {
-    if (!p) return fail(CS_ERR_INVALID, "handle is NULL");
-    const ExtractState* S = p->ext;
-    if (label_ms) *label_ms = S ? S->label_ms : 0.0;
-    if (region_ms) *region_ms = S ? S->region_ms : 0.0;
-    if (cells_ms) *cells_ms = S ? S->cells_ms : 0.0;
-    return CS_OK;
+    return clock_read(p, p && p->ext ? &p->ext->clk : nullptr, {label_ms, region_ms, nullptr, cells_ms});
 }

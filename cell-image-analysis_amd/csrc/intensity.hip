@@ -5,34 +5,29 @@
 // sum v, sum v^2, sum v*r, sum v*c, min v, max v.  All integers; mean, standard deviation, centroid and intensity-weighted
 // centroid follow from them on the host.  Scattered global atomics are slow (the guides put single-lane ones at about 1/17 of
 // the shaped rate), so, as lm_count (match.hip), the design makes them rare instead of fast:
-//   li_pass      ONE read of every plane, 16-byte label loads where width and pointers allow (ex_label_pass's tiling: a lane
-//                owns 4 columns x 16 rows, a wave 256 columns, a workgroup 64 rows).  A lane keeps one open run of its label
-//                with the sums of the run, coordinates relative to the tile so that all but sum v^2 stay in 32 bits; the tile's
-//                origin is added once, when the run is flushed.  Flushes go into a table in LDS that the workgroup owns, keyed
-//                by the label (64-bit integer adds, 32-bit min / max); the lanes' last runs are first merged per distinct label
-//                by the ballot loop of lm_count.  Only the distinct labels of the tile go on to the dense tables in global
-//                memory, as 64-bit integer atomics: 3 + 6 C per label and tile, not per run.  A record is 3 + 4 C sums of 8
-//                bytes and 2 C words, 28 + 40 C bytes with its key, so the table has LI_SLOTS<C> slots: 512 at C = 1, 256
-//                above (DESIGN 3u has the occupancy).  A label that finds no room in LDS goes to the global tables directly.
+//   li_pass      ONE read of every plane, 16-byte label loads where width and pointers allow, on the tile of label_tile.hpp.
+//                A lane keeps one open run of its label with the sums of the run, coordinates relative to the tile so that
+//                all but sum v^2 stay in 32 bits; the tile's origin is added once, when the run is flushed.  Flushes go into
+//                a table in LDS that the workgroup owns, keyed by the label (64-bit integer adds, 32-bit min / max); the
+//                lanes' last runs are first merged per distinct label.  Only the distinct labels of the
+//                tile go on to the dense tables in global memory, as 64-bit integer atomics: 3 + 6 C per label and tile, not
+//                per run.  A record is 3 + 4 C sums of 8 bytes and 2 C words, 28 + 40 C bytes with its key, so the table has
+//                LI_SLOTS<C> slots: 512 at C = 1, 256 above (DESIGN 3u has the occupancy).  A label that finds no room in LDS
+//                goes to the global tables directly.
 //   li_close     the minimum travels as 65536 - v under an atomic maximum, so that cleared tables need no second initial
 //                value; this pass turns it back, and an absent object keeps its zeros.
 // No floating point; every result is a sum, a minimum or a maximum of integers, so it does not depend on the order of
 // arrival or on slot placement, and is bit-identical run to run.  A label is range-checked before it is a key or an index.
+#include "label_tile.hpp"
 #include "segment_internal.hpp"
-
-#include <hip/hip_runtime.h>
 
 #include <algorithm>
 
 namespace cs {
 
-static constexpr int LI_THREADS = 256;
-static constexpr int LI_WAVES = LI_THREADS / 64;
-static constexpr int LI_ROWS = 16;                      // rows per wave
-static constexpr int LI_COLS = 4 * 64;                  // columns per wave (4 per lane)
+static constexpr int LI_THREADS = LT_THREADS;           // of li_close too
 static constexpr int LI_LDS_PROBES = 16;
 static constexpr int kLiMaxChannels = 4;
-static constexpr int kLiMaxLabel = 1 << 20;             // per image
 static constexpr int64_t kLiMaxCells = 1 << 22;         // batch * max_label * channels
 static constexpr unsigned int LI_MIN_BIAS = 65536u;     // a minimum v travels as LI_MIN_BIAS - v >= 1
 
@@ -131,13 +126,9 @@ template <int C> __device__ inline void li_insert(LiLds<C>& L, const LiTables& T
     li_global<C>(T, b, label, o);                       // no room: straight to the global tables
 }
 
-__device__ inline unsigned long long li_wave_sum(unsigned long long v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
-
+// li_pass keeps its own load of a row, its own closing merge and its own claim of an LDS slot (li_insert) instead of
+// label_load4, merge_open_runs and table_claim of label_tile.hpp: with them it takes up to 31 fewer VGPRs, and its pass at one
+// channel without `exclude` measured 3 % slower than this form on an MI355X (profiles/label_tools_refactor.json).
 // grid (ceil(W/256), ceil(H/64), B).  image: [B][H][W][C] PIX; labels, exclude (or null): [B][H][W] int.  vec: the width is a
 // multiple of 4 and every plane's pointer allows the wide loads (decided on the host).
 template <typename PIX, int C>
@@ -159,11 +150,9 @@ __global__ __launch_bounds__(LI_THREADS) void li_pass(const PIX* __restrict__ im
     }
     __syncthreads();
 
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int b = blockIdx.z;
-    const unsigned int r0 = blockIdx.y * (LI_WAVES * LI_ROWS), c0 = blockIdx.x * LI_COLS;
-    const int c_base = (int)c0 + 4 * lane;
-    const int r_base = (int)r0 + wave * LI_ROWS;
+    const LabelTile tile = label_tile();
+    const int lane = tile.lane, b = tile.b, c_base = tile.c_base;
+    const unsigned int r0 = tile.r0, c0 = tile.c0;
     const size_t plane = (size_t)b * H * W;
     const int* ll = labels + plane;
     const int* ee = exclude ? exclude + plane : nullptr;
@@ -178,8 +167,8 @@ __global__ __launch_bounds__(LI_THREADS) void li_pass(const PIX* __restrict__ im
     LiRun<C> run;
     li_reset<C>(run);
 #pragma unroll 2
-    for (int i = 0; i < LI_ROWS; ++i) {
-        const int r = r_base + i;
+    for (int i = 0; i < LT_ROWS; ++i) {
+        const int r = tile.r_base + i;
         if (r >= H) break;                              // uniform over the wave
         int x[4], e[4] = {0, 0, 0, 0};
         PIX px[4 * C];
@@ -202,7 +191,7 @@ __global__ __launch_bounds__(LI_THREADS) void li_pass(const PIX* __restrict__ im
                 for (int ch = 0; ch < C; ++ch) px[k * C + ch] = in ? im[(at + k) * C + ch] : (PIX)0;
             }
         }
-        const unsigned int rr = (unsigned int)(wave * LI_ROWS + i);
+        const unsigned int rr = (unsigned int)(tile.wave * LT_ROWS + i);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int lab = x[k];
@@ -244,7 +233,7 @@ __global__ __launch_bounds__(LI_THREADS) void li_pass(const PIX* __restrict__ im
         const bool mine = open && cur == lw;
         LiRec<C> o;
 #pragma unroll
-        for (int j = 0; j < 3 + 4 * C; ++j) o.s[j] = li_wave_sum(mine ? mine_rec.s[j] : 0ull);
+        for (int j = 0; j < 3 + 4 * C; ++j) o.s[j] = wave_sum(mine ? mine_rec.s[j] : 0ull);
 #pragma unroll
         for (int ch = 0; ch < C; ++ch) {
             unsigned int lo = mine ? mine_rec.mn[ch] : 0xFFFFFFFFu, hi = mine ? mine_rec.mx[ch] : 0u;
@@ -291,8 +280,7 @@ template <typename PIX, int C>
 static void li_launch(const void* image, const int* labels, const int* exclude, int batch, int H, int W, int vec, const LiTables& T,
                       unsigned int* ctrl, hipStream_t st)
 {
-    const dim3 grid((unsigned)((W + LI_COLS - 1) / LI_COLS), (unsigned)((H + LI_WAVES * LI_ROWS - 1) / (LI_WAVES * LI_ROWS)), (unsigned)batch);
-    hipLaunchKernelGGL((li_pass<PIX, C>), grid, dim3(LI_THREADS), 0, st, (const PIX*)image, labels, exclude, H, W, vec, T, ctrl);
+    hipLaunchKernelGGL((li_pass<PIX, C>), label_tile_grid(batch, H, W), dim3(LI_THREADS), 0, st, (const PIX*)image, labels, exclude, H, W, vec, T, ctrl);
 }
 
 template <typename PIX>
@@ -318,19 +306,14 @@ int cs_label_intensity(cs_preproc* p, const void* image, int pixel_type, int32_t
 {
     if (!image || !labels || !geom || !stats) return fail(CS_ERR_INVALID, "NULL argument");
     if (pixel_type != CS_PIX_U8 && pixel_type != CS_PIX_U16) return fail(CS_ERR_INVALID, "pixel_type must be CS_PIX_U8 or CS_PIX_U16");
-    if ((in_kind != CS_MEM_HOST && in_kind != CS_MEM_DEVICE) || (out_kind != CS_MEM_HOST && out_kind != CS_MEM_DEVICE))
-        return fail(CS_ERR_INVALID, "in_kind / out_kind must be CS_MEM_HOST or CS_MEM_DEVICE");
+    if (!mem_kind(in_kind) || !mem_kind(out_kind)) return fail(CS_ERR_INVALID, "in_kind / out_kind must be CS_MEM_HOST or CS_MEM_DEVICE");
     if (channels < 1) return fail(CS_ERR_INVALID, "channels %d: must be >= 1", (int)channels);
-    if (batch < 1 || height < 1 || width < 1) return fail(CS_ERR_INVALID, "batch %d, height %d, width %d: all must be >= 1", (int)batch,
-                                                          (int)height, (int)width);
+    int rc;
+    if ((rc = stack_dims(batch, height, width))) return rc;
     if (max_label < 1) return fail(CS_ERR_INVALID, "max_label %d: must be >= 1", (int)max_label);
     if (channels > kLiMaxChannels)
         return fail(CS_ERR_UNSUPPORTED, "channels %d: at most %d are measured per call (split the stack)", (int)channels, kLiMaxChannels);
-    if (max_label > kLiMaxLabel || (int64_t)batch * max_label * channels > kLiMaxCells)
-        return fail(CS_ERR_UNSUPPORTED, "max_label %d x batch %d x channels %d: the tables are capped at %d labels per image and %lld cells",
-                    (int)max_label, (int)batch, (int)channels, kLiMaxLabel, (long long)kLiMaxCells);
-    int rc;
-    if ((rc = image_limits(batch, height, width)) || (rc = handle_check(p)) || (rc = state_begin(p))) return rc;
+    if ((rc = label_cap("max_label", max_label, batch, channels, kLiMaxCells, "the tables", "cells")) || (rc = image_limits(batch, height, width)) || (rc = handle_check(p)) || (rc = state_begin(p))) return rc;
     SegmentState& S = *p->seg;
     hipStream_t st = p->stream;
     const int H = height, W = width, C = channels;

@@ -5,10 +5,10 @@
 // the background.  It lives in an open-addressing table in global memory, keyed by (image, p, t) in 58 bits with 0 for an empty
 // slot: a 64-bit atomicCAS claims the key, a 32-bit atomicAdd adds the count.  Scattered global atomics are slow (the guides put
 // single-lane ones at about 1/17 of the shaped rate), so the design makes them rare instead of fast:
-//   lm_count     ONE read of the two planes, 8 bytes per pixel, 16-byte loads where width and pointers allow (ex_label_pass's
-//                tiling: a lane owns 4 columns x 16 rows, a wave 256 columns, a workgroup 64 rows).  A lane keeps one open run of
-//                (p, t) with its count and flushes when the pair changes; flushes go into a table in LDS that the workgroup
-//                owns (1024 slots), the lanes' last runs merged per distinct pair by the ballot loop of ex_label_pass first.
+//   lm_count     ONE read of the two planes, 8 bytes per pixel, 16-byte loads where width and pointers allow, on the tile
+//                of label_tile.hpp.  A lane keeps one open run of (p, t) with its count and flushes when the pair changes;
+//                flushes go into a table in LDS that the workgroup owns (1024 slots), the lanes' last runs merged per distinct
+//                pair (merge_open_runs) first.
 //                Only the distinct entries of the LDS table go on to the global one: one global atomic pair per distinct pair
 //                and tile, not per run.  A pair that finds no room in LDS goes to the global table directly.  Pairs with one
 //                side 0 are kept (they complete the areas); (0, 0) is not counted.
@@ -21,24 +21,18 @@
 // everything again.  No floating point; every result is a sum, a maximum or a count of integers, so it does not depend on
 // insertion order, slot placement or capacity, and is bit-identical run to run.  A label is range-checked before it forms a key,
 // and the reduction decodes only keys that passed: no kernel indexes with an unchecked label.
-#include "api_internal.hpp"
-
-#include <hip/hip_runtime.h>
+#include "label_tile.hpp"
+#include "stage_host.hpp"
 
 #include <algorithm>
 
 namespace cs {
 
-static constexpr int LM_THREADS = 256;
-static constexpr int LM_WAVES = LM_THREADS / 64;
-static constexpr int LM_ROWS = 16;                      // rows per wave
-static constexpr int LM_COLS = 4 * 64;                  // columns per wave (4 per lane)
+static constexpr int LM_THREADS = LT_THREADS;           // of the slot sweeps too
 static constexpr int LM_LDS_LOG2 = 10;
 static constexpr int LM_LDS_SLOTS = 1 << LM_LDS_LOG2;   // 12 KB of LDS
 static constexpr int LM_LDS_PROBES = 16;
 static constexpr int LM_PROBES = 64;                    // of the global table, before the call asks for a larger one
-static constexpr int kLmMaxSide = 4096, kLmMaxBatch = 65535;
-static constexpr int kLmMaxLabel = 1 << 20;             // per image
 static constexpr int64_t kLmMaxRows = 1 << 22;          // batch * max, for each side
 static constexpr int kLmMinLog2 = 10, kLmMaxLog2 = 26, kLmAutoMinLog2 = 16;
 static constexpr unsigned long long kLmMul = 0x9E3779B97F4A7C15ull;
@@ -51,41 +45,12 @@ __device__ inline unsigned long long lm_key(int b, int p, int t)
     return ((unsigned long long)b << 42) | ((unsigned long long)p << 21) | (unsigned long long)t;   // p, t <= 2^20; not both 0
 }
 
-__device__ inline bool lm_lds_insert(unsigned long long* lk, unsigned int* lc, unsigned long long key, unsigned int n)
+// n more pixels of `key` in a table of 2^log2 slots, in LDS or global; false: no room within `probes` slots
+__device__ inline bool lm_add(unsigned long long* keys, unsigned int* cnt, int log2, int probes, unsigned long long key, unsigned int n)
 {
-    unsigned int h = (unsigned int)((key * kLmMul) >> (64 - LM_LDS_LOG2));
-    for (int i = 0; i < LM_LDS_PROBES; ++i) {
-        const unsigned long long old = atomicCAS(&lk[h], 0ull, key);
-        if (old == 0ull || old == key) {
-            atomicAdd(&lc[h], n);
-            return true;
-        }
-        h = (h + 1) & (LM_LDS_SLOTS - 1);
-    }
-    return false;
-}
-
-__device__ inline bool lm_insert(unsigned long long* __restrict__ keys, unsigned int* __restrict__ cnt, int cap_log2,
-                                 unsigned long long key, unsigned int n)
-{
-    const unsigned int mask = (1u << cap_log2) - 1u;
-    unsigned int h = (unsigned int)((key * kLmMul) >> (64 - cap_log2));
-    for (int i = 0; i < LM_PROBES; ++i) {
-        const unsigned long long old = atomicCAS(&keys[h], 0ull, key);
-        if (old == 0ull || old == key) {
-            atomicAdd(&cnt[h], n);
-            return true;
-        }
-        h = (h + 1) & mask;
-    }
-    return false;
-}
-
-__device__ inline unsigned int lm_wave_sum(unsigned int v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
+    const int slot = table_claim(keys, log2, (unsigned int)((key * kLmMul) >> (64 - log2)), key, probes);
+    if (slot >= 0) atomicAdd(&cnt[slot], n);
+    return slot >= 0;
 }
 
 // grid (ceil(W/256), ceil(H/64), B)
@@ -101,34 +66,25 @@ __global__ __launch_bounds__(LM_THREADS) void lm_count(const int* __restrict__ p
     }
     __syncthreads();
 
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int b = blockIdx.z;
-    const int c_base = blockIdx.x * LM_COLS + 4 * lane;
-    const int r_base = (blockIdx.y * LM_WAVES + wave) * LM_ROWS;
+    const LabelTile tile = label_tile();
+    const int b = tile.b, c_base = tile.c_base;
     const int* pp = pred + (size_t)b * H * W;
     const int* tt = truth + (size_t)b * H * W;
     const bool vec = (W & 3) == 0 && (((uintptr_t)pred | (uintptr_t)truth) & 15) == 0 && c_base + 3 < W;
+    // to the workgroup's table, or past it when that has no room
+    const auto put = [&](unsigned long long key, unsigned int n) {
+        return lm_add(lk, lc, LM_LDS_LOG2, LM_LDS_PROBES, key, n) || lm_add(keys, cnt, cap_log2, LM_PROBES, key, n);
+    };
 
     unsigned int flags = 0u, n = 0u;
     int cp = 0, ct = 0;                                 // the open run: n pixels of (cp, ct)
 #pragma unroll 4
-    for (int i = 0; i < LM_ROWS; ++i) {
-        const int r = r_base + i;
+    for (int i = 0; i < LT_ROWS; ++i) {
+        const int r = tile.r_base + i;
         if (r >= H) break;                              // uniform over the wave
         int x[4], y[4];
-        if (vec) {
-            const int4 q = *(const int4*)(pp + (size_t)r * W + c_base);
-            const int4 u = *(const int4*)(tt + (size_t)r * W + c_base);
-            x[0] = q.x; x[1] = q.y; x[2] = q.z; x[3] = q.w;
-            y[0] = u.x; y[1] = u.y; y[2] = u.z; y[3] = u.w;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const bool in = c_base + k < W;
-                x[k] = in ? pp[(size_t)r * W + c_base + k] : 0;
-                y[k] = in ? tt[(size_t)r * W + c_base + k] : 0;
-            }
-        }
+        label_load4(pp + (size_t)r * W + c_base, W - c_base, vec, x);
+        label_load4(tt + (size_t)r * W + c_base, W - c_base, vec, y);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int p = x[k], t = y[k];
@@ -139,33 +95,21 @@ __global__ __launch_bounds__(LM_THREADS) void lm_count(const int* __restrict__ p
             if (n != 0u && p == cp && t == ct) {
                 ++n;
             } else {
-                if (n != 0u) {
-                    const unsigned long long key = lm_key(b, cp, ct);
-                    if (!lm_lds_insert(lk, lc, key, n) && !lm_insert(keys, cnt, cap_log2, key, n)) flags |= LM_FULL;
-                }
+                if (n != 0u && !put(lm_key(b, cp, ct), n)) flags |= LM_FULL;
                 cp = p; ct = t; n = 1u;
             }
         }
     }
     // the open run of every lane: one insertion per distinct pair of the wave
-    for (;;) {
-        const unsigned long long m = __ballot(n != 0u);
-        if (m == 0ull) break;
-        const int leader = __ffsll((long long)m) - 1;
-        const int pw = __shfl(cp, leader), tw = __shfl(ct, leader);
-        const bool mine = n != 0u && cp == pw && ct == tw;
-        const unsigned int sum = lm_wave_sum(mine ? n : 0u);
-        if (lane == leader) {
-            const unsigned long long key = lm_key(b, pw, tw);
-            if (!lm_lds_insert(lk, lc, key, sum) && !lm_insert(keys, cnt, cap_log2, key, sum)) flags |= LM_FULL;
-        }
-        if (mine) n = 0u;
-    }
+    merge_open_runs(n != 0u, lm_key(b, cp, ct), tile.lane, [&](unsigned long long key, bool mine, bool leader) {
+        const unsigned int sum = wave_sum(mine ? n : 0u);
+        if (leader && !put(key, sum)) flags |= LM_FULL;
+    });
     __syncthreads();
     // the distinct pairs of the tile
     for (int s = threadIdx.x; s < LM_LDS_SLOTS; s += LM_THREADS) {
         const unsigned long long key = lk[s];
-        if (key != 0ull && !lm_insert(keys, cnt, cap_log2, key, lc[s])) flags |= LM_FULL;
+        if (key != 0ull && !lm_add(keys, cnt, cap_log2, LM_PROBES, key, lc[s])) flags |= LM_FULL;
     }
     if (flags) atomicOr(ctrl, flags);
 }
@@ -200,8 +144,8 @@ __global__ __launch_bounds__(LM_THREADS) void lm_reduce(const unsigned long long
         if (p > 0) atomicAdd(&T.pred[prow * 4], (int)I);
         if (t > 0) atomicAdd(&T.truth[trow * 4], (int)I);
         if (p > 0 && t > 0) {
-            atomicMax(&T.ppart[prow], ((unsigned long long)I << 20) | (unsigned long long)(kLmMaxLabel - t));
-            atomicMax(&T.tpart[trow], ((unsigned long long)I << 20) | (unsigned long long)(kLmMaxLabel - p));
+            atomicMax(&T.ppart[prow], ((unsigned long long)I << 20) | (unsigned long long)(kMaxLabel - t));
+            atomicMax(&T.tpart[trow], ((unsigned long long)I << 20) | (unsigned long long)(kMaxLabel - p));
             atomicAdd(&T.pairs[b], 1ull);
         }
     }
@@ -233,7 +177,7 @@ __global__ __launch_bounds__(LM_THREADS) void lm_unpack(LmTables T, int64_t prow
         const unsigned long long w = ps ? T.ppart[row] : T.tpart[row];
         if (w == 0ull) continue;                         // the table was cleared: partner 0, overlap 0
         int* out = (ps ? T.pred : T.truth) + row * 4;
-        out[1] = kLmMaxLabel - (int)(w & (unsigned long long)(kLmMaxLabel - 1));
+        out[1] = kMaxLabel - (int)(w & (unsigned long long)(kMaxLabel - 1));
         out[2] = (int)(w >> 20);
     }
 }
@@ -242,14 +186,8 @@ struct MatchState {
     DevBuf pred, truth;                                 // uploads of host inputs
     DevBuf keys, cnt, ppart, tpart, pairs, ctrl;
     DevBuf ptab, ttab;                                  // tables on their way to host buffers
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    double count_ms = 0.0, reduce_ms = 0.0;
+    StageClock clk;                                     // spans: count, reduce
     int table_log2 = 0, grows = 0;
-    ~MatchState()
-    {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
 };
 
 void match_state_free(MatchState* s) { delete s; }
@@ -264,10 +202,9 @@ int cs_label_match(cs_preproc* p, const int32_t* pred, const int32_t* truth, int
                    int table_kind, int64_t* n_pairs)
 {
     if (!pred || !truth || !pred_table || !truth_table) return fail(CS_ERR_INVALID, "NULL argument");
-    if ((in_kind != CS_MEM_HOST && in_kind != CS_MEM_DEVICE) || (table_kind != CS_MEM_HOST && table_kind != CS_MEM_DEVICE))
-        return fail(CS_ERR_INVALID, "in_kind / table_kind must be CS_MEM_HOST or CS_MEM_DEVICE");
-    if (batch < 1 || height < 1 || width < 1) return fail(CS_ERR_INVALID, "batch %d, height %d, width %d: all must be >= 1", (int)batch,
-                                                          (int)height, (int)width);
+    if (!mem_kind(in_kind) || !mem_kind(table_kind)) return fail(CS_ERR_INVALID, "in_kind / table_kind must be CS_MEM_HOST or CS_MEM_DEVICE");
+    int rc;
+    if ((rc = stack_dims(batch, height, width))) return rc;
     if (max_pred < 1 || max_truth < 1) return fail(CS_ERR_INVALID, "max_pred %d, max_truth %d: both must be >= 1", (int)max_pred,
                                                    (int)max_truth);
     int log2 = 0;
@@ -277,24 +214,12 @@ int cs_label_match(cs_preproc* p, const int32_t* pred, const int32_t* truth, int
         if (log2 != 0 && (log2 < kLmMinLog2 || log2 > kLmMaxLog2))
             return fail(CS_ERR_INVALID, "table_log2 %d: 0 (automatic) or %d..%d", log2, kLmMinLog2, kLmMaxLog2);
     }
-    if (height > kLmMaxSide || width > kLmMaxSide)
-        return fail(CS_ERR_UNSUPPORTED, "image %dx%d: sides above %d are not supported", (int)height, (int)width, kLmMaxSide);
-    if (batch > kLmMaxBatch) return fail(CS_ERR_UNSUPPORTED, "batch %d: at most %d images per call", (int)batch, kLmMaxBatch);
-    if (max_pred > kLmMaxLabel || (int64_t)batch * max_pred > kLmMaxRows)
-        return fail(CS_ERR_UNSUPPORTED, "max_pred %d x batch %d: the tables are capped at %d labels per image and %lld per batch",
-                    (int)max_pred, (int)batch, kLmMaxLabel, (long long)kLmMaxRows);
-    if (max_truth > kLmMaxLabel || (int64_t)batch * max_truth > kLmMaxRows)
-        return fail(CS_ERR_UNSUPPORTED, "max_truth %d x batch %d: the tables are capped at %d labels per image and %lld per batch",
-                    (int)max_truth, (int)batch, kLmMaxLabel, (long long)kLmMaxRows);
-    if (!p) {
-        const int rc = require_gfx950(0);
-        return rc ? rc : fail(CS_ERR_INVALID, "handle is NULL");
-    }
+    if ((rc = image_limits(batch, height, width)) || (rc = label_cap("max_pred", max_pred, batch, 0, kLmMaxRows, "the tables", "per batch")) ||
+        (rc = label_cap("max_truth", max_truth, batch, 0, kLmMaxRows, "the tables", "per batch")) || (rc = handle_check(p)))
+        return rc;
     HIPCHK(hipSetDevice(p->device));
     if (!p->match) p->match = new MatchState();
     MatchState& S = *p->match;
-    for (hipEvent_t& e : S.ev)
-        if (!e) HIPCHK(hipEventCreate(&e));
 
     const size_t npx = (size_t)batch * height * width;
     const int64_t prows = (int64_t)batch * max_pred, trows = (int64_t)batch * max_truth;
@@ -302,7 +227,6 @@ int cs_label_match(cs_preproc* p, const int32_t* pred, const int32_t* truth, int
         log2 = kLmAutoMinLog2;
         while (((int64_t)1 << log2) < 2 * (prows + trows)) ++log2;       // at most 2^24
     }
-    int rc;
     const int *d_pred = pred, *d_truth = truth;
     if (in_kind == CS_MEM_HOST) {
         if ((rc = S.pred.ensure(npx * sizeof(int32_t))) || (rc = S.truth.ensure(npx * sizeof(int32_t)))) return rc;
@@ -319,20 +243,19 @@ int cs_label_match(cs_preproc* p, const int32_t* pred, const int32_t* truth, int
         return rc;
     const LmTables T{tdev ? pred_table : S.ptab.as<int>(), tdev ? truth_table : S.ttab.as<int>(), S.ppart.as<unsigned long long>(),
                      S.tpart.as<unsigned long long>(), S.pairs.as<unsigned long long>(), (int)max_pred, (int)max_truth};
-    const dim3 cgrid((unsigned)((width + LM_COLS - 1) / LM_COLS), (unsigned)((height + LM_WAVES * LM_ROWS - 1) / (LM_WAVES * LM_ROWS)),
-                     (unsigned)batch);
+    const dim3 cgrid = label_tile_grid(batch, height, width);
     S.grows = 0;
     for (;;) {
         const int64_t cap = (int64_t)1 << log2;
         if ((rc = S.keys.ensure(cap * sizeof(unsigned long long))) || (rc = S.cnt.ensure(cap * sizeof(unsigned int)))) return rc;
-        HIPCHK(hipEventRecord(S.ev[0], p->stream));
+        if ((rc = S.clk.record(0, p->stream))) return rc;
         HIPCHK(hipMemsetAsync(S.keys.p, 0, cap * sizeof(unsigned long long), p->stream));
         HIPCHK(hipMemsetAsync(S.cnt.p, 0, cap * sizeof(unsigned int), p->stream));
         HIPCHK(hipMemsetAsync(S.ctrl.p, 0, sizeof(unsigned int), p->stream));
         hipLaunchKernelGGL(lm_count, cgrid, dim3(LM_THREADS), 0, p->stream, d_pred, d_truth, (int)height, (int)width, (int)max_pred,
                            (int)max_truth, S.keys.as<unsigned long long>(), S.cnt.as<unsigned int>(), log2, S.ctrl.as<unsigned int>());
         HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(S.ev[1], p->stream));
+        if ((rc = S.clk.record(1, p->stream))) return rc;
         HIPCHK(hipMemsetAsync(T.pred, 0, pbytes, p->stream));
         HIPCHK(hipMemsetAsync(T.truth, 0, tbytes, p->stream));
         HIPCHK(hipMemsetAsync(T.ppart, 0, prows * sizeof(unsigned long long), p->stream));
@@ -348,7 +271,7 @@ int cs_label_match(cs_preproc* p, const int32_t* pred, const int32_t* truth, int
         const unsigned ublocks = (unsigned)std::min<int64_t>((prows + trows + LM_THREADS - 1) / LM_THREADS, 4096);
         hipLaunchKernelGGL(lm_unpack, dim3(ublocks), dim3(LM_THREADS), 0, p->stream, T, prows, trows);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(S.ev[2], p->stream));
+        if ((rc = S.clk.record(2, p->stream))) return rc;
         unsigned int flags = 0u;
         HIPCHK(hipMemcpyAsync(&flags, S.ctrl.p, sizeof(unsigned int), hipMemcpyDeviceToHost, p->stream));
         if (!tdev) {                                    // wasted when the table has to grow, which is the rare case
@@ -357,11 +280,7 @@ int cs_label_match(cs_preproc* p, const int32_t* pred, const int32_t* truth, int
         }
         if (n_pairs) HIPCHK(hipMemcpyAsync(n_pairs, T.pairs, batch * sizeof(int64_t), hipMemcpyDeviceToHost, p->stream));
         HIPCHK(hipStreamSynchronize(p->stream));          // the one host synchronisation of an attempt
-        float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, S.ev[0], S.ev[1]));
-        S.count_ms = ms;
-        HIPCHK(hipEventElapsedTime(&ms, S.ev[1], S.ev[2]));
-        S.reduce_ms = ms;
+        if ((rc = S.clk.finish())) return rc;
         S.table_log2 = log2;
         if (flags & LM_NEG) return fail(CS_ERR_INVALID, "negative label in the label images");
         if (flags & LM_PRED) return fail(CS_ERR_INVALID, "a pred label exceeds max_pred = %d", (int)max_pred);
@@ -375,11 +294,7 @@ int cs_label_match(cs_preproc* p, const int32_t* pred, const int32_t* truth, int
 
 int cs_label_match_last_timing(const cs_preproc* p, double* count_ms, double* reduce_ms)
 {
-    if (!p) return fail(CS_ERR_INVALID, "handle is NULL");
-    const MatchState* S = p->match;
-    if (count_ms) *count_ms = S ? S->count_ms : 0.0;
-    if (reduce_ms) *reduce_ms = S ? S->reduce_ms : 0.0;
-    return CS_OK;
+    return clock_read(p, p && p->match ? &p->match->clk : nullptr, {count_ms, reduce_ms});
 }
 
 int cs_label_match_last_table(const cs_preproc* p, int32_t* table_log2, int32_t* grows)

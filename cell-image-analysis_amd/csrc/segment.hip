@@ -55,8 +55,6 @@ static constexpr int HIST_THREADS = 1024;
 static constexpr int HIST_WINDOW = 32768;               // 32-bit LDS bins per workgroup
 static constexpr int HIST_MAX_PARTS = 16;
 static constexpr int HIST_PART_PX = 16384;              // no part smaller than this
-static constexpr int kSegMaxSide = 4096;
-static constexpr int kSegMaxBatch = 65535;              // grid.y / grid.z
 
 // ---- histogram ---------------------------------------------------------------------------------------------------------------
 // One LDS add per distinct value among the first rounds' leaders (background-heavy images put most of a wave on one or two
@@ -1315,7 +1313,7 @@ __global__ __launch_bounds__(SG_THREADS) void sm_cols(const unsigned int* __rest
 // Components come from label_mask (tile union-find, border merge, flatten), so a component spread over many tiles is counted
 // as one.  Shifts, ANDs, ORs and integer adds only: the plane is a function of the mask alone.
 static constexpr int CL_MAX_R = 15;
-static constexpr int CL_MAX_AREA = 1 << 24;             // kSegMaxSide^2: no component is larger
+static constexpr int CL_MAX_AREA = 1 << 24;             // kMaxSide^2: no component is larger
 static constexpr int CL_TWW = 4, CL_TW = 64 * CL_TWW;   // words and pixels of a tile's row
 static constexpr int CL_TH = 32;                        // rows of a tile
 static constexpr int CL_LW = CL_TWW + 2;                // words of a row in LDS: the tile and one halo word on either side
@@ -1718,21 +1716,10 @@ static int image_check(const void* image, const void* out, int pixel_type, int32
 {
     if (!image || !out) return fail(CS_ERR_INVALID, "NULL argument");
     if (pixel_type != CS_PIX_U8 && pixel_type != CS_PIX_U16) return fail(CS_ERR_INVALID, "pixel_type must be CS_PIX_U8 or CS_PIX_U16");
-    if ((in_kind != CS_MEM_HOST && in_kind != CS_MEM_DEVICE) || (out_kind != CS_MEM_HOST && out_kind != CS_MEM_DEVICE))
-        return fail(CS_ERR_INVALID, "in_kind / %s must be CS_MEM_HOST or CS_MEM_DEVICE", out_name);
+    if (!mem_kind(in_kind) || !mem_kind(out_kind)) return fail(CS_ERR_INVALID, "in_kind / %s must be CS_MEM_HOST or CS_MEM_DEVICE", out_name);
     if (channels < 1 || channel < 0 || channel >= channels)
         return fail(CS_ERR_INVALID, "channel %d of %d: need 0 <= channel < channels", (int)channel, (int)channels);
-    if (batch < 1 || height < 1 || width < 1) return fail(CS_ERR_INVALID, "batch %d, height %d, width %d: all must be >= 1", (int)batch,
-                                                          (int)height, (int)width);
-    return CS_OK;
-}
-
-int image_limits(int32_t batch, int32_t height, int32_t width)
-{
-    if (height > kSegMaxSide || width > kSegMaxSide)
-        return fail(CS_ERR_UNSUPPORTED, "image %dx%d: sides above %d are not supported", (int)height, (int)width, kSegMaxSide);
-    if (batch > kSegMaxBatch) return fail(CS_ERR_UNSUPPORTED, "batch %d: at most %d images per call", (int)batch, kSegMaxBatch);
-    return CS_OK;
+    return stack_dims(batch, height, width);
 }
 
 // The rules of cs_segment_params; sp receives the parameters in force.
@@ -1749,14 +1736,6 @@ static int segment_check(const cs_segment_params* params, cs_segment_params& sp)
         if (sp.fill_holes != 0 && sp.fill_holes != 1) return fail(CS_ERR_INVALID, "fill_holes %d: 0 or 1", (int)sp.fill_holes);
     }
     return CS_OK;
-}
-
-// after the argument rules: without a handle the device's absence is reported before the handle's
-int handle_check(const cs_preproc* p)
-{
-    if (p) return CS_OK;
-    const int rc = require_gfx950(0);
-    return rc ? rc : fail(CS_ERR_INVALID, "handle is NULL");
 }
 
 int state_begin(cs_preproc* p)
@@ -1817,24 +1796,6 @@ static int plane_end(const PlaneCall& c, StageClock& clk, int32_t* thresholds, i
     if (c.host) HIPCHK(hipMemcpyAsync(c.host, c.d_out, c.out_bytes, hipMemcpyDeviceToHost, c.st));
     HIPCHK(hipStreamSynchronize(c.st));                   // the one host synchronisation: the caller's host buffers are free / filled
     return clk.finish();
-}
-
-// What every cs_segment_*_last_timing does: the spans of the family's last call, read now if that call left them on the
-// device; a handle that has not segmented yet reports zeros.
-int clock_read(const cs_preproc* p, StageClock SegmentState::*which, std::initializer_list<double*> out)
-{
-    if (!p) return fail(CS_ERR_INVALID, "handle is NULL");
-    StageClock* clk = p->seg ? &(p->seg->*which) : nullptr;
-    if (clk && clk->pending) {
-        HIPCHK(hipSetDevice(p->device));
-        if (const int rc = clk->finish()) return rc;
-    }
-    int k = 0;
-    for (double* o : out) {
-        if (o) *o = clk ? clk->ms[k] : 0.0;
-        ++k;
-    }
-    return CS_OK;
 }
 
 // What the labelling entry points do up to the mask: the state, the uploads, the common workspace, the thresholds, the mask

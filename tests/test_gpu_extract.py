@@ -70,7 +70,9 @@ def check_against_restatement(r, images, labels, proc, channel=None, qc=None):
 
 
 @pytest.mark.parametrize("dtype,channels,hw", [(np.uint16, 3, (256, 256)), (np.uint8, 3, (192, 224)), (np.uint8, 1, (160, 200)),
-                                               (np.uint16, 1, (250, 203))])
+                                               (np.uint16, 1, (250, 203)),
+                                               # 515 columns: three column tiles of the label pass, the last ragged, scalar loads
+                                               (np.uint8, 1, (130, 515)), (np.uint16, 3, (197, 515))])
 def test_batch_matches_restatement(ext, proc, dtype, channels, hw):
     imgs, labs = synth.label_images(11, 3, hw=hw, dtype=dtype, channels=channels)
     if channels == 1:
@@ -81,8 +83,13 @@ def test_batch_matches_restatement(ext, proc, dtype, channels, hw):
 
 
 def test_batch_equals_single_images_and_is_deterministic(ext):
+    fresh = X.CellExtractor(0)
+    assert fresh.last_timing() == {"label_ms": 0.0, "region_ms": 0.0, "cells_ms": 0.0}      # before any call
+    fresh.close()
     imgs, labs = synth.label_images(12, 4)
     r = ext.extract_batch(imgs, labs)
+    t = ext.last_timing()
+    assert set(t) == {"label_ms", "region_ms", "cells_ms"} and all(np.isfinite(v) and v >= 0.0 for v in t.values()), t
     r2 = ext.extract_batch(imgs, labs)
     assert np.array_equal(r.cells, r2.cells) and np.array_equal(r.regions, r2.regions) and np.array_equal(r.status, r2.status)
     cells, regs = [], []
