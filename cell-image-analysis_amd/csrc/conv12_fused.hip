@@ -31,7 +31,8 @@
 //              max (those two rows are one pool row), store p2.                                                        1.4 k
 // (+ four barriers: 1.4 k.)  LDS map: V 73,728 | ring 10 x (34 x 32 + 8) x 4 = 43,840 | exchange 16,384 | crop 67 x 72 x 4 =
 // 19,296 | conv1 fragments (both forms) and epilogue constants 9,344 | the crop's maximum 16.
-#include "common.hpp"
+#include "kernel_setup.hpp"
+#include "split16.hpp"
 
 #include <cmath>
 #include <cstdlib>
@@ -115,45 +116,12 @@ __device__ __forceinline__ void bt6(const float d[6], float o[6])
 // differences per wave: [0] P1, [1] wait at barrier 1, [2] P2, [3] barrier 2,
 // [4] P3, [5] barrier 3, [6] P4 (fold, epilogue, stores; the next cell's records), [7] barrier 4.
 // Never used for results or timing.
-__device__ __forceinline__ unsigned long long c12_stamp()
-{
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
 #define C12_STAMP(k)                                                       \
     if constexpr (DIAG) {                                                  \
-        const unsigned long long t__ = c12_stamp();                        \
+        const unsigned long long t__ = cycle_stamp();                        \
         dg[k] += t__ - dt;                                                 \
         dt = t__;                                                          \
     }
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-// max over the 16 lanes of a DPP row of non-negative float bit patterns
-__device__ __forceinline__ unsigned int c12_rowmax(unsigned int m)
-{
-    unsigned int o;
-    o = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)m, 0xB1, 0xF, 0xF, true);  m = m > o ? m : o;     // quad_perm [1,0,3,2]
-    o = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)m, 0x4E, 0xF, 0xF, true);  m = m > o ? m : o;     // quad_perm [2,3,0,1]
-    o = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)m, 0x124, 0xF, 0xF, true); m = m > o ? m : o;     // row_ror:4
-    o = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)m, 0x128, 0xF, 0xF, true); m = m > o ? m : o;     // row_ror:8
-    return m;
-}
-__device__ __forceinline__ unsigned int c12_absmax8(const f32x4& a, const f32x4& b)
-{
-    // scalars first: __builtin_bit_cast of a vector ELEMENT expression reads element 0 whatever the index (clang 19, ROCm 7.2)
-    const float a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[3], b0 = b[0], b1 = b[1], b2 = b[2], b3 = b[3];
-    const float m = fmaxf(fmaxf(fmaxf(fabsf(a0), fabsf(a1)), fmaxf(fabsf(a2), fabsf(a3))), fmaxf(fmaxf(fabsf(b0), fabsf(b1)), fmaxf(fabsf(b2), fabsf(b3))));
-    return __builtin_bit_cast(unsigned int, m);
-}
 
 // A crop with a non-finite pixel is screened as if that pixel were 0: its NaN / Inf must not reach the LDS images other cells of this
 // persistent workgroup are built in (zero weights against neighbouring records would turn a stale NaN into a NaN of the NEXT cell).
@@ -200,37 +168,6 @@ __device__ __forceinline__ void bt6_pair(const f32x2 (&d)[6], f32x2 (&o)[6])
     o[3] = pfma(2.0f, t4, t3);
     o[4] = pfma(-2.0f, t4, t3);
 }
-// Six channel pairs -> [hi c | hi c+1] and [lo c | lo c+1] dwords (hi = fp16(v), lo = fp16(v - hi)): one v_cvt_pk_f16_f32 and two
-// v_fma_mix per pair, no lane exchange.  Both hi are fp16 of the fp32 value the transform stored (see P2's comment on the fold).
-__device__ __forceinline__ void f16x2_split6_pairs(const f32x2 (&v)[6], unsigned int (&hi)[6], unsigned int (&lo)[6])
-{
-    float a[6], b[6];
-#pragma unroll
-    for (int c = 0; c < 6; ++c) { a[c] = v[c][0]; b[c] = v[c][1]; }
-    asm("v_cvt_pk_f16_f32 %0, %12, %18\n\t"
-        "v_cvt_pk_f16_f32 %1, %13, %19\n\t"
-        "v_cvt_pk_f16_f32 %2, %14, %20\n\t"
-        "v_cvt_pk_f16_f32 %3, %15, %21\n\t"
-        "v_cvt_pk_f16_f32 %4, %16, %22\n\t"
-        "v_cvt_pk_f16_f32 %5, %17, %23\n\t"
-        "v_fma_mixlo_f16 %6, %12, 1.0, -%0 op_sel:[0,0,0] op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixlo_f16 %7, %13, 1.0, -%1 op_sel:[0,0,0] op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixlo_f16 %8, %14, 1.0, -%2 op_sel:[0,0,0] op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixlo_f16 %9, %15, 1.0, -%3 op_sel:[0,0,0] op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixlo_f16 %10, %16, 1.0, -%4 op_sel:[0,0,0] op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixlo_f16 %11, %17, 1.0, -%5 op_sel:[0,0,0] op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixhi_f16 %6, %18, 1.0, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixhi_f16 %7, %19, 1.0, -%1 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixhi_f16 %8, %20, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixhi_f16 %9, %21, 1.0, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixhi_f16 %10, %22, 1.0, -%4 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixhi_f16 %11, %23, 1.0, -%5 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
-        : "=&v"(hi[0]), "=&v"(hi[1]), "=&v"(hi[2]), "=&v"(hi[3]), "=&v"(hi[4]), "=&v"(hi[5]),
-          "=&v"(lo[0]), "=&v"(lo[1]), "=&v"(lo[2]), "=&v"(lo[3]), "=&v"(lo[4]), "=&v"(lo[5])
-        : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(a[4]), "v"(a[5]),
-          "v"(b[0]), "v"(b[1]), "v"(b[2]), "v"(b[3]), "v"(b[4]), "v"(b[5]));
-}
-
 // C2H: conv2's contraction M = V U (P3) as a TWO-term fp16 split on v_mfma_f32_16x16x32_f16 (conv_wino_up.hip, conv67_h2_kernel, has
 // the algebra and the hardware facts; tests/study_split_fp16.py the error: p2 1.1e-6 of its range, the fp32 chain 1.2e-6).  A
 // transform point's 32 channels are ONE K = 32 instruction, so 36 points x 4 tile groups x 4 filter slices x 3 products = 1,728
@@ -303,7 +240,7 @@ __global__ __launch_bounds__(NTHR, 2) void conv12_fused_kernel(const float* __re
         *(f32x4*)dst = c0;
         *(f32x4*)(dst + 32 * INP_STRIDE) = c1;
         if constexpr (C2H) {
-            const unsigned int mx = c12_rowmax(c12_absmax8(c0, c1));
+            const unsigned int mx = f16x2_rowmax(f16x2_absmax8(c0, c1));
             if ((lane & 15) == 0) atomicMax((unsigned int*)(smem + OFF_XMAX), mx);
         }
     }
@@ -346,7 +283,7 @@ __global__ __launch_bounds__(NTHR, 2) void conv12_fused_kernel(const float* __re
         __syncthreads();
     }
 
-    if constexpr (DIAG) dt = c12_stamp();
+    if constexpr (DIAG) dt = cycle_stamp();
     for (long ci = 0; ci < my_cells; ++ci) {
         const long cell = blockIdx.x + ci * gridDim.x;
         const bool has_next = ci + 1 < my_cells;
@@ -540,7 +477,7 @@ __global__ __launch_bounds__(NTHR, 2) void conv12_fused_kernel(const float* __re
                             c12_sanitize(stg1);
                             *(f32x4*)dst = stg0;
                             *(f32x4*)(dst + 32 * INP_STRIDE) = stg1;
-                            const unsigned int mx = c12_rowmax(c12_absmax8(stg0, stg1));
+                            const unsigned int mx = f16x2_rowmax(f16x2_absmax8(stg0, stg1));
                             if ((l2 & 15) == 0) atomicMax((unsigned int*)(smem + OFF_XMAX), mx);
                         }
                         // rows first (B^T d): this thread's three rows of every column
@@ -889,47 +826,31 @@ size_t pack_conv12_conv1_h2(const float* hwio /* [3][3][1][32] */, const float* 
     return total;
 }
 
-unsigned long long* g_c12_diag = nullptr;
-int g_c12_diag_blocks = 0;
+StampTable g_c12_stamps = {64};       // DIAG builds: 8 waves x 8 phases per workgroup
 
 hipError_t launch_conv12_fused(const float* x, const float* w1frag, const float* ep1, const float* ufrag, const float* ep2, float* p2,
                                int64_t n_cells, hipStream_t stream, const unsigned int* ufrag_h2, float p1a, float p1b,
                                float inv_sw, const unsigned int* w1h2, float inv_sw1)
 {
-    static int cus = 0;
     static const bool diag = getenv("CS_C12_DIAG") != nullptr;       // tools/c12_diag.py: the stamped build, never for results
-    if (!cus) {
-        hipError_t e;
-#define C12_ATTR(...)                                                                                                                \
-    if ((e = hipFuncSetAttribute((const void*)conv12_fused_kernel<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES)) != hipSuccess) return e
-        C12_ATTR(false, false); C12_ATTR(true, false);
-        C12_ATTR(false, true); C12_ATTR(true, true);
-#undef C12_ATTR
-        int dev = 0;
-        if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
-        if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
-        if (cus < 1) cus = 1;
-        if (diag) {
-            if ((e = hipMalloc(&g_c12_diag, (size_t)cus * 64 * sizeof(unsigned long long))) != hipSuccess) return e;
-            g_c12_diag_blocks = cus;
-        }
-    }
     if (n_cells <= 0) return hipSuccess;
     if ((w1h2 == nullptr) != (ufrag_h2 == nullptr)) return hipErrorInvalidValue;
-    const unsigned grid = (unsigned)(n_cells < cus ? n_cells : cus);      // one workgroup per CU (LDS-bound), persistent over cells
-    unsigned long long* const dp = diag ? g_c12_diag : nullptr;
-#define C12_GO(UF, W1, ISW1, ...)                                                                                                    \
-    hipLaunchKernelGGL((conv12_fused_kernel<__VA_ARGS__>), dim3(grid), dim3(NTHR), LDS_BYTES, stream, x, w1frag, ep1, UF, ep2, p2,   \
-                       (long)n_cells, dp, W1, p1a, p1b, inv_sw, ISW1)
-    if (w1h2) {      // CS_PRECISION_SPLIT16: conv1 and conv2 as fp16 splits
-        if (diag) C12_GO((const float*)ufrag_h2, w1h2, inv_sw1, true, true);
-        else C12_GO((const float*)ufrag_h2, w1h2, inv_sw1, false, true);
-    } else {         // CS_PRECISION_FP32_EXACT
-        if (diag) C12_GO(ufrag, (const unsigned int*)nullptr, 1.0f, true, false);
-        else C12_GO(ufrag, (const unsigned int*)nullptr, 1.0f, false, false);
-    }
-#undef C12_GO
-    return hipGetLastError();
+    // one workgroup per CU (LDS-bound), persistent over cells
+    auto go = [&](auto DIAG, auto H, const float* uf, const unsigned int* w1, float isw1) -> hipError_t {
+        constexpr bool D = decltype(DIAG)::value;
+        KernelSetup ks;
+        const hipError_t e = kernel_setup<conv12_fused_kernel<D, decltype(H)::value>>(NTHR, LDS_BYTES, ks, D ? &g_c12_stamps : nullptr);
+        if (e != hipSuccess) return e;
+        const unsigned grid = (unsigned)(n_cells < ks.cus ? n_cells : ks.cus);
+        hipLaunchKernelGGL((conv12_fused_kernel<D, decltype(H)::value>), dim3(grid), dim3(NTHR), LDS_BYTES, stream, x, w1frag, ep1, uf, ep2,
+                           p2, (long)n_cells, D ? g_c12_stamps.begin(ks, grid) : nullptr, w1, p1a, p1b, inv_sw, isw1);
+        return hipGetLastError();
+    };
+    const std::false_type F;
+    const std::true_type T;
+    if (!w1h2) return !diag ? go(F, F, ufrag, nullptr, 1.0f) : go(T, F, ufrag, nullptr, 1.0f);      // CS_PRECISION_FP32_EXACT
+    // CS_PRECISION_SPLIT16: conv1 and conv2 as fp16 splits
+    return !diag ? go(F, T, (const float*)ufrag_h2, w1h2, inv_sw1) : go(T, T, (const float*)ufrag_h2, w1h2, inv_sw1);
 }
 
 }  // namespace cs
@@ -937,15 +858,5 @@ hipError_t launch_conv12_fused(const float* x, const float* w1frag, const float*
 // Diagnostic only (CS_C12_DIAG=1): per-wave phase cycles of the LAST launch of the fused conv1 + conv2 kernel, averaged over waves.
 extern "C" int cs_debug_conv12_diag(double out8[8])
 {
-    using namespace cs;
-    if (!g_c12_diag) return -1;
-    if (hipDeviceSynchronize() != hipSuccess) return -2;
-    const size_t n = (size_t)g_c12_diag_blocks * 64;
-    unsigned long long* h = new unsigned long long[n];
-    if (hipMemcpy(h, g_c12_diag, n * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) { delete[] h; return -3; }
-    for (int k = 0; k < 8; ++k) out8[k] = 0.0;
-    for (size_t i = 0; i < n; ++i) out8[i % 8] += (double)h[i];
-    for (int k = 0; k < 8; ++k) out8[k] /= (double)(n / 8);
-    delete[] h;
-    return 0;
+    return cs::stamp_table_average(cs::g_c12_stamps, 8, out8);
 }

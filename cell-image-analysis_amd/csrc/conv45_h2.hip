@@ -10,7 +10,8 @@
 //   cout l&15 of the wave's slice.  The weights stay in registers; the cell is split ONCE per element when it is staged
 //   into two fp16 planes in LDS with a zero halo, pixel stride 64 B and row stride 672 B (the lane groups of a ds_read_b128
 //   land on 16 distinct 16-byte slots), and every tap's A fragment is one ds_read_b128 per plane.
-#include "common.hpp"
+#include "kernel_setup.hpp"
+#include "split16.hpp"
 
 #include <cstring>
 
@@ -37,42 +38,13 @@ constexpr int C5_OUT = 64;
 // and two thirds of the weight registers of the bf16 kernels above; the staged layout is theirs with two planes.  The maximum of
 // the NEXT cell is taken while this cell's MFMAs run (its loads are in flight then anyway) and read behind the barrier that
 // ends the cell: no extra barrier.
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 constexpr int H2_OFF_MAX = 2 * PLANE;              // two words: cell maxima, alternating
 constexpr int H2_LDS_BYTES = 2 * PLANE + 16;
 
-__device__ __forceinline__ unsigned int h2_rowmax(unsigned int m)
-{
-    unsigned int o;
-    o = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)m, 0xB1, 0xF, 0xF, true);  m = m > o ? m : o;     // quad_perm [1,0,3,2]
-    o = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)m, 0x4E, 0xF, 0xF, true);  m = m > o ? m : o;     // quad_perm [2,3,0,1]
-    o = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)m, 0x124, 0xF, 0xF, true); m = m > o ? m : o;     // row_ror:4
-    o = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)m, 0x128, 0xF, 0xF, true); m = m > o ? m : o;     // row_ror:8
-    return m;
-}
-__device__ __forceinline__ void h2_scale(unsigned int mbits, float& S, float& invS)
-{
-    int E = (int)((mbits >> 23) & 0xffu);
-    E = E < 40 ? 40 : (E > 254 ? 254 : E);
-    S = __builtin_bit_cast(float, (unsigned int)(268 - E) << 23);          // 2^(14 - (E - 127))
-    invS = __builtin_bit_cast(float, (unsigned int)(E - 14) << 23);
-}
-// max|.| of four values into a running maximum kept as float bits (non-negative floats order like their bit patterns).  The
-// elements are copied to scalars first: __builtin_bit_cast applied to a vector ELEMENT expression reads element 0 whatever the
-// index (clang 19 of ROCm 7.2 -- found as a scale taken from a quarter of the data).
-__device__ __forceinline__ void h2_absmax4(const f32x4& v, unsigned int& mx)
-{
-    const float a = v[0], b = v[1], c = v[2], d = v[3];
-    const float m = fmaxf(fmaxf(fabsf(a), fabsf(b)), fmaxf(fabsf(c), fabsf(d)));
-    const unsigned int u = __builtin_bit_cast(unsigned int, m);
-    mx = mx > u ? mx : u;
-}
 __device__ __forceinline__ void h2_split_store(char* dst, const f32x4& x, float S)
 {
-    const f32x4 v = x * S;
-    const f16x4 hi = __builtin_convertvector(v, f16x4);
-    const f32x4 r = v - __builtin_convertvector(hi, f32x4);            // exact in fp32
+    f16x4 hi;
+    const f32x4 r = f16x2_residual4(x, S, hi);
     *(f16x4*)dst = hi;
     *(f16x4*)(dst + PLANE) = __builtin_convertvector(r, f16x4);
 }
@@ -109,14 +81,14 @@ __global__ __launch_bounds__(256, WG_PER_CU) void conv4_h2_kernel(const float* _
     __syncthreads();
     {
         unsigned int mx = 0;
-        h2_absmax4(stg[0], mx);
-        h2_absmax4(stg[1], mx);
-        mx = h2_rowmax(mx);
+        f16x2_absmax4(stg[0], mx);
+        f16x2_absmax4(stg[1], mx);
+        mx = f16x2_rowmax(mx);
         if (li == 0) atomicMax(&mxw[0], mx);
     }
     __syncthreads();
     float S, invS;
-    h2_scale(mxw[0], S, invS);
+    f16x2_scale(mxw[0], S, invS);
 
     int woff[2];
 #pragma unroll
@@ -164,13 +136,13 @@ __global__ __launch_bounds__(256, WG_PER_CU) void conv4_h2_kernel(const float* _
         }
         if (ncell < n_cells) {
             unsigned int mx = 0;
-            h2_absmax4(stg[0], mx);
-            h2_absmax4(stg[1], mx);
-            mx = h2_rowmax(mx);
+            f16x2_absmax4(stg[0], mx);
+            f16x2_absmax4(stg[1], mx);
+            mx = f16x2_rowmax(mx);
             if (li == 0) atomicMax(&mxw[(it + 1) & 1], mx);
         }
         __syncthreads();           // every wave is done reading the planes; the next cell's maximum is complete
-        h2_scale(mxw[(it + 1) & 1], S, invS);
+        f16x2_scale(mxw[(it + 1) & 1], S, invS);
     }
 }
 
@@ -208,13 +180,13 @@ __global__ __launch_bounds__(512, 2) void conv5_h2_kernel(const float* __restric
     __syncthreads();
     {
         unsigned int mx = 0;
-        h2_absmax4(stg, mx);
-        mx = h2_rowmax(mx);
+        f16x2_absmax4(stg, mx);
+        mx = f16x2_rowmax(mx);
         if (li == 0) atomicMax(&mxw[0], mx);
     }
     __syncthreads();
     float S, invS;
-    h2_scale(mxw[0], S, invS);
+    f16x2_scale(mxw[0], S, invS);
     const int woff = ((tid >> 6) + 1) * ROWB + (((tid >> 3) & 7) + 1) * PXB + (tid & 7) * 8;
     const int abase = ((li >> 3) + pa) * ROWB + ((li & 7) + pb) * PXB + kq * 16;
 
@@ -256,12 +228,12 @@ __global__ __launch_bounds__(512, 2) void conv5_h2_kernel(const float* __restric
         }
         if (ncell < n_cells) {
             unsigned int mx = 0;
-            h2_absmax4(stg, mx);
-            mx = h2_rowmax(mx);
+            f16x2_absmax4(stg, mx);
+            mx = f16x2_rowmax(mx);
             if (li == 0) atomicMax(&mxw[(it + 1) & 1], mx);
         }
         __syncthreads();           // every wave is done reading the planes; the next cell's maximum is complete
-        h2_scale(mxw[(it + 1) & 1], S, invS);
+        f16x2_scale(mxw[(it + 1) & 1], S, invS);
     }
 }
 
@@ -320,13 +292,13 @@ __global__ __launch_bounds__(512, 2) void conv45_h2_kernel(const float* __restri
     f32x4 stg = *(const f32x4*)(in + (size_t)cell * (G * G * CH) + tid * 4);
     {
         unsigned int mx = 0;
-        h2_absmax4(stg, mx);
-        mx = h2_rowmax(mx);
+        f16x2_absmax4(stg, mx);
+        mx = f16x2_rowmax(mx);
         if (li == 0) atomicMax(&mxw[0], mx);
     }
     __syncthreads();
     float S3, invS3;
-    h2_scale(mxw[0], S3, invS3);
+    f16x2_scale(mxw[0], S3, invS3);
     const int woff = ((tid >> 6) + 1) * ROWB + (((tid >> 3) & 7) + 1) * PXB + (tid & 7) * 8;      // this thread's p3 element
     const int abase4 = (2 * tile4 + (li >> 3)) * ROWB + (li & 7) * PXB + kq * 16;               // conv4 A operand (image P)
     const char* const w4l = smem + F45_OFF_W4 + (size_t)slice4 * 9 * 2 * 64 * 16 + lane * 16;    // + (tap * 2 + plane) * 1024
@@ -361,12 +333,12 @@ __global__ __launch_bounds__(512, 2) void conv45_h2_kernel(const float* __restri
                 a4v[r] = fmaf(v, bns4, bnt4);
                 am = fmaxf(am, fabsf(a4v[r]));
             }
-            const unsigned int m = h2_rowmax(__builtin_bit_cast(unsigned int, am));
+            const unsigned int m = f16x2_rowmax(__builtin_bit_cast(unsigned int, am));
             if (li == 0) atomicMax(&mxw[2 + (it & 1)], m);
         }
         __syncthreads();                                   // a4's maximum complete; image P fully read
         float S4, invS4;
-        h2_scale(mxw[2 + (it & 1)], S4, invS4);
+        f16x2_scale(mxw[2 + (it & 1)], S4, invS4);
         {   // D row 4 kq + r = pixel 16 tile4 + 4 kq + r, column = channel co4: [hi | lo] into image A
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -413,12 +385,12 @@ __global__ __launch_bounds__(512, 2) void conv45_h2_kernel(const float* __restri
         }
         if (ncell < n_cells) {
             unsigned int mx = 0;
-            h2_absmax4(stg, mx);
-            mx = h2_rowmax(mx);
+            f16x2_absmax4(stg, mx);
+            mx = f16x2_rowmax(mx);
             if (li == 0) atomicMax(&mxw[(it + 1) & 1], mx);
         }
         __syncthreads();           // every wave is done reading image A; the next cell's p3 maximum is complete
-        h2_scale(mxw[(it + 1) & 1], S3, invS3);
+        f16x2_scale(mxw[(it + 1) & 1], S3, invS3);
     }
 }
 
@@ -443,27 +415,12 @@ size_t pack_conv4_f16x2(const float* hwio, uint16_t* dst, float* inv_sw)
     return n;
 }
 
-template <class K>
-static hipError_t resident_grid(K kernel, int threads, int lds, int& resident)
-{
-    int dev = 0, cus = 0, per_cu = 0;
-    hipError_t e;
-    if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
-    if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
-    if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kernel, threads, lds)) != hipSuccess) return e;
-    resident = cus * (per_cu < 1 ? 1 : per_cu);
-    return hipSuccess;
-}
-
 hipError_t launch_conv4_h2(const float* in, const uint16_t* wfrag, float inv_sw, const float* ep, float* out, int64_t n_cells, hipStream_t stream)
 {
     if (n_cells <= 0) return hipSuccess;
-    static int resident = 0;
-    if (!resident) {
-        hipError_t e = resident_grid(conv4_h2_kernel, 256, H2_LDS_BYTES, resident);
-        if (e != hipSuccess) return e;
-    }
-    const long grid = n_cells < resident ? n_cells : resident;
+    KernelSetup ks;
+    if (hipError_t e = kernel_setup<conv4_h2_kernel>(256, H2_LDS_BYTES, ks); e != hipSuccess) return e;
+    const long grid = n_cells < ks.resident ? n_cells : ks.resident;
     hipLaunchKernelGGL(conv4_h2_kernel, dim3((unsigned)grid), dim3(256), H2_LDS_BYTES, stream, in, (const f16x8*)wfrag, ep, out,
                        (long)n_cells, inv_sw);
     return hipGetLastError();
@@ -492,12 +449,9 @@ size_t pack_conv5_f16x2(const float* weff, uint16_t* dst, float* inv_sw)
 hipError_t launch_conv5_h2(const float* in, const uint16_t* wfrag, float inv_sw, const float* ep, float* out, int64_t n_cells, hipStream_t stream)
 {
     if (n_cells <= 0) return hipSuccess;
-    static int resident = 0;
-    if (!resident) {
-        hipError_t e = resident_grid(conv5_h2_kernel, 512, H2_LDS_BYTES, resident);
-        if (e != hipSuccess) return e;
-    }
-    const long grid = n_cells < resident ? n_cells : resident;
+    KernelSetup ks;
+    if (hipError_t e = kernel_setup<conv5_h2_kernel>(512, H2_LDS_BYTES, ks); e != hipSuccess) return e;
+    const long grid = n_cells < ks.resident ? n_cells : ks.resident;
     hipLaunchKernelGGL(conv5_h2_kernel, dim3((unsigned)grid), dim3(512), H2_LDS_BYTES, stream, in, (const f16x8*)wfrag, ep, out,
                        (long)n_cells, inv_sw);
     return hipGetLastError();
@@ -508,14 +462,9 @@ hipError_t launch_conv45_h2(const float* in, const uint16_t* w4, float inv_sw4, 
                             const float* ep5, float* out, int64_t n_cells, hipStream_t stream)
 {
     if (n_cells <= 0) return hipSuccess;
-    static int resident = 0;
-    if (!resident) {
-        hipError_t e = hipFuncSetAttribute((const void*)conv45_h2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, F45_LDS_BYTES);
-        if (e != hipSuccess) return e;
-        e = resident_grid(conv45_h2_kernel, 512, F45_LDS_BYTES, resident);
-        if (e != hipSuccess) return e;
-    }
-    const long grid = n_cells < resident ? n_cells : resident;
+    KernelSetup ks;
+    if (hipError_t e = kernel_setup<conv45_h2_kernel>(512, F45_LDS_BYTES, ks); e != hipSuccess) return e;
+    const long grid = n_cells < ks.resident ? n_cells : ks.resident;
     hipLaunchKernelGGL(conv45_h2_kernel, dim3((unsigned)grid), dim3(512), F45_LDS_BYTES, stream, in, (const f16x8*)w4, ep4, inv_sw4,
                        (const f16x8*)w5, ep5, inv_sw5, out, (long)n_cells);
     return hipGetLastError();

@@ -2,8 +2,8 @@
 // fp32 contraction carried by the bf16 matrix pipe, for the inference path of NON-reference architectures
 // (create_improved_autoencoder(input_shape), CAE_improved_modeltrain.py:184; BASELINE.json configs[4]).
 //
-// Every fp32 operand is split into three bf16 terms (x = x1 + x2 + x3 to 2^-24; conv45_bf16x3.hip has the algebra and
-// the hardware check of the technique) and a product is taken as six v_mfma_f32_16x16x32_bf16 partial products, each
+// Every fp32 operand is split into three bf16 terms (x = x1 + x2 + x3 to 2^-24; split4 and mac6 below are the algebra,
+// DESIGN.md 3g has the hardware check of the technique) and a product is taken as six v_mfma_f32_16x16x32_bf16 partial products, each
 // exact in the fp32 accumulator: six 16-cycle instructions per 32 channels against eight 32-cycle
 // v_mfma_f32_16x16x4_f32, and the bf16 instruction leaves half of its issue slots to the VALU, LDS and memory
 // instructions around it.
@@ -16,7 +16,7 @@
 //     per lane and plane and (tap, block), reused for every tile the wave owns (TPW = 4 or 8 live accumulators).
 // Tile ownership, strips, epilogues and the folded upsample (four 2x2-tap phase convs on the stored grid, 4/9 of the
 // multiply-adds) are those of conv_generic.hip.  Training keeps the fp32 kernels (its weights change every step).
-#include "common.hpp"
+#include "split16.hpp"
 
 #include <cstdlib>
 #include <cstring>
@@ -25,8 +25,6 @@ namespace cs {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -36,23 +34,6 @@ namespace {
 // be known before anything is split), then split IN PLACE -- a pixel's fp32 values and its [hi plane | lo plane] are the same
 // 4 cin bytes, and one wave owns a pixel (all of a wave's reads of an instruction precede its writes), so the second pass needs
 // no barrier of its own beyond the one that publishes the maximum.
-__device__ __forceinline__ unsigned int g3h_rowmax(unsigned int m)
-{
-    unsigned int o;
-    o = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)m, 0xB1, 0xF, 0xF, true);  m = m > o ? m : o;     // quad_perm [1,0,3,2]
-    o = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)m, 0x4E, 0xF, 0xF, true);  m = m > o ? m : o;     // quad_perm [2,3,0,1]
-    o = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)m, 0x124, 0xF, 0xF, true); m = m > o ? m : o;     // row_ror:4
-    o = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)m, 0x128, 0xF, 0xF, true); m = m > o ? m : o;     // row_ror:8
-    return m;
-}
-__device__ __forceinline__ void g3h_scale(unsigned int mbits, float& S, float& invS)
-{
-    int E = (int)((mbits >> 23) & 0xffu);
-    E = E < 40 ? 40 : (E > 254 ? 254 : E);
-    S = __builtin_bit_cast(float, (unsigned int)(268 - E) << 23);          // 2^(14 - (E - 127))
-    invS = __builtin_bit_cast(float, (unsigned int)(E - 14) << 23);
-}
-
 struct Gen3Args {
     const float* in;       // stored input [n][Hs][Ws][cin]  (Hs = H/2 for the folded form)
     const uint16_t* w;     // pack_generic_bf16x3: [step = tap * cin/32 + block][plane][cout_pad][kq][8] bf16 (H2: two fp16 planes)
@@ -133,14 +114,13 @@ __global__ __launch_bounds__(512, 2) void conv_generic_x3_kernel(Gen3Args g)
                 f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
                 if (sy >= 0 && sy < Hs && sx >= 0 && sx < Ws) v = *(const f32x4*)(src + ((size_t)sy * Ws + sx) * cin + 4 * c4);
                 *(f32x4*)(smem + pix * psb + c4 * 16) = v;                 // fp32 for now: the same bytes become [hi | lo] below
-                const float a0 = v[0], a1 = v[1], a2 = v[2], a3 = v[3];   // (scalars: see conv45_bf16x3.hip, h2_absmax4)
-                am = fmaxf(am, fmaxf(fmaxf(fabsf(a0), fabsf(a1)), fmaxf(fabsf(a2), fabsf(a3))));
+                am = fmaxf(am, f16x2_absmax4(v));
             }
-            const unsigned int m = g3h_rowmax(__builtin_bit_cast(unsigned int, am));
+            const unsigned int m = f16x2_rowmax(__builtin_bit_cast(unsigned int, am));
             if (li == 0) atomicMax(mxw, m);
             __syncthreads();
             float S, invS;
-            g3h_scale(*mxw, S, invS);
+            f16x2_scale(*mxw, S, invS);
             us = invS * g.inv_sw;
             // in place, one wave per pixel group: lane = (pixel of the group, channel quad)
             constexpr int ppw = 64 / c4n;                 // pixels per wave and pass (2, 4 or 8)
@@ -149,9 +129,8 @@ __global__ __launch_bounds__(512, 2) void conv_generic_x3_kernel(Gen3Args g)
                 const int pix = p0 + pl;
                 if (pix < R * WP) {
                     char* base = smem + pix * psb;
-                    const f32x4 v = *(const f32x4*)(base + c4 * 16) * S;
-                    const f16x4 hi = __builtin_convertvector(v, f16x4);
-                    const f32x4 rr = v - __builtin_convertvector(hi, f32x4);      // exact in fp32
+                    f16x4 hi;
+                    const f32x4 rr = f16x2_residual4(*(const f32x4*)(base + c4 * 16), S, hi);
                     *(f16x4*)(base + c4 * 8) = hi;
                     *(f16x4*)(base + PB + c4 * 8) = __builtin_convertvector(rr, f16x4);
                 }

@@ -17,6 +17,7 @@
 // Accumulation is a k-ordered fp32 fma chain (the MFMA's exact semantics), one rounding
 // per product, bias added after the sum -- same numerics class as the fp32 oracle.
 #include "common.hpp"
+#include "kernel_setup.hpp"
 
 #include <cstdlib>
 #include <type_traits>
@@ -605,25 +606,11 @@ template <class C>
 static hipError_t launch_cfg(const float* in, const float* wfrag, const float* ep, float* out,
                              int64_t n_cells, hipStream_t stream, float* stats_part = nullptr, int* stats_parts = nullptr)
 {
-    // Persistent grid = exactly the number of workgroups the chip holds at once (CUs x resident
-    // workgroups per CU for this kernel's registers and LDS): a larger grid would queue the
-    // surplus behind the first wave of workgroups and run it at a fraction of the occupancy.
-    static int resident = 0, cus = 0;
-    if (!resident) {
-        hipError_t e = hipFuncSetAttribute((const void*)conv_mfma_kernel<C>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES + kStatsLds<C>);
-        if (e != hipSuccess) return e;
-        int dev = 0, per_cu = 0;
-        if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
-        if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)conv_mfma_kernel<C>, 256, C::LDS_BYTES + kStatsLds<C>);
-        if (e != hipSuccess) return e;
-        if (per_cu < 1) per_cu = 1;
-        resident = cus * per_cu;
-    }
+    KernelSetup ks;       // persistent grid = what the chip holds at once (kernel_setup.hpp)
+    if (hipError_t e = kernel_setup<conv_mfma_kernel<C>>(256, C::LDS_BYTES + kStatsLds<C>, ks); e != hipSuccess) return e;
     const long total = (long)n_cells * C::NSTRIP;
     if (total <= 0) return hipSuccess;
-    unsigned grid = (unsigned)(total < resident ? total : resident);
+    unsigned grid = (unsigned)(total < ks.resident ? total : ks.resident);
     if (stats_part) {      // one {count, mean, M2} x COUT partial per workgroup in a BN_MAX_PARTS x 3 x 64-float buffer
         const unsigned cap = (unsigned)(BN_MAX_PARTS * 64 / C::COUT);
         if (grid > cap) grid = cap;

@@ -13,6 +13,7 @@
 // upsampled grid coincides with the zero halo of the stored grid.  The weight indices are
 // wave-uniform, so W_eff is fetched with scalar loads into SGPRs.
 #include "common.hpp"
+#include "kernel_setup.hpp"
 
 namespace cs {
 
@@ -167,21 +168,11 @@ static hipError_t launch_conv7_err_t(const float* a6, const float* x, const floa
                                      float* recon, float* dz, float* dzsum_part, int64_t n_cells, hipStream_t stream)
 {
     constexpr int LDS = C7_LDS + 48;
-    static int resident = 0;   // persistent grid = what the chip holds at once (see conv_mfma.hip)
-    if (!resident) {
-        hipError_t e = hipFuncSetAttribute((const void*)conv7_err_kernel<TRAIN>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) return e;
-        int dev = 0, cus = 0, per_cu = 0;
-        if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
-        if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)conv7_err_kernel<TRAIN>, 256, LDS);
-        if (e != hipSuccess) return e;
-        if (per_cu < 1) per_cu = 1;
-        resident = cus * per_cu;
-    }
+    KernelSetup ks;            // persistent grid = what the chip holds at once (kernel_setup.hpp)
+    if (hipError_t e = kernel_setup<conv7_err_kernel<TRAIN>>(256, LDS, ks); e != hipSuccess) return e;
     const long total = (long)n_cells * C7_NSTRIP;
     if (total <= 0) return hipSuccess;
-    const unsigned grid = (unsigned)(total < resident ? total : resident);
+    const unsigned grid = (unsigned)(total < ks.resident ? total : ks.resident);
     hipLaunchKernelGGL(conv7_err_kernel<TRAIN>, dim3(grid), dim3(256), LDS, stream, a6, x, weff_dev, b7_dev, errpart, recon,
                        (long)n_cells, dz, dzsum_part);
     return hipGetLastError();

@@ -15,7 +15,8 @@
 // (slice, tile) pairs: bias -> relu -> BN -> 2x2 max -> store.  Compared with the previous kernel
 // (every wave transformed every column for its own output slice) the LDS patch reads and transform
 // VALU work drop 4x; the price is the exchange and a second barrier per group.
-#include "common.hpp"
+#include "kernel_setup.hpp"
+#include "split16.hpp"
 
 #include <cmath>
 #include <cstdlib>
@@ -78,15 +79,6 @@ __device__ __forceinline__ void wn_store(float* strip, int y0, int r, int loff, 
 // differences per wave: [0] prefetch issue + transform + MFMA + row fold + exchange write, [1] next-strip
 // LDS writes, [2] wait at barrier A, [3] column fold + epilogue + stores, [4] wait at barrier B, [5] the
 // part of [0] spent issuing the next strip's global loads.  Never used for results or timing.
-__device__ __forceinline__ unsigned long long wcs_stamp()
-{
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
-
 template <class C, bool DIAG>
 __global__ __launch_bounds__(256, 2) void conv_wino_cs_kernel(const float* __restrict__ in, const float* __restrict__ ufrag,
                                                              const float* __restrict__ ep /* [3][cout] */,
@@ -146,12 +138,12 @@ __global__ __launch_bounds__(256, 2) void conv_wino_cs_kernel(const float* __res
         const float* strip = (const float*)(smem + buf * C::STRIP);
         float* nstrip = (float*)(smem + (buf ^ 1) * C::STRIP);
 
-        if constexpr (DIAG) dt = wcs_stamp();
+        if constexpr (DIAG) dt = cycle_stamp();
         if (has_next) {
 #pragma unroll
             for (int j = 0; j < C::NLD; ++j) stg[j] = wn_load<C>(cell_ptr(nitem / C::NGRP), (int)(nitem % C::NGRP) * C::SR, j, goff);
         }
-        if constexpr (DIAG) { const unsigned long long t = wcs_stamp(); dg[5] += t - dt; }
+        if constexpr (DIAG) { const unsigned long long t = cycle_stamp(); dg[5] += t - dt; }
         const float* da_p = strip + poff + ca * C::PS;
         const float* db_p = strip + poff + cb * C::PS;
         auto transform = [&](int q, f32x4 v[4]) {
@@ -218,14 +210,14 @@ __global__ __launch_bounds__(256, 2) void conv_wino_cs_kernel(const float* __res
 #pragma unroll
             for (int s = 0; s < C::NS; ++s) fold_store(s, acc[s]);
         }
-        if constexpr (DIAG) { const unsigned long long t = wcs_stamp(); dg[0] += t - dt; dt = t; }
+        if constexpr (DIAG) { const unsigned long long t = cycle_stamp(); dg[0] += t - dt; dt = t; }
         if (has_next) {
 #pragma unroll
             for (int j = 0; j < C::NLD; ++j) wn_store<C>(nstrip, (int)(nitem % C::NGRP) * C::SR, j, loff, stg[j]);
         }
-        if constexpr (DIAG) { const unsigned long long t = wcs_stamp(); dg[1] += t - dt; dt = t; }
+        if constexpr (DIAG) { const unsigned long long t = cycle_stamp(); dg[1] += t - dt; dt = t; }
         __syncthreads();   // s of all four columns in LDS; this strip fully read; next strip complete
-        if constexpr (DIAG) { const unsigned long long t = wcs_stamp(); dg[2] += t - dt; dt = t; }
+        if constexpr (DIAG) { const unsigned long long t = cycle_stamp(); dg[2] += t - dt; dt = t; }
         // column fold Y = s A for this wave's (slice, tiles), then bias -> relu -> BN -> 2x2 max
         f32x4 t0[4], t1[4];
 #pragma unroll
@@ -253,9 +245,9 @@ __global__ __launch_bounds__(256, 2) void conv_wino_cs_kernel(const float* __res
             const int ty = grp * C::TR + t / C::TW, tx = t % C::TW;
             out[(((size_t)cell * (C::H / 2) + ty) * (C::W / 2) + tx) * C::COUT + co] = res;
         }
-        if constexpr (DIAG) { const unsigned long long t = wcs_stamp(); dg[3] += t - dt; dt = t; }
+        if constexpr (DIAG) { const unsigned long long t = cycle_stamp(); dg[3] += t - dt; dt = t; }
         __syncthreads();   // exchange area free again
-        if constexpr (DIAG) { const unsigned long long t = wcs_stamp(); dg[4] += t - dt; dt = t; }
+        if constexpr (DIAG) { const unsigned long long t = cycle_stamp(); dg[4] += t - dt; dt = t; }
         buf ^= 1;
     }
     if constexpr (DIAG) {
@@ -287,9 +279,6 @@ struct W3X {
 //           maximum is taken where the next strip is staged (registers -> DPP row max -> LDS atomic max, read behind the
 //           barrier that is there anyway).  The strip itself stays fp32 in LDS (the transform runs in fp32); V S is split in
 //           registers; 1 / (S S_w) is applied with the bias in the epilogue's fma.
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-
 struct W3H {
     using C = WinoL3;
     static constexpr int OFF_MAX = 2 * W3X::STRIP + C::XCH;        // two words: strip maxima, alternating
@@ -297,53 +286,6 @@ struct W3H {
     static_assert(2 * LDS <= 160 * 1024, "two workgroups per CU");
 };
 
-__device__ __forceinline__ unsigned int w3h_rowmax(unsigned int m)
-{
-    unsigned int o;
-    o = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)m, 0xB1, 0xF, 0xF, true);  m = m > o ? m : o;     // quad_perm [1,0,3,2]
-    o = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)m, 0x4E, 0xF, 0xF, true);  m = m > o ? m : o;     // quad_perm [2,3,0,1]
-    o = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)m, 0x124, 0xF, 0xF, true); m = m > o ? m : o;     // row_ror:4
-    o = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)m, 0x128, 0xF, 0xF, true); m = m > o ? m : o;     // row_ror:8
-    return m;
-}
-// S = the power of two that puts 4 x (a maximum with float bits mbits) into [2^14, 2^15), and 1 / S (exponents clamped so that
-// both stay normal floats)
-__device__ __forceinline__ void w3h_scale(unsigned int mbits, float& S, float& invS)
-{
-    int E = (int)((mbits >> 23) & 0xffu) + 2;
-    E = E < 40 ? 40 : (E > 254 ? 254 : E);
-    S = __builtin_bit_cast(float, (unsigned int)(268 - E) << 23);
-    invS = __builtin_bit_cast(float, (unsigned int)(E - 14) << 23);
-}
-// Eight scaled values -> their hi and lo fragments as ONE block of 12 instructions (v_cvt_pk_f16_f32 per pair, then the residuals as
-// v_fma_mix{lo,hi}_f16: exact in fp32, one rounding); the convert / convert back / subtract / convert form compiled to ~ 20 and the
-// kernel ran 2.3 % slower (24.7 vs 24.1 ms per 1 M cells; per-VALUE asm blocks had measured slower in round 3: common.hpp).  -0
-// residuals come out +0.  The results feed MFMAs directly, which the hazard recogniser cannot see through the asm: the block ends with the two wait
-// states a VALU write -> MFMA read needs.
-__device__ __forceinline__ void w3h_split8(const f32x4& lo4, const f32x4& hi4, float S, f16x8& ah, f16x8& al)
-{
-    const f32x4 a = lo4 * S, b = hi4 * S;
-    const float a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[3], b0 = b[0], b1 = b[1], b2 = b[2], b3 = b[3];
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-    unsigned int h0, h1, h2, h3, l0, l1, l2, l3;
-    asm("v_cvt_pk_f16_f32 %0, %8, %9\n\t"
-        "v_cvt_pk_f16_f32 %1, %10, %11\n\t"
-        "v_cvt_pk_f16_f32 %2, %12, %13\n\t"
-        "v_cvt_pk_f16_f32 %3, %14, %15\n\t"
-        "v_fma_mixlo_f16 %4, %8, 1.0, -%0 op_sel:[0,0,0] op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixlo_f16 %5, %10, 1.0, -%1 op_sel:[0,0,0] op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixlo_f16 %6, %12, 1.0, -%2 op_sel:[0,0,0] op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixlo_f16 %7, %14, 1.0, -%3 op_sel:[0,0,0] op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixhi_f16 %4, %9, 1.0, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixhi_f16 %5, %11, 1.0, -%1 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixhi_f16 %6, %13, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixhi_f16 %7, %15, 1.0, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-        "s_nop 1"
-        : "=&v"(h0), "=&v"(h1), "=&v"(h2), "=&v"(h3), "=&v"(l0), "=&v"(l1), "=&v"(l2), "=&v"(l3)
-        : "v"(a0), "v"(a1), "v"(a2), "v"(a3), "v"(b0), "v"(b1), "v"(b2), "v"(b3));
-    ah = __builtin_bit_cast(f16x8, u32x4{h0, h1, h2, h3});
-    al = __builtin_bit_cast(f16x8, u32x4{l0, l1, l2, l3});
-}
 __global__ __launch_bounds__(256, 2) void conv3_wino_h2_kernel(const float* __restrict__ in, const f16x8* __restrict__ ufrag,
                                                               const float* __restrict__ ep /* [3][32] */, float* __restrict__ out,
                                                               long n_cells, float inv_sw)
@@ -386,9 +328,7 @@ __global__ __launch_bounds__(256, 2) void conv3_wino_h2_kernel(const float* __re
     auto st_prep = [&](int y0, int r, f32x4 v, unsigned int& mx) {
         const int sy = y0 - 1 + r;
         if (sy < 0 || sy >= C::H) v = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-        const float a = v[0], b = v[1], c = v[2], d = v[3];         // scalars first (see conv45_bf16x3.hip, h2_absmax4)
-        const unsigned int u = __builtin_bit_cast(unsigned int, fmaxf(fmaxf(fabsf(a), fabsf(b)), fmaxf(fabsf(c), fabsf(d))));
-        mx = mx > u ? mx : u;
+        f16x2_absmax4(v, mx);
         return v;
     };
     for (int i = tid; i < W3H::LDS / 16; i += 256) ((f32x4*)smem)[i] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
@@ -401,10 +341,10 @@ __global__ __launch_bounds__(256, 2) void conv3_wino_h2_kernel(const float* __re
             const f32x4 v = st_prep((int)(first % C::NGRP) * C::SR, r, wn_load<C>(cell_ptr(first / C::NGRP), (int)(first % C::NGRP) * C::SR, r, goff), mx);
             *(f32x4*)((float*)smem + r * W3X::ROWP + loff) = v;
         }
-        mx = w3h_rowmax(mx);
+        mx = f16x2_rowmax(mx);
         if (li == 0) atomicMax(&mxw[0], mx);
         __syncthreads();
-        w3h_scale(mxw[0], S, invS);
+        f16x2_scale<2>(mxw[0], S, invS);
         __syncthreads();
         if (tid == 0) mxw[0] = 0;
     }
@@ -450,7 +390,7 @@ __global__ __launch_bounds__(256, 2) void conv3_wino_h2_kernel(const float* __re
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 f16x8 ah, al;
-                w3h_split8(v[r][0], v[r][1], S, ah, al);
+                f16x2_split8(v[r][0], v[r][1], S, ah, al);
 #pragma unroll
                 for (int s = 0; s < C::NS; ++s) {
                     f32x4 d = acc[s][r];
@@ -481,11 +421,11 @@ __global__ __launch_bounds__(256, 2) void conv3_wino_h2_kernel(const float* __re
                 stg[j] = st_prep((int)(nitem % C::NGRP) * C::SR, j, stg[j], mx);
                 *(f32x4*)(nstrip + j * W3X::ROWP + loff) = stg[j];
             }
-            mx = w3h_rowmax(mx);
+            mx = f16x2_rowmax(mx);
             if (li == 0) atomicMax(mword, mx);
         }
         __syncthreads();   // s of all four columns in LDS; this strip fully read; next strip and its maximum complete
-        if (has_next) w3h_scale(*mword, S, invS);
+        if (has_next) f16x2_scale<2>(*mword, S, invS);
         f32x4 t0[4], t1[4];
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
@@ -704,37 +644,24 @@ size_t pack_frags(const float* hwio, float* dst)
     return total;
 }
 
-unsigned long long* g_diag[3] = {nullptr, nullptr, nullptr};
-int g_diag_blocks[3] = {0, 0, 0};
+// DIAG builds: 4 waves x 6 phases per workgroup; [layer - 1]
+StampTable g_wcs_stamps[2] = {{24}, {24}};
 
 template <class C>
 hipError_t launch(int layer, const float* in, const float* ufrag, const float* ep, float* out, int64_t n_cells, hipStream_t stream)
 {
-    static int resident = 0;
     static const bool diag = getenv("CS_WINO_DIAG") != nullptr;
-    if (!resident) {
-        hipError_t e = hipFuncSetAttribute((const void*)conv_wino_cs_kernel<C, false>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute((const void*)conv_wino_cs_kernel<C, true>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-        if (e != hipSuccess) return e;
-        int dev = 0, cus = 0, per_cu = 0;
-        if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
-        if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)conv_wino_cs_kernel<C, false>, 256, C::LDS);
-        if (e != hipSuccess) return e;
-        if (per_cu < 1) per_cu = 1;
-        resident = cus * per_cu;
-        if (diag) {
-            if ((e = hipMalloc(&g_diag[layer], (size_t)resident * 24 * sizeof(unsigned long long))) != hipSuccess) return e;
-            g_diag_blocks[layer] = resident;
-        }
-    }
+    StampTable& stamps = g_wcs_stamps[layer - 1];
+    KernelSetup ks;
+    const hipError_t e = !diag ? kernel_setup<conv_wino_cs_kernel<C, false>>(256, C::LDS, ks)
+                               : kernel_setup<conv_wino_cs_kernel<C, true>>(256, C::LDS, ks, &stamps);
+    if (e != hipSuccess) return e;
     const long total = (long)n_cells * C::NGRP;
     if (total <= 0) return hipSuccess;
-    const unsigned grid = (unsigned)(total < resident ? total : resident);
+    const unsigned grid = (unsigned)(total < ks.resident ? total : ks.resident);
     if (diag)
         hipLaunchKernelGGL((conv_wino_cs_kernel<C, true>), dim3(grid), dim3(256), C::LDS, stream, in, ufrag, ep, out, (long)n_cells,
-                           g_diag[layer]);
+                           stamps.begin(ks, grid));
     else
         hipLaunchKernelGGL((conv_wino_cs_kernel<C, false>), dim3(grid), dim3(256), C::LDS, stream, in, ufrag, ep, out, (long)n_cells,
                            (unsigned long long*)nullptr);
@@ -788,20 +715,11 @@ size_t pack_wino3_h2(const float* hwio /* [3][3][64][32] */, uint16_t* dst, floa
 hipError_t launch_conv3_wino_h2(const float* in, const uint16_t* uplanes, float inv_sw, const float* ep, float* out, int64_t n_cells,
                                 hipStream_t stream)
 {
-    static int resident = 0;
-    if (!resident) {
-        hipError_t e = hipFuncSetAttribute((const void*)conv3_wino_h2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, W3H::LDS);
-        if (e != hipSuccess) return e;
-        int dev = 0, cus = 0, per_cu = 0;
-        if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
-        if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
-        if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)conv3_wino_h2_kernel, 256, W3H::LDS)) != hipSuccess) return e;
-        if (per_cu < 1) per_cu = 1;
-        resident = cus * per_cu;
-    }
+    KernelSetup ks;
+    if (hipError_t e = kernel_setup<conv3_wino_h2_kernel>(256, W3H::LDS, ks); e != hipSuccess) return e;
     const long total = (long)n_cells * WinoL3::NGRP;
     if (total <= 0) return hipSuccess;
-    const unsigned grid = (unsigned)(total < resident ? total : resident);
+    const unsigned grid = (unsigned)(total < ks.resident ? total : ks.resident);
     hipLaunchKernelGGL(conv3_wino_h2_kernel, dim3(grid), dim3(256), W3H::LDS, stream, in, (const f16x8*)uplanes, ep, out, (long)n_cells, inv_sw);
     return hipGetLastError();
 }
@@ -811,20 +729,11 @@ hipError_t launch_conv_wino_cs(int layer, const float* in, const float* ufrag, c
 {
     static const bool no_ring = getenv("CS_WINO_DIAG") != nullptr;       // tools/wino_diag.py stamps the strip kernel
     if (layer == 1 && !no_ring) {
-        static int resident = 0;
         constexpr int lds = 2 * WinoL2::STRIP + WinoL2::XCH;
-        if (!resident) {
-            hipError_t e = hipFuncSetAttribute((const void*)conv2_wino_ring_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            if (e != hipSuccess) return e;
-            int dev = 0, cus = 0, per_cu = 0;
-            if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
-            if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
-            if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)conv2_wino_ring_kernel, 256, lds)) != hipSuccess) return e;
-            if (per_cu < 1) per_cu = 1;
-            resident = cus * per_cu;
-        }
+        KernelSetup ks;
+        if (hipError_t e = kernel_setup<conv2_wino_ring_kernel>(256, lds, ks); e != hipSuccess) return e;
         if (n_cells <= 0) return hipSuccess;
-        const unsigned grid = (unsigned)(n_cells < resident ? n_cells : resident);
+        const unsigned grid = (unsigned)(n_cells < ks.resident ? n_cells : ks.resident);
         hipLaunchKernelGGL(conv2_wino_ring_kernel, dim3(grid), dim3(256), lds, stream, in, ufrag, ep, out, (long)n_cells);
         return hipGetLastError();
     }
@@ -838,15 +747,6 @@ hipError_t launch_conv_wino_cs(int layer, const float* in, const float* ufrag, c
 // Diagnostic only (CS_WINO_DIAG=1): per-wave phase cycles of the LAST launch of `layer`, averaged over waves.
 extern "C" int cs_debug_wino_cs_diag(int layer, double out6[6])
 {
-    using namespace cs;
-    if (layer < 1 || layer > 2 || !g_diag[layer]) return -1;
-    if (hipDeviceSynchronize() != hipSuccess) return -2;
-    const size_t n = (size_t)g_diag_blocks[layer] * 24;
-    unsigned long long* h = new unsigned long long[n];
-    if (hipMemcpy(h, g_diag[layer], n * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) { delete[] h; return -3; }
-    for (int k = 0; k < 6; ++k) out6[k] = 0.0;
-    for (size_t i = 0; i < n; ++i) out6[i % 6] += (double)h[i];
-    for (int k = 0; k < 6; ++k) out6[k] /= (double)(n / 6);
-    delete[] h;
-    return 0;
+    if (layer < 1 || layer > 2) return -1;
+    return cs::stamp_table_average(cs::g_wcs_stamps[layer - 1], 6, out6);
 }

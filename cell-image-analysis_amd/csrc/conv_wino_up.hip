@@ -21,7 +21,8 @@
 // per 16-tile group and finishes its own outputs: no cross-wave traffic, one barrier per group (strip
 // double buffer).  conv5's waves handle their two slices one after the other and repeat the (cheap)
 // transform, so only nine accumulators are live at a time.
-#include "common.hpp"
+#include "kernel_setup.hpp"
+#include "split16.hpp"
 
 #include <type_traits>
 
@@ -82,15 +83,6 @@ __device__ __forceinline__ void wu_store(float* strip, int y0, int j, int rsub, 
 
 // DIAG: diagnostic build, s_memtime stamps summed per wave: [0] next-strip load issue, [1] transforms + MFMAs,
 // [2] output transform + epilogue + stores, [3] next-strip LDS writes, [4] barrier.  Never used for results or timing.
-__device__ __forceinline__ unsigned long long wu_stamp()
-{
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
-
 template <class C, bool DIAG>
 __global__ __launch_bounds__(C::THREADS, 2) void conv_wino_up_kernel(const float* __restrict__ in, const float* __restrict__ ufrag,
                                                                      const float* __restrict__ ep /* [3][cout] */,
@@ -148,13 +140,13 @@ __global__ __launch_bounds__(C::THREADS, 2) void conv_wino_up_kernel(const float
         const float* strip = (const float*)(smem + buf * C::STRIP);
         float* nstrip = (float*)(smem + (buf ^ 1) * C::STRIP);
 
-        if constexpr (DIAG) dt = wu_stamp();
+        if constexpr (DIAG) dt = cycle_stamp();
         f32x4 stg[C::NLD];
         if (has_next) {
 #pragma unroll
             for (int j = 0; j < C::NLD; ++j) stg[j] = wu_load<C>(cell_ptr(nitem / C::NGRP), (int)(nitem % C::NGRP) * C::SR, j, rsub, goff);
         }
-        if constexpr (DIAG) { const unsigned long long t = wu_stamp(); dg[0] += t - dt; dt = t; }
+        if constexpr (DIAG) { const unsigned long long t = cycle_stamp(); dg[0] += t - dt; dt = t; }
 
         const float* d0 = strip + poff;
 #pragma unroll
@@ -200,7 +192,7 @@ __global__ __launch_bounds__(C::THREADS, 2) void conv_wino_up_kernel(const float
             }
             if constexpr (DIAG) {
                 asm volatile("" ::"v"(acc[0][0]), "v"(acc[8][3]));
-                const unsigned long long t = wu_stamp(); dg[1] += t - dt; dt = t;
+                const unsigned long long t = cycle_stamp(); dg[1] += t - dt; dt = t;
             }
             // Y = A^T M A per tile register, bias -> relu -> BN, scatter to the phase's output pixels
             const int co = (wsl * C::NSW + k) * 16 + li;
@@ -221,15 +213,15 @@ __global__ __launch_bounds__(C::THREADS, 2) void conv_wino_up_kernel(const float
                 o[(size_t)2 * C::WO * C::COUT] = post(y10);                         // (1,0): output row + 2
                 o[(size_t)2 * C::WO * C::COUT + 2 * C::COUT] = post(y11);
             }
-            if constexpr (DIAG) { const unsigned long long t = wu_stamp(); dg[2] += t - dt; dt = t; }
+            if constexpr (DIAG) { const unsigned long long t = cycle_stamp(); dg[2] += t - dt; dt = t; }
         }
         if (has_next) {
 #pragma unroll
             for (int j = 0; j < C::NLD; ++j) wu_store<C>(nstrip, (int)(nitem % C::NGRP) * C::SR, j, rsub, loff, stg[j]);
         }
-        if constexpr (DIAG) { const unsigned long long t = wu_stamp(); dg[3] += t - dt; dt = t; }
+        if constexpr (DIAG) { const unsigned long long t = cycle_stamp(); dg[3] += t - dt; dt = t; }
         __syncthreads();   // this strip fully read; the next strip complete in the other buffer
-        if constexpr (DIAG) { const unsigned long long t = wu_stamp(); dg[4] += t - dt; dt = t; }
+        if constexpr (DIAG) { const unsigned long long t = cycle_stamp(); dg[4] += t - dt; dt = t; }
         buf ^= 1;
     }
     if constexpr (DIAG) {
@@ -333,7 +325,7 @@ __global__ __launch_bounds__(WUL6::THREADS, 1) void conv67_fused_kernel(
             const float* strip = (const float*)(smem + buf * C::STRIP);
             float* nstrip = (float*)(smem + (buf ^ 1) * C::STRIP);
 
-            if constexpr (DIAG) dt = wu_stamp();
+            if constexpr (DIAG) dt = cycle_stamp();
             f32x4 stg[C::NLD];
             if (has_next) {
 #pragma unroll
@@ -349,7 +341,7 @@ __global__ __launch_bounds__(WUL6::THREADS, 1) void conv67_fused_kernel(
             float xtail = 0.0f;
             if (grp == C::NGRP - 1 && wave == 0) xtail = xc[63 * 64 + lane];
 
-            if constexpr (DIAG) { const unsigned long long t = wu_stamp(); dg[0] += t - dt; dt = t; }
+            if constexpr (DIAG) { const unsigned long long t = cycle_stamp(); dg[0] += t - dt; dt = t; }
             // ---- conv6: transforms + MFMAs, as in conv_wino_up_kernel
             const float* d0 = strip + poff;
             f32x4 acc[9];
@@ -381,7 +373,7 @@ __global__ __launch_bounds__(WUL6::THREADS, 1) void conv67_fused_kernel(
             }
             if constexpr (DIAG) {
                 asm volatile("" ::"v"(acc[0][0]), "v"(acc[8][3]));
-                const unsigned long long t = wu_stamp(); dg[1] += t - dt; dt = t;
+                const unsigned long long t = cycle_stamp(); dg[1] += t - dt; dt = t;
             }
             // ---- Y = A^T M A, bias -> relu -> BN; the group's a6 block goes to LDS: local row 2 (2 (t / 8) + u) + a
             auto post = [&](float v) { v = fmaxf(v, 0.0f); return fmaf(v, bns, bnt); };
@@ -402,7 +394,7 @@ __global__ __launch_bounds__(WUL6::THREADS, 1) void conv67_fused_kernel(
                 o[(2 * 32 + 2) * F67::PA] = post(y11);
             }
             __syncthreads();
-            if constexpr (DIAG) { const unsigned long long t = wu_stamp(); dg[2] += t - dt; dt = t; }
+            if constexpr (DIAG) { const unsigned long long t = cycle_stamp(); dg[2] += t - dt; dt = t; }
             // ---- T = a6 W_eff^T for local row `wave`, 16 pixels per MFMA chain; K order: channel 8 kq + s
             float wc[8];                                                                 // W_eff[n = li][c = 8 kq + s]
             *(f32x4*)&wc[0] = *(const f32x4*)(wl + li * 36 + kq * 8);
@@ -431,7 +423,7 @@ __global__ __launch_bounds__(WUL6::THREADS, 1) void conv67_fused_kernel(
                 for (int j = 0; j < C::NLD; ++j) wu_store<C>(nstrip, ngrp * C::SR, j, rsub, loff, stg[j]);
             }
             __syncthreads();
-            if constexpr (DIAG) { const unsigned long long t = wu_stamp(); dg[3] += t - dt; dt = t; }
+            if constexpr (DIAG) { const unsigned long long t = cycle_stamp(); dg[3] += t - dt; dt = t; }
             // ---- gather: new a6 row y finishes output rows 2y - 1 (phase a = 1 of row y - 1) and 2y (a = 0)
             const int px = lane & 1, xh = (lane >> 1) + px;                              // halo column of rx = 0
 #pragma unroll
@@ -462,7 +454,7 @@ __global__ __launch_bounds__(WUL6::THREADS, 1) void conv67_fused_kernel(
             }
             if constexpr (DIAG) {
                 asm volatile("" ::"v"(s2), "v"(s1));
-                const unsigned long long t = wu_stamp(); dg[4] += t - dt; dt = t;
+                const unsigned long long t = cycle_stamp(); dg[4] += t - dt; dt = t;
             }
             buf ^= 1;
         }
@@ -517,9 +509,6 @@ struct F67T {
 // its products are exact -- tools/microbench/fp16_mfma_probe.hip, profiles/r03_fp16_mfma_probe.json).  One MFMA carries ONE
 // magnitude (hi hi | hi lo, lo hi on a second accumulator), as in the bf16 kernels.  Error against the fp64 oracle:
 // tests/study_split_fp16.py (CPU emulation: a6 1.8e-7 of its range; the fp32 MFMA chain 7.2e-7) and the unchanged -m gpu bars.
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-
 struct F67H {
     static constexpr int PLB = 2 * 64;                         // bytes of one plane of a pixel: 64 channels
     static constexpr int PXB = 2 * PLB + 32;                   // 288 B per staged pixel = twice an odd number of 16-byte slots
@@ -542,41 +531,11 @@ struct F67H {
     static_assert(LDS <= 160 * 1024 && STRIP % 16 == 0, "LDS budget");
 };
 
-// max|v| over the 16 lanes of a DPP row (quad swaps, then row rotations by 4 and 8)
-__device__ __forceinline__ unsigned int h2_rowmax(unsigned int m)
-{
-    unsigned int o;
-    o = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)m, 0xB1, 0xF, 0xF, true);  m = m > o ? m : o;     // quad_perm [1,0,3,2]
-    o = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)m, 0x4E, 0xF, 0xF, true);  m = m > o ? m : o;     // quad_perm [2,3,0,1]
-    o = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)m, 0x124, 0xF, 0xF, true); m = m > o ? m : o;     // row_ror:4
-    o = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)m, 0x128, 0xF, 0xF, true); m = m > o ? m : o;     // row_ror:8
-    return m;
-}
-
-// the power of two S that puts a maximum with float bits `mbits` (>= 0) into [2^14, 2^15), and 1 / S.  The exponent is clamped
-// so that both stay normal floats: a strip whose maximum is below 2^-87 (or zero) is scaled by 2^101 -- its values then sit in
-// fp16's lowest binades or vanish, 2^-87 of anything the next layer can see.
-__device__ __forceinline__ void h2_scale(unsigned int mbits, float& S, float& invS)
-{
-    int E = (int)((mbits >> 23) & 0xffu);
-    E = E < 40 ? 40 : (E > 254 ? 254 : E);
-    S = __builtin_bit_cast(float, (unsigned int)(268 - E) << 23);          // 2^(14 - (E - 127))
-    invS = __builtin_bit_cast(float, (unsigned int)(E - 14) << 23);
-}
-
-__device__ __forceinline__ void h2_split4(const f32x4& x, float S, f16x4& hi, f16x4& lo)
-{
-    const f32x4 v = x * S;
-    hi = __builtin_convertvector(v, f16x4);
-    const f32x4 r = v - __builtin_convertvector(hi, f32x4);            // exact in fp32
-    lo = __builtin_convertvector(r, f16x4);
-}
-
 __device__ __forceinline__ void h2_store(char* strip, int j, int rsub, int loffb, const f32x4& v, float S)
 {
     const int r = rsub + WUL6::RPP * j;
     f16x4 hi, lo;
-    h2_split4(v, S, hi, lo);
+    f16x2_split4(v, S, hi, lo);
     char* d = strip + r * F67H::ROWB + loffb;
     *(f16x4*)d = hi;
     *(f16x4*)(d + F67H::PLB) = lo;
@@ -587,10 +546,7 @@ __device__ __forceinline__ f32x4 h2_prep(int y0, int j, int rsub, f32x4 v, unsig
 {
     const int sy = y0 - 1 + rsub + WUL6::RPP * j;
     if (sy < 0 || sy >= WUL6::HS) v = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    // (scalars first: __builtin_bit_cast of a vector ELEMENT expression reads element 0 whatever the index -- clang 19, ROCm 7.2)
-    const float a = v[0], b = v[1], c = v[2], d = v[3];
-    const unsigned int u = __builtin_bit_cast(unsigned int, fmaxf(fmaxf(fabsf(a), fabsf(b)), fmaxf(fabsf(c), fabsf(d))));
-    mx = mx > u ? mx : u;
+    f16x2_absmax4(v, mx);
     return v;
 }
 
@@ -644,11 +600,11 @@ __global__ __launch_bounds__(WUL6::THREADS, 2) void conv67_h2_kernel(
         unsigned int mx = 0;
 #pragma unroll
         for (int j = 0; j < C::NLD; ++j) stg[j] = h2_prep(0, j, rsub, wu_load<C>(cell_ptr(first), 0, j, rsub, goff), mx);
-        mx = h2_rowmax(mx);
+        mx = f16x2_rowmax(mx);
         if (li == 0) atomicMax(&mxw[0], mx);
         __syncthreads();
         float S, invS;
-        h2_scale(mxw[0], S, invS);
+        f16x2_scale(mxw[0], S, invS);
         unscale = invS * inv_sw;
 #pragma unroll
         for (int j = 0; j < C::NLD; ++j) h2_store(smem, j, rsub, loffb, stg[j], S);
@@ -670,7 +626,7 @@ __global__ __launch_bounds__(WUL6::THREADS, 2) void conv67_h2_kernel(
             ++strip_no;
             unsigned int* const mword = mxw + (strip_no & 1);
 
-            if constexpr (DIAG) dt = wu_stamp();
+            if constexpr (DIAG) dt = cycle_stamp();
             f32x4 stg[C::NLD];
             if (has_next) {
 #pragma unroll
@@ -686,7 +642,7 @@ __global__ __launch_bounds__(WUL6::THREADS, 2) void conv67_h2_kernel(
             float xtail = 0.0f;
             if (grp == C::NGRP - 1 && wave == 0) xtail = xc[63 * 64 + lane];
 
-            if constexpr (DIAG) { const unsigned long long t = wu_stamp(); dg[0] += t - dt; dt = t; }
+            if constexpr (DIAG) { const unsigned long long t = cycle_stamp(); dg[0] += t - dt; dt = t; }
             // ---- conv6, folded direct, three fp16 products per (tile, tap, 32-channel block); the large products and the two
             // cross terms on separate accumulators
             f32x4 ah[4], al[4];
@@ -724,7 +680,7 @@ __global__ __launch_bounds__(WUL6::THREADS, 2) void conv67_h2_kernel(
             }
             if constexpr (DIAG) {
                 asm volatile("" ::"v"(ah[0][0]), "v"(al[3][3]));
-                const unsigned long long t = wu_stamp(); dg[1] += t - dt; dt = t;
+                const unsigned long long t = cycle_stamp(); dg[1] += t - dt; dt = t;
             }
             // ---- undo the scales, bias -> relu -> BN; D row 4 kq + r = stored pixel xs of stored row t -> a6 block row 2 t + a, column 2 xs + b
 #pragma unroll
@@ -739,11 +695,11 @@ __global__ __launch_bounds__(WUL6::THREADS, 2) void conv67_h2_kernel(
                 unsigned int mx = 0;
 #pragma unroll
                 for (int j = 0; j < C::NLD; ++j) stg[j] = h2_prep(ngrp * C::SR, j, rsub, stg[j], mx);
-                mx = h2_rowmax(mx);
+                mx = f16x2_rowmax(mx);
                 if (li == 0) atomicMax(mword, mx);
             }
             __syncthreads();
-            if constexpr (DIAG) { const unsigned long long t = wu_stamp(); dg[2] += t - dt; dt = t; }
+            if constexpr (DIAG) { const unsigned long long t = cycle_stamp(); dg[2] += t - dt; dt = t; }
             // ---- T^T = W_eff a6^T for local row `wave`: the 16 transform rows n are the MFMA's rows, 16 pixels its columns, two chains
             // (pixels x and 16 + x).  K order: step s of lane kq is channel 4 kq + (s & 3) + 16 (s >> 2).  D then has row 4 kq + r in
             // register r of lane (pixel, kq): a ds_write_b32 of one r puts 16 neighbouring pixels of one T row on neighbouring floats.
@@ -779,14 +735,14 @@ __global__ __launch_bounds__(WUL6::THREADS, 2) void conv67_h2_kernel(
             }
             if (has_next) {      // every wave is past the first barrier: nobody reads the current strip any more, and the word holds the maximum
                 float S, invS;
-                h2_scale(*mword, S, invS);
+                f16x2_scale(*mword, S, invS);
                 unscale = invS * inv_sw;
 #pragma unroll
                 for (int j = 0; j < C::NLD; ++j) h2_store(smem, j, rsub, loffb, stg[j], S);
             }
             __syncthreads();
             if (tid == 0) *mword = 0;            // read by everyone before the barrier above; its next atomics come two groups later
-            if constexpr (DIAG) { const unsigned long long t = wu_stamp(); dg[3] += t - dt; dt = t; }
+            if constexpr (DIAG) { const unsigned long long t = cycle_stamp(); dg[3] += t - dt; dt = t; }
             // ---- gather: new a6 row y finishes output rows 2y - 1 (phase a = 1 of row y - 1) and 2y (a = 0)
             // n-block (e, px) sits at ring block row {0, 1, 3, 2}[(1 - e) 2 + px]; the px = 1 blocks are stored one float to the left, so
             // the halo column of rx = 0 is float lane >> 1 in both
@@ -819,7 +775,7 @@ __global__ __launch_bounds__(WUL6::THREADS, 2) void conv67_h2_kernel(
             }
             if constexpr (DIAG) {
                 asm volatile("" ::"v"(s2), "v"(s1));
-                const unsigned long long t = wu_stamp(); dg[4] += t - dt; dt = t;
+                const unsigned long long t = cycle_stamp(); dg[4] += t - dt; dt = t;
             }
         }
 #pragma unroll
@@ -872,38 +828,25 @@ size_t pack_frags(const float* hwio, float* dst)
     return total;
 }
 
-unsigned long long* g_wu_diag[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-int g_wu_diag_blocks[6] = {0, 0, 0, 0, 0, 0};
+// DIAG builds: 8 waves x 5 phases per workgroup; [0] the fused conv6 + conv7 kernel (either form), [1] / [2] layers 4 / 5
+StampTable g_wu_stamps[3] = {{40}, {40}, {40}};
 
 template <class C>
 hipError_t launch(int layer, const float* in, const float* ufrag, const float* ep, float* out, int64_t n_cells, hipStream_t stream)
 {
-    static int resident = 0;
     static const bool diag = getenv("CS_WINO_DIAG") != nullptr;
     constexpr int LDSB = C::LDS;
-    if (!resident) {
-        hipError_t e = hipFuncSetAttribute((const void*)conv_wino_up_kernel<C, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute((const void*)conv_wino_up_kernel<C, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB);
-        if (e != hipSuccess) return e;
-        int dev = 0, cus = 0, per_cu = 0;
-        if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
-        if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)conv_wino_up_kernel<C, false>, C::THREADS, LDSB);
-        if (e != hipSuccess) return e;
-        if (per_cu < 1) per_cu = 1;
-        resident = cus * per_cu;
-        if (diag) {
-            if ((e = hipMalloc(&g_wu_diag[layer], (size_t)resident * 40 * sizeof(unsigned long long))) != hipSuccess) return e;
-            g_wu_diag_blocks[layer] = resident;
-        }
-    }
+    StampTable& stamps = g_wu_stamps[layer - 3];
+    KernelSetup ks;
+    const hipError_t e = !diag ? kernel_setup<conv_wino_up_kernel<C, false>>(C::THREADS, LDSB, ks)
+                               : kernel_setup<conv_wino_up_kernel<C, true>>(C::THREADS, LDSB, ks, &stamps);
+    if (e != hipSuccess) return e;
     const long total = (long)n_cells * C::NGRP;
     if (total <= 0) return hipSuccess;
-    const unsigned grid = (unsigned)(total < resident ? total : resident);
+    const unsigned grid = (unsigned)(total < ks.resident ? total : ks.resident);
     if (diag)
         hipLaunchKernelGGL((conv_wino_up_kernel<C, true>), dim3(grid), dim3(C::THREADS), LDSB, stream, in, ufrag, ep, out, (long)n_cells,
-                           g_wu_diag[layer]);
+                           stamps.begin(ks, grid));
     else
         hipLaunchKernelGGL((conv_wino_up_kernel<C, false>), dim3(grid), dim3(C::THREADS), LDSB, stream, in, ufrag, ep, out, (long)n_cells,
                            (unsigned long long*)nullptr);
@@ -917,51 +860,20 @@ int conv67_fused_nparts() { return F67::NPARTS; }
 hipError_t launch_conv67_fused(const float* a5, const float* ufrag, const float* ep, const float* x, const float* weff_dev,
                                const float* b7_dev, float* errpart, int64_t n_cells, hipStream_t stream)
 {
-    static int cus = 0;
     static const bool diag = getenv("CS_WINO_DIAG") != nullptr;
-    if (!cus) {
-        hipError_t e = hipFuncSetAttribute((const void*)conv67_fused_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, F67::LDS);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute((const void*)conv67_fused_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, F67::LDS);
-        if (e != hipSuccess) return e;
-        int dev = 0;
-        if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
-        if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
-        if (diag && !g_wu_diag[3]) {                               // slot 3 of the diagnostic table: the fused kernel
-            if ((e = hipMalloc(&g_wu_diag[3], (size_t)cus * 40 * sizeof(unsigned long long))) != hipSuccess) return e;
-            g_wu_diag_blocks[3] = cus;
-        }
-    }
+    KernelSetup ks;
+    const hipError_t e = !diag ? kernel_setup<conv67_fused_kernel<false>>(WUL6::THREADS, F67::LDS, ks)
+                               : kernel_setup<conv67_fused_kernel<true>>(WUL6::THREADS, F67::LDS, ks, &g_wu_stamps[0]);
+    if (e != hipSuccess) return e;
     if (n_cells <= 0) return hipSuccess;
-    const unsigned grid = (unsigned)(n_cells < cus ? n_cells : cus);
+    const unsigned grid = (unsigned)(n_cells < ks.cus ? n_cells : ks.cus);
     if (diag)
         hipLaunchKernelGGL(conv67_fused_kernel<true>, dim3(grid), dim3(WUL6::THREADS), F67::LDS, stream, a5, ufrag, ep, x, weff_dev, b7_dev,
-                           errpart, (long)n_cells, g_wu_diag[3]);
+                           errpart, (long)n_cells, g_wu_stamps[0].begin(ks, grid));
     else
         hipLaunchKernelGGL(conv67_fused_kernel<false>, dim3(grid), dim3(WUL6::THREADS), F67::LDS, stream, a5, ufrag, ep, x, weff_dev, b7_dev,
                            errpart, (long)n_cells, (unsigned long long*)nullptr);
     return hipGetLastError();
-}
-
-// helpers of every fp16-split packer: the power of two that puts max|w| into [2^14, 2^15), and one value's two fp16 terms
-float f16x2_weight_scale(const float* w, size_t n)
-{
-    float m = 0.0f;
-    for (size_t i = 0; i < n; ++i) m = fmaxf(m, fabsf(w[i]));
-    if (!(m > 0.0f) || !std::isfinite(m)) return 1.0f;
-    int e;
-    frexpf(m, &e);                       // m = f 2^e, f in [0.5, 1)
-    return ldexpf(1.0f, 15 - e);         // S m = f 2^15 in [2^14, 2^15)
-}
-
-// one value -> its two fp16 terms (bit patterns): hi = fp16(S w), lo = fp16(S w - hi)
-void f16x2_split(float w, float S, uint16_t& hi, uint16_t& lo)
-{
-    const float v = w * S;
-    const _Float16 h = (_Float16)v;
-    const _Float16 l = (_Float16)(v - (float)h);
-    memcpy(&hi, &h, 2);
-    memcpy(&lo, &l, 2);
 }
 
 // conv6's folded weights (pack_generic_folded(64, 32, ...): [phase 4][tap 4][cin 64][cout 32]) as two fp16 planes in conv67_h2_kernel's
@@ -990,27 +902,16 @@ size_t pack_conv6_f16x2(const float* weff, uint16_t* dst, float* inv_sw)
 hipError_t launch_conv67_h2(const float* a5, const uint16_t* wplanes, float inv_sw, const float* ep, const float* x, const float* weff_dev,
                             const float* b7_dev, float* errpart, int64_t n_cells, hipStream_t stream)
 {
-    static int cus = 0;
     static const bool diag = getenv("CS_WINO_DIAG") != nullptr;
-    if (!cus) {
-        hipError_t e = hipFuncSetAttribute((const void*)conv67_h2_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, F67H::LDS);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute((const void*)conv67_h2_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, F67H::LDS);
-        if (e != hipSuccess) return e;
-
-        int dev = 0;
-        if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
-        if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
-        if (diag && !g_wu_diag[3]) {                               // slot 3 of the diagnostic table: the fused kernel (any form)
-            if ((e = hipMalloc(&g_wu_diag[3], (size_t)cus * 40 * sizeof(unsigned long long))) != hipSuccess) return e;
-            g_wu_diag_blocks[3] = cus;
-        }
-    }
+    KernelSetup ks;
+    const hipError_t e = !diag ? kernel_setup<conv67_h2_kernel<false>>(WUL6::THREADS, F67H::LDS, ks)
+                               : kernel_setup<conv67_h2_kernel<true>>(WUL6::THREADS, F67H::LDS, ks, &g_wu_stamps[0]);
+    if (e != hipSuccess) return e;
     if (n_cells <= 0) return hipSuccess;
-    const unsigned grid = (unsigned)(n_cells < cus ? n_cells : cus);
+    const unsigned grid = (unsigned)(n_cells < ks.cus ? n_cells : ks.cus);
     if (diag)
         hipLaunchKernelGGL(conv67_h2_kernel<true>, dim3(grid), dim3(WUL6::THREADS), F67H::LDS, stream, a5, (const f16x8*)wplanes, ep, x,
-                           weff_dev, b7_dev, errpart, (long)n_cells, inv_sw, g_wu_diag[3]);
+                           weff_dev, b7_dev, errpart, (long)n_cells, inv_sw, g_wu_stamps[0].begin(ks, grid));
     else
         hipLaunchKernelGGL(conv67_h2_kernel<false>, dim3(grid), dim3(WUL6::THREADS), F67H::LDS, stream, a5, (const f16x8*)wplanes, ep, x,
                            weff_dev, b7_dev, errpart, (long)n_cells, inv_sw, (unsigned long long*)nullptr);
@@ -1035,15 +936,6 @@ hipError_t launch_conv_wino_up(int layer, const float* in, const float* ufrag, c
 // Diagnostic only (CS_WINO_DIAG=1): per-wave phase cycles of the LAST launch of `layer` (4 or 5), averaged over waves.
 extern "C" int cs_debug_wino_up_diag(int layer, double out5[5])
 {
-    using namespace cs;
-    if (layer < 3 || layer > 5 || !g_wu_diag[layer]) return -1;    // 3: the fused conv6 + conv7 kernel
-    if (hipDeviceSynchronize() != hipSuccess) return -2;
-    const size_t n = (size_t)g_wu_diag_blocks[layer] * 40;
-    unsigned long long* h = new unsigned long long[n];
-    if (hipMemcpy(h, g_wu_diag[layer], n * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) { delete[] h; return -3; }
-    for (int k = 0; k < 5; ++k) out5[k] = 0.0;
-    for (size_t i = 0; i < n; ++i) out5[i % 5] += (double)h[i];
-    for (int k = 0; k < 5; ++k) out5[k] /= (double)(n / 5);
-    delete[] h;
-    return 0;
+    if (layer < 3 || layer > 5) return -1;                         // 3: the fused conv6 + conv7 kernel
+    return cs::stamp_table_average(cs::g_wu_stamps[layer - 3], 5, out5);
 }

@@ -7,6 +7,7 @@
 // plus the per-cell mean of the squared / absolute error partial sums (:126-127) and the
 // counter-based synthetic crop generator used by the benchmark and the parity tests.
 #include "common.hpp"
+#include "kernel_setup.hpp"
 
 #include <cstring>
 
@@ -125,7 +126,7 @@ __global__ __launch_bounds__(256) void scaler_pca_kernel(
 }
 
 // ---------------------------------------------------------------- scaler + PCA on the bf16 matrix pipe
-// The same GEMM with the fp32 contraction as six bf16 products (conv45_bf16x3.hip has the algebra and the hardware check):
+// The same GEMM with the fp32 contraction as six bf16 products (conv_generic_x3.hip has the algebra, DESIGN.md 3g the hardware check):
 // the scaled feature -- still (f - center) / scale in double, rounded once to fp32 -- is split into three bf16 terms when it
 // is staged, components_ is split on the host (pack_pca_bf16x3).  A one-hot component row reproduces the scaled feature
 // bit for bit (x1 + x2 + x3 = x exactly, every partial sum representable): the scaler test holds unchanged.
@@ -536,12 +537,8 @@ hipError_t launch_scaler_pca(const float* feat, const float* center, const doubl
     if (n_cells <= 0) return hipSuccess;
     if (cpad % 16 || cpad > 128 || fpad % PCA_KC) return hipErrorInvalidValue;
     const unsigned grid = (unsigned)((n_cells + PCA_CELLS - 1) / PCA_CELLS);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)scaler_pca_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PCA_LDS);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
+    KernelSetup ks;            // for the LDS opt-in only: the grid is the cells'
+    if (hipError_t e = kernel_setup<scaler_pca_kernel>(256, PCA_LDS, ks); e != hipSuccess) return e;
     hipLaunchKernelGGL(scaler_pca_kernel, dim3(grid), dim3(256), PCA_LDS, stream, feat, center, scale,
                        comps_pad, mean_proj, F, fpad, C, cpad, pca_out, (long)n_cells);
     return hipGetLastError();
@@ -595,15 +592,12 @@ hipError_t launch_scaler_pca_x3(const float* feat, const float* center, const do
     if (n_cells <= 0) return hipSuccess;
     if (cpad % 16 || cpad > 128 || fpad % PX_KC) return hipErrorInvalidValue;
     const unsigned grid = (unsigned)((n_cells + PCA_CELLS - 1) / PCA_CELLS);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)scaler_pca_x3_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, PX_LDS);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute((const void*)scaler_pca_x3_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, PX_LDS);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
-    if (split_ws && n_cells <= DET_SPLIT_MAX_CELLS) {       // a small call: the ranges side by side, then their sum in the same order
+    const bool split = split_ws && n_cells <= DET_SPLIT_MAX_CELLS;
+    KernelSetup ks;            // for the LDS opt-in only: the grid is the cells'
+    const hipError_t e = !split ? kernel_setup<scaler_pca_x3_kernel<false>>(256, PX_LDS, ks)
+                                : kernel_setup<scaler_pca_x3_kernel<true>>(256, PX_LDS, ks);
+    if (e != hipSuccess) return e;
+    if (split) {       // a small call: the ranges side by side, then their sum in the same order
         hipLaunchKernelGGL(scaler_pca_x3_kernel<true>, dim3(grid, DET_RANGES), dim3(256), PX_LDS, stream, feat, center, scale,
                            (const bf16x8*)comps_planes, mean_proj, F, fpad, C, cpad, (float*)split_ws, (long)n_cells);
         const long tot = (long)n_cells * C;

@@ -5,6 +5,7 @@
 // Reductions over the batch are two-level and summed in a fixed order: results are
 // deterministic run to run (no float atomics anywhere).
 #include "common.hpp"
+#include "kernel_setup.hpp"
 
 namespace cs {
 
@@ -508,12 +509,8 @@ template <class C>
 hipError_t launch_wg(const float* xin, const float* dz, float* part, int64_t n_cells, int max_parts, int* nparts,
                      hipStream_t stream)
 {
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void*)wgrad_mfma_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
+    KernelSetup ks;            // for the LDS opt-in only: the grid is the partial sums'
+    if (hipError_t e = kernel_setup<wgrad_mfma_kernel<C>>(256, C::LDS_BYTES, ks); e != hipSuccess) return e;
     const long total = (long)n_cells * C::NSTRIP;
     const int grid = (int)(total < max_parts ? total : max_parts);
     *nparts = grid;

@@ -13,7 +13,7 @@ import generic_plans as G
 from cellscreen import spec
 
 DET_RANGES = 8                  # detector.hip:147
-DET_SPLIT_MAX_CELLS = 16384     # common.hpp:253
+DET_SPLIT_MAX_CELLS = 16384     # common.hpp:195
 PCA_KC = 256                    # detector.hip:23  (scaler_pca_kernel: features per LDS chunk)
 PX_KC = 128                     # detector.hip:136 (scaler_pca_x3_kernel: features per LDS chunk)
 PCA_CELLS = 64                  # detector.hip:22  (cells per PCA workgroup)

@@ -87,6 +87,18 @@ def test_product_package_never_touches_the_oracle():
                 assert "liboracle" not in txt and "import oracle" not in txt and "from oracle" not in txt, f
 
 
+def test_build_lists_every_kernel_header():
+    """build.py's HEADERS is what source_hash() covers and what a rebuild depends on: a header in csrc/ that it does not list
+    would change kernels without changing the hash."""
+    import importlib.util
+    pkg = os.path.join(H.ROOT, "cell-image-analysis_amd")
+    spec_ = importlib.util.spec_from_file_location("cellscreen_build", os.path.join(pkg, "build.py"))
+    build = importlib.util.module_from_spec(spec_)
+    spec_.loader.exec_module(build)
+    on_disk = sorted(f for f in os.listdir(os.path.join(pkg, "csrc")) if f.endswith(".hpp"))
+    assert sorted(h for h in build.HEADERS if os.sep not in h) == on_disk
+
+
 def test_bad_arguments_are_rejected_before_any_device_work():
     lib = L.load_library()
     h = C.c_void_p()

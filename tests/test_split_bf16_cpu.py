@@ -1,5 +1,5 @@
-"""CPU tests (numpy) of the arithmetic the split-bf16 kernels rest on (csrc/conv45_bf16x3.hip, conv_generic_x3.hip,
-conv67_x3_kernel, scaler_pca_x3_kernel, P1 of conv12_fused.hip).  No GPU: these pin the algebra --
+"""CPU tests (numpy) of the arithmetic the split-bf16 kernels rest on (csrc/conv_generic_x3.hip, scaler_pca_x3_kernel;
+DESIGN.md section 3g).  No GPU: these pin the algebra --
 what the hardware adds to it is measured by the -m gpu tests."""
 import numpy as np
 

@@ -20,8 +20,8 @@ import generic_plans as GP
 
 CUS = GP.CUS
 LDS_PER_CU = 160 * 1024
-BN_MAX_PARTS = 1024          # common.hpp:158
-TRAIN_MAX_PARTS = 256        # common.hpp:157
+BN_MAX_PARTS = 1024          # common.hpp:100
+TRAIN_MAX_PARTS = 256        # common.hpp:99
 TRAIN_MAX_BATCH = 8192       # train_api.hip:30 kTrainMaxBatch
 REF_CH = GP.REF[1]
 REF_GRID = (64, 32, 16, 8, 16, 32, 64)          # conv grid of each conv (api_internal.hpp kConvGrid)
