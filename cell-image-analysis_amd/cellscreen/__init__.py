@@ -4,7 +4,8 @@ Engine / ProductionMutantScreening do, and fail loudly when the library or a GPU
 from . import spec  # noqa: F401
 from .expand import LabelExpander, expand_params  # noqa: F401
 from .intensity import IntensityMeasurer, ObjectTable  # noqa: F401
+from .quantile import QuantileMeasurer, QuantileTable  # noqa: F401
 from .spec import CAEWeights, DetectorParams, OCSVMParams  # noqa: F401
 
 __all__ = ["spec", "CAEWeights", "DetectorParams", "OCSVMParams", "LabelExpander", "expand_params", "IntensityMeasurer",
-           "ObjectTable"]
+           "ObjectTable", "QuantileMeasurer", "QuantileTable"]

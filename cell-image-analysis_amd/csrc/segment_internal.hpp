@@ -1,5 +1,5 @@
 // segment_internal.hpp -- the state behind cs_preproc::seg as its translation units share it (segment.hip, expand.hip,
-// intensity.hip): the shared buffers and a clock per family of entry points.  The clock itself and the argument rules are
+// intensity.hip, quantile.hip): the shared buffers and a clock per family of entry points.  The clock itself and the argument rules are
 // stage_host.hpp's, which extract.hip and match.hip use with states of their own.
 #pragma once
 #include "stage_host.hpp"
@@ -22,7 +22,10 @@ struct SegmentState {
     // labels in lab, a host d2 plane in stage, its status word in ctrl.
     // cs_label_intensity (intensity.hip) has none either: a host image in img, its labels in lab, its exclude plane in parent,
     // the two tables on their way to the host in stage, its status word in ctrl.
-    StageClock clk_thr, clk_sp, clk_si, clk_bg, clk_lt, clk_cl, clk_sm, clk_hy, clk_ns, clk_ex, clk_in;
+    // cs_label_quantiles (quantile.hip) shares img, lab, parent, stage and ctrl as cs_label_intensity does, and has two buffers of
+    // its own: the objects' values gathered into segments, and the segments' starts with the cursors that fill them.
+    DevBuf lq_val, lq_off;                              // [C][B * H * W] uint16; [2][B][max_label] uint32
+    StageClock clk_thr, clk_sp, clk_si, clk_bg, clk_lt, clk_cl, clk_sm, clk_hy, clk_ns, clk_ex, clk_in, clk_lq;
     int sp_recon_reads = 0, sp_flood_reads = 0;         // control-word reads (one host synchronisation each) of the last split of either kind
 };
 

@@ -43,6 +43,10 @@
  *        min / max intensity and the intensity-weighted centroid, as exact integer sums
  *        (skimage.measure.regionprops with an intensity image, scipy.ndimage's labelled statistics,
  *        CellProfiler's MeasureObjectIntensity; no reference counterpart)
+ *   cs_label_quantiles
+ *        the robust half of the same measurement: per object and channel the median, any quantiles and the
+ *        median absolute deviation, as exact integer order statistics (scipy.ndimage.median, numpy.quantile
+ *        per object, CellProfiler's MedianIntensity / MADIntensity / quartiles; no reference counterpart)
  *   cs_fit_scaler / cs_fit_pca_moments / cs_fit_pca_subspace / cs_fit_project / cs_fit_ocsvm
  *        RobustScaler / PCA / OneClassSVM fits of create_anomaly_detector
  *                                                 CAE_improved_modeltrain.py:408-427
@@ -842,6 +846,38 @@ int cs_label_intensity(cs_preproc *p, const void *image, int pixel_type, int32_t
                        int64_t *geom, int64_t *stats, int out_kind);
 /* Device time of the last cs_label_intensity: clearing the tables and the status word, and the pass with its closing step. */
 int cs_label_intensity_last_timing(const cs_preproc *p, double *clear_ms, double *pass_ms);
+
+/* ---- per-object median, quantiles and MAD ----------------------------------------------------------- */
+/* Exact integer order statistics of every object of a label image in every channel of an image (DESIGN 3v;
+ * tests/quantile_reference.py restates the rule).  The objects are cs_label_intensity's: the pixels of one image with one
+ * label > 0, connected or not, less the pixels where `exclude` is non-zero.  A quantile is a rational num / den with
+ * 0 <= num <= den and 1 <= den <= 65536.  For an object of n >= 1 pixels whose values in a channel, sorted, are s[0 .. n-1]:
+ *     t = num * (n - 1)        (int64: below 2^40)
+ *     lo = t / den,  rem = t % den,  hi = lo + (rem > 0)
+ * The device writes s[lo] and s[hi]; the caller takes value = s[lo] + (s[hi] - s[lo]) * rem / den in float64, which is
+ * numpy.quantile's method="linear"; s[lo] and s[hi] themselves are its "lower" and "higher".
+ * With want_mad the device also takes the median's ranks (num / den = 1 / 2), m_lo and m_hi, then the doubled deviations
+ * d = |2 v - (m_lo + m_hi)| (17 bits) and their order statistics d_lo, d_hi at the same two ranks.  median = (m_lo + m_hi) / 2
+ * and MAD = (d_lo + d_hi) / 4 are exact in float64; no scale factor is applied (scipy.stats.median_abs_deviation, scale=1).
+ * image, labels, exclude, in_kind, the sizes and max_label: as cs_label_intensity, a bad label included (CS_ERR_INVALID,
+ *         detected on the device, whatever `exclude` holds there; the handle stays usable).
+ * q_num, q_den: host arrays [n_q], n_q 1..8 (above: CS_ERR_UNSUPPORTED); duplicates and any order are kept.
+ *         max_label above 2^20, or batch * max_label * channels * n_q above 2^22: CS_ERR_UNSUPPORTED.
+ * count:  out, [batch][max_label] int32: the pixels of the object, row b * max_label + label - 1.
+ * order:  out, [batch][max_label][channels][n_q][2] int32: s[lo], s[hi].
+ * mad:    out, [batch][max_label][channels][4] int32: m_lo, m_hi, d_lo, d_hi; required iff want_mad.  All three out_kind.
+ *         An object that does not occur, or that `exclude` covers whole, has all-zero rows.
+ * No floating point on the device; bit-identical run to run and independent of the other images of the batch.  Besides the
+ * buffers cs_label_intensity shares, the handle keeps 2 bytes per pixel and channel for the gathered values and 8 bytes per
+ * row.  One host synchronisation per call.  Other bad arguments: CS_ERR_INVALID before any device work; without a gfx950
+ * device (p == NULL): CS_ERR_NO_DEVICE. */
+int cs_label_quantiles(cs_preproc *p, const void *image, int pixel_type, int32_t channels,
+                       const int32_t *labels, const int32_t *exclude /* or NULL */,
+                       int32_t batch, int32_t height, int32_t width, int in_kind, int32_t max_label,
+                       const int32_t *q_num, const int32_t *q_den, int32_t n_q, int want_mad,
+                       int32_t *count, int32_t *order, int32_t *mad /* or NULL */, int out_kind);
+/* Device time of the last cs_label_quantiles: clearing + counting + offsets, the scatter into segments, the selection. */
+int cs_label_quantiles_last_timing(const cs_preproc *p, double *count_ms, double *scatter_ms, double *select_ms);
 
 /* ---- detector fitting (create_anomaly_detector, CAE_improved_modeltrain.py:394-446) -------- */
 /* The fit of what cs_screen's tail evaluates, for the training set's encoder features
