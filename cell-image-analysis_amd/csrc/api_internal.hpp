@@ -85,7 +85,7 @@ hipError_t launch_preprocess(const void* pix, int pixel_type, const CropDesc* de
                              uint16_t* clahe, float* out, int out_h, int out_w, hipStream_t stream);
 struct ExtractState;                            // extract.hip: the state between cs_extract_measure and cs_extract_fill
 void extract_state_free(ExtractState* s);
-struct SegmentState;                            // segment_internal.hpp: the buffers and clocks of cs_segment_*, cs_label_expand, cs_label_intensity, cs_label_quantiles
+struct SegmentState;                            // segment_internal.hpp: the buffers and clocks of cs_segment_* and of the label tools on its state
 void segment_state_free(SegmentState* s);
 struct MatchState;                              // match.hip: the buffers, the pair table and the clock of cs_label_match
 void match_state_free(MatchState* s);
@@ -98,9 +98,9 @@ int require_gfx950(int device_id);
 
 // The preprocess handle (include/cellscreen.h); its extraction entry points live in extract.hip, its segmenter in segment.hip,
 // its label scoring in match.hip, its label expansion in expand.hip, its intensity measurement in intensity.hip, its order
-// statistics in quantile.hip.  All six take their argument rules, the handle check and their clocks from stage_host.hpp; each
-// keeps a state of its own below (expand, intensity and quantile share the segmenter's), since what must survive between calls
-// differs: extract's uploads from measure to fill, match's pair table.
+// statistics in quantile.hip, its texture records in texture.hip.  All seven take their argument rules, the handle check and
+// their clocks from stage_host.hpp; each keeps a state of its own below (expand, intensity, quantile and texture share the
+// segmenter's), since what must survive between calls differs: extract's uploads from measure to fill, match's pair table.
 struct cs_preproc {
     int device = 0;
     hipStream_t stream = nullptr;

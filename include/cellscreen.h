@@ -47,6 +47,10 @@
  *        the robust half of the same measurement: per object and channel the median, any quantiles and the
  *        median absolute deviation, as exact integer order statistics (scipy.ndimage.median, numpy.quantile
  *        per object, CellProfiler's MedianIntensity / MADIntensity / quartiles; no reference counterpart)
+ *   cs_label_texture
+ *        the texture of the same objects: per object, channel and direction the grey-level co-occurrence
+ *        matrix, reduced to the exact records Haralick's 13 features follow from (mahotas.features.haralick,
+ *        skimage's graycomatrix / graycoprops, CellProfiler's MeasureTexture; no reference counterpart)
  *   cs_fit_scaler / cs_fit_pca_moments / cs_fit_pca_subspace / cs_fit_project / cs_fit_ocsvm
  *        RobustScaler / PCA / OneClassSVM fits of create_anomaly_detector
  *                                                 CAE_improved_modeltrain.py:408-427
@@ -878,6 +882,43 @@ int cs_label_quantiles(cs_preproc *p, const void *image, int pixel_type, int32_t
                        int32_t *count, int32_t *order, int32_t *mad /* or NULL */, int out_kind);
 /* Device time of the last cs_label_quantiles: clearing + counting + offsets, the scatter into segments, the selection. */
 int cs_label_quantiles_last_timing(const cs_preproc *p, double *count_ms, double *scatter_ms, double *select_ms);
+
+/* ---- per-object Haralick texture -------------------------------------------------------------------- */
+/* The grey-level co-occurrence matrices of every object of a label image in every channel of an image, reduced to exact
+ * records from which Haralick's 13 features follow on the host (tests/texture_reference.py restates the rule).
+ * The objects are cs_label_intensity's: the pixels of one image with one label > 0, connected or not, less the pixels where
+ * `exclude` is non-zero.
+ * Levels: per channel c a value v becomes q(v) = ((min(max(v, lo[c]), hi[c]) - lo[c]) * levels) / (hi[c] - lo[c] + 1), an
+ *         integer division, exact for every value and span; 2 <= levels <= 64, 0 <= lo <= hi <= 65535.
+ * Pairs:  one distance d, 1..127, and four directions k with the (row, column) steps (0, d), (d, d), (d, 0), (d, -d), the 2-D
+ *         order of mahotas.  The pair (p, p + step_k) counts iff both pixels lie in the image, carry the same label > 0 and
+ *         neither is excluded; it adds 1 to G[k][q(p)][q(p')] and 1 to G[k][q(p')][q(p)].  G is symmetric and its total N_k is
+ *         twice the number of pairs, at most 2^25.  Pairs between objects or through an excluded pixel count nowhere.
+ * image, labels, exclude, in_kind, the sizes and max_label: as cs_label_intensity, a bad label included (CS_ERR_INVALID,
+ *         detected on the device, whatever `exclude` holds there; the handle stays usable).
+ * range_lo, range_hi: host arrays [channels].
+ * The rules apply in this order: those of cs_label_intensity up to its channel limit, then levels, distance and the ranges
+ *         (CS_ERR_INVALID), then the caps (CS_ERR_UNSUPPORTED): max_label above 2^20, batch * max_label * channels * levels
+ *         above 2^24, and with glcm batch * max_label * channels * levels^2 above 2^24; then the limits of the image.
+ * count:  out, [batch][max_label] int32: the pixels of the object, row b * max_label + label - 1.
+ * marg:   out, [batch][max_label][channels][4][4 * levels] int32, per direction: the row marginal px[i] = sum_j G[i][j]
+ *         (levels entries), the sum marginal ps[s] = sum over i + j = s (2 * levels - 1 entries and one zero), the difference
+ *         marginal pd[t] = sum over |i - j| = t (levels entries).  N_k = sum px.
+ * sumsq:  out, [batch][max_label][channels][4] int64: sum of G^2.
+ * clogc:  out, [batch][max_label][channels][4] double: sum over the cells with G > 0 of G * log2(G), the one value that is not
+ *         an integer; summed in a fixed order, so bit-identical run to run.  The joint entropy is log2(N) - clogc / N.
+ * glcm:   out or NULL, [batch][max_label][channels][4][levels][levels] int32: the matrices themselves.  All five out_kind.
+ *         An object that does not occur, or that `exclude` covers whole, has all-zero rows, as has a direction without pairs.
+ * Bit-identical run to run and independent of the other images of the batch.  Besides the buffers cs_label_intensity shares,
+ * the handle keeps 16 bytes per row for the bounding boxes.  One host synchronisation per call.  Other bad arguments:
+ * CS_ERR_INVALID before any device work; without a gfx950 device (p == NULL): CS_ERR_NO_DEVICE. */
+int cs_label_texture(cs_preproc *p, const void *image, int pixel_type, int32_t channels,
+                     const int32_t *labels, const int32_t *exclude /* or NULL */,
+                     int32_t batch, int32_t height, int32_t width, int in_kind, int32_t max_label,
+                     int32_t levels, int32_t distance, const int32_t *range_lo, const int32_t *range_hi,
+                     int32_t *count, int32_t *marg, int64_t *sumsq, double *clogc, int32_t *glcm /* or NULL */, int out_kind);
+/* Device time of the last cs_label_texture: clearing + the boxes, and the matrices with their reduction. */
+int cs_label_texture_last_timing(const cs_preproc *p, double *boxes_ms, double *matrices_ms);
 
 /* ---- detector fitting (create_anomaly_detector, CAE_improved_modeltrain.py:394-446) -------- */
 /* The fit of what cs_screen's tail evaluates, for the training set's encoder features
