@@ -230,6 +230,8 @@ SIGNATURES = {
     "cs_label_texture": (_I, [_P, _P, _I, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _I, C.c_int32, C.c_int32, C.c_int32, _P, _P,
                               _P, _P, _P, _P, _P, _I]),
     "cs_label_texture_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "cs_label_shape": (_I, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _I, C.c_int32, _I, _P, _P, _P, _P, _P, _I]),
+    "cs_label_shape_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "cs_fit_create": (_I, [_I, C.POINTER(_P)]),
     "cs_fit_free": (None, [_P]),
     "cs_fit_wait_stream": (_I, [_P, _P]),

@@ -19,6 +19,7 @@
 //                   analysis channel into the ragged layout preprocess.hip reads.
 // Integers throughout up to the final quotients; no float atomics, so every output is bit-identical run to run and
 // independent of which other images share the batch (a slot's work reads nothing but its own image).
+#include "hull_chain.hpp"
 #include "label_tile.hpp"
 #include "stage_host.hpp"
 
@@ -52,9 +53,6 @@ struct SlotIdx {
 struct GatherDesc {
     int image, minr, minc, pad;
 };
-
-__device__ inline long long floor_div(long long a, long long d) { return a >= 0 ? a / d : -((-a + d - 1) / d); }   // d > 0
-__device__ inline long long ceil_div(long long a, long long d) { return -floor_div(-a, d); }
 
 // a*b - c*d for a, b, c, d >= 0 whose products stay below 2^85 and whose difference is >= 0, as the correctly rounded double
 // (the rounding Python's float(int) applies): the exact difference in 128 bits, then one fp64 addition of two exact parts
@@ -147,57 +145,7 @@ __global__ __launch_bounds__(EX_THREADS) void ex_label_pass(const int* __restric
 // ---- per-region pass -------------------------------------------------------------------------------------------------------
 // One workgroup per slot.  Dynamic LDS: rowL / rowR (int16, [H] each) + the two chains (packed (y+1) << 16 | (x+1), [2H+2] each).
 // Coordinates inside the bbox window: row i, column j; doubled coordinates of the hull: y = 2i, x = 2j, pixel-edge
-// midpoints at (2i +- 1, 2j) and (2i, 2j +- 1).
-__device__ inline int pack_pt(int y, int x) { return ((y + 1) << 16) | (x + 1); }
-__device__ inline int pt_y(int p) { return (p >> 16) - 1; }
-__device__ inline int pt_x(int p) { return (p & 0xffff) - 1; }
-
-// Andrew's monotone chain over the left (right) extreme points in increasing y: the convex minorant (concave majorant) of x(y)
-__device__ int build_chain(const short* rowE, int h, bool right, int* ch)
-{
-    int k = 0;
-    for (int t = 0; t <= 2 * h; ++t) {
-        const int y = t - 1;
-        int x;
-        bool have = false;
-        if ((y & 1) == 0) {
-            const int e = rowE[y >> 1];
-            if (right ? e >= 0 : e < 0x7fff) { x = right ? 2 * e + 1 : 2 * e - 1; have = true; }
-        } else {
-            const int i0 = (y - 1) >> 1, i1 = i0 + 1;                     // rows above and below the odd line
-            x = right ? INT_MIN : INT_MAX;
-            if (i0 >= 0) {
-                const int e = rowE[i0];
-                if (right ? e >= 0 : e < 0x7fff) { x = right ? max(x, 2 * e) : min(x, 2 * e); have = true; }
-            }
-            if (i1 < h) {
-                const int e = rowE[i1];
-                if (right ? e >= 0 : e < 0x7fff) { x = right ? max(x, 2 * e) : min(x, 2 * e); have = true; }
-            }
-        }
-        if (!have) continue;
-        while (k >= 2) {
-            const int o = ch[k - 2], a = ch[k - 1];
-            const long long cr = (long long)(pt_y(a) - pt_y(o)) * (long long)(x - pt_x(o)) -
-                                 (long long)(pt_x(a) - pt_x(o)) * (long long)(y - pt_y(o));
-            if (right ? cr >= 0 : cr <= 0) --k; else break;
-        }
-        ch[k++] = pack_pt(y, x);
-    }
-    return k;
-}
-
-// the chain's segment that holds y (chain sorted by y, y within its range): largest k <= n-2 with y_k <= y
-__device__ inline int chain_segment(const int* ch, int n, int y)
-{
-    int lo = 0, hi = n - 2;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (pt_y(ch[mid]) <= y) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
+// midpoints at (2i +- 1, 2j) and (2i, 2j +- 1).  The chains and their packing are hull_chain.hpp's, which shape.hip shares.
 template <typename PIX>
 __global__ __launch_bounds__(EX_THREADS) void ex_region_pass(const int* __restrict__ labels, const PIX* __restrict__ image, int C, int ch,
                                                              int H, int W, int max_label, const int4* __restrict__ bbox, ExQc qc,

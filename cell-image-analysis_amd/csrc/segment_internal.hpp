@@ -1,5 +1,5 @@
 // segment_internal.hpp -- the state behind cs_preproc::seg as its translation units share it (segment.hip, expand.hip,
-// intensity.hip, quantile.hip, texture.hip): the shared buffers and a clock per family of entry points.  The clock itself and
+// intensity.hip, quantile.hip, texture.hip, shape.hip): the shared buffers and a clock per family of entry points.  The clock itself and
 // the argument rules are stage_host.hpp's, which extract.hip and match.hip use with states of their own.
 #pragma once
 #include "stage_host.hpp"
@@ -26,8 +26,9 @@ struct SegmentState {
     // its own: the objects' values gathered into segments, and the segments' starts with the cursors that fill them.
     DevBuf lq_val, lq_off;                              // [C][B * H * W] uint16; [2][B][max_label] uint32
     // cs_label_texture (texture.hip) shares img, lab, parent, stage and ctrl in the same way, and keeps the objects' bounding boxes.
-    DevBuf tx_box;                                      // [B][max_label][4] int32, encoded (texture.hip, TxExtent)
-    StageClock clk_thr, clk_sp, clk_si, clk_bg, clk_lt, clk_cl, clk_sm, clk_hy, clk_ns, clk_ex, clk_in, clk_lq, clk_tx;
+    // cs_label_shape (shape.hip) shares lab, parent, stage and ctrl in the same way, and the bounding boxes with cs_label_texture.
+    DevBuf tx_box;                                      // [B][max_label][4] int32, encoded (label_boxes.hpp, LbExtent)
+    StageClock clk_thr, clk_sp, clk_si, clk_bg, clk_lt, clk_cl, clk_sm, clk_hy, clk_ns, clk_ex, clk_in, clk_lq, clk_tx, clk_sh;
     int sp_recon_reads = 0, sp_flood_reads = 0;         // control-word reads (one host synchronisation each) of the last split of either kind
 };
 

@@ -5,9 +5,10 @@
 // Per object (cs_label_intensity's: a label > 0 of an image, less the pixels where `exclude` is non-zero), channel and direction
 // k of (0, d), (d, d), (d, 0), (d, -d): the symmetric matrix G[k] of the quantised values of every pixel pair one step apart with
 // both ends in the object.  Two steps, and the kernel boundary is the only ordering between workgroups:
-//   tx_boxes     the walk of label_tile.hpp over labels and exclude alone: one open run per lane with its count and its extent,
-//                merged per wave, then per workgroup in a table in LDS keyed by the label; only the distinct labels of a tile
-//                reach `count` (an integer add) and the bounding boxes (integer maxima of an encoding that a cleared table starts).
+//   tx_boxes     lb_pass of label_boxes.hpp, which cs_label_shape shares: the walk of label_tile.hpp over labels and exclude
+//                alone; one open run per lane with its count and its extent, merged per wave, then per workgroup in a table of
+//                1024 labels in LDS; only the distinct labels of a tile reach `count` (an integer add) and the bounding boxes
+//                (integer maxima of an encoding that a cleared table starts).
 //   tx_matrices  one workgroup per (object, channel), absent ones leave before they touch LDS.  It walks the object's box, a
 //                thread per pixel and a loop over boxes of any size, and counts every pair once under (min, max) of its two
 //                levels: the four upper triangles in LDS, 4 * L (L + 1) / 2 words, 33 KB at L = 64.  Equal bins of a wave are
@@ -23,15 +24,12 @@
 // tree, the waves in order), so the records are bit-identical run to run.  A label is range-checked before it is a key or an
 // index, a box is clamped to the image before it is walked, and a neighbour is tested against the image before it is read: what
 // fails the test reads the box's first pixel instead and is not counted.
-#include "label_tile.hpp"
+#include "label_boxes.hpp"
 #include "segment_internal.hpp"
 
 namespace cs {
 
 static constexpr int TX_THREADS = LT_THREADS;
-static constexpr int TX_LOG2 = 10;                      // the table of a tile in LDS: 1024 labels
-static constexpr int TX_SLOTS = 1 << TX_LOG2;
-static constexpr int TX_PROBES = 16;
 static constexpr int kTxMaxChannels = 4;
 static constexpr int kTxMinLevels = 2, kTxMaxLevels = 64;
 static constexpr int kTxMaxDistance = 127;
@@ -42,100 +40,9 @@ static constexpr int TX_SHIFT = 40;
 static constexpr int TX_ROUNDS = 2;                     // of the wave's merge of equal bins before the plain adds
 static constexpr int TX_STEPS = 4;                      // steps of the walk over a box whose labels are loaded together
 
-__device__ inline unsigned int tx_hash(int label) { return ((unsigned int)label * 0x9E3779B1u) >> (32 - TX_LOG2); }
-
-// An extent travels as four numbers that only grow, so that a cleared table is the empty extent and one maximum merges two:
-// kMaxSide - first row, last row + 1, kMaxSide - first column, last column + 1.
-struct TxExtent {
-    int e[4];
-};
-
-// grid (ceil(W/256), ceil(H/64), B).  labels, exclude (or null): [B][H][W] int.  count: [B][max_label], box: [B][max_label][4],
-// both cleared.
-__global__ __launch_bounds__(TX_THREADS) void tx_boxes(const int* __restrict__ labels, const int* __restrict__ exclude, int H, int W, int vec,
-                                                       int max_label, int* __restrict__ count, int* __restrict__ box,
-                                                       unsigned int* __restrict__ ctrl)
-{
-    __shared__ int key[TX_SLOTS];                       // 0: empty
-    __shared__ unsigned int cnt[TX_SLOTS];
-    __shared__ int ext[4][TX_SLOTS];
-    for (int s = threadIdx.x; s < TX_SLOTS; s += TX_THREADS) {
-        key[s] = 0;
-        cnt[s] = 0u;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) ext[j][s] = 0;
-    }
-    __syncthreads();
-    const LabelTile tile = label_tile();
-    const size_t plane = (size_t)tile.b * H * W;
-    const int* ll = labels + plane;
-    const int* ee = exclude ? exclude + plane : nullptr;
-    int* crow = count + (size_t)tile.b * max_label;
-    int* brow = box + (size_t)tile.b * max_label * 4;
-    const bool wide = vec && tile.c_base + 3 < W;
-    auto flush = [&](int label, unsigned int n, const TxExtent& x) {
-        const int s = table_claim(key, TX_LOG2, tx_hash(label), label, TX_PROBES);
-        if (s >= 0) {
-            atomicAdd(&cnt[s], n);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) atomicMax(&ext[j][s], x.e[j]);
-        } else {                                        // no room: straight to the global tables
-            atomicAdd(&crow[label - 1], (int)n);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) atomicMax(&brow[(size_t)(label - 1) * 4 + j], x.e[j]);
-        }
-    };
-
-    unsigned int bad = 0u, n = 0u;
-    int cur = 0;
-    TxExtent x = {{0, 0, 0, 0}};
-    for (int i = 0; i < LT_ROWS; ++i) {
-        const int r = tile.r_base + i;
-        if (r >= H) break;                              // uniform over the wave
-        int v[4], e[4] = {0, 0, 0, 0};
-        const size_t at = (size_t)r * W + tile.c_base;
-        label_load4(ll + at, W - tile.c_base, wide, v);
-        if (ee) label_load4(ee + at, W - tile.c_base, wide, e);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int lab = v[k];
-            if (lab == 0) continue;
-            if (lab < 0 || lab > max_label) { bad = 1u; continue; }
-            if (e[k] != 0) continue;
-            if (n != 0u && lab != cur) {
-                flush(cur, n, x);
-                n = 0u;
-            }
-            const int c = tile.c_base + k;
-            if (n == 0u) {
-                cur = lab;
-                x.e[0] = kMaxSide - r;
-                x.e[2] = kMaxSide - c;
-                x.e[3] = c + 1;
-            }
-            ++n;
-            x.e[1] = r + 1;                             // the rows only grow
-            x.e[2] = max(x.e[2], kMaxSide - c);
-            x.e[3] = max(x.e[3], c + 1);
-        }
-    }
-    merge_open_runs(n != 0u, cur, tile.lane, [&](int lw, bool mine, bool leader) {
-        const unsigned int t = wave_sum(mine ? n : 0u);
-        TxExtent m;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) m.e[j] = wave_max(mine ? x.e[j] : 0);
-        if (leader) flush(lw, t, m);
-    });
-    __syncthreads();
-    for (int s = threadIdx.x; s < TX_SLOTS; s += TX_THREADS) {
-        const int label = key[s];
-        if (label == 0) continue;
-        atomicAdd(&crow[label - 1], (int)cnt[s]);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) atomicMax(&brow[(size_t)(label - 1) * 4 + j], ext[j][s]);
-    }
-    if (bad) *ctrl = 1u;                                // a plain store of a constant
-}
+// tx_boxes is lb_pass of label_boxes.hpp without the moments: grid (ceil(W/256), ceil(H/64), B); count: [B][max_label],
+// box: [B][max_label][4] (LbExtent), both cleared.
+static constexpr auto tx_boxes = lb_pass<false>;
 
 // ---- matrices -------------------------------------------------------------------------------------------------------------------
 struct TxParams {
@@ -403,7 +310,8 @@ int cs_label_texture(cs_preproc* p, const void* image, int pixel_type, int32_t c
     HIPCHK(hipMemsetAsync(d_count, 0, cbytes, st));
     HIPCHK(hipMemsetAsync(d_marg, 0, mbytes, st));
     if (d_glcm) HIPCHK(hipMemsetAsync(d_glcm, 0, gbytes, st));
-    hipLaunchKernelGGL(tx_boxes, label_tile_grid(batch, H, W), dim3(TX_THREADS), 0, st, d_lab, d_ex, H, W, vec, (int)max_label, d_count, d_box, d_ctrl);
+    hipLaunchKernelGGL(tx_boxes, label_tile_grid(batch, H, W), dim3(TX_THREADS), 0, st, d_lab, d_ex, H, W, vec, (int)max_label, d_count, d_box,
+                       (unsigned long long*)nullptr, d_ctrl);
     HIPCHK(hipGetLastError());
     if ((rc = S.clk_tx.record(1, st))) return rc;
     if (pixel_type == CS_PIX_U8)

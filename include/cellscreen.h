@@ -51,6 +51,11 @@
  *        the texture of the same objects: per object, channel and direction the grey-level co-occurrence
  *        matrix, reduced to the exact records Haralick's 13 features follow from (mahotas.features.haralick,
  *        skimage's graycomatrix / graycoprops, CellProfiler's MeasureTexture; no reference counterpart)
+ *   cs_label_shape
+ *        the size and shape of the same objects: ten moments, the bounding box, the 2 x 2 bit quads, the perimeter
+ *        classes and the convex hull's records as exact integers, from which area, axes, orientation, Hu moments,
+ *        perimeter, form factor, Euler number, solidity and Feret diameters follow (skimage.measure.regionprops'
+ *        geometry properties, CellProfiler's MeasureObjectSizeShape; no reference counterpart)
  *   cs_fit_scaler / cs_fit_pca_moments / cs_fit_pca_subspace / cs_fit_project / cs_fit_ocsvm
  *        RobustScaler / PCA / OneClassSVM fits of create_anomaly_detector
  *                                                 CAE_improved_modeltrain.py:408-427
@@ -919,6 +924,48 @@ int cs_label_texture(cs_preproc *p, const void *image, int pixel_type, int32_t c
                      int32_t *count, int32_t *marg, int64_t *sumsq, double *clogc, int32_t *glcm /* or NULL */, int out_kind);
 /* Device time of the last cs_label_texture: clearing + the boxes, and the matrices with their reduction. */
 int cs_label_texture_last_timing(const cs_preproc *p, double *boxes_ms, double *matrices_ms);
+
+/* ---- per-object size and shape ------------------------------------------------------------------------ */
+/* The geometry of every object of a label image as exact integer records, from which the host derives area, bounding box, extent,
+ * centroid, central moments, inertia tensor, axis lengths, eccentricity, orientation, Hu's moments, perimeter, form factor, Euler
+ * numbers, convex area, solidity and Feret diameters (tests/shape_reference.py restates the rule, cellscreen/shape.py
+ * derives).  The objects are cs_label_intensity's: the pixels of one image with one label > 0, connected or not, less the pixels
+ * where `exclude` is non-zero.  Let e be the effective plane: the label, or 0 where excluded or outside the image.  Everything
+ * below is a function of e alone; no image is read.  Per (image b, label L), row b * max_label + L - 1:
+ * moments: out, [batch][max_label][10] int64: n, sum r, sum c, sum r^2, sum rc, sum c^2, sum r^3, sum r^2 c, sum r c^2, sum c^3
+ *         over the pixels (r, c) of the object, image coordinates.  One label over a 4096 x 4096 plane keeps every sum below 2^59.
+ * box:    out, [batch][max_label][4] int32: minr, minc, maxr, maxc, the max exclusive (regionprops' bbox).
+ * quads:  out, [batch][max_label][16] int32: the histogram of the 2 x 2 bit quads over the (H + 1) (W + 1) corner positions of the
+ *         plane padded by one background pixel, the code [e(r,c)==L] + 2 [e(r+1,c)==L] + 4 [e(r,c+1)==L] + 8 [e(r+1,c+1)==L] for
+ *         r = -1 .. H-1 and c = -1 .. W-1; bin 0 is left zero.  Gray's counts are Q1 (one bit set), Q3 (three) and QD (codes 6 and
+ *         9); the Euler number is (Q1 - Q3 + 2 QD) / 4 for 4-connectivity and (Q1 - Q3 - 2 QD) / 4 for 8-connectivity.
+ * perim:  out, [batch][max_label][3] int32: the three classes of skimage.measure.perimeter(mask, neighbourhood=4).  A border pixel
+ *         is a pixel of the object with a 4-neighbour that is not the object's, outside the image included.  For a border pixel a
+ *         is the number of its 4-neighbours that are border pixels of the same object and d that of its diagonal neighbours; the
+ *         value 1 + 2a + 10d counts in class 0 if it is one of {5, 7, 15, 17, 25, 27}, in class 1 if one of {21, 33}, in class 2 if
+ *         one of {13, 23}.  perimeter = n0 + n1 sqrt(2) + n2 (1 + sqrt(2)) / 2.  Neighbouring objects are background to each other.
+ * hull:   out, [batch][max_label][4] int64, required iff want_hull (else NULL): convex_area, feret_max2, feret_min_num,
+ *         feret_min_den.  The hull is that of the pixel-edge midpoints (2r +- 1, 2c), (2r, 2c +- 1) of the object's pixels in
+ *         doubled coordinates, the one cs_extract_measure builds.  convex_area counts the pixel centres inside or on it.  feret_max2
+ *         is the largest squared distance between two of its vertices: the diameter is sqrt(feret_max2) / 2.  Every edge (a, b) of
+ *         the hull has the width w = max over the vertices v of |cross(b - a, v - a)|; the edge with the smallest w^2 / |b - a|^2,
+ *         among equal quotients the one with the smaller |b - a|^2, gives feret_min_num = w and feret_min_den = |b - a|^2: the
+ *         diameter is w / (2 sqrt(den)).  This is the width of the object's own hull; scikit-image's feret_diameter_max traces the
+ *         contour of the convex image instead, a deliberate difference.
+ * labels, exclude, in_kind, the sizes and max_label: as cs_label_intensity, a bad label included (CS_ERR_INVALID "negative or
+ *         exceeds max_label", detected on the device, whatever `exclude` holds there; the handle stays usable).
+ * The rules apply in cs_label_intensity's order: NULL arguments and hull against want_hull, the memory kinds, the sizes, max_label
+ *         (CS_ERR_INVALID), then the caps (CS_ERR_UNSUPPORTED): max_label above 2^20, batch * max_label above 2^22; then the
+ *         limits of the image.  All five out_kind.  An object that does not occur, or that `exclude` covers whole, has all-zero
+ *         rows.
+ * No floating point on the device; bit-identical run to run and independent of the other images of the batch.  The handle shares
+ * cs_label_intensity's buffers and cs_label_texture's 16 bytes per row for the bounding boxes.  One host synchronisation per call.
+ * Other bad arguments: CS_ERR_INVALID before any device work; without a gfx950 device (p == NULL): CS_ERR_NO_DEVICE. */
+int cs_label_shape(cs_preproc *p, const int32_t *labels, const int32_t *exclude /* or NULL */,
+                   int32_t batch, int32_t height, int32_t width, int in_kind, int32_t max_label, int want_hull,
+                   int64_t *moments, int32_t *box, int32_t *quads, int32_t *perim, int64_t *hull /* or NULL */, int out_kind);
+/* Device time of the last cs_label_shape: clearing + the moments and boxes, and the outline pass (quads, perimeter, hull). */
+int cs_label_shape_last_timing(const cs_preproc *p, double *moments_ms, double *outline_ms);
 
 /* ---- detector fitting (create_anomaly_detector, CAE_improved_modeltrain.py:394-446) -------- */
 /* The fit of what cs_screen's tail evaluates, for the training set's encoder features
