@@ -144,6 +144,10 @@ class CSExpandParams(C.Structure):
     _fields_ = [("max_d2", C.c_int32), ("reserved", C.c_int32)]
 
 
+class CSNeighborsParams(C.Structure):
+    _fields_ = [("max_d2", C.c_int32), ("table_log2", C.c_int32), ("reserved", C.c_int32)]
+
+
 SMOOTH_MAX_RADIUS = 64                  # cs_smooth_params.weights holds 65 taps
 
 
@@ -232,6 +236,11 @@ SIGNATURES = {
     "cs_label_texture_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "cs_label_shape": (_I, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _I, C.c_int32, _I, _P, _P, _P, _P, _P, _I]),
     "cs_label_shape_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "cs_label_neighbors": (_I, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _I, C.c_int32, C.POINTER(CSNeighborsParams), _P, _P, _P, _I,
+                           C.POINTER(_L)]),
+    "cs_label_neighbors_pairs": (_I, [_P, _P, _L, _I]),
+    "cs_label_neighbors_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "cs_label_neighbors_last_table": (_I, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "cs_fit_create": (_I, [_I, C.POINTER(_P)]),
     "cs_fit_free": (None, [_P]),
     "cs_fit_wait_stream": (_I, [_P, _P]),

@@ -1,5 +1,5 @@
 // segment_internal.hpp -- the state behind cs_preproc::seg as its translation units share it (segment.hip, expand.hip,
-// intensity.hip, quantile.hip, texture.hip, shape.hip): the shared buffers and a clock per family of entry points.  The clock itself and
+// intensity.hip, quantile.hip, texture.hip, shape.hip, neighbors.hip): the shared buffers and a clock per family of entry points.  The clock itself and
 // the argument rules are stage_host.hpp's, which extract.hip and match.hip use with states of their own.
 #pragma once
 #include "stage_host.hpp"
@@ -28,7 +28,13 @@ struct SegmentState {
     // cs_label_texture (texture.hip) shares img, lab, parent, stage and ctrl in the same way, and keeps the objects' bounding boxes.
     // cs_label_shape (shape.hip) shares lab, parent, stage and ctrl in the same way, and the bounding boxes with cs_label_texture.
     DevBuf tx_box;                                      // [B][max_label][4] int32, encoded (label_boxes.hpp, LbExtent)
-    StageClock clk_thr, clk_sp, clk_si, clk_bg, clk_lt, clk_cl, clk_sm, clk_hy, clk_ns, clk_ex, clk_in, clk_lq, clk_tx, clk_sh;
+    // cs_label_neighbors (neighbors.hip) shares lab, stage and ctrl in the same way; its pair table is in key (keys), dq (D2) and rec
+    // (n_near), the unsorted rows in slab, the rows' cursors in counts.  Only the sorted pair list is its own: it stays on the
+    // handle until cs_label_neighbors_pairs copies it out, whatever other stage runs between.
+    DevBuf nb_pairs;                                    // [nb_n][3] int32
+    int64_t nb_n = -1;                                  // -1: no successful cs_label_neighbors yet
+    int nb_log2 = 0, nb_grows = 0;                      // the table the last call ended with, and its doublings
+    StageClock clk_thr, clk_sp, clk_si, clk_bg, clk_lt, clk_cl, clk_sm, clk_hy, clk_ns, clk_ex, clk_in, clk_lq, clk_tx, clk_sh, clk_nb;
     int sp_recon_reads = 0, sp_flood_reads = 0;         // control-word reads (one host synchronisation each) of the last split of either kind
 };
 

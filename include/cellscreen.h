@@ -56,6 +56,10 @@
  *        classes and the convex hull's records as exact integers, from which area, axes, orientation, Hu moments,
  *        perimeter, form factor, Euler number, solidity and Feret diameters follow (skimage.measure.regionprops'
  *        geometry properties, CellProfiler's MeasureObjectSizeShape; no reference counterpart)
+ *   cs_label_neighbors / cs_label_neighbors_pairs
+ *        the neighbourhood of the same objects: per object its border pixels, how many of them have a foreign label
+ *        within a distance, and its neighbours within that distance with their smallest squared distance, as exact
+ *        integers in CSR rows (CellProfiler's MeasureObjectNeighbors; no reference counterpart)
  *   cs_fit_scaler / cs_fit_pca_moments / cs_fit_pca_subspace / cs_fit_project / cs_fit_ocsvm
  *        RobustScaler / PCA / OneClassSVM fits of create_anomaly_detector
  *                                                 CAE_improved_modeltrain.py:408-427
@@ -966,6 +970,56 @@ int cs_label_shape(cs_preproc *p, const int32_t *labels, const int32_t *exclude 
                    int64_t *moments, int32_t *box, int32_t *quads, int32_t *perim, int64_t *hull /* or NULL */, int out_kind);
 /* Device time of the last cs_label_shape: clearing + the moments and boxes, and the outline pass (quads, perimeter, hull). */
 int cs_label_shape_last_timing(const cs_preproc *p, double *moments_ms, double *outline_ms);
+
+/* ---- per-object neighbours and contact --------------------------------------------------------------- */
+/* Who lies near every object of a label image, and how much of its outline is in contact, as exact integer records (DESIGN 3y;
+ * tests/neighbors_reference.py restates the rule, cellscreen/neighbors.py derives).  The objects are cs_label_intensity's without an
+ * `exclude` plane: the pixels of one image with one label > 0, connected or not.  Nothing crosses between the images of a batch, and
+ * outside the image there is nothing.  Distances are squared Euclidean distances between pixel centres, in integers.
+ *   A border pixel of a is a pixel of a with a 4-neighbour that is not a's, outside the image included (cs_label_shape's rule).
+ *   D2(a, b), a != b, is the smallest squared distance between a pixel of a and a pixel of b; b is a neighbour of a iff
+ *         D2(a, b) <= max_d2, whatever lies between them: CellProfiler's dilation of a by strel_disk(d) with max_d2 = d * d.
+ *   A border pixel of a is touching iff a pixel with a label other than 0 and a lies within max_d2 of it; its nearest foreign label
+ *         is the label of that pixel at the smallest (d2, label).
+ * params: not NULL.  max_d2 1..1024 (1: 4-adjacent, 2: 8-adjacent; distances up to 32 px, above: CS_ERR_UNSUPPORTED); table_log2 0
+ *         (automatic) or 10..26: the first capacity of the pair table; reserved 0.
+ * geom:   out, [batch][max_label][3] int64: area, sum r, sum c -- cs_label_intensity's geom, bit for bit.
+ * objects: out, [batch][max_label][3] int32: border, touching, degree (the number of neighbours); all zero for a label that does
+ *         not occur.
+ * offsets: out, [batch * max_label + 1] int64: the CSR row starts, row b * max_label + l - 1 for label l of image b; the last entry
+ *         is the number of directed pairs.  All three out_kind.
+ * n_pairs: out, host, not NULL: that number.
+ * The pairs stay on the handle until the next cs_label_neighbors: [n_pairs][3] int32 {neighbour label, D2(a, b), n_near}, every row
+ *         sorted by neighbour label whatever its length.  n_near is the number of a's border pixels whose nearest foreign label is
+ *         that neighbour (it may be 0); the n_near of a row sum to a's touching.  cs_label_neighbors_pairs copies them out.
+ * labels, in_kind, the sizes and max_label: as cs_label_intensity, a bad label included (CS_ERR_INVALID "negative or exceeds
+ *         max_label", detected on the device, never an index or a key; the handle stays usable).
+ * The rules apply in cs_label_intensity's order: NULL arguments, the memory kinds, the sizes, max_label, max_d2 < 1, reserved,
+ *         table_log2 (CS_ERR_INVALID), then the caps (CS_ERR_UNSUPPORTED): sides above 4096, batch above 65535, max_label above 2^20,
+ *         batch * max_label above 2^22, max_d2 above 1024.
+ * The pairs are collected in an open-addressing table on the device, 16 bytes per slot, and leave through 28 more bytes per slot.
+ *         Automatic: the power of two >= 8 * batch * max_label, 2^16 to 2^24.  A table that proves too small is doubled and the call
+ *         runs again (cs_label_neighbors_last_table counts the doublings); beyond 2^26 slots: CS_ERR_NOMEM.
+ * No floating point on the device.  Every value is a count, a minimum or a sum of integers: bit-identical run to run, independent of
+ * the capacity, of the slot placement and of the other images of the batch.  Scratch comes from the buffers the handle's segmenter
+ * stages share.  One host synchronisation per attempt.  Other bad arguments: CS_ERR_INVALID before any device work; without a gfx950
+ * device (p == NULL): CS_ERR_NO_DEVICE. */
+typedef struct cs_neighbors_params {
+    int32_t max_d2;                   /* 1..1024 */
+    int32_t table_log2;               /* 0: automatic; else 10..26: the first capacity */
+    int32_t reserved;                 /* must be 0 */
+} cs_neighbors_params;
+int cs_label_neighbors(cs_preproc *p, const int32_t *labels, int32_t batch, int32_t height, int32_t width, int in_kind,
+                       int32_t max_label, const cs_neighbors_params *params, int64_t *geom, int32_t *objects, int64_t *offsets,
+                       int out_kind, int64_t *n_pairs);
+/* The pair list of the last successful cs_label_neighbors on this handle into pairs, [capacity][3] int32, pairs_kind.  Without such a
+ * call, or with a capacity below its n_pairs: CS_ERR_INVALID.  One host synchronisation. */
+int cs_label_neighbors_pairs(cs_preproc *p, int32_t *pairs, int64_t capacity, int pairs_kind);
+/* Device time of the last cs_label_neighbors (its last attempt): clearing + the scan of the disks, and the rows (degrees, offsets,
+ * scatter, sort). */
+int cs_label_neighbors_last_timing(const cs_preproc *p, double *scan_ms, double *rows_ms);
+/* The capacity (as log2) the last cs_label_neighbors ended with, and how many times it doubled the table. */
+int cs_label_neighbors_last_table(const cs_preproc *p, int32_t *table_log2, int32_t *grows);
 
 /* ---- detector fitting (create_anomaly_detector, CAE_improved_modeltrain.py:394-446) -------- */
 /* The fit of what cs_screen's tail evaluates, for the training set's encoder features
