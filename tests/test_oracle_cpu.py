@@ -127,3 +127,55 @@ def test_oracle_screen_uses_second_encoder():
     fe = oracle.cae_forward(enc, x, want=("features",))["features"]
     assert fe.shape == fa.shape == (3, 2048)
     assert np.abs(fa - fe).max() > 1e-4
+
+
+def _torch_forward64(w, x):
+    """The graph in torch float64 for any instance of the layer grammar: every layer's output, (n, h, w, c)."""
+    import torch
+    import torch.nn.functional as F
+    T = lambda a: torch.from_numpy(np.asarray(a)).double()
+    h, out, last = T(x)[:, None], [], w.n_conv - 1
+    for l in range(w.n_conv):
+        if l > w.n_enc:
+            h = F.interpolate(h, scale_factor=2, mode="nearest")
+        h = F.conv2d(h, T(w.kernels[l]).permute(3, 2, 0, 1), T(w.biases[l]), padding=1)
+        if l < last:
+            h = F.batch_norm(F.relu(h), T(w.bn_mean[l]), T(w.bn_var[l]), T(w.bn_gamma[l]), T(w.bn_beta[l]), False, 0.0, w.bn_eps)
+            if l < w.n_enc:
+                h = F.max_pool2d(h, 2)
+        else:
+            h = torch.sigmoid(h)
+        out.append(h.permute(0, 2, 3, 1).numpy())
+    return out
+
+
+@pytest.mark.parametrize("family", ["trained_like", "compensated12", "trained_like-64x128", "trained_like-48x64"])
+def test_oracle_under_trained_like_weights(family):
+    """The C oracle's bias and BN paths on what a checkpoint holds -- a non-zero bias in every conv, dead and never-clipped
+    filters, gamma = 0, variance 0, gains over orders of magnitude (tests/weight_families.py) -- against torch float64,
+    per layer at the bar of the random-weight test above and per CHANNEL relative to the channel's magnitude budget."""
+    pytest.importorskip("torch")
+    import weight_families as WF
+    if family == "trained_like-64x128":
+        w = WF.trained_like(8, (64, 128), (8, 16, 32, 32, 16, 8, 1), 3)
+    elif family == "trained_like-48x64":
+        w = WF.trained_like(9, (48, 64), (64, 32, 1), 1)
+    else:
+        w = WF.trained_like(7)
+        if family == "compensated12":
+            w = WF.compensated(w, 12)
+    x = WF.edge_crops(w.input_hw, 6)
+    r = oracle.cae_forward(w, x, acc64=True, layers=True)
+    ref = _torch_forward64(w, x)
+    prev = x
+    for l in range(w.n_conv):
+        H.assert_close_scaled(r["layers"][l], ref[l], 2e-6, f"layer {l}")
+        if l < w.n_conv - 1:
+            B = WF.channel_budget(w, l, prev)
+            err = np.abs(r["layers"][l] - ref[l]).reshape(-1, len(B)).max(axis=0)
+            assert (err <= 2e-6 * B).all(), f"layer {l}: channel {int((err / B).argmax())} off by {(err / B).max():.2e} of its budget"
+        prev = ref[l]
+    assert np.abs(r["recon"] - ref[-1][..., 0]).max() <= 2e-6
+    d = x.astype(np.float64) - ref[-1][..., 0]
+    H.assert_rel(r["mse"], (d * d).mean(axis=(1, 2)), 2e-6, "mse")
+    H.assert_rel(r["mae"], np.abs(d).mean(axis=(1, 2)), 2e-6, "mae")
