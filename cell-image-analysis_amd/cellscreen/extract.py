@@ -234,8 +234,10 @@ class CellExtractor:
             L.check(self._lib.cs_extract_fill(self._handle, regions.ctypes.data, status.ctypes.data, L.CS_MEM_HOST,
                                               cells.ctypes.data, cell_image.ctypes.data, L.CS_MEM_HOST))
         if maps is not None:
+            # the table is in (image, label) order: one slice per image, not one pass over the table per image
+            edge = np.searchsorted(regions["image"], np.arange(B + 1))
             for b, u in enumerate(maps):
-                m = regions["image"] == b
+                m = slice(edge[b], edge[b + 1])
                 regions["label"][m] = u[regions["label"][m]]
         return Extraction(cells, cell_image, regions, status)
 

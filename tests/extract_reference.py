@@ -50,13 +50,15 @@ def convex_area(mask: np.ndarray) -> int:
 
 
 def eccentricity(rr: np.ndarray, cc: np.ndarray) -> float:
-    n = len(rr)
     i = [int(x) for x in rr]
     j = [int(x) for x in cc]
-    si, sj = sum(i), sum(j)
-    sii = sum(x * x for x in i)
-    sjj = sum(x * x for x in j)
-    sij = sum(x * y for x, y in zip(i, j))
+    return eccentricity_from_sums(len(i), sum(i), sum(j), sum(x * x for x in i), sum(x * x for x in j),
+                                  sum(x * y for x, y in zip(i, j)))
+
+
+def inertia_eigenvalues(n: int, si: int, sj: int, sii: int, sjj: int, sij: int):
+    """(rad, l1, l2) of the inertia tensor from the region's exact moment sums (Python ints): pixel count, sums of the rows,
+    of the columns, of their squares and of their products.  l1 = mean + rad >= l2 = mean - rad."""
     n2 = float(n) * float(n)
     trr = float(n * sii - si * si) / n2
     tcc = float(n * sjj - sj * sj) / n2
@@ -64,8 +66,11 @@ def eccentricity(rr: np.ndarray, cc: np.ndarray) -> float:
     mean2 = (tcc + trr) * 0.5
     half = (tcc - trr) * 0.5
     rad = math.sqrt(half * half + trc * trc)
-    l1 = mean2 + rad
-    l2 = mean2 - rad
+    return rad, mean2 + rad, mean2 - rad
+
+
+def eccentricity_from_sums(n: int, si: int, sj: int, sii: int, sjj: int, sij: int) -> float:
+    rad, l1, l2 = inertia_eigenvalues(n, si, sj, sii, sjj, sij)
     if l1 == 0.0:
         return 0.0
     if l2 <= 0.0:
