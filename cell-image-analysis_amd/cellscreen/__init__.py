@@ -2,6 +2,7 @@
 libcellscreen.so (hand-written gfx950 HIP).  Importing this package loads no native code;
 Engine / ProductionMutantScreening do, and fail loudly when the library or a GPU is missing."""
 from . import spec  # noqa: F401
+from .colocalize import ColocalizationMeasurer, ColocalizationTable, colocalization_table, colocalize_params  # noqa: F401
 from .expand import LabelExpander, expand_params  # noqa: F401
 from .intensity import IntensityMeasurer, ObjectTable  # noqa: F401
 from .neighbors import NeighborMeasurer, NeighborTable, neighbor_params, neighbor_table  # noqa: F401
@@ -12,4 +13,5 @@ from .texture import TextureMeasurer, TextureTable, texture_table  # noqa: F401
 
 __all__ = ["spec", "CAEWeights", "DetectorParams", "OCSVMParams", "LabelExpander", "expand_params", "IntensityMeasurer",
            "ObjectTable", "QuantileMeasurer", "QuantileTable", "TextureMeasurer", "TextureTable", "texture_table",
-           "ShapeMeasurer", "ShapeTable", "shape_table", "NeighborMeasurer", "NeighborTable", "neighbor_params", "neighbor_table"]
+           "ShapeMeasurer", "ShapeTable", "shape_table", "NeighborMeasurer", "NeighborTable", "neighbor_params", "neighbor_table",
+           "ColocalizationMeasurer", "ColocalizationTable", "colocalization_table", "colocalize_params"]

@@ -148,7 +148,11 @@ class CSNeighborsParams(C.Structure):
     _fields_ = [("max_d2", C.c_int32), ("table_log2", C.c_int32), ("reserved", C.c_int32)]
 
 
-SMOOTH_MAX_RADIUS = 64                  # cs_smooth_params.weights holds 65 taps
+class CSColocalizeParams(C.Structure):
+    _fields_ = [("thr_num", C.c_int32), ("thr_den", C.c_int32), ("absolute", C.c_int32), ("abs_thr", C.c_int32 * 4), ("rwc", C.c_int32)]
+
+
+SMOOTH_MAX_RADIUS = 64                 # cs_smooth_params.weights holds 65 taps
 
 
 class CSSmoothParams(C.Structure):
@@ -241,6 +245,9 @@ SIGNATURES = {
     "cs_label_neighbors_pairs": (_I, [_P, _P, _L, _I]),
     "cs_label_neighbors_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "cs_label_neighbors_last_table": (_I, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "cs_label_colocalize": (_I, [_P, _P, _I, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _I, C.c_int32, C.POINTER(CSColocalizeParams),
+                                 _P, _P, _P, _P, _I]),
+    "cs_label_colocalize_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "cs_fit_create": (_I, [_I, C.POINTER(_P)]),
     "cs_fit_free": (None, [_P]),
     "cs_fit_wait_stream": (_I, [_P, _P]),

@@ -60,6 +60,10 @@
  *        the neighbourhood of the same objects: per object its border pixels, how many of them have a foreign label
  *        within a distance, and its neighbours within that distance with their smallest squared distance, as exact
  *        integers in CSR rows (CellProfiler's MeasureObjectNeighbors; no reference counterpart)
+ *   cs_label_colocalize
+ *        how the channels go together inside the same objects: per object and pair of channels the sums behind Pearson's
+ *        correlation, the regression slope, Manders' coefficients, the overlap and K coefficients and the rank-weighted
+ *        coefficients, as exact integers (CellProfiler's MeasureColocalization; no reference counterpart)
  *   cs_fit_scaler / cs_fit_pca_moments / cs_fit_pca_subspace / cs_fit_project / cs_fit_ocsvm
  *        RobustScaler / PCA / OneClassSVM fits of create_anomaly_detector
  *                                                 CAE_improved_modeltrain.py:408-427
@@ -1020,6 +1024,48 @@ int cs_label_neighbors_pairs(cs_preproc *p, int32_t *pairs, int64_t capacity, in
 int cs_label_neighbors_last_timing(const cs_preproc *p, double *scan_ms, double *rows_ms);
 /* The capacity (as log2) the last cs_label_neighbors ended with, and how many times it doubled the table. */
 int cs_label_neighbors_last_table(const cs_preproc *p, int32_t *table_log2, int32_t *grows);
+
+/* ---- per-object colocalization between channels ------------------------------------------------------ */
+/* How the channels of an image go together inside every object of a label image, as exact integer sums (DESIGN 3z;
+ * tests/colocalize_reference.py restates the rule, cellscreen/colocalize.py derives).  The objects are cs_label_intensity's: the
+ * pixels of one image with one label > 0, connected or not, less the pixels where `exclude` is non-zero.  The pairs of channels
+ * (i, j), i < j, come in lexicographic order: P = channels * (channels - 1) / 2.  Pearson's correlation and the regression slope
+ * (scipy.stats.pearsonr, linregress), Manders' M1 / M2, the overlap coefficient, K1 / K2 and the rank-weighted coefficients of
+ * CellProfiler's MeasureColocalization follow from the sums on the host.
+ * A pixel of an object is "above" in channel c
+ *   absolute == 0:  iff v * thr_den >= thr_num * max_c, max_c the object's own maximum in c; 0 <= thr_num <= thr_den, thr_den in
+ *                   1..65536.  A tie is above.
+ *   absolute == 1:  iff v >= abs_thr[c], each 0..65536.
+ * and "both" of a pair where it is above in both channels.  With rwc, per image and channel, the dense rank of a value among the
+ * values that occur on the image's object pixels (0 upwards; R_c distinct values), and per pair R = max(R_i, R_j),
+ * w = R - |rank_i - rank_j| in 1..65536.
+ * image:  [batch][height][width][channels] uint8 / uint16 (pixel_type), channels 2..4; 1: CS_ERR_INVALID, above 4:
+ *         CS_ERR_UNSUPPORTED.
+ * labels, exclude, in_kind, the sizes and max_label: as cs_label_intensity, a bad label included (CS_ERR_INVALID "negative or
+ *         exceeds max_label", detected on the device, never an index; the handle stays usable).
+ * geom:   out, [batch][max_label][3] int64: area, sum r, sum c -- cs_label_intensity's geom, bit for bit.
+ * chan:   out, [batch][max_label][channels][5] int64: sum v, sum v^2, max v, n_above, sum v[above].
+ * pair:   out, [batch][max_label][P][9] int64: sum v_i v_j over all pixels; over "both": n, sum v_i, sum v_j, sum v_i^2,
+ *         sum v_j^2, sum v_i v_j, sum v_i w, sum v_j w (the last two zero when rwc == 0).
+ * levels: out, [batch][channels] int32: R_c; zeros when rwc == 0.  All four out_kind.  Rows of absent objects are all zero.
+ * The rules apply in cs_label_intensity's order, the parameters' ranges (CS_ERR_INVALID) after the channel limit.  With rwc the
+ * handle keeps 192 KB per image and channel for the presence and rank tables; above 1 GiB: CS_ERR_UNSUPPORTED (split the batch),
+ * before any device work.  No floating point: bit-identical run to run and independent of the other images of the batch.  One
+ * host synchronisation per call.  Without a gfx950 device (p == NULL): CS_ERR_NO_DEVICE. */
+typedef struct cs_colocalize_params {
+    int32_t thr_num, thr_den;         /* used when absolute == 0 */
+    int32_t absolute;                 /* 0 / 1 */
+    int32_t abs_thr[4];               /* used when absolute == 1 */
+    int32_t rwc;                      /* 0 / 1 */
+} cs_colocalize_params;
+int cs_label_colocalize(cs_preproc *p, const void *image, int pixel_type, int32_t channels,
+                        const int32_t *labels, const int32_t *exclude /* or NULL */,
+                        int32_t batch, int32_t height, int32_t width, int in_kind, int32_t max_label,
+                        const cs_colocalize_params *params, int64_t *geom, int64_t *chan, int64_t *pair, int32_t *levels,
+                        int out_kind);
+/* Device time of the last cs_label_colocalize: clearing, the moments walk, the ranks (0 without rwc) and the thresholded walk. */
+int cs_label_colocalize_last_timing(const cs_preproc *p, double *clear_ms, double *moments_ms, double *ranks_ms,
+                                    double *thresholded_ms);
 
 /* ---- detector fitting (create_anomaly_detector, CAE_improved_modeltrain.py:394-446) -------- */
 /* The fit of what cs_screen's tail evaluates, for the training set's encoder features
