@@ -17,9 +17,11 @@
 // recomputed (N x D fp64 FMAs, the training set stays in the Infinity Cache) and rounded to float exactly
 // where libsvm rounds them (Qfloat), the gradient is kept in double and updated with libsvm's expression,
 // and both selections break ties the way libsvm's sequential `>=` / `<=` scans do (last index wins).
-// Shrinking only removes variables that cannot be selected, so the iterates agree with libsvm's until
-// rounding in the kernel values (BLAS ddot vs a sequential FMA chain, libm vs ocml exp) flips a float or a
-// near-tie; the solution then still agrees to the solver's own stopping tolerance.
+// Shrinking removes variables that cannot be selected when libsvm shrinks them (first after min(n, 1000)
+// iterations) but also permutes libsvm's index order, which decides exact ties.  The iterates agree
+// with libsvm's until such a tie is met after a shrink, or rounding in the kernel values (BLAS ddot vs a
+// sequential FMA chain, libm vs ocml exp) flips a float or a near-tie; the solution then still agrees to the
+// solver's own stopping tolerance.
 #include "api_internal.hpp"
 
 #include <hip/hip_runtime.h>
@@ -47,7 +49,7 @@ __device__ __forceinline__ float key2f(unsigned k)
     return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
 }
 
-// features [n][F] fp32 -> keysT [F][ld] (32x32 tiles through LDS); counts NaNs
+// features [n][F] fp32 -> keysT [F][ld] (32x32 tiles through LDS); counts the non-finite values (NaN, +-inf)
 __global__ __launch_bounds__(256) void keys_transpose_kernel(const float* __restrict__ x, long n, int F, long ld,
                                                              unsigned* __restrict__ keysT, int* __restrict__ nan_count)
 {
@@ -63,7 +65,7 @@ __global__ __launch_bounds__(256) void keys_transpose_kernel(const float* __rest
         unsigned key = 0u;
         if (r < n && c < F) {
             const float v = x[r * F + c];
-            nans += (v != v);
+            nans += (__float_as_uint(v) & 0x7F800000u) == 0x7F800000u;   // exponent all ones: NaN or +-inf
             key = f2key(v);
         }
         tile[ty + 8 * k][tx] = key;
@@ -830,7 +832,9 @@ int cs_fit_scaler(cs_fit* f, const float* features, int64_t n, int32_t n_feature
     HIPCHK(hipMemcpyAsync(sel.data(), f->sel.p, sel.size() * sizeof(float), hipMemcpyDeviceToHost, f->stream));
     HIPCHK(hipMemcpyAsync(&nans, f->nanc.p, sizeof(int), hipMemcpyDeviceToHost, f->stream));
     if ((rc = tm.stop())) return rc;
-    if (nans) return fail(CS_ERR_UNSUPPORTED, "features hold %d NaNs: nanmedian / nanpercentile semantics are not implemented", nans);
+    if (nans)        // RobustScaler.fit's check_array lets NaN through to nanmedian / nanpercentile and refuses +-inf
+        return fail(CS_ERR_UNSUPPORTED, "features hold %d non-finite values (NaN or +-inf): nanmedian / nanpercentile semantics are not "
+                    "implemented, and scikit-learn refuses infinities", nans);
 
     for (int c = 0; c < F; ++c) {
         const float* s = &sel[(size_t)c * SEL_T];
@@ -1021,7 +1025,12 @@ int cs_fit_ocsvm(cs_fit* f, const double* x, int64_t n, int32_t n_components, do
             else if (alpha[i] <= 0.0) ub = std::min(ub, yG);
             else { ++nr_free; sum_free += yG; }
         }
-        *rho = nr_free > 0 ? sum_free / (double)nr_free : (ub + lb) / 2;
+        const double r = nr_free > 0 ? sum_free / (double)nr_free : (ub + lb) / 2;
+        // no free alpha and one of the two bounds empty (nu = 1: every alpha at C): libsvm returns +-inf here and
+        // scikit-learn then refuses the fit (svm/_base.py: "The dual coefficients or intercepts are not finite")
+        if (!std::isfinite(r))
+            return fail(CS_ERR_INVALID, "rho is not finite (nu=%g leaves every alpha at a bound): scikit-learn refuses this fit", nu);
+        *rho = r;
         if (obj) {
             double v = 0.0;
             for (int64_t i = 0; i < n; ++i) { volatile double t = alpha[i] * (G[(size_t)i] + 0.0); v += t; }

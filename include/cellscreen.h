@@ -1072,7 +1072,8 @@ int cs_label_colocalize_last_timing(const cs_preproc *p, double *clear_ms, doubl
  * (cs_encode output, [n][n_features] fp32, host or device).  Own handle, own stream.
  *   cs_fit_scaler       RobustScaler().fit (:408-409): center_ = per-feature median (float32), scale_ = 75th - 25th
  *                       percentile (float64, numpy's linear interpolation; spreads below 10 eps become 1).  Exact
- *                       (radix select of the order statistics + numpy's arithmetic on them).  NaNs: CS_ERR_UNSUPPORTED.
+ *                       (radix select of the order statistics + numpy's arithmetic on them).  NaNs and infinities:
+ *                       CS_ERR_UNSUPPORTED.
  *   cs_fit_pca_moments  what PCA(...).fit (:412-414) needs from the data: mean_ (float32, numpy's row-after-row sum)
  *                       of the scaled features and the fp64 scatter matrix Xc^T Xc of the centred scaled features
  *                       ([F][F], host).  The principal axes are the leading eigenvectors of scatter / (n - 1); the
@@ -1098,7 +1099,8 @@ int cs_label_colocalize_last_timing(const cs_preproc *p, double *clear_ms, doubl
  *                       float64 host (what sklearn hands libsvm), gamma as resolved by sklearn ('scale':
  *                       1 / (n_components * x.var())), eps = tol (sklearn default 1e-3), max_iter < 0 = unbounded.
  *                       alpha: [n] dual variables (support vectors are the points with alpha > 0; dual_coef_ = alpha),
- *                       rho = -intercept_ = offset_.  status: 0 converged, 1 stopped at max_iter. */
+ *                       rho = -intercept_ = offset_.  status: 0 converged, 1 stopped at max_iter.  A solve that leaves rho
+ *                       non-finite (nu = 1: every alpha at its bound) is CS_ERR_INVALID, as scikit-learn refuses it. */
 typedef struct cs_fit cs_fit;
 int cs_fit_create(int device_id, cs_fit **out);
 void cs_fit_free(cs_fit *f);
