@@ -7,6 +7,7 @@ from .expand import LabelExpander, expand_params  # noqa: F401
 from .intensity import IntensityMeasurer, ObjectTable  # noqa: F401
 from .neighbors import NeighborMeasurer, NeighborTable, neighbor_params, neighbor_table  # noqa: F401
 from .quantile import QuantileMeasurer, QuantileTable  # noqa: F401
+from .radial import RadialMeasurer, RadialTable, radial_params, radial_table  # noqa: F401
 from .shape import ShapeMeasurer, ShapeTable, shape_table  # noqa: F401
 from .spec import CAEWeights, DetectorParams, OCSVMParams  # noqa: F401
 from .texture import TextureMeasurer, TextureTable, texture_table  # noqa: F401
@@ -14,4 +15,5 @@ from .texture import TextureMeasurer, TextureTable, texture_table  # noqa: F401
 __all__ = ["spec", "CAEWeights", "DetectorParams", "OCSVMParams", "LabelExpander", "expand_params", "IntensityMeasurer",
            "ObjectTable", "QuantileMeasurer", "QuantileTable", "TextureMeasurer", "TextureTable", "texture_table",
            "ShapeMeasurer", "ShapeTable", "shape_table", "NeighborMeasurer", "NeighborTable", "neighbor_params", "neighbor_table",
-           "ColocalizationMeasurer", "ColocalizationTable", "colocalization_table", "colocalize_params"]
+           "ColocalizationMeasurer", "ColocalizationTable", "colocalization_table", "colocalize_params",
+           "RadialMeasurer", "RadialTable", "radial_params", "radial_table"]

@@ -152,7 +152,11 @@ class CSColocalizeParams(C.Structure):
     _fields_ = [("thr_num", C.c_int32), ("thr_den", C.c_int32), ("absolute", C.c_int32), ("abs_thr", C.c_int32 * 4), ("rwc", C.c_int32)]
 
 
-SMOOTH_MAX_RADIUS = 64                 # cs_smooth_params.weights holds 65 taps
+class CSRadialParams(C.Structure):
+    _fields_ = [("bins", C.c_int32), ("reserved", C.c_int32)]
+
+
+SMOOTH_MAX_RADIUS = 64                # cs_smooth_params.weights holds 65 taps
 
 
 class CSSmoothParams(C.Structure):
@@ -248,6 +252,9 @@ SIGNATURES = {
     "cs_label_colocalize": (_I, [_P, _P, _I, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _I, C.c_int32, C.POINTER(CSColocalizeParams),
                                  _P, _P, _P, _P, _I]),
     "cs_label_colocalize_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "cs_label_radial": (_I, [_P, _P, _I, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _I, C.c_int32, C.POINTER(CSRadialParams),
+                             _P, _P, _P, _P, _P, _P, _I]),
+    "cs_label_radial_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "cs_fit_create": (_I, [_I, C.POINTER(_P)]),
     "cs_fit_free": (None, [_P]),
     "cs_fit_wait_stream": (_I, [_P, _P]),

@@ -15,7 +15,8 @@ values are taken from them here in Python ints and float64, so they do not depen
     centroid = (sum r, sum c) / n        weighted_centroid = (sum v*r, sum v*c) / sum v, NaN where sum v = 0
 
 Median, quantiles and MAD need a selection per object and are QuantileMeasurer's (cellscreen/quantile.py); texture is
-TextureMeasurer's (cellscreen/texture.py).  No edge measures, 2-D only, at most 4 channels per call."""
+TextureMeasurer's (cellscreen/texture.py); the edge measures are RadialMeasurer's (cellscreen/radial.py).
+2-D only, at most 4 channels per call."""
 from __future__ import annotations
 
 import ctypes as C

@@ -1,5 +1,5 @@
 // segment_internal.hpp -- the state behind cs_preproc::seg as its translation units share it (segment.hip, expand.hip,
-// intensity.hip, quantile.hip, texture.hip, shape.hip, neighbors.hip, colocalize.hip): the shared buffers and a clock per family of entry points.  The clock itself and
+// intensity.hip, quantile.hip, texture.hip, shape.hip, neighbors.hip, colocalize.hip, radial.hip): the shared buffers and a clock per family of entry points.  The clock itself and
 // the argument rules are stage_host.hpp's, which extract.hip and match.hip use with states of their own.
 #pragma once
 #include "stage_host.hpp"
@@ -37,7 +37,9 @@ struct SegmentState {
     // cs_label_colocalize (colocalize.hip) shares img, lab, parent, stage and ctrl as cs_label_intensity does, and keeps the presence
     // and rank tables of its rank-weighted sums.
     DevBuf co_rank;                                     // [B][C][65536] bytes, then [B][C][65536] uint16
-    StageClock clk_thr, clk_sp, clk_si, clk_bg, clk_lt, clk_cl, clk_sm, clk_hy, clk_ns, clk_ex, clk_in, clk_lq, clk_tx, clk_sh, clk_nb, clk_co;
+    // cs_label_radial (radial.hip) shares img, lab, parent, stage and ctrl as cs_label_intensity does and has no buffer of its own:
+    // column distances in mask, the depth plane in dq, the deepest pixels' keys in key, the caller's centres in rec.
+    StageClock clk_thr, clk_sp, clk_si, clk_bg, clk_lt, clk_cl, clk_sm, clk_hy, clk_ns, clk_ex, clk_in, clk_lq, clk_tx, clk_sh, clk_nb, clk_co, clk_ra;
     int sp_recon_reads = 0, sp_flood_reads = 0;         // control-word reads (one host synchronisation each) of the last split of either kind
 };
 

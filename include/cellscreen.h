@@ -64,6 +64,11 @@
  *        how the channels go together inside the same objects: per object and pair of channels the sums behind Pearson's
  *        correlation, the regression slope, Manders' coefficients, the overlap and K coefficients and the rank-weighted
  *        coefficients, as exact integers (CellProfiler's MeasureColocalization; no reference counterpart)
+ *   cs_label_radial
+ *        where the intensity of the same objects sits between centre and outline: the exact depth of every object pixel
+ *        (a per-label Euclidean distance transform), per object, ring and wedge the pixel count and the sums, and the
+ *        records of the outline's intensities, as exact integers (CellProfiler's MeasureObjectIntensityDistribution and
+ *        the Edge measures of MeasureObjectIntensity; no reference counterpart)
  *   cs_fit_scaler / cs_fit_pca_moments / cs_fit_pca_subspace / cs_fit_project / cs_fit_ocsvm
  *        RobustScaler / PCA / OneClassSVM fits of create_anomaly_detector
  *                                                 CAE_improved_modeltrain.py:408-427
@@ -1066,6 +1071,57 @@ int cs_label_colocalize(cs_preproc *p, const void *image, int pixel_type, int32_
 /* Device time of the last cs_label_colocalize: clearing, the moments walk, the ranks (0 without rwc) and the thresholded walk. */
 int cs_label_colocalize_last_timing(const cs_preproc *p, double *clear_ms, double *moments_ms, double *ranks_ms,
                                     double *thresholded_ms);
+
+/* ---- per-object radial intensity distribution and edge intensities ------------------------------------ */
+/* Where the intensity of every object of a label image sits between its centre and its outline, and how bright its outline is, as
+ * exact integer records (tests/radial_reference.py restates the rule, cellscreen/radial.py derives): CellProfiler's
+ * MeasureObjectIntensityDistribution (FracAtD, MeanFrac, RadialCV per ring) and the Edge measures of MeasureObjectIntensity.  The
+ * objects are cs_label_intensity's: the pixels of one image with one label > 0, connected or not, less the pixels where `exclude`
+ * is non-zero; a pixel's effective label is 0 where `exclude` is set.  Nothing crosses between the images of a batch.
+ *   E2(p), the depth of an object pixel p: the smallest squared Euclidean distance between pixel centres from p to a position that
+ *         is not the object's: a pixel of another label, background, an excluded pixel, or any position outside the image.  E2 == 1
+ *         exactly on the border pixels of cs_label_shape and cs_label_neighbors; per object it is
+ *         scipy.ndimage.distance_transform_edt(np.pad(labels == l, 1)) ** 2.  Depths are exact up to CS_RADIAL_MAX_D2 = 127^2: an
+ *         object with a deeper pixel is CS_ERR_UNSUPPORTED, detected on the device as a bad label is; the handle stays usable.
+ *   The centre of an object is its deepest pixel, among equally deep ones the one with the smallest raster index r * width + c
+ *         (scipy.ndimage.maximum_position), or the caller's.  C2(p) is the squared Euclidean distance from p to the centre along
+ *         the straight line; CellProfiler propagates that distance inside the object instead, a deliberate difference: the two
+ *         agree wherever the segment from p to the centre stays inside the object.
+ *   ring(p), with B = bins: the number of k in 1..B-1 with (B - k)^2 * C2 >= k^2 * E2, in 64-bit integers: floor(B dc / (dc + de))
+ *         with dc = sqrt(C2), de = sqrt(E2), decided without a root; an exact multiple belongs to the outer ring, the centre to
+ *         ring 0.
+ *   wedge(p) = (r > rc) + 2 * (c > cc) + 4 * (|r - rc| > |c - cc|) around the centre (rc, cc): CellProfiler's eight.
+ * image, pixel_type, channels 1..4, labels, exclude, in_kind, the sizes and max_label: as cs_label_intensity, a bad label included
+ *         (CS_ERR_INVALID "negative or exceeds max_label", detected on the device, never an index or a key; the handle stays usable).
+ * params: not NULL.  bins 1..CS_RADIAL_MAX_BINS (below 1: CS_ERR_INVALID, above: CS_ERR_UNSUPPORTED); reserved 0.
+ * centers: NULL, or a HOST table [batch][max_label][2] int32 of rows and columns, whatever in_kind: every row, those of absent
+ *         objects too, must lie inside the image (else CS_ERR_INVALID before any device work).  A centre need not lie in its object.
+ * geom:   out, [batch][max_label][3] int64: area, sum r, sum c -- cs_label_intensity's geom, bit for bit.
+ * center: out, [batch][max_label][4] int32: the centre's row and column, E2 at the object's deepest pixel (also with given
+ *         centres), the number of pixels with E2 == 1.
+ * ring:   out, [batch][max_label][bins][8][1 + channels] int64: per (object, ring, wedge) the pixel count and per channel sum v.
+ * edge:   out, [batch][max_label][channels][4] int64: sum v, sum v^2, min v, max v over the pixels with E2 == 1.
+ * d2:     out or NULL, [batch][height][width] uint16: E2, 0 off the objects.  All five out_kind.  Rows of absent objects are all
+ *         zero.
+ * The rules apply in cs_label_intensity's order, the parameters' ranges after the channel limit; then the caps (CS_ERR_UNSUPPORTED):
+ *         max_label above 2^20, batch * max_label * channels above 2^22, sides above 4096, batch above 65535, a ring table above
+ *         1 GiB (split the batch); then the centres.
+ * No floating point: bit-identical run to run and independent of the other images of the batch.  Scratch comes from the buffers the
+ * handle's stages share (1 byte per pixel of column distances, 2 of depths, 8 per table row); the handle keeps nothing beyond them.
+ * One host synchronisation per call.  Without a gfx950 device (p == NULL): CS_ERR_NO_DEVICE. */
+#define CS_RADIAL_MAX_D2 16129        /* 127^2: the deepest E2 an object may hold */
+#define CS_RADIAL_MAX_BINS 16
+typedef struct cs_radial_params {
+    int32_t bins;                     /* 1..CS_RADIAL_MAX_BINS */
+    int32_t reserved;                 /* must be 0 */
+} cs_radial_params;
+int cs_label_radial(cs_preproc *p, const void *image, int pixel_type, int32_t channels,
+                    const int32_t *labels, const int32_t *exclude /* or NULL */,
+                    int32_t batch, int32_t height, int32_t width, int in_kind, int32_t max_label,
+                    const cs_radial_params *params, const int32_t *centers /* or NULL */,
+                    int64_t *geom, int32_t *center, int64_t *ring, int64_t *edge, uint16_t *d2 /* or NULL */, int out_kind);
+/* Device time of the last cs_label_radial: clearing + the column pass, the row pass with the centres, and the bin pass. */
+int cs_label_radial_last_timing(const cs_preproc *p, double *columns_ms, double *rows_ms, double *bins_ms);
 
 /* ---- detector fitting (create_anomaly_detector, CAE_improved_modeltrain.py:394-446) -------- */
 /* The fit of what cs_screen's tail evaluates, for the training set's encoder features
