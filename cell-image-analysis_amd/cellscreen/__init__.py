@@ -4,6 +4,7 @@ Engine / ProductionMutantScreening do, and fail loudly when the library or a GPU
 from . import spec  # noqa: F401
 from .colocalize import ColocalizationMeasurer, ColocalizationTable, colocalization_table, colocalize_params  # noqa: F401
 from .expand import LabelExpander, expand_params  # noqa: F401
+from .granularity import GranularityMeasurer, GranularityTable, granularity_params, granularity_table  # noqa: F401
 from .intensity import IntensityMeasurer, ObjectTable  # noqa: F401
 from .neighbors import NeighborMeasurer, NeighborTable, neighbor_params, neighbor_table  # noqa: F401
 from .quantile import QuantileMeasurer, QuantileTable  # noqa: F401
@@ -16,4 +17,5 @@ __all__ = ["spec", "CAEWeights", "DetectorParams", "OCSVMParams", "LabelExpander
            "ObjectTable", "QuantileMeasurer", "QuantileTable", "TextureMeasurer", "TextureTable", "texture_table",
            "ShapeMeasurer", "ShapeTable", "shape_table", "NeighborMeasurer", "NeighborTable", "neighbor_params", "neighbor_table",
            "ColocalizationMeasurer", "ColocalizationTable", "colocalization_table", "colocalize_params",
-           "RadialMeasurer", "RadialTable", "radial_params", "radial_table"]
+           "RadialMeasurer", "RadialTable", "radial_params", "radial_table",
+           "GranularityMeasurer", "GranularityTable", "granularity_params", "granularity_table"]

@@ -156,6 +156,10 @@ class CSRadialParams(C.Structure):
     _fields_ = [("bins", C.c_int32), ("reserved", C.c_int32)]
 
 
+class CSGranularityParams(C.Structure):
+    _fields_ = [("steps", C.c_int32), ("subsample", C.c_int32), ("masked", C.c_int32), ("reserved", C.c_int32)]
+
+
 SMOOTH_MAX_RADIUS = 64                # cs_smooth_params.weights holds 65 taps
 
 
@@ -255,6 +259,10 @@ SIGNATURES = {
     "cs_label_radial": (_I, [_P, _P, _I, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _I, C.c_int32, C.POINTER(CSRadialParams),
                              _P, _P, _P, _P, _P, _P, _I]),
     "cs_label_radial_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "cs_label_granularity": (_I, [_P, _P, _I, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _I, C.c_int32, C.POINTER(CSGranularityParams),
+                                  _P, _P, _P, _P, _I]),
+    "cs_label_granularity_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "cs_label_granularity_last_rounds": (_I, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "cs_fit_create": (_I, [_I, C.POINTER(_P)]),
     "cs_fit_free": (None, [_P]),
     "cs_fit_wait_stream": (_I, [_P, _P]),

@@ -1,5 +1,5 @@
 // label_tile.hpp -- the walk over an int32 label stack [B][H][W] that ex_label_pass (extract.hip), lm_count (match.hip),
-// li_pass (intensity.hip), lq_count / lq_scatter (quantile.hip), lb_pass (label_boxes.hpp: texture.hip, shape.hip) , lc_moments / lc_thresholded (colocalize.hip) and lr_bins (radial.hip) share: the tile, the load
+// li_pass (intensity.hip), lq_count / lq_scatter (quantile.hip), lb_pass (label_boxes.hpp: texture.hip, shape.hip) , lc_moments / lc_thresholded (colocalize.hip), lr_bins (radial.hip) and gs_sums (granularity.hip) share: the tile, the load
 // of a lane's four labels, the wave reductions, the closing merge of the lanes' open runs and the claim of a slot in an
 // open-addressing table.  nb_scan (neighbors.hip) has a tile of its own, with a halo, and takes the claim and the reductions; lr_rows (radial.hip) works on row strips and takes the closing merge and the reductions.  Each kernel keeps its own row loop, its unroll and its run bookkeeping: what they do per pixel
 // differs, and so does what they hold in registers.

@@ -1,5 +1,5 @@
 // segment_internal.hpp -- the state behind cs_preproc::seg as its translation units share it (segment.hip, expand.hip,
-// intensity.hip, quantile.hip, texture.hip, shape.hip, neighbors.hip, colocalize.hip, radial.hip): the shared buffers and a clock per family of entry points.  The clock itself and
+// intensity.hip, quantile.hip, texture.hip, shape.hip, neighbors.hip, colocalize.hip, radial.hip, granularity.hip): the shared buffers and a clock per family of entry points.  The clock itself and
 // the argument rules are stage_host.hpp's, which extract.hip and match.hip use with states of their own.
 #pragma once
 #include "stage_host.hpp"
@@ -39,7 +39,12 @@ struct SegmentState {
     DevBuf co_rank;                                     // [B][C][65536] bytes, then [B][C][65536] uint16
     // cs_label_radial (radial.hip) shares img, lab, parent, stage and ctrl as cs_label_intensity does and has no buffer of its own:
     // column distances in mask, the depth plane in dq, the deepest pixels' keys in key, the caller's centres in rec.
-    StageClock clk_thr, clk_sp, clk_si, clk_bg, clk_lt, clk_cl, clk_sm, clk_hy, clk_ns, clk_ex, clk_in, clk_lq, clk_tx, clk_sh, clk_nb, clk_co, clk_ra;
+    // cs_label_granularity (granularity.hip) shares img, lab, parent, stage and ctrl in the same way and has no buffer of its own: the
+    // working plane P in dq, the erosion E in rec, the reconstruction R in key, uint16 [B][C][Hs][Ws] each, and in ttop an int per
+    // reconstruction tile: the round in which it last changed.
+    StageClock clk_thr, clk_sp, clk_si, clk_bg, clk_lt, clk_cl, clk_sm, clk_hy, clk_ns, clk_ex, clk_in, clk_lq, clk_tx, clk_sh, clk_nb, clk_co, clk_ra, clk_gr, clk_gs;   // clk_gs: one sums pass of cs_label_granularity at a time
+    double gr_ms[3] = {0.0, 0.0, 0.0};                  // cs_label_granularity's last call: prepare, erosions + reconstructions, sums
+    int gr_rounds = 0, gr_reads = 0;                    // its reconstruction rounds (all steps) and control-word reads
     int sp_recon_reads = 0, sp_flood_reads = 0;         // control-word reads (one host synchronisation each) of the last split of either kind
 };
 

@@ -1,5 +1,5 @@
 // stage_host.hpp -- what the entry points on the preprocess handle share on the host, whichever state they keep (segment.hip,
-// expand.hip, intensity.hip, quantile.hip, texture.hip, shape.hip, neighbors.hip, colocalize.hip and radial.hip on SegmentState, extract.hip on ExtractState, match.hip on
+// expand.hip, intensity.hip, quantile.hip, texture.hip, shape.hip, neighbors.hip, colocalize.hip, radial.hip and granularity.hip on SegmentState, extract.hip on ExtractState, match.hip on
 // MatchState): the limits, the argument rules with their texts, the handle check, and the one clock with its read.
 #pragma once
 #include "api_internal.hpp"

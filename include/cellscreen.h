@@ -69,6 +69,10 @@
  *        (a per-label Euclidean distance transform), per object, ring and wedge the pixel count and the sums, and the
  *        records of the outline's intensities, as exact integers (CellProfiler's MeasureObjectIntensityDistribution and
  *        the Edge measures of MeasureObjectIntensity; no reference counterpart)
+ *   cs_label_granularity
+ *        the size spectrum of the bright structures inside the same objects: per spectrum step a grey-level erosion and
+ *        a reconstruction by dilation of the whole plane, and per object, step and channel the sum of the reconstructed
+ *        plane, as exact integers (CellProfiler's MeasureGranularity; no reference counterpart)
  *   cs_fit_scaler / cs_fit_pca_moments / cs_fit_pca_subspace / cs_fit_project / cs_fit_ocsvm
  *        RobustScaler / PCA / OneClassSVM fits of create_anomaly_detector
  *                                                 CAE_improved_modeltrain.py:408-427
@@ -1122,6 +1126,62 @@ int cs_label_radial(cs_preproc *p, const void *image, int pixel_type, int32_t ch
                     int64_t *geom, int32_t *center, int64_t *ring, int64_t *edge, uint16_t *d2 /* or NULL */, int out_kind);
 /* Device time of the last cs_label_radial: clearing + the column pass, the row pass with the centres, and the bin pass. */
 int cs_label_radial_last_timing(const cs_preproc *p, double *columns_ms, double *rows_ms, double *bins_ms);
+
+/* ---- per-object granularity spectrum --------------------------------------------------------------------- */
+/* The size spectrum of the bright structures inside every object of a label image, as exact integer records (DESIGN 3zb;
+ * tests/granularity_reference.py restates the rule, cellscreen/granularity.py derives): CellProfiler's MeasureGranularity.  The
+ * objects are cs_label_intensity's: the pixels of one image with one label > 0, connected or not, less the pixels where `exclude`
+ * is non-zero; a pixel's effective label is 0 where `exclude` is set.  Nothing crosses between the images of a batch or between
+ * channels.
+ *   P, the working plane of a channel: uint16 [Hs][Ws], Hs = ceil(height / s), Ws = ceil(width / s), s = subsample.
+ *         P[R][C] = (2 * sum v + n) / (2 * n) (integer division) over the in-image pixels of the s x s block, n their count: the
+ *         rounded block mean, the pixel itself at s = 1; uint8 is widened.  With masked = 1 a pixel whose effective label is 0
+ *         contributes v = 0 and still counts in n (CellProfiler with the objects as the image's mask).
+ *   E_k = the erosion of E_(k-1) by the 3 x 3 cross (CellProfiler's disk(1)), E_0 = P; neighbours outside the plane are ignored:
+ *         scipy.ndimage.grey_erosion(E, footprint=cross, mode='reflect').
+ *   R_k = the reconstruction by dilation of E_k under P with the same cross: the fixed point of
+ *         R <- min(max over the cross of R, P) started at R = E_k, neighbours outside ignored; R_0 = P.  k = 1..steps.
+ * Deliberate differences from CellProfiler: the subsampling is an integer block mean read back by the nearest block (CellProfiler:
+ * bilinear map_coordinates); there is no background removal (pass a plane corrected by cs_segment_background); the reconstruction
+ * is image-wide, so a bright structure shared by two touching objects is held up for both, as in CellProfiler.
+ * image, pixel_type, channels 1..4, labels, exclude, in_kind, the sizes and max_label: as cs_label_intensity, a bad label included
+ *         (CS_ERR_INVALID "negative or exceeds max_label", detected on the device, never an index or a key; the handle stays usable).
+ * params: not NULL.  steps 1..CS_GRANULARITY_MAX_STEPS (below 1: CS_ERR_INVALID, above: CS_ERR_UNSUPPORTED); subsample 1, 2, 4 or
+ *         8, masked 0 or 1, reserved 0 (else CS_ERR_INVALID).
+ * geom:   out, [batch][max_label][3] int64: area, sum r, sum c -- cs_label_intensity's geom, bit for bit.
+ * sums:   out, [batch][max_label][steps + 1][channels] int64: for k = 0..steps the sum over the object's full-resolution pixels
+ *         (r, c) of R_k[r / s][c / s].
+ * image_sums: out, [batch][steps + 1][channels] int64: the sum over the whole working plane of R_k (CellProfiler's image-level
+ *         Granularity_k follows from it).
+ * planes: out or NULL, uint16 [batch][steps + 1][channels][Hs][Ws]: the R_k themselves.  All four out_kind.  Rows of absent
+ *         objects are all zero.
+ * The rules apply in cs_label_intensity's order, the parameters' ranges after the channel limit; then the caps (CS_ERR_UNSUPPORTED):
+ *         max_label above 2^20, batch * max_label * channels above 2^22, sides above 4096, batch above 65535, a sums table or a
+ *         planes stack above 1 GiB (split the batch).  A refused call writes nothing.
+ * The reconstruction runs in rounds over tiles until a round changes nothing, at most Hs * Ws rounds per step: reaching that cap
+ * is CS_ERR_UNSUPPORTED, never an endless loop.  No floating point: bit-identical run to run and independent of the other images of
+ * the batch.  Scratch comes from the buffers the handle's stages share (three uint16 working planes per channel, 4 bytes per
+ * 64 x 32 tile of them, the control words, the tables on their way to the host); the handle keeps nothing beyond them.  A bad label
+ * ends the call at its first read of the control word, before the tables are written.  One host synchronisation per group of rounds.
+ * Without a gfx950 device (p == NULL): CS_ERR_NO_DEVICE. */
+#define CS_GRANULARITY_MAX_STEPS 64
+typedef struct cs_granularity_params {
+    int32_t steps;                    /* 1..CS_GRANULARITY_MAX_STEPS */
+    int32_t subsample;                /* 1, 2, 4 or 8 */
+    int32_t masked;                   /* 0, or 1: pixels off the objects count as 0 in P */
+    int32_t reserved;                 /* must be 0 */
+} cs_granularity_params;
+int cs_label_granularity(cs_preproc *p, const void *image, int pixel_type, int32_t channels,
+                         const int32_t *labels, const int32_t *exclude /* or NULL */,
+                         int32_t batch, int32_t height, int32_t width, int in_kind, int32_t max_label,
+                         const cs_granularity_params *params,
+                         int64_t *geom, int64_t *sums, int64_t *image_sums, uint16_t *planes /* or NULL */, int out_kind);
+/* Device time of the last cs_label_granularity: clearing + the working planes, the erosions with their reconstructions, and the
+ * sums passes (steps + 1 of them). */
+int cs_label_granularity_last_timing(const cs_preproc *p, double *prepare_ms, double *steps_ms, double *sums_ms);
+/* The reconstruction rounds of the last cs_label_granularity, all steps together, and its reads of the control word (one host
+ * synchronisation each); either pointer may be NULL. */
+int cs_label_granularity_last_rounds(const cs_preproc *p, int32_t *rounds, int32_t *reads);
 
 /* ---- detector fitting (create_anomaly_detector, CAE_improved_modeltrain.py:394-446) -------- */
 /* The fit of what cs_screen's tail evaluates, for the training set's encoder features
