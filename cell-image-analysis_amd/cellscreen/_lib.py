@@ -160,6 +160,14 @@ class CSGranularityParams(C.Structure):
     _fields_ = [("steps", C.c_int32), ("subsample", C.c_int32), ("masked", C.c_int32), ("reserved", C.c_int32)]
 
 
+class CSPropagateParams(C.Structure):
+    _fields_ = [("metric", C.c_int32), ("lam", C.c_int32), ("guide_channel", C.c_int32), ("reserved", C.c_int32), ("max_cost", C.c_int64)]
+
+
+PROPAGATE_CITYBLOCK, PROPAGATE_CHESSBOARD, PROPAGATE_CHAMFER = 0, 1, 2      # cs_propagate_params.metric
+PROPAGATE_NO_LIMIT = (1 << 40) - 2      # cs_propagate_params.max_cost: no limit
+
+
 SMOOTH_MAX_RADIUS = 64                # cs_smooth_params.weights holds 65 taps
 
 
@@ -263,6 +271,8 @@ SIGNATURES = {
                                   _P, _P, _P, _P, _I]),
     "cs_label_granularity_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "cs_label_granularity_last_rounds": (_I, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "cs_label_propagate": (_I, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _I, _P, _P, C.c_int32, _I, C.POINTER(CSPropagateParams), _P, _P, _I]),
+    "cs_label_propagate_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     "cs_fit_create": (_I, [_I, C.POINTER(_P)]),
     "cs_fit_free": (None, [_P]),
     "cs_fit_wait_stream": (_I, [_P, _P]),

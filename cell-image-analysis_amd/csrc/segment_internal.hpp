@@ -42,7 +42,11 @@ struct SegmentState {
     // cs_label_granularity (granularity.hip) shares img, lab, parent, stage and ctrl in the same way and has no buffer of its own: the
     // working plane P in dq, the erosion E in rec, the reconstruction R in key, uint16 [B][C][Hs][Ws] each, and in ttop an int per
     // reconstruction tile: the round in which it last changed.
-    StageClock clk_thr, clk_sp, clk_si, clk_bg, clk_lt, clk_cl, clk_sm, clk_hy, clk_ns, clk_ex, clk_in, clk_lq, clk_tx, clk_sh, clk_nb, clk_co, clk_ra, clk_gr, clk_gs;   // clk_gs: one sums pass of cs_label_granularity at a time
+    // cs_label_propagate (propagate.hip) has no buffer of its own: the 64-bit keys in key, the open plane in mask, the guide's channel
+    // as a planar uint16 in dq, an int per tile in ttop (the round in which it last changed), its control words in ctrl; a host
+    // image's seeds and the labels on their way back in lab, a host mask in parent, a host guide in img, a host cost plane in stage.
+    StageClock clk_thr, clk_sp, clk_si, clk_bg, clk_lt, clk_cl, clk_sm, clk_hy, clk_ns, clk_ex, clk_in, clk_lq, clk_tx, clk_sh, clk_nb, clk_co, clk_ra, clk_gr, clk_gs, clk_pg;   // clk_gs: one sums pass of cs_label_granularity at a time
+    int pg_rounds = 0;                                  // cs_label_propagate's last call: its rounds, the closing quiet one included
     double gr_ms[3] = {0.0, 0.0, 0.0};                  // cs_label_granularity's last call: prepare, erosions + reconstructions, sums
     int gr_rounds = 0, gr_reads = 0;                    // its reconstruction rounds (all steps) and control-word reads
     int sp_recon_reads = 0, sp_flood_reads = 0;         // control-word reads (one host synchronisation each) of the last split of either kind

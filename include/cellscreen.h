@@ -73,6 +73,10 @@
  *        the size spectrum of the bright structures inside the same objects: per spectrum step a grey-level erosion and
  *        a reconstruction by dilation of the whole plane, and per object, step and channel the sum of the reconstructed
  *        plane, as exact integers (CellProfiler's MeasureGranularity; no reference counterpart)
+ *   cs_label_propagate
+ *        grows the seeds of a label image inside a mask along the cheapest paths of an integer cost, geometric plus the
+ *        differences of a guide stain: whole cells from nuclei (CellProfiler's IdentifySecondaryObjects "Propagation",
+ *        skimage.segmentation.watershed with markers and a mask; no reference counterpart)
  *   cs_fit_scaler / cs_fit_pca_moments / cs_fit_pca_subspace / cs_fit_project / cs_fit_ocsvm
  *        RobustScaler / PCA / OneClassSVM fits of create_anomaly_detector
  *                                                 CAE_improved_modeltrain.py:408-427
@@ -1182,6 +1186,57 @@ int cs_label_granularity_last_timing(const cs_preproc *p, double *prepare_ms, do
 /* The reconstruction rounds of the last cs_label_granularity, all steps together, and its reads of the control word (one host
  * synchronisation each); either pointer may be NULL. */
 int cs_label_granularity_last_rounds(const cs_preproc *p, int32_t *rounds, int32_t *reads);
+
+/* ---- growing labels inside a mask by geodesic cost ------------------------------------------------------- */
+/* The seeds of a label image grow inside a mask along the cheapest paths (tests/propagate_reference.py restates the
+ * rule): CellProfiler's IdentifySecondaryObjects "Propagation" / "Watershed - Image", skimage.segmentation.watershed(guide, markers,
+ * mask=) with an explicit cost.  All integers, per image of the batch:
+ *   A seed pixel (seeds > 0) is a source: cost 0, it keeps its label whatever the mask says, is never relabelled and is never
+ *   entered by a path.  A path starts at a seed pixel and then moves only through pixels that are no seed and whose mask is
+ *   non-zero, to 4- or 8-neighbours inside the image.  A step q -> p costs lam * w + |g(p) - g(q)|: w by the metric
+ *   (CS_PROPAGATE_CITYBLOCK: 1, 4-neighbours; _CHESSBOARD: 1, 8-neighbours; _CHAMFER: 5 axial and 7 diagonal, 8-neighbours), g
+ *   the guide's channel (the term is 0 without a guide).  A candidate whose cost exceeds max_cost is not taken.  The key of a
+ *   pixel is the lexicographic minimum over all such paths of (cost, label of the path's seed): the smallest cost, and among the
+ *   labels that reach it at that cost the smallest.  A pixel that no path reaches keeps label 0 and cost -1.
+ * Deliberate differences from CellProfiler's Propagation: the geometric and the intensity term add (there: under a square root);
+ * the intensity term is the difference of two pixels (there: of 3 x 3 neighbourhoods); lam >= 1, so there is no pure-intensity
+ * limit; a tie goes to the smallest label.
+ * seeds:  [batch][height][width] int32, in_kind, 0 = background, labels 1..2^20.  Left on the device by cs_segment_* on this handle
+ *         they are read in stream order.  A negative seed or one above 2^20 is CS_ERR_INVALID, detected on the device before it
+ *         is a key and reported by this call; `out` is then undefined and the handle stays usable.  height, width 1..4096, batch
+ *         1..65535, and batch * height * width * 8 bytes of keys at most 1 GiB (above: CS_ERR_UNSUPPORTED, split the batch).
+ * mask:   NULL (everywhere), or [batch][height][width] uint8 where `seeds` is, non-zero = may be grown into.
+ * guide:  NULL, or [batch][height][width][guide_channels] of guide_pixel_type (CS_PIX_U8 / CS_PIX_U16) where `seeds` is,
+ *         guide_channels 1..4, cs_label_intensity's layout; params->guide_channel picks the channel.  Without a guide
+ *         guide_channels and guide_pixel_type are not read and guide_channel must be 0.
+ * params: not NULL; lam 1..255, max_cost 1..CS_PROPAGATE_NO_LIMIT (CS_PROPAGATE_NO_LIMIT = 2^40 - 2: no limit), reserved 0.
+ * out:    [batch][height][width] int32, out_kind; may be `seeds` itself.
+ * cost:   NULL, or [batch][height][width] int64 where `out` is: 0 on seeds, the cost where a path reached, -1 elsewhere.
+ * The keys are the least fixed point of K(p) = min(K(p), min over q of K(q) + step(q, p)); the device relaxes 64 x 16 tiles in
+ * rounds until a round changes nothing, only the tiles at the moving front after the first round, at most height * width rounds
+ * that change something: reaching that cap is CS_ERR_UNSUPPORTED, never an endless loop.  The cost of a call grows with the winding
+ * of the mask, one round per tile crossing.  No floating point, atomics only on the control words: the result is bit-identical
+ * run to run and nothing crosses between the images of a batch.  Scratch (8 + 1 bytes per pixel, 2 more with a guide, 4 per tile,
+ * and the uploads of host planes) comes from the buffers the handle's segmenter stages share.  One host synchronisation per group
+ * of rounds (8, 16, 32, then 64 rounds).  Other bad arguments: CS_ERR_INVALID before any device work; without a gfx950 device
+ * (p == NULL): CS_ERR_NO_DEVICE. */
+#define CS_PROPAGATE_CITYBLOCK 0
+#define CS_PROPAGATE_CHESSBOARD 1
+#define CS_PROPAGATE_CHAMFER 2
+#define CS_PROPAGATE_NO_LIMIT 1099511627774LL
+typedef struct cs_propagate_params {
+    int32_t metric;                   /* CS_PROPAGATE_* */
+    int32_t lam;                      /* 1..255 */
+    int32_t guide_channel;            /* 0..guide_channels - 1; 0 without a guide */
+    int32_t reserved;                 /* must be 0 */
+    int64_t max_cost;                 /* 1..CS_PROPAGATE_NO_LIMIT */
+} cs_propagate_params;
+int cs_label_propagate(cs_preproc *p, const int32_t *seeds, int32_t batch, int32_t height, int32_t width, int in_kind,
+                       const uint8_t *mask /* or NULL */, const void *guide /* or NULL */, int32_t guide_channels, int guide_pixel_type,
+                       const cs_propagate_params *params, int32_t *out, int64_t *cost /* or NULL */, int out_kind);
+/* Device time of the last cs_label_propagate: clearing + the key plane, the rounds, and the labels' pass; and the number of rounds
+ * (the closing quiet one included).  Any pointer may be NULL. */
+int cs_label_propagate_last_timing(const cs_preproc *p, double *init_ms, double *relax_ms, double *finish_ms, int32_t *rounds);
 
 /* ---- detector fitting (create_anomaly_detector, CAE_improved_modeltrain.py:394-446) -------- */
 /* The fit of what cs_screen's tail evaluates, for the training set's encoder features
