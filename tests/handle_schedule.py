@@ -2,8 +2,8 @@
 tests/test_gpu_shared_handle.py, and the CPU restatement of every call in it.  Nothing here touches a device.
 
   ACTORS     the tools that share one SegmentState: two split segmenters (the second with smoothing and background correction, so
-             that the median, smoothing and top-hat planes are dirty too), the label expander, the eight measurers, the matcher and
-             the cell extractor, each with cheap but non-default parameters
+             that the median, smoothing and top-hat planes are dirty too), the label expander, the eight measurers, the matcher,
+             the cell extractor and the propagator, each with cheap but non-default parameters
   circuit    an Eulerian circuit of the complete directed graph on n vertices: n (n - 1) + 1 stops, every ordered pair of
              different vertices adjacent exactly once
   schedule   the circuit on the actors as (actor, input, on_device, exclude) steps; every actor has a counter of its own that
@@ -23,13 +23,14 @@ import intensity_reference as IR
 import match_reference as MA
 import neighbors_reference as NB
 import pipeline_reference as P
+import propagate_reference as PG
 import quantile_reference as QR
 import radial_reference as RR
 import shape_reference as SH
 import texture_reference as TR
 
 ACTORS = ("split", "split_intensity", "expand", "intensity", "quantiles", "texture", "shape", "neighbors", "colocalize", "radial",
-          "granularity", "match", "extract")
+          "granularity", "match", "extract", "propagate")
 SEGMENTERS = {"split": dict(split_touching=True, split_h=2, connectivity=2, fill_holes=False),
               "split_intensity": dict(split_touching=True, split_by="intensity", split_depth=24, smooth_sigma=1.0, denoise=True,
                                       background_radius=9)}
@@ -39,6 +40,7 @@ INPUTS = ((2, 130, 520), (1, 33, 67), (1, 64, 256))
 DTYPES = (np.uint16, np.uint8, np.uint16)
 EXPAND_DISTANCE, QUANTILES, TEXTURE, NEIGHBOR_D2 = 4, ((1, 10), (1, 2)), (2, 8), 25         # TEXTURE: distance, levels
 COLOC_THRESHOLD, RADIAL_BINS, GRANULARITY = (20, 50), 3, (4, 2)                             # GRANULARITY: steps, subsample
+PROPAGATE = dict(metric="cityblock", lam=2, guide_channel=1)          # and a max_cost per input: inputs_of()["max_cost"]
 
 
 def circuit(n):
@@ -72,7 +74,9 @@ def schedule():
 def inputs_of(k):
     """One input: image [B,H,W,2] of DTYPES[k] (uniform noise, bright on the objects in channel 0), labels int32 [B,H,W] (random
     disks, the images different), exclude int32 [B,H,W] (smaller disks from other seeds), truth (the labels shifted), centres of
-    the radial measurer int32 [B,max_label,2], and the largest label."""
+    the radial measurer int32 [B,max_label,2], and the largest label; for the propagator seeds (the labels eroded three times by the
+    4-neighbourhood: the few pixels of an object three steps inside it, none of a small one), mask (labels > 0 dilated by three
+    such steps) and max_cost (about four of the guide's noise steps, so that part of the mask stays unreached)."""
     B, H, W = INPUTS[k]
     dtype = DTYPES[k]
     top = int(np.iinfo(dtype).max)
@@ -84,10 +88,24 @@ def inputs_of(k):
     m = int(labels.max())
     rng = np.random.default_rng(90 + k)
     centers = np.stack([rng.integers(0, H, (B, m)), rng.integers(0, W, (B, m))], axis=-1).astype(np.int32)
-    for a in (image, labels, exclude, truth, centers):
+    seeds = labels
+    for _ in range(3):
+        seeds = np.where(_all_neighbours(seeds, lambda q, s=seeds: q == s), seeds, 0).astype(np.int32)
+    mask = labels > 0
+    for _ in range(3):
+        mask = ~_all_neighbours(mask, lambda q: ~q)
+    mask = mask.astype(np.uint8)
+    for a in (image, labels, exclude, truth, centers, seeds, mask):
         a.setflags(write=False)
     return dict(image=image, labels=labels, exclude=exclude, truth=truth, centers=centers, max_label=m,
-                plane=np.ascontiguousarray(image[..., 0]))
+                plane=np.ascontiguousarray(image[..., 0]), seeds=seeds, mask=mask, max_cost=top // 4 + 1)
+
+
+def _all_neighbours(a, pred):
+    """[B,H,W] bool: pred holds of all four neighbours of a pixel of the stack a; outside the image the plane repeats its edge."""
+    p = np.pad(a, ((0, 0), (1, 1), (1, 1)), mode="edge")
+    H, W = a.shape[1:]
+    return pred(p[:, :H, 1:W + 1]) & pred(p[:, 2:, 1:W + 1]) & pred(p[:, 1:H + 1, :W]) & pred(p[:, 1:H + 1, 2:])
 
 
 @functools.lru_cache(maxsize=None)
@@ -126,6 +144,8 @@ def expected(actor, k, exclude=False):
             status.append(st)
             rows += [(b,) + tuple(int(r[f]) for f in EXTRACT_FIELDS) for r in regs]
         return np.array(status, np.int32), np.array(rows, np.int64).reshape(len(rows), 1 + len(EXTRACT_FIELDS))
+    if actor == "propagate":
+        return PG.propagate(x["seeds"], x["mask"], image, max_cost=x["max_cost"], **PROPAGATE)
     raise KeyError(actor)
 
 

@@ -19,6 +19,7 @@ from cellscreen import extract as X
 from cellscreen import granularity as GR
 from cellscreen import intensity as IN
 from cellscreen import neighbors as NB
+from cellscreen import propagate as PG
 from cellscreen import quantile as QU
 from cellscreen import radial as RA
 from cellscreen import score as SC
@@ -39,7 +40,8 @@ def tools():
                 quantiles=QU.QuantileMeasurer(0, extractor=seg), texture=TX.TextureMeasurer(0, extractor=seg),
                 shape=SH.ShapeMeasurer(0, extractor=seg), neighbors=NB.NeighborMeasurer(0, extractor=seg),
                 colocalize=CO.ColocalizationMeasurer(0, extractor=seg), radial=RA.RadialMeasurer(0, extractor=seg),
-                granularity=GR.GranularityMeasurer(0, extractor=seg), match=SC.LabelMatcher(0, extractor=seg), extract=ext)
+                granularity=GR.GranularityMeasurer(0, extractor=seg), match=SC.LabelMatcher(0, extractor=seg), extract=ext,
+                propagate=PG.LabelPropagator(0, extractor=seg))
     assert set(made) == set(HS.ACTORS) and all(t._handle is ext._handle for t in made.values())
     yield made
     assert all(t._pre is None for name, t in made.items() if name != "extract")   # nobody made a handle of its own
@@ -73,7 +75,7 @@ def on(k, name, on_device):
 
 def call(tools, actor, k, on_device=False, exclude=False, labels=None, max_label=None):
     """One call of one actor on input k, its integer tables in the order of handle_schedule.expected.  labels, max_label: in the
-    input's place, for the calls that must fail."""
+    input's place, for the calls that must fail (the propagator takes `labels` as its seeds)."""
     t = tools[actor]
     image = on(k, "image", on_device)
     lab = on(k, "labels", on_device) if labels is None else labels
@@ -102,6 +104,9 @@ def call(tools, actor, k, on_device=False, exclude=False, labels=None, max_label
     elif actor == "match":
         m = t.match_batch(lab, on(k, "truth", on_device), max_pred=max_label)
         out = m.pred, m.truth, m.n_pairs
+    elif actor == "propagate":
+        out = t.propagate_batch(on(k, "seeds", on_device) if labels is None else labels, mask=on(k, "mask", on_device), guide=image,
+                                max_cost=HS.inputs_of(k)["max_cost"], return_cost=True, **HS.PROPAGATE)
     else:
         r = t.extract_batch(on(k, "plane", on_device), lab)
         reg = r.regions
@@ -135,20 +140,24 @@ def test_every_tool_behind_every_other_on_one_handle(tools):
 
 
 def test_a_refused_call_leaks_nothing_into_the_next_tool(tools):
-    """Every tool that range-checks its labels is handed one label above max_label and refuses it with status -1; the very next
-    call goes to another of the tools that share its status words (the control buffer), with good input."""
+    """Every tool that range-checks its labels is handed one label above max_label and refuses it with status -1, and the
+    propagator one seed above the largest label there is; the very next call goes to another of the tools that share its status
+    words (the control buffer), with good input."""
     k = 1
     x = HS.inputs_of(k)
     m = x["max_label"]
     bad = x["labels"].copy()
     bad[0, 20, 40] = m + 1
-    nexts = HS.RANGE_CHECKED + ("expand",) + tuple(HS.SEGMENTERS)        # all of them keep their status words in ctrl
-    for n, failing in enumerate(HS.RANGE_CHECKED):
+    bad_seed = x["seeds"].copy()
+    bad_seed[0, 20, 40] = PG.MAX_LABEL + 1
+    nexts = HS.RANGE_CHECKED + ("expand", "propagate") + tuple(HS.SEGMENTERS)        # all of them keep their status words in ctrl
+    for n, failing in enumerate(HS.RANGE_CHECKED + ("propagate",)):
+        wrong, text = (bad_seed, "a seed is negative or exceeds") if failing == "propagate" else (bad, "exceeds max_")
         for j, after in enumerate(a for a in nexts if a != failing):
             on_device = bool((n + j) % 2)
             with pytest.raises(L.CellScreenError) as ei:
-                call(tools, failing, k, on_device, labels=as_tensor(bad) if on_device else bad, max_label=m)
-            assert ei.value.status == -1 and "exceeds max_" in str(ei.value), (failing, str(ei.value))
+                call(tools, failing, k, on_device, labels=as_tensor(wrong) if on_device else wrong, max_label=m)
+            assert ei.value.status == -1 and text in str(ei.value), (failing, str(ei.value))
             exclude = after in HS.HAS_EXCLUDE and bool(j % 2)
             same(call(tools, after, k, not on_device, exclude), HS.expected(after, k, exclude), f"{after} behind a refused {failing}")
     # and once on the large input, where the refused call has written most before it is found out
@@ -163,7 +172,8 @@ def test_a_refused_call_leaks_nothing_into_the_next_tool(tools):
 def test_pair_list_survives_other_stages(tools):
     """cs_label_neighbors leaves its sorted pair list on the handle "until cs_label_neighbors_pairs copies it out, whatever other
     stage runs between": here a split segmentation, the granularity spectrum and the radial distribution, which use the same
-    buffers as the pair table for their own planes and keys, run between the two calls."""
+    buffers as the pair table for their own planes and keys, and a propagation, which writes the key, queue and mask planes, run
+    between the two calls."""
     lib, h = tools["neighbors"]._lib, tools["neighbors"]._handle
     for k in (2, 0):
         x = HS.inputs_of(k)
@@ -177,7 +187,8 @@ def test_pair_list_survives_other_stages(tools):
         assert lib.cs_label_neighbors(h, lab.ctypes.data, B, H, W, L.CS_MEM_HOST, m, C.byref(prm), geom.ctypes.data, objects.ctypes.data,
                                       offsets.ctypes.data, L.CS_MEM_HOST, C.byref(n)) == 0
         assert n.value == len(want[3]) > 0
-        for actor, kk in (("split", 0), ("granularity", 0), ("radial", 0), ("split_intensity", 1), ("granularity", 1)):
+        for actor, kk in (("split", 0), ("granularity", 0), ("propagate", 0), ("radial", 0), ("split_intensity", 1), ("propagate", 1),
+                          ("granularity", 1)):
             exclude = actor in HS.HAS_EXCLUDE
             same(call(tools, actor, kk, False, exclude), HS.expected(actor, kk, exclude), f"{actor} between the two calls")
         pairs = np.full((n.value, 3), -1, np.int32)

@@ -38,6 +38,13 @@ def test_inputs_are_what_the_tools_accept():
             assert x[name].shape == (B, H, W) and x[name].dtype == np.int32 and x[name].min() == 0
         assert x["max_label"] == x["labels"].max() >= 3 and x["centers"].shape == (B, x["max_label"], 2)
         assert ((x["exclude"] > 0) & (x["labels"] > 0)).any() and (x["truth"] != x["labels"]).any()
+        seeds, mask = x["seeds"], x["mask"]                             # the propagator's: a few pixels inside the objects, a wider mask
+        assert seeds.dtype == np.int32 and mask.dtype == np.uint8 and seeds.shape == mask.shape == (B, H, W)
+        assert 0 < (seeds > 0).sum() < (x["labels"] > 0).sum() // 3 and len(np.unique(seeds)) > 3
+        assert np.array_equal(seeds[seeds > 0], x["labels"][seeds > 0])
+        assert mask[x["labels"] > 0].all() and mask.sum() > (x["labels"] > 0).sum()
+        grown, cost = HS.expected("propagate", k)
+        assert (grown > 0).sum() > 2 * (seeds > 0).sum() and ((mask > 0) & (grown == 0)).any() and cost.max() <= x["max_cost"]
     for name, kw in HS.SEGMENTERS.items():
         n = HS.expected(name, 1)[1]
         assert (n >= 2).all(), (name, n)
