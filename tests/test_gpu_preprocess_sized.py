@@ -144,10 +144,13 @@ def test_ratio_rule_accepts_sixteen_and_refuses_beyond():
         for i, c in enumerate(ok):
             err = np.abs(out[i].astype(np.float64) - PR.preprocess_crop(c, (8, 8))).max()
             assert err <= TOL_OUT, f"{c.shape} -> (8, 8): {err:.3e}"
-        c = synth.raw_crops(9, 1, np.uint16, 512, 512)[0]
-        wide = np.ascontiguousarray(np.tile(c, (1, 2)))                 # 512 x 1024 = (16 x 32, 16 x 64)
-        assert wide.shape == (512, 1024)
-        err = np.abs(q([wide])[0].astype(np.float64) - PR.preprocess_crop(wide, (32, 64))).max()
+        # 512 x 1024 = (16 x 32, 16 x 64): two different blob crops side by side under noise, so that no half repeats the other
+        a, b = synth.raw_crops(9, 2, np.uint16, 512, 512)
+        wide = np.concatenate([a, b], axis=1) // 2 + rng.integers(0, 32768, (512, 1024)).astype(np.uint16)
+        assert wide.shape == (512, 1024) and wide.dtype == np.uint16 and not np.array_equal(wide[:, :512], wide[:, 512:])
+        out, cl = _run(q, [wide])
+        assert np.array_equal(cl[0], po.clahe_u16(wide)), "CLAHE stage of the 512 x 1024 crop is not bit-exact"
+        err = np.abs(out[0].astype(np.float64) - PR.preprocess_crop(wide, (32, 64))).max()
         assert err <= TOL_OUT, f"(512, 1024) -> (32, 64): {err:.3e}"
         # one more pixel on either axis: CS_ERR_UNSUPPORTED naming the crop, the side and the output size; nothing written
         for proc, shape, hw in ((p, (129, 20), (8, 8)), (p, (20, 129), (8, 8)), (q, (513, 64), (32, 64))):
