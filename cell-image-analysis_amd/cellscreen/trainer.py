@@ -98,20 +98,42 @@ class Trainer:
         except Exception:
             pass
 
-    def _buf(self, a):
+    def _buf(self, a, name="x"):
+        """(array kept alive, address, memory kind, n) of a batch [n, H, W] or [n, H, W, 1] of this trainer's crops: a numpy array of
+        any real dtype (converted to float32) or a float32 CUDA tensor on the trainer's device (made contiguous).  The library
+        receives a bare pointer and n: a batch of another H x W, another dtype or another device would be read -- and by
+        cs_train_augment written -- out of range, so it is refused here, before any library call."""
+        shape = tuple(getattr(a, "shape", ()))
+        h, w = self.input_hw
+        if len(shape) not in (3, 4) or shape[1:3] != (h, w) or (len(shape) == 4 and shape[3] != 1):
+            raise ValueError(f"{name} must be [n, {h}, {w}] or [n, {h}, {w}, 1] (this trainer's crops), got shape {shape}")
         if isinstance(a, np.ndarray):
+            if a.dtype.kind not in "buif":
+                raise ValueError(f"{name} must be a numpy array of a real dtype, got {a.dtype}")
             a = np.ascontiguousarray(a, dtype=np.float32)
-            return a, a.ctypes.data, L.CS_MEM_HOST, a.shape[0]
+            return a, a.ctypes.data, L.CS_MEM_HOST, shape[0]
+        if not getattr(a, "is_cuda", False) or a.device.index != self._device_id:
+            raise ValueError(f"{name} must be a numpy array or a CUDA tensor on this trainer's device cuda:{self._device_id}")
+        if str(a.dtype) != "torch.float32":
+            raise ValueError(f"{name} must be a float32 CUDA tensor, got {a.dtype}")
         if not a.is_contiguous():
             a = a.contiguous()
-        L.order_after_torch(self._lib.cs_train_wait_stream, self._h, a)    # the batch may still be being gathered on torch's stream
-        return a, a.data_ptr(), L.mem_kind(a), a.shape[0]
+        return a, a.data_ptr(), L.CS_MEM_DEVICE, shape[0]
+
+    def _pair(self, x, y):
+        """_buf of an (input, target) pair, which must agree in n and in kind (both numpy, or both CUDA tensors)."""
+        xb, xp, kind, n = self._buf(x, "x")
+        yb, yp, kind2, n2 = self._buf(y, "y")
+        if n != n2:
+            raise ValueError(f"x and y must hold the same number of crops, got {n} and {n2}")
+        if kind != kind2:
+            raise ValueError("x and y must both be numpy arrays or both be CUDA tensors")
+        L.order_after_torch(self._lib.cs_train_wait_stream, self._h, xb, yb)    # the batch may still be being gathered on torch's stream
+        return xb, xp, yb, yp, kind, n
 
     def step(self, x, y, lr: float = spec.ADAM_LR) -> Tuple[float, float]:
         """forward + backward + Adam on one batch; returns (loss, mae) of the batch."""
-        xb, xp, kind, n = self._buf(x)
-        yb, yp, kind2, n2 = self._buf(y)
-        assert kind == kind2 and n == n2
+        xb, xp, yb, yp, kind, n = self._pair(x, y)
         loss, mae = C.c_float(), C.c_float()
         L.check(self._lib.cs_train_step(self._h, xp, yp, n, kind, lr, C.byref(loss), C.byref(mae)))
         return loss.value, mae.value
@@ -119,9 +141,7 @@ class Trainer:
     def step_async(self, x, y, lr: float = spec.ADAM_LR) -> None:
         """cs_train_step_async: the same batch enqueued without a host synchronisation; its loss / mae go into the running
         sums read_metrics() returns (Keras's epoch metrics: the mean over the epoch's batches)."""
-        xb, xp, kind, n = self._buf(x)
-        yb, yp, kind2, n2 = self._buf(y)
-        assert kind == kind2 and n == n2
+        xb, xp, yb, yp, kind, n = self._pair(x, y)
         L.check(self._lib.cs_train_step_async(self._h, xp, yp, n, kind, lr))
         L.order_torch_after(self._lib.cs_train_inputs_consumed, self._h, xb, yb)    # torch may reuse the batch's memory only after the copies
 
@@ -155,9 +175,7 @@ class Trainer:
         self.read_metrics(reset=True)
 
     def forward_backward(self, x, y) -> Tuple[float, float]:
-        xb, xp, kind, n = self._buf(x)
-        yb, yp, kind2, n2 = self._buf(y)
-        assert kind == kind2 and n == n2
+        xb, xp, yb, yp, kind, n = self._pair(x, y)
         loss, mae = C.c_float(), C.c_float()
         try:
             L.check(self._lib.cs_train_forward_backward(self._h, xp, yp, n, kind, C.byref(loss), C.byref(mae)))
@@ -170,10 +188,21 @@ class Trainer:
         return loss.value, mae.value
 
     def augment(self, x, transforms):
-        """cs_train_augment: x [n,64,64] (numpy or torch CUDA), transforms = (CSAugAffine * n) built by
-        cellscreen.augment.ImageDataGenerator.pack.  Returns a new array / tensor of the same kind."""
-        xb, xp, kind, n = self._buf(x)
-        assert len(transforms) == n
+        """cs_train_augment: x [n, H, W] of this trainer's input_hw (numpy or torch CUDA, as _buf accepts them), transforms = the
+        batch's n cs_aug_affine: (CSAugAffine * n) built by cellscreen.augment.ImageDataGenerator.pack, or a C-contiguous numpy
+        array of ImageDataGenerator.AFFINE_DTYPE (random_transforms / keyed_transforms).  Returns a new array / tensor of the
+        same kind."""
+        from .augment import ImageDataGenerator
+        xb, xp, kind, n = self._buf(x, "x")
+        # the library reads n records of 64 bytes from a bare pointer
+        if isinstance(transforms, np.ndarray):
+            if transforms.dtype != ImageDataGenerator.AFFINE_DTYPE or transforms.ndim != 1 or not transforms.flags["C_CONTIGUOUS"]:
+                raise ValueError("transforms must be a C-contiguous 1-D numpy array of ImageDataGenerator.AFFINE_DTYPE, "
+                                 f"got dtype {transforms.dtype}, shape {transforms.shape}")
+        elif not (isinstance(transforms, C.Array) and transforms._type_ is L.CSAugAffine):
+            raise ValueError(f"transforms must be a ctypes array of CSAugAffine or a numpy array of AFFINE_DTYPE, got {type(transforms)}")
+        if len(transforms) != n:
+            raise ValueError(f"transforms must hold one record per crop: {len(transforms)} for {n} crops")
         if kind == L.CS_MEM_HOST:
             out = np.empty_like(xb)
             op = out.ctypes.data
@@ -181,7 +210,7 @@ class Trainer:
             import torch
             out = torch.empty_like(xb)
             op = out.data_ptr()
-            L.order_after_torch(self._lib.cs_train_wait_stream, self._h, out)
+            L.order_after_torch(self._lib.cs_train_wait_stream, self._h, xb, out)    # x may still be being gathered on torch's stream
         tp = C.c_void_p(transforms.ctypes.data) if isinstance(transforms, np.ndarray) else C.cast(transforms, C.c_void_p)
         L.check(self._lib.cs_train_augment(self._h, xp, n, tp, op, kind))
         L.order_torch_after(self._lib.cs_train_inputs_consumed, self._h, out if kind != L.CS_MEM_HOST else None)   # device output: torch reads it after the kernel
@@ -271,17 +300,16 @@ class Trainer:
         L.check(self._lib.cs_train_set_grad_buffer(self._h, t.data_ptr()))
 
     def evaluate(self, x, y) -> Tuple[float, float]:
-        xb, xp, kind, n = self._buf(x)
-        yb, yp, kind2, n2 = self._buf(y)
-        assert kind == kind2 and n == n2
+        xb, xp, yb, yp, kind, n = self._pair(x, y)
         loss, mae = C.c_float(), C.c_float()
         L.check(self._lib.cs_train_eval(self._h, xp, yp, n, kind, C.byref(loss), C.byref(mae)))
         return loss.value, mae.value
 
     def tensor(self, which: int, layer: int, batch: int) -> np.ndarray:
-        """Stage tap (parity tests): which 0 relu out, 1 BN out, 2 dz, 3 dBN-out, 4 sigmoid out."""
+        """Stage tap (parity tests): which 0 relu out, 1 BN out, 2 dz, 3 dBN-out, 4 sigmoid out, 5 the step's input, 6 the step's
+        target (5 and 6: layer 0, shape (batch,) + input_hw -- after fit_step, what it gathered and resampled)."""
         rows = spec.layer_table(self.input_hw, self.channels, self.n_enc)
-        if which == 4 or (which == 2 and layer == len(self.channels) - 1):
+        if which in (4, 5, 6) or (which == 2 and layer == len(self.channels) - 1):
             shape = (batch,) + self.input_hw
         elif which in (0, 2):
             shape = (batch,) + rows[layer]["conv_hw"] + (rows[layer]["cout"],)

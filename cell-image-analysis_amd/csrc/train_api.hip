@@ -750,6 +750,8 @@ int cs_train_tensor(cs_trainer* t, int which, int layer, int64_t batch, float* h
         case 2: b = &t->dz[layer]; per = layer < last ? t->rfl[layer] : npix; break;   // dL/dz
         case 3: if (layer < last) { b = &t->da[layer]; per = t->afl[layer]; } break;   // dL/d(BN output)
         case 4: b = &t->out; per = npix; break;                                         // sigmoid output
+        case 5: if (layer == 0) { b = &t->x; per = npix; } break;                       // the step's input (what cs_train_fit_step gathered + resampled)
+        case 6: if (layer == 0) { b = &t->y; per = npix; } break;                       // the step's target
         default: break;
     }
     if (!b) return fail(CS_ERR_INVALID, "no such tensor");

@@ -1431,7 +1431,9 @@ int cs_train_fit_step(cs_trainer *t, const float *train_device, int64_t n_train,
 /* Copies to host (each pointer may be NULL): trainable parameters, moving statistics, last gradients. */
 int cs_train_export(cs_trainer *t, float *params_host, float *moving_host, float *grads_host);
 /* Stage tap for parity tests: copies one tensor of the last forward_backward to host.
- * which: 0 relu(conv) output, 1 BN(+pool) output, 2 dL/dz, 3 dL/d(BN output), 4 sigmoid output. */
+ * which: 0 relu(conv) output, 1 BN(+pool) output, 2 dL/dz, 3 dL/d(BN output), 4 sigmoid output,
+ * 5 the step's input, 6 the step's target (both batch x H x W floats, layer must be 0: what the last step -- for
+ * cs_train_fit_step the gather and the resampling -- left in the handle's batch buffers).  Synchronises the handle's stream. */
 int cs_train_tensor(cs_trainer *t, int which, int layer, int64_t batch, float *host);
 /* Overwrites trainable parameters and/or moving statistics from host arrays (restore best weights). */
 int cs_train_import(cs_trainer *t, const float *params_host, const float *moving_host);

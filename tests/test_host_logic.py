@@ -327,3 +327,86 @@ def test_fit_step_refuses_a_training_set_it_would_read_out_of_range():
                   on(0, (8, 64, 64, 3)), on(0, (8, 32, 64, 1))):
         with pytest.raises(ValueError):
             t.fit_step(train, idx)
+
+
+def test_batch_entry_points_refuse_what_the_library_would_read_out_of_range():
+    """step, step_async, forward_backward, evaluate and augment hand the library a bare pointer and n = shape[0]: a batch of another
+    H x W, a CPU tensor, a CUDA tensor on another device or of another dtype, and a pair that differs in n or in kind are refused
+    with a ValueError naming the argument before any library call (a handle whose library records every call: none may arrive);
+    an accepted numpy call reaches it with the array's address, n and CS_MEM_HOST."""
+    import ctypes as C
+    import types
+    import torch
+    from cellscreen import _lib as L
+    from cellscreen.augment import ImageDataGenerator
+    from cellscreen.trainer import Trainer
+    hw = (8, 32)                                                   # H != W: (n, 32, 8) must not pass for (n, 8, 32)
+    calls = []
+
+    class Lib:
+        def __getattr__(self, name):
+            def fn(*a):
+                calls.append((name, a))
+                return 0
+            return fn
+    t = Trainer.__new__(Trainer)
+    t._lib, t._h, t._device_id, t.input_hw, t._sync_error = Lib(), None, 0, hw, None
+
+    def on(dev, shape, dtype=torch.float32):                       # what _buf looks at of a CUDA tensor
+        return types.SimpleNamespace(is_cuda=True, device=torch.device("cuda", dev), shape=shape, dtype=dtype, dim=lambda: len(shape),
+                                     is_contiguous=lambda: True, data_ptr=lambda: 0)
+    good = np.zeros((4,) + hw, np.float32)
+    tf4 = np.zeros(4, ImageDataGenerator.AFFINE_DTYPE)
+    bad = {"another H x W": np.zeros((4, 32, 8), np.float32), "square": np.zeros((4, 8, 8), np.float32),
+           "three channels": np.zeros((4,) + hw + (3,), np.float32), "one image": np.zeros(hw, np.float32),
+           "five axes": np.zeros((4,) + hw + (1, 1), np.float32), "complex": np.zeros((4,) + hw, np.complex64),
+           "objects": np.zeros((4,) + hw, object), "a list": [[0.0]],
+           "CPU tensor": torch.zeros((4,) + hw), "another device": on(1, (4,) + hw), "float64 CUDA": on(0, (4,) + hw, torch.float64),
+           "float16 CUDA": on(0, (4,) + hw, torch.float16), "CUDA of another H x W": on(0, (4, 32, 8)),
+           "CUDA with three channels": on(0, (4,) + hw + (3,))}
+    pairs = {"step": t.step, "step_async": t.step_async, "forward_backward": t.forward_backward, "evaluate": t.evaluate}
+    for what, b in bad.items():
+        for name, fn in pairs.items():
+            with pytest.raises(ValueError, match=r"\bx\b"):
+                fn(b, good)
+            with pytest.raises(ValueError, match=r"\by\b"):
+                fn(good, b)
+        with pytest.raises(ValueError, match=r"\bx\b"):
+            t.augment(b, tf4)
+    for name, fn in pairs.items():
+        with pytest.raises(ValueError, match="x and y"):           # n differs
+            fn(good, good[:3])
+        with pytest.raises(ValueError, match="x and y"):           # kind differs: the library takes ONE kind for both
+            fn(good, on(0, (4,) + hw))
+        with pytest.raises(ValueError, match="x and y"):
+            fn(on(0, (4,) + hw), good)
+    # augment's transforms: one 64-byte record per crop, from a bare pointer
+    for tf in (np.zeros(3, ImageDataGenerator.AFFINE_DTYPE), np.zeros(5, ImageDataGenerator.AFFINE_DTYPE), (L.CSAugAffine * 3)(),
+               np.zeros((4, 8), np.float64), np.zeros(4 * 64, np.uint8), np.zeros(8, ImageDataGenerator.AFFINE_DTYPE)[::2],
+               np.zeros((4, 1), ImageDataGenerator.AFFINE_DTYPE), (C.c_double * 32)(), [None] * 4, bytes(256)):
+        with pytest.raises(ValueError, match="transforms"):
+            t.augment(good, tf)
+    assert calls == [], calls
+    # accepted: numpy of any real dtype, [n, H, W] or [n, H, W, 1]; the library sees the float32 array's address, n and the kind
+    for name, fn in pairs.items():
+        calls.clear()
+        fn(good, good[..., None])
+        (cname, a), = [c for c in calls if c[0].startswith("cs_train_") and c[0] not in ("cs_train_inputs_consumed", "cs_train_wait_stream")]
+        assert a[1] == good.ctypes.data and a[2] == good.ctypes.data and a[3] == 4 and a[4] == L.CS_MEM_HOST, (name, cname, a)
+    for dt in (np.float64, np.uint8, np.int16, bool, np.float16):
+        calls.clear()
+        t.step(good.astype(dt), good)
+        assert calls[0][1][3] == 4 and calls[0][1][4] == L.CS_MEM_HOST
+    for tf in (tf4, (L.CSAugAffine * 4)()):
+        calls.clear()
+        out = t.augment(good, tf)
+        (cname, a), = calls
+        assert cname == "cs_train_augment" and a[1] == good.ctypes.data and a[2] == 4 and a[4] == out.ctypes.data and a[5] == L.CS_MEM_HOST
+        assert out.shape == good.shape and out.dtype == np.float32
+    calls.clear()
+    assert t.augment(good[:0], tf4[:0]).shape == (0,) + hw
+    # a float32 CUDA tensor on the trainer's device passes the checks (ordering the streams needs a GPU: the check alone here)
+    calls.clear()
+    for shape in ((4,) + hw, (4,) + hw + (1,)):
+        assert t._buf(on(0, shape), "x")[1:] == (0, L.CS_MEM_DEVICE, 4)
+    assert calls == []
