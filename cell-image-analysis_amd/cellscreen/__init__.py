@@ -8,6 +8,7 @@ from .granularity import GranularityMeasurer, GranularityTable, granularity_para
 from .intensity import IntensityMeasurer, ObjectTable  # noqa: F401
 from .neighbors import NeighborMeasurer, NeighborTable, neighbor_params, neighbor_table  # noqa: F401
 from .propagate import LabelPropagator, propagate_params  # noqa: F401
+from .quality import ImageQualityMeasurer, ImageQualityTable, ObjectFocusTable, image_quality_table, object_focus_table  # noqa: F401
 from .quantile import QuantileMeasurer, QuantileTable  # noqa: F401
 from .radial import RadialMeasurer, RadialTable, radial_params, radial_table  # noqa: F401
 from .shape import ShapeMeasurer, ShapeTable, shape_table  # noqa: F401
@@ -19,4 +20,5 @@ __all__ = ["spec", "CAEWeights", "DetectorParams", "OCSVMParams", "LabelExpander
            "ShapeMeasurer", "ShapeTable", "shape_table", "NeighborMeasurer", "NeighborTable", "neighbor_params", "neighbor_table",
            "ColocalizationMeasurer", "ColocalizationTable", "colocalization_table", "colocalize_params",
            "RadialMeasurer", "RadialTable", "radial_params", "radial_table",
-           "GranularityMeasurer", "GranularityTable", "granularity_params", "granularity_table", "LabelPropagator", "propagate_params"]
+           "GranularityMeasurer", "GranularityTable", "granularity_params", "granularity_table", "LabelPropagator", "propagate_params",
+           "ImageQualityMeasurer", "ImageQualityTable", "ObjectFocusTable", "image_quality_table", "object_focus_table"]

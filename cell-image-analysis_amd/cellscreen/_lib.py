@@ -273,6 +273,10 @@ SIGNATURES = {
     "cs_label_granularity_last_rounds": (_I, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "cs_label_propagate": (_I, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _I, _P, _P, C.c_int32, _I, C.POINTER(CSPropagateParams), _P, _P, _I]),
     "cs_label_propagate_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
+    "cs_image_quality": (_I, [_P, _P, _I, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _I, C.c_int32, _P, _P, _P, _I]),
+    "cs_image_quality_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "cs_object_focus": (_I, [_P, _P, _I, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _I, C.c_int32, _P, _P, _I]),
+    "cs_object_focus_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "cs_fit_create": (_I, [_I, C.POINTER(_P)]),
     "cs_fit_free": (None, [_P]),
     "cs_fit_wait_stream": (_I, [_P, _P]),

@@ -1,5 +1,5 @@
 // segment_internal.hpp -- the state behind cs_preproc::seg as its translation units share it (segment.hip, expand.hip,
-// intensity.hip, quantile.hip, texture.hip, shape.hip, neighbors.hip, colocalize.hip, radial.hip, granularity.hip): the shared buffers and a clock per family of entry points.  The clock itself and
+// intensity.hip, quantile.hip, texture.hip, shape.hip, neighbors.hip, colocalize.hip, radial.hip, granularity.hip, propagate.hip, quality.hip): the shared buffers and a clock per family of entry points.  The clock itself and
 // the argument rules are stage_host.hpp's, which extract.hip and match.hip use with states of their own.
 #pragma once
 #include "stage_host.hpp"
@@ -45,6 +45,10 @@ struct SegmentState {
     // cs_label_propagate (propagate.hip) has no buffer of its own: the 64-bit keys in key, the open plane in mask, the guide's channel
     // as a planar uint16 in dq, an int per tile in ttop (the round in which it last changed), its control words in ctrl; a host
     // image's seeds and the labels on their way back in lab, a host mask in parent, a host guide in img, a host cost plane in stage.
+    // cs_image_quality and cs_object_focus (quality.hip) have no buffer of their own: a host image in img, its labels in lab, its
+    // exclude plane in parent, the tables on their way to the host in stage, the status word in ctrl; the image pass keeps the
+    // workgroups' (extreme, count) partials in slab and, without a mesh, a tile of sums per workgroup and channel in hist.
+    StageClock clk_iq, clk_lf;
     StageClock clk_thr, clk_sp, clk_si, clk_bg, clk_lt, clk_cl, clk_sm, clk_hy, clk_ns, clk_ex, clk_in, clk_lq, clk_tx, clk_sh, clk_nb, clk_co, clk_ra, clk_gr, clk_gs, clk_pg;   // clk_gs: one sums pass of cs_label_granularity at a time
     int pg_rounds = 0;                                  // cs_label_propagate's last call: its rounds, the closing quiet one included
     double gr_ms[3] = {0.0, 0.0, 0.0};                  // cs_label_granularity's last call: prepare, erosions + reconstructions, sums

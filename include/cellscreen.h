@@ -38,6 +38,10 @@
  *        grows the objects of a label image outwards by a fixed distance, halfway to their neighbours at
  *        most: skimage.segmentation.expand_labels between a nuclear segmentation and the extraction
  *        (no reference counterpart)
+ *   cs_image_quality / cs_object_focus
+ *        whether an image, a mesh tile of it or an object is worth measuring: intensity, extreme and saturation counts and
+ *        the sums behind the Laplacian variance, Tenengrad and Brenner focus measures, as exact integers (CellProfiler's
+ *        MeasureImageQuality: FocusScore, LocalFocusScore, PercentMinimal / PercentMaximal; no reference counterpart)
  *   cs_label_intensity
  *        measures every object of a label image in every channel: area, centroid, integrated / mean / std /
  *        min / max intensity and the intensity-weighted centroid, as exact integer sums
@@ -1237,6 +1241,55 @@ int cs_label_propagate(cs_preproc *p, const int32_t *seeds, int32_t batch, int32
 /* Device time of the last cs_label_propagate: clearing + the key plane, the rounds, and the labels' pass; and the number of rounds
  * (the closing quiet one included).  Any pointer may be NULL. */
 int cs_label_propagate_last_timing(const cs_preproc *p, double *init_ms, double *relax_ms, double *finish_ms, int32_t *rounds);
+
+/* ---- image and per-object focus and saturation records ---------------------------------------------------- */
+/* Whether an image is worth measuring, as exact integer records (tests/quality_reference.py restates the rule,
+ * cellscreen/quality.py derives): CellProfiler's MeasureImageQuality.  Every channel x of an image [height][width] is measured on
+ * its own.  A pixel (r, c) is interior iff 1 <= r <= height - 2 and 1 <= c <= width - 2: there is no reflection and no padding, a
+ * pixel without a full 3 x 3 neighbourhood has no focus value, and an image with a side below 3 has n_int = 0.  At an interior pixel
+ *   L  = x[r-1][c] + x[r+1][c] + x[r][c-1] + x[r][c+1] - 4 x[r][c]       (scipy.ndimage.laplace, cv2.Laplacian(ksize=1))
+ *   G  = gx^2 + gy^2, gx and gy the 3 x 3 Sobel responses, weights 1-2-1 (Tenengrad; scipy.ndimage.sobel along each axis)
+ *   Br = (x[r][c+1] - x[r][c-1])^2 + (x[r+1][c] - x[r-1][c])^2           (Brenner's gradient, centred)
+ * image:  [batch][height][width][channels] uint8 / uint16 (pixel_type), in_kind, channels 1..4 (more: CS_ERR_UNSUPPORTED).
+ *         height, width 1..4096, batch 1..65535 (above: CS_ERR_UNSUPPORTED).
+ * tile:   0: no mesh, or 16..1024 (else CS_ERR_INVALID): a mesh of m_r = ceil(height / tile) by m_c = ceil(width / tile) tiles,
+ *         pixel (r, c) in tile ((r * m_r) / height, (c * m_c) / width) (integer division; CellProfiler's LocalFocusScore grid).
+ *         batch * channels * m_r * m_c above 2^20: CS_ERR_UNSUPPORTED.
+ * sat_level: NULL (the top of the pixel type: 255 / 65535), or [channels] int32 on the host, each 0..65536 (else CS_ERR_INVALID).
+ * records: out, [batch][channels][CS_QUALITY_RECORD] int64: n, sum v, sum v^2, min, max, n_at_min, n_at_max (the pixels equal to
+ *         the image's own minimum / maximum in that channel), n_sat (v >= sat_level), n_int, sum L, sum L^2, sum G, sum Br.
+ * mesh:   with tile > 0 out, [batch][channels][m_r][m_c][CS_QUALITY_TILE] int64: n, sum v, sum v^2, n_int, sum L, sum L^2, sum G,
+ *         sum Br of the tile's pixels; the stencil reads across tile borders, a pixel's values go to the tile that holds the pixel,
+ *         and the tile records of an image sum to its record.  With tile == 0 it is not written and may be NULL.  Both out_kind.
+ * At 4096 x 4096 uint16 sum L^2 <= (4 * 65535)^2 * 2^24 < 1.16e18 and sum G <= twice that, below 2^63.  No floating point and no
+ * float atomics: bit-identical run to run and independent of the other images of the batch.  Uploads, the tables on their way to
+ * the host and the workgroups' partial extremes go through the buffers the handle's segmenter stages share.  One host
+ * synchronisation per call.  Other bad arguments: CS_ERR_INVALID before any device work; without a gfx950 device (p == NULL):
+ * CS_ERR_NO_DEVICE. */
+#define CS_QUALITY_RECORD 13
+#define CS_QUALITY_TILE 8
+#define CS_QUALITY_FOCUS 5
+int cs_image_quality(cs_preproc *p, const void *image, int pixel_type, int32_t channels,
+                     int32_t batch, int32_t height, int32_t width, int in_kind, int32_t tile,
+                     const int32_t *sat_level /* or NULL */, int64_t *records, int64_t *mesh /* or NULL */, int out_kind);
+/* Device time of the last cs_image_quality: clearing the tables, and the pass with its closing step. */
+int cs_image_quality_last_timing(const cs_preproc *p, double *clear_ms, double *pass_ms);
+/* The same focus values per object of a label image.  The objects are cs_label_intensity's: the pixels of one image with one
+ * label > 0, connected or not, less the pixels where `exclude` is non-zero.  The stencil reads the image, not the labels, so the
+ * sharpness of an object's own edge counts; a pixel of an object has focus values iff it is interior to the IMAGE.
+ * image, pixel_type, channels 1..4, labels, exclude, in_kind, the sizes and max_label: as cs_label_intensity, a bad label included
+ *         (CS_ERR_INVALID "negative or exceeds max_label", detected on the device, never an index or a key; the handle stays usable).
+ * geom:   out, [batch][max_label][3] int64: area, sum r, sum c -- cs_label_intensity's geom, bit for bit.
+ * focus:  out, [batch][max_label][channels][CS_QUALITY_FOCUS] int64: n_int, sum L, sum L^2, sum G, sum Br over the object's
+ *         interior pixels.  Both out_kind; rows of absent objects are all zero.
+ * The rules and the caps are cs_label_intensity's, in its order.  No floating point; bit-identical run to run and independent of
+ * the other images of the batch; scratch from the shared buffers only; one host synchronisation per call. */
+int cs_object_focus(cs_preproc *p, const void *image, int pixel_type, int32_t channels,
+                    const int32_t *labels, const int32_t *exclude /* or NULL */,
+                    int32_t batch, int32_t height, int32_t width, int in_kind, int32_t max_label,
+                    int64_t *geom, int64_t *focus, int out_kind);
+/* Device time of the last cs_object_focus: clearing the tables and the status word, and the pass. */
+int cs_object_focus_last_timing(const cs_preproc *p, double *clear_ms, double *pass_ms);
 
 /* ---- detector fitting (create_anomaly_detector, CAE_improved_modeltrain.py:394-446) -------- */
 /* The fit of what cs_screen's tail evaluates, for the training set's encoder features
