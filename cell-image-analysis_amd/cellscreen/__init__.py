@@ -13,6 +13,7 @@ from .quantile import QuantileMeasurer, QuantileTable  # noqa: F401
 from .radial import RadialMeasurer, RadialTable, radial_params, radial_table  # noqa: F401
 from .shape import ShapeMeasurer, ShapeTable, shape_table  # noqa: F401
 from .spec import CAEWeights, DetectorParams, OCSVMParams  # noqa: F401
+from .spots import SpotDetector, SpotTable, dog_noise_gain, spot_params, spot_table  # noqa: F401
 from .texture import TextureMeasurer, TextureTable, texture_table  # noqa: F401
 
 __all__ = ["spec", "CAEWeights", "DetectorParams", "OCSVMParams", "LabelExpander", "expand_params", "IntensityMeasurer",
@@ -21,4 +22,5 @@ __all__ = ["spec", "CAEWeights", "DetectorParams", "OCSVMParams", "LabelExpander
            "ColocalizationMeasurer", "ColocalizationTable", "colocalization_table", "colocalize_params",
            "RadialMeasurer", "RadialTable", "radial_params", "radial_table",
            "GranularityMeasurer", "GranularityTable", "granularity_params", "granularity_table", "LabelPropagator", "propagate_params",
-           "ImageQualityMeasurer", "ImageQualityTable", "ObjectFocusTable", "image_quality_table", "object_focus_table"]
+           "ImageQualityMeasurer", "ImageQualityTable", "ObjectFocusTable", "image_quality_table", "object_focus_table",
+           "SpotDetector", "SpotTable", "dog_noise_gain", "spot_params", "spot_table"]

@@ -175,6 +175,12 @@ class CSSmoothParams(C.Structure):
     _fields_ = [("radius", C.c_int32), ("median", C.c_int32), ("weights", C.c_int32 * (SMOOTH_MAX_RADIUS + 1)), ("reserved", C.c_int32)]
 
 
+class CSSpotParams(C.Structure):
+    _fields_ = [("radius_a", C.c_int32), ("radius_b", C.c_int32), ("weights_a", C.c_int32 * (SMOOTH_MAX_RADIUS + 1)),
+                ("weights_b", C.c_int32 * (SMOOTH_MAX_RADIUS + 1)), ("min_distance", C.c_int32), ("channel", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 # cs_region of include/cellscreen.h as a numpy record (80 bytes)
 REGION_DTYPE = np.dtype([("image", np.int32), ("label", np.int32), ("minr", np.int32), ("minc", np.int32), ("maxr", np.int32),
                          ("maxc", np.int32), ("area", np.int64), ("convex_area", np.int64), ("eccentricity", np.float64),
@@ -277,6 +283,10 @@ SIGNATURES = {
     "cs_image_quality_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "cs_object_focus": (_I, [_P, _P, _I, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _I, C.c_int32, _P, _P, _I]),
     "cs_object_focus_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "cs_spot_detect": (_I, [_P, _P, _I, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _I, C.c_int32, C.POINTER(CSSpotParams), _P, _P,
+                            _P, _P, _P, _I, C.POINTER(_L)]),
+    "cs_spot_fill": (_I, [_P, _P, _L, _P, _I]),
+    "cs_spot_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "cs_fit_create": (_I, [_I, C.POINTER(_P)]),
     "cs_fit_free": (None, [_P]),
     "cs_fit_wait_stream": (_I, [_P, _P]),

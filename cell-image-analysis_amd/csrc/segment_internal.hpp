@@ -1,5 +1,5 @@
 // segment_internal.hpp -- the state behind cs_preproc::seg as its translation units share it (segment.hip, expand.hip,
-// intensity.hip, quantile.hip, texture.hip, shape.hip, neighbors.hip, colocalize.hip, radial.hip, granularity.hip, propagate.hip, quality.hip): the shared buffers and a clock per family of entry points.  The clock itself and
+// intensity.hip, quantile.hip, texture.hip, shape.hip, neighbors.hip, colocalize.hip, radial.hip, granularity.hip, propagate.hip, quality.hip, spots.hip): the shared buffers and a clock per family of entry points.  The clock itself and
 // the argument rules are stage_host.hpp's, which extract.hip and match.hip use with states of their own.
 #pragma once
 #include "stage_host.hpp"
@@ -49,6 +49,13 @@ struct SegmentState {
     // exclude plane in parent, the tables on their way to the host in stage, the status word in ctrl; the image pass keeps the
     // workgroups' (extreme, count) partials in slab and, without a mesh, a tile of sums per workgroup and channel in hist.
     StageClock clk_iq, clk_lf;
+    // cs_spot_detect (spots.hip) shares img, lab, parent, stage and ctrl as cs_label_intensity does; its two planes of row sums are in
+    // sm_t, the response in dq, the peak pass's ballot words in mask, the rows' counts in counts, the chunks' offsets in chunks, the
+    // thresholds in thr.  Only the sorted list and its offsets are its own: they stay on the handle until cs_spot_fill copies them out.
+    DevBuf sp_list, sp_off;                             // [sp_n][8] int32; [sp_batch + 1] int64
+    int64_t sp_n = -1;                                  // -1: no successful cs_spot_detect yet
+    int sp_batch = 0;
+    StageClock clk_sd;
     StageClock clk_thr, clk_sp, clk_si, clk_bg, clk_lt, clk_cl, clk_sm, clk_hy, clk_ns, clk_ex, clk_in, clk_lq, clk_tx, clk_sh, clk_nb, clk_co, clk_ra, clk_gr, clk_gs, clk_pg;   // clk_gs: one sums pass of cs_label_granularity at a time
     int pg_rounds = 0;                                  // cs_label_propagate's last call: its rounds, the closing quiet one included
     double gr_ms[3] = {0.0, 0.0, 0.0};                  // cs_label_granularity's last call: prepare, erosions + reconstructions, sums

@@ -42,6 +42,11 @@
  *        whether an image, a mesh tile of it or an object is worth measuring: intensity, extreme and saturation counts and
  *        the sums behind the Laplacian variance, Tenengrad and Brenner focus measures, as exact integers (CellProfiler's
  *        MeasureImageQuality: FocusScore, LocalFocusScore, PercentMinimal / PercentMaximal; no reference counterpart)
+ *   cs_spot_detect / cs_spot_fill
+ *        puncta in one channel and how many of them every object holds: the local maxima of a difference-of-Gaussians
+ *        response, computed in integers, as a list sorted by image and raster order and as per-object records
+ *        (skimage.feature.blob_dog / peak_local_max, TrackMate's DoG detector, CellProfiler's IdentifyPrimaryObjects +
+ *        RelateObjects on speckles; no reference counterpart)
  *   cs_label_intensity
  *        measures every object of a label image in every channel: area, centroid, integrated / mean / std /
  *        min / max intensity and the intensity-weighted centroid, as exact integer sums
@@ -1290,6 +1295,62 @@ int cs_object_focus(cs_preproc *p, const void *image, int pixel_type, int32_t ch
                     int64_t *geom, int64_t *focus, int out_kind);
 /* Device time of the last cs_object_focus: clearing the tables and the status word, and the pass. */
 int cs_object_focus_last_timing(const cs_preproc *p, double *clear_ms, double *pass_ms);
+
+/* ---- spots: local maxima of a difference of Gaussians, listed and counted per object ---------------------------------- */
+/* Puncta in one channel (tests/spots_reference.py restates the rule, cellscreen/spots.py derives).  All integers.
+ * Response.  A_t(i, j) = sum_k w_t[|k|] sum_l w_t[|l|] x(fold(i + k, height), fold(j + l, width)) for the two tables t = a (fine)
+ *         and b (coarse) of cs_spot_params: cs_segment_smooth's separable 48-bit sum and its reflection (a radius may exceed a
+ *         side).  R = (A_a - A_b + 2^23) >> 24, a floor shift of the signed difference: int32 in 1/256 counts, |R| < 2^24; a
+ *         constant image has R = 0 everywhere.
+ * Peaks.  The key of a pixel is (R, -raster index).  A pixel of image b is a spot iff R >= thresholds[b] and its key is strictly
+ *         the greatest among the pixels with |dr| <= min_distance and |dc| <= min_distance, clipped to the image.  So no two spots
+ *         lie within Chebyshev distance min_distance, and of a plateau the first pixel in raster order is the one that can be one.
+ * Label.  labels[b][r][c], or 0 where exclude is non-zero there or labels is NULL.  Excluded pixels still take part in the
+ *         response and in the window.
+ * image:  [batch][height][width][channels] uint8 / uint16 (pixel_type), in_kind; params->channel is read.  height, width 1..4096,
+ *         batch 1..65535 (above: CS_ERR_UNSUPPORTED); batch * height * width * 12 bytes of response scratch must stay under
+ *         2^30 (else CS_ERR_UNSUPPORTED).
+ * labels, exclude: NULL, or [batch][height][width] int32, in_kind; exclude needs labels.  With labels max_label >= 1 bounds them
+ *         (batch * max_label above 2^22 or max_label above 2^20: CS_ERR_UNSUPPORTED); a negative label or one above max_label:
+ *         CS_ERR_INVALID "negative or exceeds max_label", detected on the device, never an index or a key; the handle stays usable.
+ * thresholds: [batch] int32 on the host, 1/256 counts, each >= 1 (else CS_ERR_INVALID).
+ * counts: out, [batch][2] int64: the spots of the image, and those of them on label 0.
+ * geom:   with labels out, [batch][max_label][3] int64: area, sum r, sum c -- cs_label_intensity's geom, bit for bit.
+ * spots:  with labels out, [batch][max_label][CS_SPOT_RECORD] int64: n, sum R, sum R^2, max R (0 without a spot), sum r, sum c
+ *         over the object's spots.  Without labels neither is written and both may be NULL.
+ * response: NULL, or out, [batch][height][width] int32: R.  counts, geom, spots and response are out_kind.
+ * n_spots: out, on the host: the length of the list, which stays on the handle until the next cs_spot_detect.  More than 2^22
+ *         spots: CS_ERR_UNSUPPORTED, and no list.
+ * cs_spot_fill copies out what the last successful cs_spot_detect on the handle left (none: CS_ERR_INVALID):
+ * list:   out, [n_spots][CS_SPOT_FIELDS] int32: r, c, label, R, R(r-1, c), R(r+1, c), R(r, c-1), R(r, c+1), INT32_MIN for a
+ *         neighbour outside the image; sorted by image, then raster order.  capacity: the spots the buffer holds, >= n_spots
+ *         (else CS_ERR_INVALID); list may be NULL where capacity is 0.
+ * offsets: out, [batch + 1] int64: the spots of image b are list[offsets[b] .. offsets[b + 1]).  Both out_kind.
+ * No floating point and no float atomics: bit-identical run to run, whatever the launch geometry, and independent of the other
+ * images of the batch.  Scratch from the buffers the handle's segmenter stages share; one host synchronisation per
+ * cs_spot_detect.  Other bad arguments: CS_ERR_INVALID before any device work; without a gfx950 device (p == NULL):
+ * CS_ERR_NO_DEVICE. */
+#define CS_SPOT_RECORD 6
+#define CS_SPOT_FIELDS 8
+#define CS_SPOT_MAX_RADIUS 64
+typedef struct cs_spot_params {
+    int32_t radius_a;                 /* 0..64; 0: the identity, weights_a[0] = 65536 */
+    int32_t radius_b;                 /* 1..64 */
+    int32_t weights_a[CS_SPOT_MAX_RADIUS + 1];   /* both tables: non-negative, w[0] >= 1, 0 beyond the radius, */
+    int32_t weights_b[CS_SPOT_MAX_RADIUS + 1];   /* w[0] + 2 * sum(w[1..radius]) == 65536; equal tables: CS_ERR_INVALID */
+    int32_t min_distance;             /* 1..8: the window's half-width */
+    int32_t channel;                  /* 0..channels - 1 */
+    int32_t reserved;                 /* must be 0 */
+} cs_spot_params;
+int cs_spot_detect(cs_preproc *p, const void *image, int pixel_type, int32_t channels,
+                   const int32_t *labels /* or NULL */, const int32_t *exclude /* or NULL */,
+                   int32_t batch, int32_t height, int32_t width, int in_kind, int32_t max_label,
+                   const cs_spot_params *params, const int32_t *thresholds, int64_t *counts,
+                   int64_t *geom /* or NULL */, int64_t *spots /* or NULL */, int32_t *response /* or NULL */, int out_kind,
+                   int64_t *n_spots);
+int cs_spot_fill(cs_preproc *p, int32_t *list, int64_t capacity, int64_t *offsets, int out_kind);
+/* Device time of the last cs_spot_detect: clearing + the response, the peaks with their counts, and the list with the records. */
+int cs_spot_last_timing(const cs_preproc *p, double *response_ms, double *peaks_ms, double *records_ms);
 
 /* ---- detector fitting (create_anomaly_detector, CAE_improved_modeltrain.py:394-446) -------- */
 /* The fit of what cs_screen's tail evaluates, for the training set's encoder features

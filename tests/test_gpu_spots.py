@@ -1,0 +1,345 @@
+"""The spot detector on the device (cs_spot_detect and cs_spot_fill through cellscreen.spots) against the CPU restatement of
+tests/spots_reference.py, which tests/test_spots_cpu.py holds to SciPy and to its own direct forms.
+
+Every output is integers, so every comparison is np.array_equal: the counts, the offsets, the list with its order, the objects'
+geometry and records with the rows of absent objects, and the response plane where it is asked for.
+
+The row pass stages segments of SD_ROW_SEG pixels, the column pass tiles of SD_COL_TR rows by 64 columns, the peak pass tiles of
+SD_PK_H by SD_PK_W with a halo of m; the sizes are read from csrc/spots.hip, so the shapes follow the code.  The spot-count cap
+(2^22 per call) is not driven here: a list that long needs a plane the cap suite is the place for."""
+import functools
+import os
+import re
+
+import numpy as np
+import pytest
+
+import helpers as H
+import spots_reference as SR
+from cellscreen import _lib as L
+from cellscreen import intensity as IN
+from cellscreen import segment as S
+from cellscreen import spots as SP
+
+pytestmark = pytest.mark.gpu
+
+
+def kernel_constants():
+    with open(os.path.join(H.ROOT, "cell-image-analysis_amd", "csrc", "spots.hip")) as f:
+        text = f.read()
+    out = {}
+    for name in ("SD_ROW_SEG", "SD_COL_TR", "SD_PK_W", "SD_PK_H"):
+        m = re.search(rf"static constexpr int {name} = (\d+);", text)
+        assert m, f"{name} is not declared in spots.hip as the suite reads it"
+        out[name] = int(m.group(1))
+    return out
+
+
+K = kernel_constants()
+PK_W, PK_H = K["SD_PK_W"], K["SD_PK_H"]
+DOG = dict(sigma=1.0)                                                    # 1 and 1.6: radii 4 and 6
+
+
+@pytest.fixture(scope="module")
+def det():
+    d = SP.SpotDetector(0)
+    yield d
+    d.close()
+
+
+def as_tensor(a):
+    import torch
+    a = a if a.flags.writeable else a.copy()
+    return torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a).to(torch.device("cuda", 0))
+
+
+def noise(shape, dtype=np.uint16, seed=0, top=None):
+    top = np.iinfo(dtype).max if top is None else top
+    return np.random.default_rng(seed).integers(0, top + 1, shape).astype(dtype)
+
+
+def bright(shape, points, dtype=np.uint16, base=100, value=4000):
+    """[1,H,W]: `base` everywhere, `value` at the points."""
+    a = np.full((1,) + tuple(shape), base, dtype)
+    for r, c in points:
+        a[0, r, c] = value
+    return a
+
+
+def want_of(images, T, params, labels=None, exclude=None, max_label=None):
+    wa, wb = SP.tables_of(params)
+    B = images.shape[0]
+    ts = list(T) if hasattr(T, "__len__") else [T] * B
+    return SR.detect(images, ts, wa, wb, params.min_distance, params.channel, labels, exclude, max_label)
+
+
+def same(got, want, plane=True):
+    names = ("counts", "offsets", "list", "geom", "records", "response")
+    for name, g, w in zip(names, got, want):
+        if name == "response" and not plane:
+            continue
+        if w is None:
+            assert g is None, name
+            continue
+        g = g.cpu().numpy() if hasattr(g, "cpu") else g
+        assert g.dtype == w.dtype and g.shape == w.shape, (name, g.dtype, g.shape, w.shape)
+        assert np.array_equal(g, w), (name, np.argwhere(g != w)[:5].tolist())
+
+
+def check(det, images, T, params, labels=None, exclude=None, max_label=None):
+    """One call with the response, compared with the restatement in everything; returns the restatement."""
+    ts = [t / 256.0 for t in T] if hasattr(T, "__len__") else T / 256.0
+    got = det.detect_dense(images, ts, labels, exclude, max_label, params, True)
+    want = want_of(images, T, params, labels, exclude, max_label)
+    same(got, want)
+    lst, off, counts = want[2], want[1], want[0]
+    assert np.array_equal(np.diff(off), counts[:, 0])
+    for b in range(len(counts)):                                         # sorted by raster order inside every image
+        rows = lst[off[b]:off[b + 1]]
+        idx = rows[:, 0].astype(np.int64) * images.shape[2] + rows[:, 1]
+        assert (np.diff(idx) > 0).all()
+    return want
+
+
+# ---- sides and strides ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("shape", [(1, 1), (1, 70), (70, 1), (70, 130), (130, 70)])
+def test_sides(det, shape):
+    img = noise((2,) + shape, np.uint16, 3, 4000)
+    for m in (1, 3):
+        want = check(det, img, 64, SP.spot_params(min_distance=m, **DOG))
+        assert shape == (1, 1) or want[0][:, 0].min() > 0
+
+
+def test_radii_above_both_sides(det):
+    img = noise((2, 5, 7), np.uint16, 4, 4000)
+    want = check(det, img, 16, SP.spot_params(3.0, sigma_coarse=5.0, min_distance=1))         # radii 12 and 20: several folds
+    assert want[0][:, 0].min() > 0
+
+
+def test_one_past_the_row_segment_and_the_column_tile(det):
+    shape = (K["SD_COL_TR"] + 1, K["SD_ROW_SEG"] + 1)
+    img = noise((1,) + shape, np.uint16, 5, 4000)
+    img[0, -1, -1] = 60000                                               # the pixel that is alone in its segment and in its tile
+    want = check(det, img, 256, SP.spot_params(min_distance=2, **DOG))
+    assert want[2][-1, 0] == shape[0] - 1 and want[2][-1, 1] == shape[1] - 1
+
+
+# ---- peaks on boundaries --------------------------------------------------------------------------------------------------------
+IDENT = dict(sigma=0, sigma_coarse=1.0)
+
+
+@pytest.mark.parametrize("m", [1, 2, 8])
+def test_single_pixels_on_corners_edges_and_tile_boundaries(det, m):
+    shape = (2 * PK_H + 6, 2 * PK_W + 2)
+    Hh, Ww = shape
+    sets = [[(0, 0), (0, Ww - 1), (Hh - 1, 0), (Hh - 1, Ww - 1)],
+            [(0, 40), (Hh - 1, 90), (30, 0), (50, Ww - 1)],
+            [(PK_H - 1, 20), (PK_H, 50), (PK_H - 1, 100), (2 * PK_H - 1, 20), (2 * PK_H, 80)],
+            [(10, PK_W - 1), (25, PK_W), (50, 2 * PK_W - 1), (60, 2 * PK_W)],
+            [(PK_H - 1, PK_W - 1)], [(PK_H - 1, PK_W)], [(PK_H, PK_W - 1)], [(PK_H, PK_W)]]
+    img = np.concatenate([bright(shape, pts) for pts in sets])
+    want = check(det, img, 256, SP.spot_params(min_distance=m, **IDENT))
+    for b, pts in enumerate(sets):
+        rows = want[2][want[1][b]:want[1][b + 1]]
+        assert sorted(map(tuple, rows[:, :2].tolist())) == sorted(pts), (b, m)
+
+
+@pytest.mark.parametrize("m", [1, 2, 8])
+def test_pairs_m_and_m_plus_one_apart(det, m):
+    shape = (PK_H + 30, PK_W + 30)
+    a = (PK_H - 3, PK_W - 3)
+    imgs, keep = [], []
+    for d in (m, m + 1):
+        for dr, dc in ((0, d), (d, 0), (d, d)):
+            imgs.append(bright(shape, [a, (a[0] + dr, a[1] + dc)]))
+            keep.append(1 if d == m else 2)
+    want = check(det, np.concatenate(imgs), 256, SP.spot_params(min_distance=m, **IDENT))
+    assert want[0][:, 0].tolist() == keep                                # equal peaks m apart: the earlier in raster order survives
+    assert all(tuple(want[2][want[1][b], :2]) == a for b in range(len(imgs)))
+
+
+# ---- ties -----------------------------------------------------------------------------------------------------------------------
+def test_constant_plateau_equal_peaks_and_checkerboard(det):
+    shape = (PK_H + 20, PK_W + 20)
+    const = np.full((1,) + shape, 777, np.uint16)
+    plateau = bright(shape, [(PK_H - 1, PK_W - 1), (PK_H - 1, PK_W), (PK_H, PK_W - 1), (PK_H, PK_W)])
+    yy, xx = np.mgrid[0:shape[0], 0:shape[1]]
+    board = (1000 + 2000 * ((yy // 2 + xx // 2) & 1)).astype(np.uint16)[None]
+    img = np.concatenate([const, plateau, board])
+    for m in (1, 2):
+        want = check(det, img, 1, SP.spot_params(min_distance=m, **IDENT))
+        assert want[0][0, 0] == 0 and not want[5][0].any()               # a constant image: R = 0, no spot at any T >= 1
+        assert want[0][1, 0] == 1 and tuple(want[2][want[1][1], :2]) == (PK_H - 1, PK_W - 1)
+        assert want[0][2, 0] > 4
+    check(det, np.concatenate([const, board]).astype(np.uint8), 1, SP.spot_params(min_distance=3, **DOG))
+
+
+# ---- parameters -----------------------------------------------------------------------------------------------------------------
+def test_identity_smallest_and_largest_radii_at_full_range(det):
+    for dtype in (np.uint8, np.uint16):
+        top = np.iinfo(dtype).max
+        img = noise((1, 40, 75), dtype, 7)
+        img[0, 10:20, 10:30] = top                                       # the sums at their bounds
+        img[0, 25:35, 40:60] = 0
+        for p in (SP.spot_params(0, sigma_coarse=0.3, min_distance=1),   # identity and a coarse table of radius 1
+                  SP.spot_params(15.9, sigma_coarse=16.1, min_distance=2),               # both radii 64
+                  SP.spot_params(0.3, sigma_coarse=16.1, min_distance=8)):               # 1 and 64
+            assert (p.radius_a, p.radius_b) in ((0, 1), (64, 64), (1, 64))
+            check(det, img, 1, p)
+    wide = np.zeros((1, 9, 9), np.uint16)
+    wide[0, 4, 4] = 65535
+    want = check(det, wide, 1, SP.spot_params(0, sigma_coarse=16.1, min_distance=1))
+    assert want[5].max() > (1 << 24) - (1 << 20) and want[5].max() < 1 << 24
+
+
+def test_every_channel_of_four(det):
+    img = noise((2, 33, 70, 4), np.uint16, 8, 3000)
+    for ch in range(4):
+        want = check(det, img, 128, SP.spot_params(min_distance=2, channel=ch, **DOG))
+        alone = want_of(np.ascontiguousarray(img[..., ch]), 128, SP.spot_params(min_distance=2, **DOG))
+        assert np.array_equal(want[2], alone[2])
+    img8 = noise((1, 20, 31, 3), np.uint8, 9)
+    check(det, img8, 64, SP.spot_params(min_distance=1, channel=2, **DOG))
+
+
+# ---- batch ----------------------------------------------------------------------------------------------------------------------
+def test_batch_of_three_thresholds_and_each_image_alone(det):
+    img = noise((3, 50, 90), np.uint16, 10, 2000)
+    img[1] = 500                                                         # no spot at all
+    T = [300, 1, 5000]
+    p = SP.spot_params(min_distance=2, **DOG)
+    want = check(det, img, T, p)
+    assert want[0][0, 0] > want[0][2, 0] > 0 and want[0][1, 0] == 0
+    for b in range(3):
+        alone = det.detect_dense(img[b:b + 1], T[b] / 256.0, params=p, return_response=True)
+        assert np.array_equal(alone[2], want[2][want[1][b]:want[1][b + 1]]) and np.array_equal(alone[0][0], want[0][b])
+        assert np.array_equal(alone[5][0], want[5][b])
+
+
+# ---- objects --------------------------------------------------------------------------------------------------------------------
+def object_scene():
+    img = noise((2, 70, 130), np.uint16, 11, 3000)
+    lab = np.zeros((2, 70, 130), np.int32)
+    lab[0, 5:30, 5:60] = 1
+    lab[0, 5:30, 60:120] = 2
+    lab[0, 40:60, 10:40] = 4                                             # 3 is absent
+    lab[0, 65, 100] = 5                                                  # one pixel, off any spot or on one: the restatement knows
+    lab[1] = np.roll(lab[0], (7, 9), axis=(0, 1))
+    lab[1, 69, 129] = 6
+    ex = np.zeros_like(lab)
+    ex[0, 10:20, 20:80] = 1
+    ex[1, :, 64] = -3
+    return img, lab, ex
+
+
+def test_objects_exclude_and_geom_equals_intensity(det):
+    img, lab, ex = object_scene()
+    p = SP.spot_params(min_distance=2, **DOG)
+    bare = check(det, img, 200, p)
+    assert bare[3] is None and bare[4] is None and not bare[2][:, 2].any() and np.array_equal(bare[0][:, 0], bare[0][:, 1])
+    # a bright single pixel inside object 4, one on an excluded pixel of object 1, and the one-pixel object made a spot
+    img = img.copy()
+    img[0, 50, 25] = img[0, 15, 30] = img[0, 65, 100] = 60000
+    im = IN.IntensityMeasurer(0)
+    for e, M in ((None, None), (ex, None), (ex, 9), (None, 40)):
+        want = check(det, img, 200, p, lab, e, M)
+        g, t = want[3], want[4]
+        assert g.shape[1] == (M or 6) and not g[:, 2].any() and not t[:, 2].any()
+        assert t[0, 4, 0] == 1 and t[0, 3, 0] >= 1                       # the one-pixel object holds its spot
+        got = det.detect_dense(img, 200 / 256.0, lab, e, M, p)
+        assert np.array_equal(got[3], im.measure_dense(img, lab, exclude=e, max_label=M)[0])        # geom, bit for bit
+        on_ex = [row for row in want[2][:want[1][1]].tolist() if (row[0], row[1]) == (15, 30)]
+        assert len(on_ex) == 1 and on_ex[0][2] == (0 if e is not None else 1)
+        assert int(t[:, :, 0].sum()) + int(want[0][:, 1].sum()) == len(want[2])
+    im.close()
+    lonely = np.where(lab == 3, 0, lab)                                  # objects that hold no spot keep a zero record
+    high = check(det, img, 1000000, p, lonely, None, None)             # only the three bright pixels are left
+    assert high[0][:, 0].tolist() == [3, 0] and (high[4][:, :, 0] == 0).sum() == 9
+
+
+# ---- list order -----------------------------------------------------------------------------------------------------------------
+def test_list_order_over_rows_and_images(det):
+    shape = (300, 200)                                                   # more rows than a workgroup of the placement owns
+    pts = [[(7, c) for c in range(3, 200, 9)] + [(r, 100) for r in range(20, 300, 9)], [(299, 199), (0, 0), (150, 7), (150, 190)],
+           [(r, (r * 37) % 190 + 4) for r in range(2, 298, 6)]]
+    img = np.concatenate([bright(shape, p) for p in pts])
+    want = check(det, img, 256, SP.spot_params(min_distance=2, **IDENT))
+    assert want[0][:, 0].tolist() == [len(p) for p in pts]
+    assert want[1].tolist() == [0] + np.cumsum([len(p) for p in pts]).tolist()
+
+
+# ---- errors ---------------------------------------------------------------------------------------------------------------------
+def test_bad_labels_are_a_status_and_the_handle_survives(det):
+    img, lab, _ = object_scene()
+    p = SP.spot_params(min_distance=2, **DOG)
+    for bad, M in ((-1, None), (7, 6)):
+        x = lab.copy()
+        x[1, 33, 77] = bad
+        with pytest.raises(L.CellScreenError) as ei:
+            det.detect_dense(img, 1.0, x, None, M, p)
+        assert ei.value.status == -1 and "max_label" in str(ei.value)
+        with pytest.raises(L.CellScreenError):                           # no list is left behind by a failed call
+            L.check(det._lib.cs_spot_fill(det._handle, None, 0, L._ptr(np.zeros(3, np.int64)), L.CS_MEM_HOST))
+        check(det, img, 256, p, lab, None, 6)
+
+
+# ---- plumbing -------------------------------------------------------------------------------------------------------------------
+def test_tensors_agree_with_numpy_and_two_runs_are_identical(det):
+    import torch
+    img, lab, ex = object_scene()
+    p = SP.spot_params(min_distance=3, **DOG)
+    want = want_of(img, 300, p, lab, ex, 8)
+    host = det.detect_dense(img, 300 / 256.0, lab, ex, 8, p, True)
+    dev = det.detect_dense(as_tensor(img), 300 / 256.0, as_tensor(lab), as_tensor(ex), 8, p, True)
+    again = det.detect_dense(as_tensor(img), 300 / 256.0, as_tensor(lab), as_tensor(ex), 8, p, True)
+    assert isinstance(host[5], np.ndarray) and isinstance(dev[5], torch.Tensor) and dev[5].is_cuda and dev[5].dtype == torch.int32
+    same(host, want)
+    same(dev, want)
+    same(again, want)
+    assert det.detect_dense(img, 300 / 256.0, params=p)[5] is None
+    t = det.detect_batch(img, 300 / 256.0, lab, ex, 8, p)
+    w = SP.spot_table(*want[:5])
+    assert len(t) == len(w) > 0 and np.array_equal(t.subpixel, w.subpixel) and np.array_equal(t.mean_response, w.mean_response, equal_nan=True)
+    assert set(det.last_timing()) == {"spot_response_ms", "spot_peaks_ms", "spot_records_ms"} and det.last_timing()["spot_response_ms"] > 0
+    with pytest.raises(TypeError):
+        det.detect_dense(img, 1.0, as_tensor(lab))
+
+
+def nuclei_scene():
+    """uint16 [2,96,128]: five bright blobs per image on a noisy background, three puncta inside them."""
+    rng = np.random.default_rng(2)
+    Hh, Ww = 96, 128
+    yy, xx = np.mgrid[0:Hh, 0:Ww]
+    imgs = np.empty((2, Hh, Ww), np.uint16)
+    for b in range(2):
+        f = 300.0 + rng.normal(0.0, 10.0, (Hh, Ww))
+        for y, x, r in ((24, 25, 9), (30, 80, 12), (70, 40, 10), (70, 100, 7 + 4 * b), (50, 62, 5)):
+            f += 4000.0 * np.exp(-(((yy - y) ** 2 + (xx - x) ** 2) / (2.0 * (r / 1.6) ** 2)) ** 2)
+        for y, x in ((24, 27), (32, 78), (69, 41)):
+            f[y, x] += 3000.0
+        imgs[b] = np.clip(np.rint(f), 0, 65535).astype(np.uint16)
+    return imgs
+
+
+def test_on_a_segmenters_handle_with_its_labels_on_the_device(det):
+    import torch
+    imgs = nuclei_scene()
+    dev = as_tensor(imgs)
+    seg = S.ThresholdSegmenter(0)
+    labels, n_labels, _ = seg.segment_batch(dev)                         # left on the device
+    assert isinstance(labels, torch.Tensor) and labels.is_cuda and int(n_labels.sum()) == 10
+    shared = SP.SpotDetector(0, extractor=seg)
+    p = SP.spot_params(min_distance=2, **DOG)
+    got = shared.detect_dense(dev, 200.0, labels, None, 5, p, True)
+    host = shared.detect_dense(imgs, 200.0, labels.cpu().numpy(), None, 5, p, True)      # host planes go through the shared uploads
+    assert shared._pre is None
+    want = want_of(imgs, 200 * 256, p, labels.cpu().numpy(), None, 5)
+    same(got, want)
+    same(host, want)
+    for b in range(2):                                                   # the three puncta are found, inside their cells
+        rows = {(r, c): lab for r, c, lab in want[2][want[1][b]:want[1][b + 1], :3].tolist()}
+        assert all(rows.get(pt, 0) > 0 for pt in ((24, 27), (32, 78), (69, 41))), b
+    same(det.detect_dense(imgs, 200.0, labels.cpu().numpy(), None, 5, p, True), want)
+    labels2 = seg.segment_batch(dev)[0]                                  # the segmenter after the detector: the same labels
+    assert torch.equal(labels2, labels)
+    seg.close()
