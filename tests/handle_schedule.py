@@ -3,7 +3,8 @@ tests/test_gpu_shared_handle.py, and the CPU restatement of every call in it.  N
 
   ACTORS     the tools that share one SegmentState: two split segmenters (the second with smoothing and background correction, so
              that the median, smoothing and top-hat planes are dirty too), the label expander, the eight measurers, the matcher,
-             the cell extractor and the propagator, each with cheap but non-default parameters
+             the cell extractor, the propagator, the spot detector and the image quality and focus records, each with cheap but
+             non-default parameters
   circuit    an Eulerian circuit of the complete directed graph on n vertices: n (n - 1) + 1 stops, every ordered pair of
              different vertices adjacent exactly once
   schedule   the circuit on the actors as (actor, input, on_device, exclude) steps; every actor has a counter of its own that
@@ -24,23 +25,32 @@ import match_reference as MA
 import neighbors_reference as NB
 import pipeline_reference as P
 import propagate_reference as PG
+import quality_reference as QY
 import quantile_reference as QR
 import radial_reference as RR
 import shape_reference as SH
+import smooth_reference as SM
+import spots_reference as SR
 import texture_reference as TR
 
 ACTORS = ("split", "split_intensity", "expand", "intensity", "quantiles", "texture", "shape", "neighbors", "colocalize", "radial",
-          "granularity", "match", "extract", "propagate")
+          "granularity", "match", "extract", "propagate", "spots", "quality", "focus")
 SEGMENTERS = {"split": dict(split_touching=True, split_h=2, connectivity=2, fill_holes=False),
               "split_intensity": dict(split_touching=True, split_by="intensity", split_depth=24, smooth_sigma=1.0, denoise=True,
                                       background_radius=9)}
-HAS_EXCLUDE = ("intensity", "quantiles", "texture", "shape", "colocalize", "radial", "granularity")
+HAS_EXCLUDE = ("intensity", "quantiles", "texture", "shape", "colocalize", "radial", "granularity", "spots", "focus")
 RANGE_CHECKED = HAS_EXCLUDE + ("neighbors", "match")     # the tools that take a largest label and refuse one above it with status -1
 INPUTS = ((2, 130, 520), (1, 33, 67), (1, 64, 256))
 DTYPES = (np.uint16, np.uint8, np.uint16)
 EXPAND_DISTANCE, QUANTILES, TEXTURE, NEIGHBOR_D2 = 4, ((1, 10), (1, 2)), (2, 8), 25         # TEXTURE: distance, levels
 COLOC_THRESHOLD, RADIAL_BINS, GRANULARITY = (20, 50), 3, (4, 2)                             # GRANULARITY: steps, subsample
 PROPAGATE = dict(metric="cityblock", lam=2, guide_channel=1)          # and a max_cost per input: inputs_of()["max_cost"]
+# the spot detector: a difference of Gaussians of sigma 1 and 1.6 in channel 1 (the plain noise), a window of 7 x 7, the response
+# plane asked for, and per input a threshold in counts that cuts into the noise's own peaks
+SPOTS = dict(sigma=1.0, min_distance=3, channel=1)
+SPOT_THRESHOLDS = (1000.0, 4.0, 1000.0)
+QUALITY_TILE = 16                                        # the image quality records: both channels, a mesh, and per input
+SAT_LEVELS = ((40000, 3000), (150, 11), (32768, 1))      # a saturation level for either channel that is not the dtype's top
 
 
 def circuit(n):
@@ -146,6 +156,14 @@ def expected(actor, k, exclude=False):
         return np.array(status, np.int32), np.array(rows, np.int64).reshape(len(rows), 1 + len(EXTRACT_FIELDS))
     if actor == "propagate":
         return PG.propagate(x["seeds"], x["mask"], image, max_cost=x["max_cost"], **PROPAGATE)
+    if actor == "spots":                                 # counts, offsets, the list, geom, records, the response
+        w_a, w_b = SM.smooth_weights(SPOTS["sigma"]), SM.smooth_weights(SPOTS["sigma"] * 1.6)
+        T = int(round(256 * SPOT_THRESHOLDS[k]))
+        return SR.detect(image, [T] * image.shape[0], w_a, w_b, SPOTS["min_distance"], SPOTS["channel"], labels, ex, x["max_label"])
+    if actor == "quality":
+        return QY.measure_image(image, QUALITY_TILE, SAT_LEVELS[k])
+    if actor == "focus":
+        return QY.measure_objects(image, labels, ex, x["max_label"])
     raise KeyError(actor)
 
 

@@ -12,6 +12,10 @@ tests/test_label_caps_cpu.py holds this file to the sources and to itself, tests
                      (4096 * factor); four images with max_label = kMaxLabel where factor is 1 ("rows4"); and the byte caps of the
                      ring table, the granularity sums and the colocalization rank tables under the parameters that reach them
              sides   (1, 4096), (4096, 1), (3, 4096) and (4096, 3), two images each
+             The three tools that are no cs_label_* add their own caps to `rows`: the spot list's (spots-list: 4096 images of
+             64 x 64 with 1024 spots and 1024 objects each, 2^22 of either) and the response scratch's (scratch: 21845 images of
+             64 x 64), the focus cells with four channels (rows-channels) and the mesh's (tiles: 32768 images of 17 x 49 x 4
+             under a 2 x 4 mesh); the image quality records take no labels, so their scenes hold an image alone.
              A family is a function from a tool's name to a list of scenes, or to a reason string where the tool has no such scene.
   expected   the restatement of a scene: directly, or of its prototypes gathered by the scene's index map
   SEGMENT_CASES, segment_scene, segment_expected    cs_segment_* at kMaxBatch images of 8 x 8, the same way
@@ -37,7 +41,10 @@ import pipeline_reference as P
 import propagate_reference as PG
 import quantile_reference as QR
 import radial_reference as RR
+import quality_reference as QY
 import shape_reference as SH
+import smooth_reference as SM
+import spots_reference as SR
 import texture_reference as TR
 
 CSRC = os.path.join(H.ROOT, "cell-image-analysis_amd", "csrc")
@@ -51,7 +58,9 @@ CAP_SOURCES = {"kMaxSide": ("stage_host.hpp", "int"), "kMaxBatch": ("stage_host.
                "kGrMaxCells": ("granularity.hip", "int64_t"), "kLmMaxRows": ("match.hip", "int64_t"),
                "kTxMaxCells": ("texture.hip", "int64_t"), "kLrMaxRing": ("radial.hip", "size_t"),
                "kGrMaxBytes": ("granularity.hip", "size_t"), "kLcMaxScratch": ("colocalize.hip", "size_t"),
-               "kPgMaxBytes": ("propagate.hip", "size_t"), "LC_LEVELS": ("colocalize.hip", "int")}
+               "kPgMaxBytes": ("propagate.hip", "size_t"), "LC_LEVELS": ("colocalize.hip", "int"),
+               "kSdMaxRows": ("spots.hip", "int64_t"), "kSdMaxSpots": ("spots.hip", "int64_t"), "kSdMaxScratch": ("spots.hip", "size_t"),
+               "kIqMaxTiles": ("quality.hip", "int64_t"), "kLfMaxCells": ("quality.hip", "int64_t"), "kIqMaxChannels": ("quality.hip", "int")}
 
 
 def read_caps():
@@ -79,12 +88,53 @@ def read_python_limits():
     return out
 
 
+def read_tool_limits():
+    """The limits cellscreen/spots.py and cellscreen/quality.py repeat for their own argument checks, read as text."""
+    out = {}
+    for fname, names in (("spots.py", ("MAX_ROWS", "MAX_SPOTS", "MAX_SCRATCH")), ("quality.py", ("MAX_TILES", "MAX_CHANNELS"))):
+        with open(os.path.join(PKG, fname)) as f:
+            text = f.read()
+        for name in names:
+            m = re.search(rf"^{name} = (\d+)(?: << (\d+))?\b", text, re.M)
+            assert m, (fname, name)
+            out[fname[:-3], name] = int(m.group(1)) << int(m.group(2) or 0)
+    return out
+
+
+def defined_entry_points():
+    """{name: body}: every `int cs_*(...)` csrc/*.hip defines at file scope, with its text up to the closing brace in column 0."""
+    out = {}
+    for fname in sorted(os.listdir(CSRC)):
+        if not fname.endswith(".hip"):
+            continue
+        with open(os.path.join(CSRC, fname)) as f:
+            text = f.read()
+        lines = text.split("\n")
+        for i, line in enumerate(lines):
+            m = re.match(r"int (cs_\w+)\(", line)
+            if not m:
+                continue
+            j = i
+            while not (lines[j].startswith("}") or (j == i and "{" in line and line.rstrip().endswith("}"))):    # or a one-line body
+                j += 1
+            out[m.group(1)] = "\n".join(lines[i:j + 1])
+    return out
+
+
 def declared_entry_points():
-    """The cs_label_* entry points of cellscreen/_lib.py that take a batch: the tools themselves, not their *_last_* readers or
-    the pair list's copy."""
+    """The entry points of cellscreen/_lib.py that run a batch on the preprocess handle: the tools themselves.  A name alone does
+    not say so (cs_image_quality, cs_object_focus and cs_spot_detect are no cs_label_*), so the rule reads the definitions: every
+    declared entry point whose definition under csrc/ calls state_begin(, the door to the SegmentState the tools share, and every
+    cs_label_* that is neither a *_last_* reader nor the pair list's copy (the matcher keeps a state of its own and never calls
+    state_begin).  Left out on purpose: the cs_segment_* stages, which SEGMENT_CASES covers."""
     with open(os.path.join(PKG, "_lib.py")) as f:
-        names = re.findall(r'^\s*"(cs_label_\w+)":', f.read(), re.M)
-    return sorted(n for n in names if "_last_" not in n and n != "cs_label_neighbors_pairs")
+        names = re.findall(r'^\s*"(cs_\w+)":', f.read(), re.M)
+    body = defined_entry_points()
+    other = {n for n in names if n.endswith("_free")} | {"cs_status_string", "cs_last_error", "cs_profile_kernel_name"}   # no int
+    assert set(names) - other <= set(body), sorted(set(names) - other - set(body))             # the rule has read every definition
+    label = {n for n in names if n.startswith("cs_label_") and "_last_" not in n and n != "cs_label_neighbors_pairs"}
+    state = {n for n in names if n in body and "state_begin(" in body[n]}
+    return sorted(n for n in label | state if not n.startswith("cs_segment_"))
 
 
 CAPS = read_caps()
@@ -160,6 +210,34 @@ def _restate_match(x, p):
     return MA.tables(x["labels"], x["truth"], x["max_label"], x["max_truth"])
 
 
+SPOTS = dict(sigma=0, sigma_coarse=1.0, min_distance=1, threshold=1.0)        # the identity against sigma 1: radii 0 and 4
+SPOTS_WIDE = dict(sigma=15.9, sigma_coarse=16.1, min_distance=8, threshold=1.0)            # both radii 64, the widest window
+
+
+def spot_tables(p):
+    """(w_a, w_b, m, T) of a spots scene's parameters as spots_reference takes them: cellscreen.spots.spot_params builds the same
+    tables from the same sigmas (tests/test_label_caps_cpu.py holds them together); T in 1/256 counts."""
+    w_a = None if p["sigma"] == 0 else SM.smooth_weights(p["sigma"])
+    return w_a, SM.smooth_weights(p["sigma_coarse"]), p["min_distance"], int(round(256 * p["threshold"]))
+
+
+def _restate_spots(x, p):
+    """counts, offsets, the list, geom, records (both None without labels) and the response, which is always asked for."""
+    w_a, w_b, m, T = spot_tables(p)
+    lab = x.get("labels")
+    out = SR.detect(x["image"], [T] * len(x["image"]), w_a, w_b, m, 0, lab, None, x["max_label"] if lab is not None else None)
+    return tuple(t for t in out if t is not None)
+
+
+def _restate_focus(x, p):
+    return QY.measure_objects(x["image"], x["labels"], None, x["max_label"])
+
+
+def _restate_quality(x, p):
+    """records and, with a mesh, the mesh."""
+    return tuple(t for t in QY.measure_image(x["image"], p["tile"], p["sat_level"]) if t is not None)
+
+
 # entry: the C entry point; caps: what binds it besides kMaxSide and kMaxBatch; channels: of its cheapest image (0: it takes none);
 # factor: cells of the row cap per (image, label) under params; float_outputs: the indices of what is compared with a bound
 TOOLS = {
@@ -183,12 +261,21 @@ TOOLS = {
     "propagate": dict(entry="cs_label_propagate", caps=("kPgMaxBytes",), channels=1, factor=0, params=dict(PROPAGATE),
                       restate=_restate_propagate),
     "match": dict(entry="cs_label_match", caps=("kMaxLabel", "kLmMaxRows"), channels=0, factor=1, params={}, restate=_restate_match),
+    # cs_spot_detect with cs_spot_fill behind it: one tool.  cs_image_quality takes no labels: its scenes hold an image alone.
+    "spots": dict(entry="cs_spot_detect", caps=("kMaxLabel", "kSdMaxRows", "kSdMaxSpots", "kSdMaxScratch"), channels=1, factor=1,
+                  params=dict(SPOTS), restate=_restate_spots),
+    "focus": dict(entry="cs_object_focus", caps=("kMaxLabel", "kLfMaxCells", "kIqMaxChannels"), channels=1, factor=1, params={},
+                  restate=_restate_focus),
+    "quality": dict(entry="cs_image_quality", caps=("kIqMaxTiles", "kIqMaxChannels"), channels=1, factor=0,
+                    params=dict(tile=0, sat_level=None), restate=_restate_quality),
 }
 ROW_CAP = {"intensity": "kLiMaxCells", "quantiles": "kLqMaxCells", "texture": "kTxMaxCells", "shape": "kShMaxRows",
            "neighbors": "kNbMaxRows", "colocalize": "kLcMaxCells", "radial": "kLrMaxCells", "granularity": "kGrMaxCells",
-           "match": "kLmMaxRows"}
+           "match": "kLmMaxRows", "spots": "kSdMaxRows", "focus": "kLfMaxCells"}
 NO_TABLE = "no max_label table: its outputs are planes of the image's size"
 NO_CAP = "no cap of its own: the image limits are all that binds it, and the batch and sides families sit on those"
+NO_LABELS = "takes no labels: its records are per image, channel and mesh tile"
+LABEL_FREE = ("quality",)                                # the tools whose scenes are images without labels
 
 
 def _frozen(x):
@@ -217,6 +304,17 @@ def _scene(tool, name, labels, max_label, seed, cap, **more):
         x["max_truth"] = int(max_label)
     x.update(more)
     return _frozen(x)
+
+
+def _image_scene(tool, name, image, cap, **params):
+    """The scene of a tool that takes no labels: an image stack and the parameters that differ from the tool's cheapest."""
+    return _frozen(dict(name=name, tool=tool, image=np.ascontiguousarray(image), cap=cap, params=dict(TOOLS[tool]["params"], **params)))
+
+
+def planes_of(x):
+    """The stack a scene is made on, with all its images: the image of a tool without labels, the propagator's seeds, else the
+    labels."""
+    return full(x)["image" if x["tool"] in LABEL_FREE else "seeds" if x["tool"] == "propagate" else "labels"]
 
 
 def _gathered(protos, index, name, cap):
@@ -279,9 +377,13 @@ def batch_protos(tool):
 
 
 def family_batch(tool):
-    protos = batch_protos(tool)
     index = index_map(MAX_BATCH, BATCH_KINDS * BATCH_VARIANTS, 2 * BATCH_VARIANTS + 4, 21)
-    return [_gathered(protos, index, "batch", "kMaxBatch")]
+    if tool == "quality":                                # one channel, and the most there are: iq_close then runs 4 * 65535 workgroups
+        n, top = BATCH_KINDS * BATCH_VARIANTS, CAPS["kIqMaxChannels"]
+        one = _image_scene(tool, "batch prototypes", QY.noise((n, BATCH_SIDE, BATCH_SIDE), 1, np.uint16, 13)[..., 0], None)
+        many = _image_scene(tool, "batch prototypes", QY.noise((n, BATCH_SIDE, BATCH_SIDE), top, np.uint16, 14), None)
+        return [_gathered(one, index, "batch", "kMaxBatch"), _gathered(many, index, "batch-channels", "kIqMaxChannels")]
+    return [_gathered(batch_protos(tool), index, "batch", "kMaxBatch")]
 
 
 # ---- labels ---------------------------------------------------------------------------------------------------------------------
@@ -298,10 +400,26 @@ def labels_planes(top):
     return lab
 
 
+def bright_inside(image, labels):
+    """A copy of image [B,H,W] with the dtype's top at one pixel of every object: the middle one of its pixels in raster order."""
+    out = image.copy()
+    for b in range(len(labels)):
+        for i in np.unique(labels[b]):
+            if i > 0:
+                at = np.argwhere(labels[b] == i)
+                out[(b,) + tuple(at[len(at) // 2])] = np.iinfo(out.dtype).max
+    return out
+
+
 def family_labels(tool):
     if tool in ("expand", "propagate"):
         return NO_TABLE
-    return [_scene(tool, "labels", labels_planes(MAX_LABEL), MAX_LABEL, 31, "kMaxLabel")]
+    if tool in LABEL_FREE:
+        return NO_LABELS
+    lab = labels_planes(MAX_LABEL)
+    if tool == "spots":                                  # a spot inside every object: the records of the largest labels are not empty
+        return [_scene(tool, "labels", lab, MAX_LABEL, 31, "kMaxLabel", image=bright_inside(_pixels(tool, lab.shape, 31), lab))]
+    return [_scene(tool, "labels", lab, MAX_LABEL, 31, "kMaxLabel")]
 
 
 # ---- rows -----------------------------------------------------------------------------------------------------------------------
@@ -323,10 +441,72 @@ def rows4_planes(top):
     return k[[2, 0, 3, 1]]                                                    # the last image holds `top` in the last pixel
 
 
+LIST_SIDE, LIST_BATCH, LIST_VARIANTS = 64, 4096, 6       # the spot list's cap: 4096 images of 64 x 64 with 1024 spots each
+SCRATCH_SIDE = 64                                        # the response scratch's cap: images of 64 x 64, 12 bytes a pixel
+TILES_SHAPE, TILES_TILE, TILES_VARIANTS = (17, 49), 16, 8                 # the mesh cap: a 2 x 4 mesh off the pixel grid
+
+
+def spots_list_protos():
+    """uint8 [6,64,64]: noise below 40 with 200 more on the (even, even) lattice, and labels that give every 2 x 2 block an id of
+    its own, 1..1024.  Under SPOTS every lattice pixel is a spot and nothing else is: 1024 spots an image, one in each object."""
+    n, s = LIST_VARIANTS, LIST_SIDE
+    img = np.random.default_rng(51).integers(0, 40, (n, s, s)).astype(np.uint8)
+    img[:, ::2, ::2] += 200
+    rr, cc = np.mgrid[0:s, 0:s]
+    lab = np.broadcast_to(((rr // 2) * (s // 2) + cc // 2 + 1).astype(np.int32), (n, s, s))
+    return _scene("spots", "spots-list prototypes", lab, (s // 2) ** 2, 0, None, image=img)
+
+
+def spots_list_index():
+    return index_map(LIST_BATCH, LIST_VARIANTS, 4, 52)
+
+
+def spots_over_the_list():
+    """The images of the spots-list scene and one more with a single bright pixel, without labels: 2^22 + 1 spots, which
+    cs_spot_detect refuses once it has counted them."""
+    protos = spots_list_protos()
+    one = np.zeros((1, LIST_SIDE, LIST_SIDE), np.uint8)
+    one[0, 33, 21] = 250
+    return _frozen(dict(name="spots-list + 1", tool="spots", image=np.concatenate([protos["image"][spots_list_index()], one]),
+                        params=dict(SPOTS), cap="kSdMaxSpots"))
+
+
+def scratch_batch():
+    """The most images of 64 x 64 cs_spot_detect takes: 12 bytes of scratch a pixel stay under kSdMaxScratch."""
+    return (CAPS["kSdMaxScratch"] - 1) // (12 * SCRATCH_SIDE * SCRATCH_SIDE)
+
+
+def spots_scratch_protos():
+    """uint16 [6,64,64]: flat planes with no, two, five, one, sixteen and two equal adjacent bright pixels, and a few objects."""
+    s = SCRATCH_SIDE
+    img = np.full((6, s, s), 300, np.uint16)
+    img[1, 0, 0] = img[1, s - 1, s - 1] = 9000
+    for r, c, v in ((5, 7, 4000), (20, 40, 8000), (33, 33, 700), (50, 3, 65535), (63, 30, 5000)):
+        img[2, r, c] = v
+    img[3, 31, 32] = 2000
+    img[4, 40, ::4] = 3000
+    img[5, 10, 10] = img[5, 10, 11] = 6000
+    lab = np.zeros((6, s, s), np.int32)
+    lab[1, :4, :4], lab[1, 60:, 60:] = 1, 8
+    lab[2, 0:10, 0:20], lab[2, 15:25, 30:50], lab[2, 45:55, 0:8] = 2, 3, 8
+    lab[3] = 5
+    lab[4, 38:43, 0:32], lab[4, 38:43, 32:64] = 6, 7
+    lab[5, 5:15, 5:11], lab[5, 5:15, 11:20] = 1, 2
+    return _scene("spots", "scratch prototypes", lab, 8, 0, None, image=img)
+
+
 def family_rows(tool):
     t = TOOLS[tool]
     if tool == "expand":
         return NO_CAP
+    if tool == "quality":                                # its own cap is the mesh's: batch * channels * mesh tiles
+        C = CAPS["kIqMaxChannels"]
+        m_r, m_c = QY.mesh_dims(*TILES_SHAPE, TILES_TILE)
+        B = CAPS["kIqMaxTiles"] // (C * m_r * m_c)
+        assert B * C * m_r * m_c == CAPS["kIqMaxTiles"] and B <= MAX_BATCH and (m_r, m_c) == (2, 4)
+        assert TILES_SHAPE[0] % m_r and TILES_SHAPE[1] % m_c              # the mesh lies off the pixel grid
+        protos = _image_scene(tool, "tiles prototypes", QY.noise((TILES_VARIANTS,) + TILES_SHAPE, C, np.uint8, 53), None, tile=TILES_TILE)
+        return [_gathered(protos, index_map(B, TILES_VARIANTS, 3, 54), "tiles", "kIqMaxTiles")]
     if tool == "propagate":
         B = CAPS["kPgMaxBytes"] // 8 // (PG_ROWS_SIDE * PG_ROWS_SIDE)
         assert B * PG_ROWS_SIDE * PG_ROWS_SIDE * 8 == CAPS["kPgMaxBytes"] and B <= MAX_BATCH
@@ -362,6 +542,23 @@ def family_rows(tool):
         p8 = _scene(tool, "rows prototypes", np.repeat(rows_label_kinds(8), ROWS_VARIANTS, axis=0), 8, 46, None,
                     params=dict(t["params"], rwc=True))
         out.append(_gathered(p8, index_map(B, ROWS_KINDS * ROWS_VARIANTS, 2 * ROWS_VARIANTS + 1, 47), "rows-scratch", "kLcMaxScratch"))
+    if tool == "spots":                                  # the list's cap and the scratch's, each met exactly
+        lp = spots_list_protos()
+        assert LIST_BATCH * lp["max_label"] == CAPS["kSdMaxRows"] and LIST_BATCH * (LIST_SIDE // 2) ** 2 == CAPS["kSdMaxSpots"]
+        out.append(_gathered(lp, spots_list_index(), "spots-list", "kSdMaxSpots"))
+        B, per = scratch_batch(), 12 * SCRATCH_SIDE * SCRATCH_SIDE
+        assert B * per < CAPS["kSdMaxScratch"] <= (B + 1) * per and B <= MAX_BATCH and B * 8 <= CAPS["kSdMaxRows"]
+        out.append(_gathered(spots_scratch_protos(), index_map(B, 6, 2, 55), "scratch", "kSdMaxScratch"))
+    if tool == "focus":                                  # the cells are rows x channels: the same 4096 images with four channels
+        C = CAPS["kIqMaxChannels"]
+        top4 = cap // (ROWS_BATCH * C)
+        assert ROWS_BATCH * top4 * C == cap and top4 == ROWS_SIDE * ROWS_SIDE
+        # a fifth kind: every pixel an object of its own, as many objects as lf_pass's table has slots above one channel (256), so
+        # that some find no slot within its 16 probes and go straight to the dense tables
+        own = np.arange(1, top4 + 1, dtype=np.int32).reshape(1, ROWS_SIDE, ROWS_SIDE)
+        labs = np.repeat(np.concatenate([rows_label_kinds(top4), own]), ROWS_VARIANTS, axis=0)
+        p4 = _scene(tool, "rows prototypes", labs, top4, 48, None, image=IR.noise(labs.shape, C, np.uint16, 48))
+        out.append(_gathered(p4, index_map(ROWS_BATCH, len(labs), 2 * ROWS_VARIANTS + 2, 49), "rows-channels", ROW_CAP[tool]))
     return out
 
 
@@ -393,8 +590,14 @@ def family_sides(tool):
             seeds, mask = corridor(shape)
             out.append(_frozen(dict(name=name, tool=tool, seeds=seeds, mask=mask, guide=None, params=dict(PROPAGATE), cap="kMaxSide")))
             continue
+        if tool == "quality":                            # without a mesh, and with one of 256 tiles along the long side
+            img = QY.noise((2,) + shape, 1, np.uint16, 70 + k)[..., 0]
+            out += [_image_scene(tool, name, img, "kMaxSide"), _image_scene(tool, name + " tile16", img, "kMaxSide", tile=16)]
+            continue
         lab = np.stack([IR.contents(shape, 50 + k)[0][1], IR.contents(shape, 60 + k)[1][1]])          # disks, then single pixels
-        out.append(_scene(tool, name, lab, max(1, int(lab.max())), 70 + k, "kMaxSide"))
+        # the spots' widest tables: both radii 64 fold many times over the short side, and at H = 4096 sd_cols asks for its most LDS
+        more = dict(params=dict(SPOTS_WIDE)) if tool == "spots" else {}
+        out.append(_scene(tool, name, lab, max(1, int(lab.max())), 70 + k, "kMaxSide", **more))
     return out
 
 
@@ -405,12 +608,14 @@ def small_scene(tool):
     k = HS.inputs_of(1)
     if tool == "propagate":
         return _frozen(dict(name="small", tool=tool, seeds=k["seeds"], mask=k["mask"], guide=k["plane"], params=dict(PROPAGATE), cap=None))
+    if tool in LABEL_FREE:
+        return _image_scene(tool, "small", k["plane"], None)
     c = TOOLS[tool]["channels"]
     return _scene(tool, "small", k["labels"], k["max_label"], 0, None, image=None if c == 0 else k["plane"] if c == 1 else k["image"])
 
 
 FAMILIES = {"batch": family_batch, "labels": family_labels, "rows": family_rows, "sides": family_sides}
-REASONS = (NO_TABLE, NO_CAP)
+REASONS = (NO_TABLE, NO_CAP, NO_LABELS)
 
 
 @functools.lru_cache(maxsize=None)
@@ -432,7 +637,13 @@ def restate(x):
 
 def gather(tool, tables, index):
     """The tables of the images index[b] of a batch whose tables are `tables`: every table has the image first, but the
-    neighbours' CSR offsets and pair list, which run through the whole batch."""
+    neighbours' CSR offsets and pair list and the spots' offsets and list, which run through the whole batch (RUNNING)."""
+    if tool == "spots":                                  # counts, offsets, the list, then geom and records (with labels), the response
+        counts, offsets, lst = tables[:3]
+        per = [lst[offsets[p]:offsets[p + 1]] for p in range(len(counts))]
+        ends = np.concatenate([[0], np.cumsum(counts[index, 0])]).astype(offsets.dtype)
+        spread = np.concatenate([per[p] for p in index]).astype(lst.dtype).reshape(-1, lst.shape[1])
+        return (counts[index], ends, spread) + tuple(t[index] for t in tables[3:])
     if tool != "neighbors":
         return tuple(t[index] for t in tables)
     geom, objects, offsets, pairs = tables
@@ -462,11 +673,23 @@ def absent_rows(x):
 def table_bytes(x):
     """The bytes of the largest table the scene's call returns, and of all of them, from the documented shapes."""
     tool, p = x["tool"], x["params"]
-    key = "seeds" if tool == "propagate" else "labels"
+    key = "image" if tool in LABEL_FREE else "seeds" if tool == "propagate" else "labels"
     images = x["batch"] if "index" in x else x[key].shape[0]
+    one = (x["protos"] if "index" in x else x)
     if tool in ("expand", "propagate"):
-        n = images * (x["protos"] if "index" in x else x)[key][0].size
+        n = images * one[key][0].size
         sizes = [4 * n, (8 if tool == "propagate" else 2) * n]
+    elif tool == "quality":                              # records, and the mesh where there is one
+        H, W = one["image"].shape[1:3]
+        C = one["image"].shape[3] if one["image"].ndim == 4 else 1
+        m_r, m_c = QY.mesh_dims(H, W, p["tile"])
+        sizes = [104 * images * C] + ([64 * images * C * m_r * m_c] if p["tile"] else [])
+    elif tool == "spots":                                # geom, records, the response, and the list at the most it can hold
+        pixels, rows = images * one["labels"][0].size, images * x["max_label"]
+        sizes = [24 * rows, 48 * rows, 4 * pixels, 32 * min(CAPS["kSdMaxSpots"], pixels), 16 * images]
+    elif tool == "focus":
+        rows = images * x["max_label"]
+        sizes = [24 * rows, 40 * rows * (one["image"].shape[3] if one["image"].ndim == 4 else 1)]
     else:
         rows = images * x["max_label"]
         C = TOOLS[tool]["channels"]

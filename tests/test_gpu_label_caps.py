@@ -1,5 +1,6 @@
-"""The ten label tools, the matcher and the segmenter run at the caps their argument checks accept (tests/label_caps.py): 65535
-images in one call, a label equal to kMaxLabel, each tool's own row, cell or byte cap met exactly, and the four thin planes with a
+"""The ten label tools, the matcher, the spot detector, the focus and image quality records and the segmenter run at the caps their
+argument checks accept (tests/label_caps.py): 65535 images in one call, a label equal to kMaxLabel, each tool's own row, cell, list,
+mesh or byte cap met exactly (and, where the library counts before it refuses, missed by one), and the four thin planes with a
 side of 4096.  Every node is one (tool, scene); every integer table is compared with np.array_equal, dtype and shape against the
 tool's own CPU restatement, texture's clogc within the CLOGC_REL of tests/test_gpu_texture.py.  Behind each cap run the same handle
 takes one small ordinary call (input 1 of tests/handle_schedule.py): a buffer grown to the cap and reused small.
@@ -7,7 +8,9 @@ takes one small ordinary call (input 1 of tests/handle_schedule.py): a buffer gr
 Memory kinds: the `labels` scenes and the `rows` scenes of the tools that also have a `rows4` scene go in as CUDA tensors, and their
 tables are written on the device and copied to the host here; everything else goes in as numpy arrays and comes back through the
 library's own staging, so each tool's tables at its cap take both ways at least once.  measure_dense and match_batch always hand
-the library host tables, so DeviceTables stands between such a wrapper and the library for that one call.
+the library host tables, so DeviceTables stands between such a wrapper and the library for that one call.  The image quality records
+take no labels: their scenes with a mesh go in as tensors.  The spot detector writes its tables on the device whenever its images
+are tensors, so it needs no proxy.
 
 Sizes: the largest table of a node is texture's marginals at its cell cap, 1 GiB (2^21 rows x 4 directions x 32 int32); the largest
 sum of a node's tables is the propagator's, 2.8 GiB on the device at kPgMaxBytes (keys 1 GiB, costs 1 GiB, labels 512 MiB, two
@@ -27,11 +30,14 @@ from cellscreen import granularity as GR
 from cellscreen import intensity as IN
 from cellscreen import neighbors as NB
 from cellscreen import propagate as PG
+from cellscreen.preprocess import PIX_U8, PIX_U16
+from cellscreen import quality as Q
 from cellscreen import quantile as QU
 from cellscreen import radial as RA
 from cellscreen import score as SC
 from cellscreen import segment as S
 from cellscreen import shape as SH
+from cellscreen import spots as SP
 from cellscreen import texture as TX
 
 pytestmark = pytest.mark.gpu
@@ -39,7 +45,8 @@ pytestmark = pytest.mark.gpu
 CLOGC_REL = 2.0 ** -40                                   # tests/test_gpu_texture.py
 MAKE = {"expand": EX.LabelExpander, "intensity": IN.IntensityMeasurer, "quantiles": QU.QuantileMeasurer, "texture": TX.TextureMeasurer,
         "shape": SH.ShapeMeasurer, "neighbors": NB.NeighborMeasurer, "colocalize": CO.ColocalizationMeasurer, "radial": RA.RadialMeasurer,
-        "granularity": GR.GranularityMeasurer, "propagate": PG.LabelPropagator, "match": SC.LabelMatcher}
+        "granularity": GR.GranularityMeasurer, "propagate": PG.LabelPropagator, "match": SC.LabelMatcher, "spots": SP.SpotDetector,
+        "focus": Q.ImageQualityMeasurer, "quality": Q.ImageQualityMeasurer}
 HAS_ROWS4 = tuple(t for t, d in LC.TOOLS.items() if d["factor"] == 1)
 
 
@@ -53,7 +60,7 @@ def as_tensor(a):
 # per entry point: how many table pointers stand in front of out_kind, and how many arguments behind it (include/cellscreen.h)
 OUT_ARGS = {"cs_label_intensity": (2, 0), "cs_label_quantiles": (3, 0), "cs_label_texture": (5, 0), "cs_label_shape": (5, 0),
             "cs_label_neighbors": (3, 1), "cs_label_colocalize": (4, 0), "cs_label_radial": (5, 0), "cs_label_granularity": (4, 0),
-            "cs_label_match": (2, 1)}
+            "cs_label_match": (2, 1), "cs_image_quality": (2, 0), "cs_object_focus": (2, 0)}
 
 
 class DeviceTables:
@@ -102,7 +109,15 @@ def call(t, x, on_device):
     if tool == "propagate":
         out = t.propagate_batch(put(x["seeds"]), mask=put(x["mask"]), guide=put(x["guide"]), return_cost=True, **p)
         return tuple(o if isinstance(o, np.ndarray) else o.cpu().numpy() for o in out)
-    lab, image, M = put(x["labels"]), put(x["image"]), x["max_label"]
+    if tool == "quality":
+        return tuple(o for o in t.measure_batch_dense(put(x["image"]), p["tile"], p["sat_level"]) if o is not None)
+    lab, image, M = put(x.get("labels")), put(x["image"]), x.get("max_label")
+    if tool == "spots":                                  # the response is always asked for; without labels no geom and no records
+        prm = SP.spot_params(p["sigma"], sigma_coarse=p["sigma_coarse"], min_distance=p["min_distance"])
+        out = t.detect_dense(image, p["threshold"], lab, None, M, prm, True)
+        return tuple(o if isinstance(o, np.ndarray) else o.cpu().numpy() for o in out if o is not None)
+    if tool == "focus":
+        return t.measure_objects_dense(image, lab, max_label=M)
     if tool == "expand":
         out = t.expand_batch(lab, p["distance"], return_d2=True)
         out = tuple(o if isinstance(o, np.ndarray) else o.cpu().numpy() for o in out)
@@ -165,7 +180,8 @@ def run_node(tool, family, n):
     want = LC.expected(LC.scenes(tool, family)[n])                                # outside the times below
     small = LC.small_scene(tool)
     small_want = LC.expected(small)
-    on_device = family == "labels" or x["name"] == "rows-scratch" or (x["name"] == "rows" and tool in HAS_ROWS4)
+    on_device = family == "labels" or x["name"] == "rows-scratch" or (x["name"] == "rows" and tool in HAS_ROWS4) or \
+        (tool == "quality" and x["params"]["tile"] > 0)
     what = f"{tool} {x['name']} on {x['cap']}, tensors={on_device}"
     t = MAKE[tool](0)
     try:
@@ -175,15 +191,17 @@ def run_node(tool, family, n):
         t0 = time.perf_counter()
         got = call(t, x, on_device)
         t1 = time.perf_counter()
+        timing = t.last_timing()                         # the cap call's own, before the small call replaces it
         assert not isinstance(t._lib, DeviceTables) or t._lib.calls == 1
         t._lib = lib
         same(tool, got, want, what)
-        if family in ("labels", "rows") and tool != "propagate":
+        # the spots-list scene has every row present (tests/test_label_caps_cpu.py), the image quality records have no label rows
+        if family in ("labels", "rows") and tool != "propagate" and tool not in LC.LABEL_FREE and x["name"] != "spots-list":
             absent_rows_are_empty(x, got)
         del got, want
         t2 = time.perf_counter()
         same(tool, call(t, small, not on_device), small_want, f"{tool}, small, behind {x['name']}")
-        print(f"\n{what}: {t1 - t0:.2f} s the call, {time.perf_counter() - t2:.2f} s the small call behind it; device {t.last_timing()}")
+        print(f"\n{what}: {t1 - t0:.2f} s the call, {time.perf_counter() - t2:.2f} s the small call behind it; device {timing}")
     finally:
         t.close()
 
@@ -210,6 +228,78 @@ def test_row_cell_or_byte_cap_met_exactly(tool, family, n):
 @pytest.mark.parametrize("tool,family,n", ids_of("sides"))
 def test_thin_planes_with_a_side_of_4096(tool, family, n):
     run_node(tool, family, n)
+
+
+CS_ERR_INVALID, CS_ERR_UNSUPPORTED = -1, -6              # include/cellscreen.h
+
+
+def small_call_is_right(t, tool, behind):
+    small = LC.small_scene(tool)
+    same(tool, call(t, small, True), LC.expected(small), f"{tool}, small, behind {behind}")
+
+
+def test_one_spot_more_than_the_list_holds_is_refused():
+    """The spots-list scene's images and one more with one bright pixel, without labels: cs_spot_detect finds 2^22 + 1 spots, writes
+    the first 2^22 (no position at or beyond the capacity is stored), and refuses the call once it has read the count; no list is
+    left for cs_spot_fill, and the handle takes the small call."""
+    x = LC.spots_over_the_list()
+    t = SP.SpotDetector(0)
+    try:
+        t0 = time.perf_counter()
+        with pytest.raises(L.CellScreenError) as ei:
+            call(t, x, False)
+        dt, timing = time.perf_counter() - t0, t.last_timing()
+        assert ei.value.status == CS_ERR_UNSUPPORTED and "capped at" in str(ei.value) and f"{LC.CAPS['kSdMaxSpots'] + 1} spots" in str(ei.value)
+        offsets = np.zeros(len(x["image"]) + 1, np.int64)
+        assert t._lib.cs_spot_fill(t._handle, None, 0, L._ptr(offsets), L.CS_MEM_HOST) == CS_ERR_INVALID
+        assert "no spot list" in t._lib.cs_last_error().decode() and not offsets.any()
+        small_call_is_right(t, "spots", "a refused list")
+        print(f"\nspots, one above kSdMaxSpots: {dt:.2f} s the refused call; device {timing}")
+    finally:
+        t.close()
+
+
+def test_one_image_more_than_the_spot_scratch_holds_is_refused():
+    """21846 images of 64 x 64 need 2^30 bytes of scratch or more: refused by the wrapper, and by the entry point itself before it
+    touches the device, so a one-image buffer stands in for the stack."""
+    B, s = LC.scratch_batch() + 1, LC.SCRATCH_SIDE
+    t = SP.SpotDetector(0)
+    try:
+        with pytest.raises(ValueError, match="scratch"):
+            t.detect_dense(np.zeros((B, s, s), np.uint16), 1.0)
+        img, thr, counts, n = np.zeros((1, s, s), np.uint16), np.full(B, 256, np.int32), np.full((1, 2), -1, np.int64), C.c_int64(-1)
+        prm = SP.spot_params(LC.SPOTS["sigma"], sigma_coarse=LC.SPOTS["sigma_coarse"], min_distance=LC.SPOTS["min_distance"])
+        for batch, status in ((B, CS_ERR_UNSUPPORTED), (1, 0)):                  # and the same arguments with one image are taken
+            rc = t._lib.cs_spot_detect(t._handle, L._ptr(img), PIX_U16, 1, None, None, batch, s, s, L.CS_MEM_HOST, 0, C.byref(prm), L._ptr(thr),
+                                       L._ptr(counts), None, None, None, L.CS_MEM_HOST, C.byref(n))
+            assert rc == status, (batch, rc, t._lib.cs_last_error().decode())
+            if status:
+                assert "scratch" in t._lib.cs_last_error().decode() and n.value == -1 and (counts == -1).all()
+        assert n.value == 0 and not counts.any()
+        small_call_is_right(t, "spots", "a refused stack")
+    finally:
+        t.close()
+
+
+def test_one_image_more_than_the_mesh_holds_is_refused():
+    """32769 images x 4 channels x a mesh of 2 x 4 are 2^20 + 32 tiles: refused by the wrapper and by the entry point."""
+    (x,) = LC.scenes("quality", "rows")
+    B, (H, W), tile, nc = x["batch"] + 1, LC.TILES_SHAPE, LC.TILES_TILE, LC.CAPS["kIqMaxChannels"]
+    t = Q.ImageQualityMeasurer(0)
+    try:
+        with pytest.raises(ValueError, match="tiles"):
+            t.measure_batch_dense(np.zeros((B, H, W, nc), np.uint8), tile=tile)
+        img, records, mesh = np.zeros((1, H, W, nc), np.uint8), np.full((1, nc, 13), -1, np.int64), np.full((1, nc, 2, 4, 8), -1, np.int64)
+        for batch, status in ((B, CS_ERR_UNSUPPORTED), (1, 0)):
+            rc = t._lib.cs_image_quality(t._handle, L._ptr(img), PIX_U8, nc, batch, H, W, L.CS_MEM_HOST, tile, None, L._ptr(records), L._ptr(mesh),
+                                         L.CS_MEM_HOST)
+            assert rc == status, (batch, rc, t._lib.cs_last_error().decode())
+            if status:
+                assert "capped at" in t._lib.cs_last_error().decode() and (records == -1).all() and (mesh == -1).all()
+        assert records[0, :, 0].tolist() == [H * W] * nc and mesh[..., 0].sum() == nc * H * W
+        small_call_is_right(t, "quality", "a refused stack")
+    finally:
+        t.close()
 
 
 @pytest.mark.parametrize("case", list(LC.SEGMENT_CASES))

@@ -8,7 +8,8 @@ A lane of either pass owns 4 columns x 16 rows, a wave 256 columns, a workgroup 
 from the next lanes: SHAPES has the sides without an interior, the smallest with one, and 64 x 256 one short, equal, one and two
 past in both axes, so that the stencil crosses lanes, waves and workgroup tiles.  Widths that are no multiple of 4 take the
 narrow loads.  Mesh tiles of 16, 17, 64 and 256 on 130 x 515 put the mesh's borders off the workgroup tile's (and, at 16, more
-mesh tiles under a workgroup than its table in LDS holds)."""
+mesh tiles under a workgroup than its table in LDS holds).  With every pixel an object of its own, 64 x 256 and 70 x 300 put more
+objects under a workgroup than lf_pass's table in LDS has slots, at one, three and four channels."""
 import functools
 
 import numpy as np
@@ -154,6 +155,27 @@ def test_object_focus_equals_the_restatement_and_geom_equals_intensity(measurer)
     image = image_of((66, 260), 3, np.uint8, 4)
     _, f = measurer.measure_objects_dense(image, whole)
     assert np.array_equal(f[:, 0], want_image((66, 260), 3, np.uint8, 4)[0][:, :, FOCUS_OF_RECORD])
+
+
+@pytest.mark.parametrize("shape", [(64, 256), (70, 300)])
+def test_every_pixel_its_own_label_overflows_the_table_in_lds(measurer, shape):
+    """lf_pass keeps the objects of a 64 x 256 tile in a table in LDS, 512 slots at one channel and 256 above; what finds no slot
+    within 16 probes goes straight to the dense tables (lf_insert -> lf_global).  With every pixel an object of its own a full
+    tile holds 16384: most of them take the direct way."""
+    H, W = shape
+    n = H * W
+    lab = np.stack([np.arange(1, n + 1, dtype=np.int32).reshape(shape), np.arange(n, 0, -1, dtype=np.int32).reshape(shape)])
+    ex = (lab % 3 == 0).astype(np.int32)
+    assert min(H, 64) * min(W, 256) > 512
+    for nc in (1, 3, 4):
+        image = image_of(shape, nc, np.uint16, 40 + nc)
+        for e in (None, ex):
+            got = measurer.measure_objects_dense(image, lab, exclude=e, max_label=n)
+            same_objects(got, QR.measure_objects(image, lab, e, n))
+            assert got[0][:, :, 0].max() == 1 and (e is None) == bool((got[0][:, :, 0] == 1).all())
+        interior = np.zeros(shape, bool)
+        interior[1:-1, 1:-1] = True                                      # n_int of a one-pixel object: whether the pixel is interior
+        assert np.array_equal(got[1][0, :, 0, 0].reshape(shape) == 1, interior & (ex[0] == 0))
 
 
 def test_a_bad_label_is_an_error_status_and_the_handle_stays_usable(measurer):

@@ -2,8 +2,8 @@
 about twenty device buffers that only grow, nearly all reused under another element type by another entry point, so that a call
 works inside whatever the one before left.  Each tool's own test runs it alone, or behind a plain segmenter and the expander; here
 every tool follows every other one (tests/handle_schedule.py: an Eulerian circuit of the complete directed graph on the tools), on
-inputs that shrink and grow, and follows every other tool's refused call; and the neighbour pair list is fetched after other stages
-ran on its handle.  All tables compared are integers: np.array_equal against each tool's own CPU restatement."""
+inputs that shrink and grow, and follows every other tool's refused call; and the neighbour pair list and the spot list are fetched
+after other stages ran on their handle.  All tables compared are integers: np.array_equal against each tool's own CPU restatement."""
 import ctypes as C
 import math
 import time
@@ -20,11 +20,14 @@ from cellscreen import granularity as GR
 from cellscreen import intensity as IN
 from cellscreen import neighbors as NB
 from cellscreen import propagate as PG
+from cellscreen.preprocess import PIX_U16
+from cellscreen import quality as Q
 from cellscreen import quantile as QU
 from cellscreen import radial as RA
 from cellscreen import score as SC
 from cellscreen import segment as S
 from cellscreen import shape as SH
+from cellscreen import spots as SP
 from cellscreen import texture as TX
 
 pytestmark = pytest.mark.gpu
@@ -41,7 +44,8 @@ def tools():
                 shape=SH.ShapeMeasurer(0, extractor=seg), neighbors=NB.NeighborMeasurer(0, extractor=seg),
                 colocalize=CO.ColocalizationMeasurer(0, extractor=seg), radial=RA.RadialMeasurer(0, extractor=seg),
                 granularity=GR.GranularityMeasurer(0, extractor=seg), match=SC.LabelMatcher(0, extractor=seg), extract=ext,
-                propagate=PG.LabelPropagator(0, extractor=seg))
+                propagate=PG.LabelPropagator(0, extractor=seg), spots=SP.SpotDetector(0, extractor=seg),
+                quality=Q.ImageQualityMeasurer(0, extractor=seg), focus=Q.ImageQualityMeasurer(0, extractor=seg))
     assert set(made) == set(HS.ACTORS) and all(t._handle is ext._handle for t in made.values())
     yield made
     assert all(t._pre is None for name, t in made.items() if name != "extract")   # nobody made a handle of its own
@@ -107,6 +111,12 @@ def call(tools, actor, k, on_device=False, exclude=False, labels=None, max_label
     elif actor == "propagate":
         out = t.propagate_batch(on(k, "seeds", on_device) if labels is None else labels, mask=on(k, "mask", on_device), guide=image,
                                 max_cost=HS.inputs_of(k)["max_cost"], return_cost=True, **HS.PROPAGATE)
+    elif actor == "spots":
+        out = t.detect_dense(image, HS.SPOT_THRESHOLDS[k], lab, ex, max_label, SP.spot_params(**HS.SPOTS), True)
+    elif actor == "quality":
+        out = t.measure_batch_dense(image, tile=HS.QUALITY_TILE, sat_level=list(HS.SAT_LEVELS[k]))
+    elif actor == "focus":
+        out = t.measure_objects_dense(image, lab, exclude=ex, max_label=max_label)
     else:
         r = t.extract_batch(on(k, "plane", on_device), lab)
         reg = r.regions
@@ -167,6 +177,39 @@ def test_a_refused_call_leaks_nothing_into_the_next_tool(tools):
         with pytest.raises(L.CellScreenError):
             call(tools, failing, 0, labels=big, max_label=HS.inputs_of(0)["max_label"])
         same(call(tools, after, 1), HS.expected(after, 1), f"{after}, small, behind a refused large {failing}")
+
+
+def test_spot_list_survives_other_stages(tools):
+    """The spot list "stays on the handle until the next cs_spot_detect" (include/cellscreen.h).  cs_spot_detect works in the
+    planes of cs_segment_smooth and of the split, in the mask, count and chunk buffers and in the staging area; between it and
+    cs_spot_fill a smoothing intensity split, the granularity spectrum, a propagation, the image quality and focus records and a
+    small split run on the handle.  The list is then fetched twice: to the host, and into CUDA tensors."""
+    import torch
+    lib, h = tools["spots"]._lib, tools["spots"]._handle
+    prm = SP.spot_params(**HS.SPOTS)
+    for k in (2, 0):
+        x = HS.inputs_of(k)
+        img, lab, m = x["image"], x["labels"], x["max_label"]
+        B, H, W = lab.shape
+        want = HS.expected("spots", k)
+        thr = np.full(B, int(round(256 * HS.SPOT_THRESHOLDS[k])), np.int32)
+        counts, geom, records = np.empty((B, 2), np.int64), np.empty((B, m, 3), np.int64), np.empty((B, m, 6), np.int64)
+        n = C.c_int64(-1)
+        assert img.dtype == np.uint16
+        assert lib.cs_spot_detect(h, img.ctypes.data, PIX_U16, img.shape[3], lab.ctypes.data, None, B, H, W, L.CS_MEM_HOST, m, C.byref(prm),
+                                  thr.ctypes.data, counts.ctypes.data, geom.ctypes.data, records.ctypes.data, None, L.CS_MEM_HOST, C.byref(n)) == 0
+        assert n.value == len(want[2]) > 0
+        for actor, kk in (("split_intensity", 0), ("granularity", 0), ("propagate", 0), ("quality", 0), ("focus", 0), ("split", 1)):
+            exclude = actor in HS.HAS_EXCLUDE
+            same(call(tools, actor, kk, False, exclude), HS.expected(actor, kk, exclude), f"{actor} between the two calls")
+        lst, offsets = np.full((n.value, 8), -1, np.int32), np.full(B + 1, -1, np.int64)
+        assert lib.cs_spot_fill(h, lst.ctypes.data, n.value, offsets.ctypes.data, L.CS_MEM_HOST) == 0
+        same((counts, offsets, lst, geom, records), want[:5], f"the spot list of input {k} after other stages, on the host")
+        dev = torch.device("cuda", 0)
+        d_lst, d_off = torch.full((n.value, 8), -1, dtype=torch.int32, device=dev), torch.full((B + 1,), -1, dtype=torch.int64, device=dev)
+        torch.cuda.synchronize()                         # the fills are done before the handle's own stream writes
+        assert lib.cs_spot_fill(h, d_lst.data_ptr(), n.value, d_off.data_ptr(), L.CS_MEM_DEVICE) == 0
+        same((d_off.cpu().numpy(), d_lst.cpu().numpy()), want[1:3], f"the spot list of input {k} after other stages, on the device")
 
 
 def test_pair_list_survives_other_stages(tools):

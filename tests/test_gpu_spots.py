@@ -6,7 +6,8 @@ geometry and records with the rows of absent objects, and the response plane whe
 
 The row pass stages segments of SD_ROW_SEG pixels, the column pass tiles of SD_COL_TR rows by 64 columns, the peak pass tiles of
 SD_PK_H by SD_PK_W with a halo of m; the sizes are read from csrc/spots.hip, so the shapes follow the code.  The spot-count cap
-(2^22 per call) is not driven here: a list that long needs a plane the cap suite is the place for."""
+(2^22 per call) is not driven here: tests/test_gpu_label_caps.py meets it exactly (4096 images of 64 x 64 with 1024 spots each)
+and misses it by one, and runs the detector at its other caps."""
 import functools
 import os
 import re
@@ -255,6 +256,48 @@ def test_objects_exclude_and_geom_equals_intensity(det):
     lonely = np.where(lab == 3, 0, lab)                                  # objects that hold no spot keep a zero record
     high = check(det, img, 1000000, p, lonely, None, None)             # only the three bright pixels are left
     assert high[0][:, 0].tolist() == [3, 0] and (high[4][:, :, 0] == 0).sum() == 9
+
+
+# ---- more objects than the tables in LDS hold -------------------------------------------------------------------------------------
+LDS_SLOTS, PLACE_ROWS = 512, 256                                         # spots.hip: 1 << SD_SLOTS_LOG2, SD_CHUNK
+
+
+@pytest.mark.parametrize("shape", [(64, 256), (70, 300)])
+def test_every_pixel_its_own_label_overflows_the_tables_in_lds(det, shape):
+    """sd_geom keeps the objects of a 64 x 256 tile, and sd_place the objects that hold the spots of its 256 image rows, in a table
+    of 512 slots in LDS; what finds no slot within 16 probes goes straight to the dense table.  Here every pixel is an object
+    of its own and every second pixel of every second row a spot, so both tables fill and most records take the direct way."""
+    Hh, Ww = shape
+    n = Hh * Ww
+    lab = np.stack([np.arange(1, n + 1, dtype=np.int32).reshape(shape), np.arange(n, 0, -1, dtype=np.int32).reshape(shape)])
+    img = noise((2,) + shape, np.uint16, 12, 300)
+    img[:, ::2, ::2] += 4000
+    ex = (lab % 3 == 0).astype(np.int32)
+    p = SP.spot_params(min_distance=1, **IDENT)
+    assert min(Hh, 64) * min(Ww, 256) > LDS_SLOTS                        # the objects of sd_geom's first tile
+    for e in (None, ex):
+        want = check(det, img, 256, p, lab, e, n)
+        counts, off, lst, geom, rec = want[:5]
+        assert counts[:, 0].tolist() == [((Hh + 1) // 2) * ((Ww + 1) // 2)] * 2          # the lattice and nothing else
+        on = lst[:, 2] > 0
+        image = np.repeat(np.arange(2), np.diff(off))
+        chunk = (image * Hh + lst[:, 0]) // PLACE_ROWS                   # the workgroup of sd_place that places the spot
+        per_chunk = [len(set(zip(image[on & (chunk == k)].tolist(), lst[on & (chunk == k), 2].tolist()))) for k in np.unique(chunk)]
+        assert max(per_chunk) > LDS_SLOTS, per_chunk
+        assert int(rec[:, :, 0].sum()) == int(on.sum()) and rec[:, :, 0].max() == 1 and geom[:, :, 0].max() == 1
+        assert (e is None) == (int(on.sum()) == len(lst)) and (e is None) == bool((geom[:, :, 0] == 1).all())
+
+
+@pytest.mark.parametrize("dtype", [np.uint8, np.uint16], ids=["uint8", "uint16"])
+def test_both_radii_64_on_a_full_column_tile(det, dtype):
+    """sd_cols asks for the most LDS it ever does, 100352 bytes (above the 64 KiB a kernel gets unasked), where both tables have
+    radius 64 and the tile has all its 64 rows: 70 rows are one such tile and one of 6."""
+    assert K["SD_COL_TR"] == 64
+    img = noise((2, 70, 130), dtype, 13)
+    p = SP.spot_params(15.9, sigma_coarse=16.1, min_distance=2)
+    assert (p.radius_a, p.radius_b) == (64, 64)
+    want = check(det, img, 1, p)
+    assert want[0][:, 0].min() > 0
 
 
 # ---- list order -----------------------------------------------------------------------------------------------------------------

@@ -50,6 +50,29 @@ def test_inputs_are_what_the_tools_accept():
         assert (n >= 2).all(), (name, n)
 
 
+def test_the_three_newest_actors_have_something_to_find():
+    assert len(HS.ACTORS) == 17 and HS.ACTORS[-3:] == ("spots", "quality", "focus") and len(HS.schedule()) == 17 * 16 + 1 == 273
+    assert {"spots", "focus"} <= set(HS.HAS_EXCLUDE) <= set(HS.RANGE_CHECKED) and "quality" not in HS.RANGE_CHECKED
+    for k, (B, H, W) in enumerate(HS.INPUTS):
+        x = HS.inputs_of(k)
+        top = int(np.iinfo(HS.DTYPES[k]).max)
+        plain = HS.expected("spots", k)
+        for exclude in (False, True):
+            counts, offsets, lst, geom, records, response = HS.expected("spots", k, exclude)
+            assert offsets[-1] == len(lst) > 0 and (lst[:, 2] > 0).any() and response.shape == (B, H, W)      # a spot on a labelled pixel
+            assert geom.shape == (B, x["max_label"], 3) and records[..., 0].sum() == (lst[:, 2] > 0).sum()
+            assert (lst[:, 3] >= 256 * HS.SPOT_THRESHOLDS[k]).all()
+        assert (response >= 256 * HS.SPOT_THRESHOLDS[k]).sum() > len(lst)          # the window prunes, and the threshold cuts:
+        assert (response >= 256).sum() > (response >= 256 * HS.SPOT_THRESHOLDS[k]).sum()      # not every positive pixel passes
+        assert not np.array_equal(HS.expected("spots", k, True)[3], plain[3])     # the exclude plane takes pixels from the objects
+        records, mesh = HS.expected("quality", k)
+        assert records.shape == (B, 2, 13) and mesh.shape == (B, 2, -(-H // 16), -(-W // 16), 8)
+        assert all(0 < s < top for s in HS.SAT_LEVELS[k]) and (records[:, :, 7] > 0).all() and (records[:, :, 7] < records[:, :, 0]).all()
+        g0, f0 = HS.expected("focus", k)
+        g1, f1 = HS.expected("focus", k, True)
+        assert f0.shape == (B, x["max_label"], 2, 5) and f0.any() and not np.array_equal(f0, f1) and np.array_equal(g0, plain[3])
+
+
 def test_windowed_expansion_is_the_whole_image_s():
     lab = np.stack([ER.disks((45, 70), 9, 4), ER.disks((45, 70), 3, 5)])
     for distance, side in ((3, 32), (4, 16), (11, 20)):
