@@ -5,6 +5,7 @@ from . import spec  # noqa: F401
 from .colocalize import ColocalizationMeasurer, ColocalizationTable, colocalization_table, colocalize_params  # noqa: F401
 from .expand import LabelExpander, expand_params  # noqa: F401
 from .granularity import GranularityMeasurer, GranularityTable, granularity_params, granularity_table  # noqa: F401
+from .illumination import IlluminationCorrector, IlluminationFunction  # noqa: F401
 from .intensity import IntensityMeasurer, ObjectTable  # noqa: F401
 from .neighbors import NeighborMeasurer, NeighborTable, neighbor_params, neighbor_table  # noqa: F401
 from .propagate import LabelPropagator, propagate_params  # noqa: F401
@@ -23,4 +24,4 @@ __all__ = ["spec", "CAEWeights", "DetectorParams", "OCSVMParams", "LabelExpander
            "RadialMeasurer", "RadialTable", "radial_params", "radial_table",
            "GranularityMeasurer", "GranularityTable", "granularity_params", "granularity_table", "LabelPropagator", "propagate_params",
            "ImageQualityMeasurer", "ImageQualityTable", "ObjectFocusTable", "image_quality_table", "object_focus_table",
-           "SpotDetector", "SpotTable", "dog_noise_gain", "spot_params", "spot_table"]
+           "SpotDetector", "SpotTable", "dog_noise_gain", "spot_params", "spot_table", "IlluminationCorrector", "IlluminationFunction"]

@@ -181,6 +181,17 @@ class CSSpotParams(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class CSIllumReduceParams(C.Structure):
+    _fields_ = [("a_num", C.c_int32), ("a_den", C.c_int32), ("mean", C.c_int32), ("offset", C.c_int32 * 4), ("floor", C.c_int32),
+                ("mesh_median", C.c_int32), ("radius", C.c_int32), ("weights", C.c_int32 * (SMOOTH_MAX_RADIUS + 1)),
+                ("reserved", C.c_int32 * 2)]
+
+
+class CSIllumApplyParams(C.Structure):
+    _fields_ = [("tile", C.c_int32), ("floor", C.c_int32), ("g8", C.c_int32 * 4), ("offset", C.c_int32 * 4), ("pedestal", C.c_int32 * 4),
+                ("reserved", C.c_int32 * 2)]
+
+
 # cs_region of include/cellscreen.h as a numpy record (80 bytes)
 REGION_DTYPE = np.dtype([("image", np.int32), ("label", np.int32), ("minr", np.int32), ("minc", np.int32), ("maxr", np.int32),
                          ("maxc", np.int32), ("area", np.int64), ("convex_area", np.int64), ("eccentricity", np.float64),
@@ -287,6 +298,11 @@ SIGNATURES = {
                             _P, _P, _P, _I, C.POINTER(_L)]),
     "cs_spot_fill": (_I, [_P, _P, _L, _P, _I]),
     "cs_spot_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "cs_illum_tile_stats": (_I, [_P, _P, _I, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _I, C.c_int32, C.c_int32, C.c_int32, _P, _I]),
+    "cs_illum_reduce": (_I, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _I, C.POINTER(CSIllumReduceParams), _P, _I]),
+    "cs_illum_apply": (_I, [_P, _P, _I, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _I, _P, C.c_int32, C.c_int32, _I,
+                            C.POINTER(CSIllumApplyParams), _P, _P]),
+    "cs_illum_last_timing": (_I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "cs_fit_create": (_I, [_I, C.POINTER(_P)]),
     "cs_fit_free": (None, [_P]),
     "cs_fit_wait_stream": (_I, [_P, _P]),

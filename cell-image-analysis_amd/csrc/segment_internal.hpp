@@ -1,5 +1,5 @@
 // segment_internal.hpp -- the state behind cs_preproc::seg as its translation units share it (segment.hip, expand.hip,
-// intensity.hip, quantile.hip, texture.hip, shape.hip, neighbors.hip, colocalize.hip, radial.hip, granularity.hip, propagate.hip, quality.hip, spots.hip): the shared buffers and a clock per family of entry points.  The clock itself and
+// intensity.hip, quantile.hip, texture.hip, shape.hip, neighbors.hip, colocalize.hip, radial.hip, granularity.hip, propagate.hip, quality.hip, spots.hip, illumination.hip): the shared buffers and a clock per family of entry points.  The clock itself and
 // the argument rules are stage_host.hpp's, which extract.hip and match.hip use with states of their own.
 #pragma once
 #include "stage_host.hpp"
@@ -56,6 +56,13 @@ struct SegmentState {
     int64_t sp_n = -1;                                  // -1: no successful cs_spot_detect yet
     int sp_batch = 0;
     StageClock clk_sd;
+    // cs_illum_tile_stats, cs_illum_reduce and cs_illum_apply (illumination.hip) share the buffers: a host image (corrected in
+    // place there and copied out) or a host stack in img, a host function in lab, a mesh on its way to the host in stage, the
+    // function between its filters in ns_mesh, the Gaussian's row sums in sm_t, the clipped counts in counts.  Only the two sticky
+    // status words are their own: a call that does not synchronise leaves them for the next one that does.  A clock per call.
+    DevBuf il_status;                                   // [2] uint32: a bad value in a device stack, in a device function
+    bool il_unread = false;                             // a call since the last read did not synchronise
+    StageClock clk_il_s, clk_il_r, clk_il_a;
     StageClock clk_thr, clk_sp, clk_si, clk_bg, clk_lt, clk_cl, clk_sm, clk_hy, clk_ns, clk_ex, clk_in, clk_lq, clk_tx, clk_sh, clk_nb, clk_co, clk_ra, clk_gr, clk_gs, clk_pg;   // clk_gs: one sums pass of cs_label_granularity at a time
     int pg_rounds = 0;                                  // cs_label_propagate's last call: its rounds, the closing quiet one included
     double gr_ms[3] = {0.0, 0.0, 0.0};                  // cs_label_granularity's last call: prepare, erosions + reconstructions, sums

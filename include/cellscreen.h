@@ -42,6 +42,10 @@
  *        whether an image, a mesh tile of it or an object is worth measuring: intensity, extreme and saturation counts and
  *        the sums behind the Laplacian variance, Tenengrad and Brenner focus measures, as exact integers (CellProfiler's
  *        MeasureImageQuality: FocusScore, LocalFocusScore, PercentMinimal / PercentMaximal; no reference counterpart)
+ *   cs_illum_tile_stats / cs_illum_reduce / cs_illum_apply
+ *        flat-field correction from a plate's own images: one multiplicative illumination function per channel on a
+ *        tile mesh, estimated across all fields and divided out of every field, in integers (CellProfiler's
+ *        CorrectIlluminationCalculate / CorrectIlluminationApply; no reference counterpart)
  *   cs_spot_detect / cs_spot_fill
  *        puncta in one channel and how many of them every object holds: the local maxima of a difference-of-Gaussians
  *        response, computed in integers, as a list sorted by image and raster order and as per-object records
@@ -1351,6 +1355,80 @@ int cs_spot_detect(cs_preproc *p, const void *image, int pixel_type, int32_t cha
 int cs_spot_fill(cs_preproc *p, int32_t *list, int64_t capacity, int64_t *offsets, int out_kind);
 /* Device time of the last cs_spot_detect: clearing + the response, the peaks with their counts, and the list with the records. */
 int cs_spot_last_timing(const cs_preproc *p, double *response_ms, double *peaks_ms, double *records_ms);
+
+/* ---- flat-field correction from a plate's own images ------------------------------------------------------------------ */
+/* One multiplicative illumination function per channel, estimated from all fields of a plate and divided out of every field
+ * (tests/illumination_reference.py restates the rule, cellscreen/illumination.py drives it) -- CellProfiler's
+ * CorrectIlluminationCalculate / CorrectIlluminationApply.  All integers, no tolerance, bit-identical run to run.  The three
+ * calls keep nothing between them: the caller owns the stack of meshes and the function.
+ * The mesh is cs_segment_noise's: tile side T a power of two in 16..256, m = max(1, n / T) tiles along an axis of n pixels,
+ * tile i = [i T, (i + 1) T), the last one runs to n.
+ *
+ * cs_illum_tile_stats: per image, channel and tile the value of rank (q_num (N - 1)) / q_den among the tile's N sorted pixels,
+ *         0 <= q_num <= q_den <= 65536 (1 / 2: the lower median; 0: the minimum).
+ * image:  [batch][height][width][channels] uint8 / uint16 (pixel_type), in_kind, channels 1..4 (more: CS_ERR_UNSUPPORTED).
+ *         height, width 1..4096, batch 1..65535 (above: CS_ERR_UNSUPPORTED).
+ * mesh:   out, [batch][channels][m_y][m_x] int32, out_kind.
+ *
+ * cs_illum_reduce: per channel and node, over the n stacked meshes (1 <= n <= 16384, above: CS_ERR_UNSUPPORTED), the value of
+ *         rank (a_num (n - 1)) / a_den across the images, or with params->mean the rounded mean (2 sum + n) / (2 n); then
+ *         F8 = 256 max(value - offset[c], floor); then, where asked for, the median of the 3 x 3 mesh neighbourhood (replicated
+ *         edges) and a Gaussian over the mesh (cs_segment_smooth's table and reflection, one rounding (A + 2^31) >> 32 at the
+ *         end, floored at 256 floor again).
+ * stack:  [n][channels][m_y][m_x] int32, in_kind, every value 0..65535 (a host stack is checked and refused with
+ *         CS_ERR_INVALID before any device work; a device stack: see the status words below).  m_y, m_x 1..256.
+ * f8:     out, [channels][m_y][m_x] int32, out_kind: 256 <= F8 < 2^24.
+ *
+ * cs_illum_apply: y = clamp(pedestal[c] + floor((2 (v - offset[c]) G8[c] D + N) / (2 N)), 0, top) per pixel and channel: the
+ *         quotient rounds half up and floors a negative numerator.  N = max(sum wy wx F8, 256 floor D) is F8 interpolated between
+ *         the tile centres at the doubled coordinates C2_i = start_i + end_i - 1 and continued LINEARLY outside the outer ones
+ *         (w1 = 2 p - C2_i is not clamped; cs_segment_noise continues constantly), D = Dy Dx, an axis with one node has D = 1.
+ * image:  as above, `kind`; out: the same type, shape and `kind`, and may be image itself (in place).
+ * f8:     [channels][m_y][m_x] int32 of (height, width, tile), mesh_kind; m_y, m_x are checked against them.  A host mesh with
+ *         a value outside [256, 2^24) is CS_ERR_INVALID before any device work; a device mesh: see the status words below.
+ * clipped: NULL, or out on the host, [batch][channels][2] int64: the pixels clamped at 0 and at top.
+ * |w| < 5 T, so |sum| < 2^47 and the numerator stays below 2^62: everything is int64.
+ * Status words.  A value of a device stack outside 0..65535, or of a device function outside [256, 2^24), is cut to that range
+ * in the kernel (it is an operand, never an index) and raises a status word on the handle that only the host clears.  The call
+ * itself answers CS_ERR_INVALID if it synchronises; if it does not, the handle's next cs_illum_* call that synchronises, or
+ * cs_illum_last_timing, answers CS_ERR_INVALID in its place ("this call, or one before it that did not synchronise"), once.
+ * The outputs of such a call are those of the cut values; the handle stays usable.
+ * Host synchronisations: none when every buffer of a call is on the device and clipped is NULL (the result is complete in
+ * stream order; cs_illum_last_timing waits for it), else one.  Uploads and tables on their way to the host go through the
+ * buffers the handle's segmenter stages share.  Bad arguments (reserved words not 0 among them): CS_ERR_INVALID before any
+ * device work; sides, batch or n above the caps: CS_ERR_UNSUPPORTED; without a gfx950 device (p == NULL): CS_ERR_NO_DEVICE. */
+#define CS_ILLUM_MAX_RADIUS 64
+#define CS_ILLUM_MAX_IMAGES 16384
+typedef struct cs_illum_reduce_params {
+    int32_t a_num, a_den;             /* 0 <= a_num <= a_den <= 65536, a_den >= 1; read without mean */
+    int32_t mean;                     /* 0: the rank above, 1: the rounded mean */
+    int32_t offset[4];                /* 0..65535 per channel: the camera's dark level in counts */
+    int32_t floor;                    /* 1..4095 */
+    int32_t mesh_median;              /* 0 or 1 */
+    int32_t radius;                   /* 0: no Gaussian, else 1..64 */
+    int32_t weights[CS_ILLUM_MAX_RADIUS + 1];    /* non-negative, w[0] >= 1, 0 beyond the radius, w[0] + 2 sum w[1..radius] == 65536 */
+    int32_t reserved[2];              /* must be 0 */
+} cs_illum_reduce_params;
+typedef struct cs_illum_apply_params {
+    int32_t tile;                     /* 16, 32, 64, 128 or 256 */
+    int32_t floor;                    /* 1..4095 */
+    int32_t g8[4];                    /* 1 <= G8 < 2^24 per channel */
+    int32_t offset[4];                /* 0..65535 per channel */
+    int32_t pedestal[4];              /* 0..65535 per channel */
+    int32_t reserved[2];              /* must be 0 */
+} cs_illum_apply_params;
+int cs_illum_tile_stats(cs_preproc *p, const void *image, int pixel_type, int32_t channels,
+                        int32_t batch, int32_t height, int32_t width, int in_kind, int32_t tile,
+                        int32_t q_num, int32_t q_den, int32_t *mesh, int out_kind);
+int cs_illum_reduce(cs_preproc *p, const int32_t *stack, int32_t n, int32_t channels, int32_t m_y, int32_t m_x, int in_kind,
+                    const cs_illum_reduce_params *params, int32_t *f8, int out_kind);
+int cs_illum_apply(cs_preproc *p, const void *image, int pixel_type, int32_t channels,
+                   int32_t batch, int32_t height, int32_t width, int kind,
+                   const int32_t *f8, int32_t m_y, int32_t m_x, int mesh_kind,
+                   const cs_illum_apply_params *params, void *out, int64_t *clipped /* or NULL */);
+/* Device time of the last cs_illum_tile_stats, cs_illum_reduce and cs_illum_apply on the handle.  Waits for a call that left
+ * its result on the device, and reports the status words such a call raised (CS_ERR_INVALID; the times are written all the same). */
+int cs_illum_last_timing(const cs_preproc *p, double *stats_ms, double *reduce_ms, double *apply_ms);
 
 /* ---- detector fitting (create_anomaly_detector, CAE_improved_modeltrain.py:394-446) -------- */
 /* The fit of what cs_screen's tail evaluates, for the training set's encoder features
